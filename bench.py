@@ -6,7 +6,16 @@ One "step" = one pass of the hot path over one synthetic batch that is already r
   events f64 (N,4) x256 -> fused augment+rasterize -> fused event_norm -> block-wise masks (host
   MT19937, overlapped) -> ViT-B masked forward + CE -> backward (RCCL all-reduce overlapped when
   N>1) -> grad-norm/clip + AdamW.
-Launch:  python bench.py [--gpus N --steps K --warmup W]
+Launch:  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
+  A plain run measures the headline only: set-up, W warm-up steps, K timed steps, the outputs of the last timed step when
+  --dump-outputs is given, the JSON line.  --full adds everything else the line can carry (per-GEMM HIP-event roofline,
+  speed of light, tokenizer / entrypoint / rasterizer / config #4 / config #5 figures, the CPU baseline, and for N > 1 the
+  steps without the gradient exchange); each of those can still be left out of a --full run with its --no-* switch.
+  --dump-outputs DIR: after the run, the last timed step's batch goes through the training step once more, from the state the
+  run started from, and what that step computed is written as DIR/<name>.npy (float32; fixed, seeded samples of the large
+  arrays, ~20 MB in all).  Inputs and starting state are seeded, so every run with the same arguments writes the same
+  arrays up to rounding (replay_last_step says why not the last timed step's own state), and two builds can be compared
+  output for output.
   N>1, either form works:
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N ...                (the driver's form: RANK / LOCAL_RANK / WORLD_SIZE come from the env)
@@ -141,6 +150,32 @@ def kernel_clock(cj=None):
     return {"gemm_p8_ghz": round(nt_g, 3), "gemm_tn_p8_ghz": round(tn_g, 3), "spec_clock_ghz": cj.get("spec_clock_ghz", 2.4),
             "at_clock_peak_tflops": round(PEAK_BF16_TFLOPS * min(nt_g, tn_g) / cj.get("spec_clock_ghz", 2.4), 1),
             "spec_peak_tflops": PEAK_BF16_TFLOPS, "source": "profiles/" + src + " (tools/clock_probe.py; " + cj.get("method", "") + ")"}
+
+
+DUMP_SAMPLE = 1 << 20                              # --dump-outputs: elements kept of a larger array (4 MB in float32)
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: device tensors -> out_dir/<name>.npy in float32.  An array of more than DUMP_SAMPLE elements is
+    written as a fixed sample of them: DUMP_SAMPLE flat indices drawn by a generator seeded from the name, in ascending
+    order -- the same elements in every run and every build.  Returns {name: [shape written, elements of the array]}."""
+    import zlib
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    info = {}
+    for name, t in sorted(arrays.items()):
+        flat = t.detach().reshape(-1)
+        n = flat.numel()
+        if n > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(zlib.crc32(name.encode())).integers(0, n, DUMP_SAMPLE))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        v = flat.float().cpu().numpy()
+        if n <= DUMP_SAMPLE:
+            v = v.reshape(tuple(t.shape))
+        np.save(os.path.join(out_dir, name + ".npy"), v)
+        info[name] = [list(v.shape), n]
+    return info
 
 
 HBM_ACHIEVABLE_TBS = 6.3                           # MI355X_MICROARCH.md: 8.0 TB/s spec, 6.29 measured (float4 copy)
@@ -547,6 +582,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--batch", type=int, default=256, help="per-GPU batch (BASELINE config: 256)")
     ap.add_argument("--events", type=int, default=30000)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the run, replay the last timed step's batch once on the starting state and write what the step computed "
+                         "(loss, gradient norm, samples of the weights, gradients, AdamW moments and input voxels) as "
+                         "DIR/<name>.npy, float32")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beside the headline too (the figures the --no-* switches below leave out, and for "
+                         "N > 1 the steps without the gradient exchange); off: the headline only")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-gemm-timer", action="store_true")
     ap.add_argument("--no-tokenizer-figure", action="store_true",
@@ -591,6 +633,10 @@ def main():
     ap.add_argument("--opt", action="append", default=[], metavar="NAME=VALUE",
                     help="kernel-selection option for A/B runs (memhip_set_option), e.g. --opt gemm_stagger=0")
     a = ap.parse_args()
+    if not a.full:
+        # a plain run: set-up, warm-up, the timed steps, the outputs, the line -- nothing that takes steps or runs of its own
+        a.no_cpu_baseline = a.no_gemm_timer = a.no_tokenizer_figure = a.no_raster_figure = True
+        a.no_entrypoint_figure = a.no_config4_figure = a.no_config5_figure = True
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         self_launch(a, sys.argv[1:])                  # never returns
 
@@ -692,12 +738,17 @@ def main():
     T = eng.T
     from mem_amd.utils import HostStager
     st_rows, st_mask = HostStager(B * 98 * 4, "cuda"), HostStager(B * 196, "cuda")
+    last_timed = a.warmup + a.steps - 1
+    last_batch = {}                                                   # --dump-outputs: the batch of the last timed step
 
-    def step(it):
+    def step(it, replay=None):
         for grp in opt.param_groups:
             grp["lr"] = lr_sched[it]
-        x = pipe(ev_dev, offsets)                                     # rasterize + event_norm (HIP)
-        m = masker.batch_u8(B).reshape(B, -1)                         # host MT19937 (bit-exact CPython stream)
+        x = pipe(ev_dev, offsets) if replay is None else replay["x"]   # rasterize + event_norm (HIP)
+        m = masker.batch_u8(B).reshape(B, -1) if replay is None else replay["m"]   # host MT19937 (bit-exact CPython stream)
+        if a.dump_outputs and replay is None and it == last_timed:
+            dps = getattr(model, "_dp_stream", None)
+            last_batch.update(x=x, m=m, dp=dps.state() if dps is not None and dps.gen is not None else None)
         bi, pi = np.nonzero(m)
         rows = st_rows.put((bi * T + 1 + pi).astype(np.int32))        # pinned ring: the host never waits for the queue
         mask_u8 = st_mask.put(m.reshape(-1))
@@ -716,6 +767,34 @@ def main():
             dist.barrier()
             torch.cuda.synchronize()
 
+    def replay_last_step():
+        """--dump-outputs, after everything timed: the training step of the timed path, run once more on the batch of the last
+        timed step (its voxels, masks, labels, stochastic-depth draws and learning rate) from the state the run started from.
+        The fp32 gradient reductions of the step use atomics, so two runs differ in the last bits of a step, and training
+        compounds that over the steps before the last; one step from the starting state is the same in every run up to
+        rounding, and is what two builds are compared on.  Every rank runs it (the gradient exchange is collective)."""
+        fence()
+        eng.flat_p.copy_(start_p)
+        eng.flat_g.zero_()
+        opt.exp_avg.zero_()
+        opt.exp_avg_sq.zero_()
+        opt.steps = 0
+        eng.weights_dirty = True                                    # the bf16 copies are cast again from the restored weights
+        if last_batch["dp"] is None:
+            model._dp_stream = None                                  # drawn from a fresh stream, as the first step did
+        else:
+            model._dp_stream.load_state(last_batch["dp"])
+        la_r = step(last_timed, replay=last_batch)
+        fence()
+        if rank != 0:
+            return None
+        return dump_outputs(a.dump_outputs, {
+            "loss_acc": la_r, "grad_norm": eng.gnorm, "weights": eng.flat_p[: eng.nflat], "grads": eng.flat_g[: eng.nflat],
+            "adamw_exp_avg": opt.exp_avg, "adamw_exp_avg_sq": opt.exp_avg_sq, "voxels": last_batch["x"]})
+
+    # --dump-outputs: the state the run starts from (weights; AdamW moments and step count are zero), to replay the last
+    # timed step's batch on after the run -- see replay_last_step
+    start_p = eng.flat_p.clone() if a.dump_outputs else None
     for it in range(a.warmup):
         step(it)
     # CPython's cyclic collector walks every tracked object of the process (model, optimizer, torch internals) when its
@@ -782,7 +861,7 @@ def main():
     # same ranks run the same steps once more with the exchange switched off (no collective is issued; backward, norm and
     # AdamW unchanged); per-step times by HIP events, median per rank, MAX over ranks
     rccl_info = None
-    if reducer is not None:
+    if reducer is not None and a.full:
         ranks = [None] * dist.get_world_size()
         prop = torch.cuda.get_device_properties(torch.cuda.current_device())
         dist.all_gather_object(ranks, {"rank": dist.get_rank(), "local_rank": local_rank, "device_index": torch.cuda.current_device(),
@@ -1082,6 +1161,7 @@ def main():
             import traceback
             traceback.print_exc()
             print(f"[bench] config #5 figure skipped: {e}", file=sys.stderr)
+    dumped = replay_last_step() if a.dump_outputs else None
     if rank == 0:
         ms = dt / a.steps * 1e3
         value = world * B * a.steps / dt
@@ -1220,7 +1300,7 @@ def main():
                "ms_per_step": round(ms, 3), "ms_per_step_p50": round(step_ms[len(step_ms) // 2], 3),
                "ms_per_step_p50_uninstrumented": round(plain[len(plain) // 2], 3) if plain else None,
                "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-               "dtype": "bf16", "data": "synthetic",
+               "dtype": "bf16", "data": "synthetic", "full": a.full,
                "config": {"workload": "MEM pretrain ViT-Base/16, 224^2 2-bin event voxels, bf16, batch 256 per GPU "
                                       "(BASELINE configs[1]); step = rasterize 256x30k events + event_norm + masks "
                                       "+ ViT fwd/CE/bwd + clip + AdamW",
@@ -1237,6 +1317,11 @@ def main():
             out["speed_of_light"] = sol
         out["library"] = {"path": os.path.relpath(_L.LIB_PATH, ROOT), "build_flags": _L.BUILD_FLAGS, "shipped_build": _L.IS_SHIPPED_LIB,
                           "abi": _L.ABI_VERSION, "options_set": sorted(a.opt)}
+        if dumped is not None:
+            out["outputs"] = {"dir": a.dump_outputs, "arrays": dumped,
+                              "step": "the last timed step's batch, replayed once on the starting state after the run",
+                              "note": "float32 .npy; [shape written, elements of the array]: an array of more than "
+                                      f"{DUMP_SAMPLE} elements is a fixed, seeded sample of them"}
         if not _L.IS_SHIPPED_LIB:
             # a measurement build (MEMHIP_LIB / extra compiler flags) is never the headline: the A/B tools read ab_value
             out["metric"] = "NOT THE HEADLINE: measurement build of libmemhip.so (MEMHIP_LIB / build flags set) -- " + out["metric"]

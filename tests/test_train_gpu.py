@@ -208,7 +208,7 @@ def test_bench_contract_and_rccl_dry_run():
     import sys
     from conftest import ROOT
     env = dict(os.environ, MEMHIP_BENCH_FORCE_DIST="1", MASTER_PORT="29577")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--batch", "16", "--steps", "3", "--warmup", "1",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--batch", "16", "--steps", "3", "--warmup", "1", "--full",
                         "--no-tokenizer-figure", "--no-raster-figure", "--no-cpu-baseline", "--no-entrypoint-figure",
                         "--no-config4-figure", "--bucket-dtype", "bf16", "--reserve-cus", "16"], env=env, capture_output=True,
                        text=True, timeout=600)
@@ -229,3 +229,48 @@ def test_bench_contract_and_rccl_dry_run():
     assert isinstance(rc["allreduce_exposed_ms"], float)
     from mem_amd import _lib
     assert _lib.get_option("reserve_cus") == 0                      # (this process: the option is per process, default off)
+
+
+def test_bench_plain_run_and_dumped_outputs(tmp_path):
+    """A plain bench.py run (no --full) times exactly --steps steps and prints the headline line only: no roofline, no
+    secondary figure, no CPU baseline.  --dump-outputs writes what the last timed step computed as float32 .npy files,
+    64 MB at most, and two runs with the same arguments write the same arrays up to rounding."""
+    import json
+    import subprocess
+    import sys
+    from conftest import ROOT
+    env = dict(os.environ, MEMHIP_BENCH_STEP_TIMES="1")
+    runs = []
+    for k in range(2):
+        d = tmp_path / f"run{k}"
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--batch", "16", "--steps", "3", "--warmup", "1",
+                            "--dump-outputs", str(d)], env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+        assert sum(ln.lstrip().startswith("{") for ln in lines) == 1
+        out = json.loads(lines[-1])
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert key in out, key
+        assert out["steps"] == 3 and out["warmup"] == 1 and out["full"] is False and out["roofline"] is None
+        for key in ("speed_of_light", "with_tokenizer", "entrypoint", "rasterizer_1m_events", "config4_end_to_end",
+                    "config5_vitl_1gpu", "cpu_baseline", "rccl"):
+            assert key not in out, key
+        # ms_per_step is one timed step: value = batch / ms_per_step, and the per-step list holds --steps entries
+        assert abs(out["value"] * out["ms_per_step"] * 1e-3 / 16 - 1.0) < 1e-3, (out["value"], out["ms_per_step"])
+        per_step = [ln for ln in r.stderr.splitlines() if ln.startswith("[bench] per-step ms:")]
+        assert len(per_step) == 1 and len(json.loads(per_step[0].split(":", 1)[1])) == 3, per_step
+        names = set(out["outputs"]["arrays"])
+        assert {"loss_acc", "grad_norm", "weights", "grads", "voxels"} <= names
+        assert sorted(os.listdir(d)) == sorted(n + ".npy" for n in names)
+        arrs = {n: np.load(d / (n + ".npy")) for n in names}
+        assert all(v.dtype == np.float32 and v.size > 0 and np.isfinite(v).all() for v in arrs.values())
+        assert sum(v.nbytes for v in arrs.values()) <= 64 << 20
+        assert arrs["loss_acc"].shape == (2,) and 0.0 < arrs["loss_acc"][0] < 20.0
+        runs.append(arrs)
+    # the same events, masks, labels and initial weights in both runs: the voxels agree, and so does the loss
+    np.testing.assert_allclose(runs[0]["voxels"], runs[1]["voxels"], rtol=1e-6, atol=1e-6)
+    np.testing.assert_allclose(runs[0]["loss_acc"], runs[1]["loss_acc"], rtol=1e-3, atol=1e-4)
+    # ... and every array the step computed agrees up to the rounding of its fp32 atomics (~1e-7 of the array's norm)
+    for n, v in runs[0].items():
+        w = runs[1][n]
+        assert np.linalg.norm(v.astype(np.float64) - w) <= 1e-5 * np.linalg.norm(v.astype(np.float64)) + 1e-12, n

@@ -14,7 +14,7 @@ shift; [ $# -gt 0 ] && shift; [ $# -gt 0 ] && shift
 cd "$(dirname "$0")/.." || exit 1
 mkdir -p gpurun_out
 OUT=gpurun_out/scale_ab_N${N}.jsonl; : > "$OUT"
-EXTRA=(--no-cpu-baseline --no-gemm-timer "$@")
+EXTRA=(--full --no-cpu-baseline --no-gemm-timer "$@")     # --full: the steps without the exchange (rccl.allreduce_exposed_ms)
 [ "${SCALE_AB_DRY:-0}" = 1 ] && EXTRA+=(--rendezvous-only)
 rc=0
 for rep in 1 2; do
