@@ -94,6 +94,9 @@ int memhip_set_option(const char* name, int value) {
   MEMHIP_REQUIRE(name, "set_option: null name");
   for (int i = 0; i < memhip::OPT_COUNT_; ++i)
     if (!strcmp(name, memhip::g_opt_name[i])) {
+      // the LayerNorm-backward launchers size their grid from this value: below 1 they would launch an empty grid
+      if (i == memhip::OPT_LN_BWD_GRID && value < 1)
+        return memhip::fail(MEMHIP_EINVAL, "set_option: ln_bwd_grid=%d must be at least 1", value);
       memhip::g_opt[i].store(value, std::memory_order_relaxed);
       return MEMHIP_OK;
     }

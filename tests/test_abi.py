@@ -58,6 +58,14 @@ def test_options_table_and_no_environment_reads():
         raise AssertionError("unknown option accepted")
     except _lib.MemhipError as e:
         assert "unknown option" in str(e)
+    grid = _lib.get_option("ln_bwd_grid")
+    for bad in (0, -1):                 # both LayerNorm-backward launchers would launch an empty grid
+        try:
+            _lib.set_option("ln_bwd_grid", bad)
+            raise AssertionError("ln_bwd_grid=%d accepted" % bad)
+        except _lib.MemhipError as e:
+            assert "ln_bwd_grid" in str(e)
+        assert _lib.get_option("ln_bwd_grid") == grid
     syms = subprocess.run(["nm", "-D", "--undefined-only", os.path.join(ROOT, "mem_amd", "libmemhip.so")],
                           capture_output=True, text=True).stdout
     assert "getenv" not in syms

@@ -252,9 +252,33 @@ def test_vit_large_480x640_step():
     la2 = m.forward_loss(x, mask.cuda(), labels)
     m.backward()
     assert la2[0].item() == la[0].item()
+    # The residual-stream gradient is the same in both steps (the attention backward stores dq / dk / dv, its atomics feed
+    # only the table and q / v biases), so a gradient can differ only where its own sum runs through fp32 atomics whose
+    # order changes.  Bars: 3 x the largest figure of the class measured over three runs of this test.
+    last = "blocks.%d." % (cfg["depth"] - 1)
+
+    def repeat_bar(k):
+        if k.startswith("rel_pos_bias.") or k.endswith("q_bias"):
+            return 4.3e-7         # attention backward: table / q-bias atomics (measured 1.4e-7)
+        if "norm" in k:
+            return 2.1e-6         # LayerNorm gamma / beta: column sums of ln_bwd / ln_bwd_branch (7.0e-7)
+        if k.endswith("bias"):
+            return 3.2e-6         # Linear biases: column sums of branch_bwd, the GEMM epilogue, colsum_bf16, gemv_acc (1.05e-6)
+        if k.startswith(last + "mlp.fc") or k == last + "gamma_2":
+            return 9.7e-8         # last block, 1200 tail rows: R < 2048 leaves gemm_tn_p8 for gemm_tn, 3 atomic K-splits (3.2e-8)
+        # Bit-equal: every other weight gradient takes the workspace + tn_reduce path (grouped qkv + proj, fc2 + fc1, the
+        # patch embedding), lm_head.weight adds two K-splits onto zero and cls / mask token two workgroups' sums onto zero
+        # (a + b == b + a); gamma = (<W, dW> + b db) / gamma with b = 0 at init is a function of dW alone.
+        return 0.0
+
     for k, p in m.named_parameters():
-        rel = (p.grad - grads[k]).norm() / (grads[k].norm() + 1e-20)
-        assert rel <= 2e-2, (k, rel.item())          # table-gradient / bias atomics reorder fp32 sums
+        rel = ((p.grad - grads[k]).norm() / (grads[k].norm() + 1e-20)).item()
+        bar = repeat_bar(k)
+        print("ViT-L repeat %-48s %.3e (bar %s)" % (k, rel, "bit-equal" if bar == 0 else "%.1e" % bar))
+        if bar == 0:
+            assert torch.equal(p.grad, grads[k]), (k, rel)
+        else:
+            assert rel <= bar, (k, rel, bar)
 
 
 @pytest.mark.parametrize("tag", ["a", "b"])

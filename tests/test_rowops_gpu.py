@@ -1,0 +1,791 @@
+"""-m gpu: the HBM-bound row kernels of the bf16 backward (rowops.hip, misc.hip) against float64 references, at the step's
+real row counts (ViT-B: 256 x 197 = 50 432 rows, ViT-L: 64 x 1201 = 76 864) where every wave walks many rows, and at the
+edge shapes.
+
+Two kinds of check per kernel:
+  * exact layouts: small integers, dyadic values and powers of two chosen so that every intermediate and every partial
+    column sum is exactly representable in fp32 (and every bf16 output in bf16).  The kernel must then equal the float64
+    reference bit for bit whatever the grid and the order of the atomics: a row dropped, counted twice or sent to the wrong
+    place shows up as a wrong value.  For the LayerNorm kernels dy * gamma is paired across columns j and j + D/2 (equal
+    xhat, opposite signs), so each row's sum(dy gamma) and sum(dy gamma xhat) are exactly 0.
+  * random values (ViT-like scales) with bars that follow from the fp32 arithmetic; the measured figure is printed next
+    to each bar.
+Regions a kernel must not write are filled with a NaN bit pattern and checked bit for bit afterwards."""
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+
+NAN32, NAN16 = 0x7FC0BEEF, 0x7FC1            # canary bit patterns (fp32 / bf16 NaN)
+_INT = {torch.float32: torch.int32, torch.bfloat16: torch.int16, torch.uint8: torch.uint8}
+
+
+def _gen(seed):
+    return torch.Generator(device="cuda").manual_seed(seed)
+
+
+def _ri(lo, hi, shape, g):
+    """integers in [lo, hi] as float64"""
+    return torch.randint(lo, hi + 1, shape, generator=g, device="cuda").double()
+
+
+def _pow2(lo, hi, shape, g, signed=False):
+    """powers of two 2^lo .. 2^hi, exact (a float64 pow on the device is not: it gives 2^-9 = 0.0019531249999999998)"""
+    table = torch.tensor([2.0 ** k for k in range(lo, hi + 1)], dtype=torch.float64, device="cuda")
+    v = table[torch.randint(0, hi - lo + 1, shape, generator=g, device="cuda")]
+    return v * (2 * _ri(0, 1, shape, g) - 1) if signed else v
+
+
+def _randn(shape, g, scale=1.0):
+    return torch.randn(shape, generator=g, device="cuda", dtype=torch.float64) * scale
+
+
+def _canvas(rows, cols, dtype):
+    """a device buffer filled with the NaN canary"""
+    t = torch.empty((rows, cols), dtype=dtype, device="cuda")
+    t.view(_INT[dtype]).fill_(NAN32 if dtype == torch.float32 else NAN16)
+    return t
+
+
+def _bits(t):
+    return t.view(_INT[t.dtype])
+
+
+def _untouched(buf, init, written):
+    """number of elements outside `written` whose bits changed"""
+    return int(((_bits(buf) != _bits(init)) & ~written).sum().item())
+
+
+def _bf(v):
+    """float64 -> the bf16 value the kernels store (fp32 first, then round to nearest even)"""
+    return v.float().bfloat16().double()
+
+
+def _ulp16(v):
+    """one bf16 ulp at |v| (0 at v == 0)"""
+    _, e = torch.frexp(v.abs())
+    return torch.where(v == 0, torch.zeros_like(v), torch.ldexp(torch.ones_like(v), e - 8))
+
+
+def _exact_sums_fit(abs_sums, unit=0.125):
+    """precondition of the exact layouts: every partial sum is a multiple of `unit` below 2^24 units"""
+    m = float(abs_sums.max().item())
+    assert m / unit < 2 ** 24, ("exact layout would round", m)
+
+
+def _check_bf16(out, ref, extra, what):
+    """bf16 outputs: within one bf16 ulp (+ the propagated fp32 error `extra`) of float64, >= 99.9 % equal after rounding"""
+    d = (out.double() - ref).abs()
+    tol = _ulp16(ref) + extra
+    worst = float((d / tol.clamp_min(1e-300)).max().item()) if d.numel() else 0.0
+    eq = float((out.double() == _bf(ref)).double().mean().item()) if d.numel() else 1.0
+    print("  %-28s max |err| / (1 ulp + fp32 term) = %.3f (bar 1), equal after rounding %.5f (bar 0.999)" % (what, worst, eq))
+    assert worst <= 1.0 and eq >= 0.999, (what, worst, eq)
+
+
+def _check_bar(out, ref, scale, k, what):
+    """|out - ref| <= 2^-k * scale, element by element"""
+    d = (out.double() - ref).abs()
+    fig = float((d / (scale * 2.0 ** -k).clamp_min(1e-300)).max().item())
+    print("  %-28s max |err| / (2^-%d scale) = %.4f (bar 1)" % (what, k, fig))
+    assert fig <= 1.0, (what, fig)
+
+
+class _Grid:
+    """ln_bwd_grid (process-global): 1 = one workgroup walks every row, 7 = a ragged grid, None = the shipped value"""
+
+    def __init__(self, g):
+        self.g = g
+
+    def __enter__(self):
+        from mem_amd import _lib
+        self.saved = _lib.get_option("ln_bwd_grid")
+        if self.g is not None:
+            _lib.set_option("ln_bwd_grid", self.g)
+
+    def __exit__(self, *a):
+        from mem_amd import _lib
+        _lib.set_option("ln_bwd_grid", self.saved)
+
+
+GRIDS = (1, 7, None)
+
+
+# ------------------------------------------------------------------------------------------------ LayerNorm inputs
+def _ln_inputs(Rc, D, g, exact):
+    """Rc rows of a LayerNorm'ed branch: dy (bf16 values), x, gamma, mean, rstd (fp32 values), all float64."""
+    if exact:
+        h = D // 2
+        dyh, xhh, gh = _ri(-4, 4, (Rc, h), g), _ri(-4, 4, (Rc, h), g) * 0.5, _pow2(-1, 1, (h,), g)
+        dy, xh, gamma = torch.cat([dyh, -dyh], 1), torch.cat([xhh, xhh], 1), torch.cat([gh, gh])
+        rstd, mean = _pow2(-1, 1, (Rc,), g), _ri(-8, 8, (Rc,), g) * 0.25
+        x = mean[:, None] + xh / rstd[:, None]
+        return dy, x, gamma, mean, rstd
+    x = (0.5 + _randn((Rc, D), g, 2.0) + _randn((Rc, 1), g)).float().double()
+    mean = x.mean(1).float().double()
+    rstd = (1.0 / torch.sqrt(x.var(1, unbiased=False) + 1e-6)).float().double()
+    dy = _bf(_randn((Rc, D), g, 0.02))
+    gamma = (1 + _randn((D,), g, 0.1)).float().double()
+    return dy, x, gamma, mean, rstd
+
+
+def _ln_ref(dy, x, gamma, mean, rstd):
+    """float64 LayerNorm backward on the kernel's inputs: (dx, xhat, the per-element error scale of the fp32 kernel)"""
+    xh = (x - mean[:, None]) * rstd[:, None]
+    gg = dy * gamma
+    ggx = gg * xh
+    m1, m2 = gg.mean(1, keepdim=True), ggx.mean(1, keepdim=True)
+    d = rstd[:, None] * (gg - m1 - xh * m2)
+    del ggx
+    scale = rstd[:, None] * (gg.abs() + gg.abs().mean(1, keepdim=True) + xh.abs() * (gg * xh).abs().mean(1, keepdim=True))
+    return d, xh, scale
+
+
+def _sample_patterns(B, mode, g):
+    """(kept by the LayerNorm'ed branch, kept by the output branch), bool [B] each, or None = no map"""
+    if mode == "maps":
+        cat = torch.randint(0, 4, (B,), generator=g, device="cuda")
+        first = [0, 1, 2, 3] if B >= 4 else [1, 2][:B]         # both / LayerNorm'ed only / output only / neither
+        cat[:len(first)] = torch.tensor(first, device="cuda")
+        return (cat == 0) | (cat == 1), (cat == 0) | (cat == 2)
+    if mode == "maps_all":
+        return torch.ones(B, dtype=torch.bool, device="cuda"), torch.ones(B, dtype=torch.bool, device="cuda")
+    if mode == "maps_none":
+        return torch.zeros(B, dtype=torch.bool, device="cuda"), torch.zeros(B, dtype=torch.bool, device="cuda")
+    if mode == "in_only":
+        cat = torch.randint(0, 2, (B,), generator=g, device="cuda").bool()
+        cat[:2] = torch.tensor([True, False], device="cuda")
+        return cat, None
+    if mode == "out_only":
+        cat = torch.randint(0, 2, (B,), generator=g, device="cuda").bool()
+        cat[:2] = torch.tensor([True, False], device="cuda")
+        return None, cat
+    return None, None
+
+
+def _cmap(kept):
+    """sample -> index among the kept samples (ascending), -1 = dropped: the engine's cmap (vit_engine.py)"""
+    m = torch.full(kept.shape, -1, dtype=torch.int32, device="cuda")
+    m[kept] = torch.arange(int(kept.sum().item()), dtype=torch.int32, device="cuda")
+    return m
+
+
+def _rows_of(kept, rps):
+    """residual-stream rows of the kept samples, in compact order"""
+    s = torch.nonzero(kept).flatten()
+    return (s[:, None] * rps + torch.arange(rps, device="cuda")[None, :]).flatten()
+
+
+# ------------------------------------------------------------------------------------------------ layernorm_bwd_branch
+LNB_CASES = [  # (D, samples, rows per sample)
+    (768, 256, 197), (1024, 64, 1201),                       # the ViT-B and ViT-L steps: 50 432 and 76 864 rows
+    (128, 2, 197), (384, 2, 197), (512, 2, 197), (768, 2, 197), (1024, 2, 1201), (260, 2, 197), (260, 300, 5),
+]
+LNB_MODES = ["plain", "rowmask", "maps", "maps_all", "maps_none", "in_only", "out_only", "no_gamma_branch", "y_branch"]
+
+
+def _lnb_case(D, B, rps, mode, exact, seed, gb_scale=0.1):
+    g = _gen(seed)
+    R = B * rps
+    kin, kout = _sample_patterns(B, mode, g)
+    maps = kin is not None or kout is not None
+    kin_ = kin if kin is not None else torch.ones(B, dtype=torch.bool, device="cuda")
+    kout_ = kout if kout is not None else torch.ones(B, dtype=torch.bool, device="cuda")
+    rowmask = None
+    if mode == "rowmask":
+        rowmask = (torch.rand(B, generator=g, device="cuda") < 0.7).double()
+        rowmask[:2] = torch.tensor([1.0, 0.0], device="cuda")
+    # the kernel divides by keep only with a rowmask or an out_map (dt = dx * mask / keep); elsewhere keep = 1
+    keep = (0.5 if exact else 0.9) if (rowmask is not None or kout is not None) else 1.0
+    rin, rout = _rows_of(kin_, rps), _rows_of(kout_, rps)
+    Rc, Ro = rin.numel(), rout.numel()
+    dy, xc, gamma, mean, rstd = _ln_inputs(max(Rc, 1), D, g, exact)
+    dy, xc, mean, rstd = dy[:Rc], xc[:Rc], mean[:Rc], rstd[:Rc]
+    prev = _ri(-4, 4, (R, D), g) if exact else _randn((R, D), g, 0.01).float().double()
+    has_gb = mode != "no_gamma_branch"
+    gb = (_pow2(0, 1, (D,), g, signed=True) if exact else (gb_scale * (1 + _randn((D,), g, 0.1))).float().double()) \
+        if has_gb else None
+    yb = (_ri(-2, 2, (R, D), g) * 0.5 if exact else _bf(_randn((R, D), g))) if mode == "y_branch" else None
+    acc0 = [_ri(-8, 8, (D,), g) * 0.5 if exact else _randn((D,), g, 0.1).float().double() for _ in range(4)]
+
+    # device buffers (ld > D; canaries in padding, past the last row, in rows nobody may read or write)
+    ldx, ldr, ldd, ldo = D + 4, D + 8, D + 12, D + 8
+    x_d = _canvas(R + 2, ldx, torch.float32)
+    x_d[rin, :D] = xc.float()
+    dy_d = _canvas(Rc + 2, ldd, torch.bfloat16)
+    dy_d[:Rc, :D] = dy.bfloat16()
+    mean_d, rstd_d = _canvas(1, Rc + 4, torch.float32)[0], _canvas(1, Rc + 4, torch.float32)[0]
+    mean_d[:Rc], rstd_d[:Rc] = mean.float(), rstd.float()
+    dres0 = _canvas(R + 2, ldr, torch.float32)
+    live = torch.zeros(R, dtype=torch.bool, device="cuda")          # rows some branch takes part in
+    live[rin] = True
+    live[rout] = True
+    dres0[:R, :D][live] = prev[live].float()
+    dyo0 = _canvas(Ro + 2, ldo, torch.bfloat16)
+    accs0 = []
+    for a in acc0:
+        t = _canvas(1, D + 4, torch.float32)[0]
+        t[:D] = a.float()
+        accs0.append(t)
+    gb_d = gb.float() if gb is not None else None
+    yb_d = None
+    if yb is not None:
+        yb_d = _canvas(R + 1, D + 4, torch.bfloat16)
+        yb_d[:R, :D] = yb.bfloat16()
+    rm_d = rowmask.float() if rowmask is not None else None
+    in_map = _cmap(kin) if kin is not None else None
+    out_map = _cmap(kout) if kout is not None else None
+
+    # float64 reference
+    d, xh, scale = _ln_ref(dy, xc, gamma, mean, rstd)
+    exp_g, exp_b = acc0[0] + (dy * xh).sum(0), acc0[1] + dy.sum(0)
+    sums_abs = [acc0[0].abs() + (dy * xh).abs().sum(0), acc0[1].abs() + dy.abs().sum(0)]
+    new = prev.clone()
+    new[rin] += d
+    sc = prev.abs()
+    sc[rin] += scale
+    del d, xh, scale, dy, xc
+    if rowmask is not None:
+        km = rowmask.repeat_interleave(rps)[:, None]
+        dt, dt_sc = (new * km / keep)[rout], (sc * km / keep)[rout]
+    else:
+        dt, dt_sc = new[rout] / keep, sc[rout] / keep
+    gbv = gb if gb is not None else torch.ones(D, dtype=torch.float64, device="cuda")
+    dyo_exp = dt * gbv
+    exp_gb, s_gb = acc0[2], acc0[2].abs()
+    if yb is not None:
+        exp_gb = exp_gb + (dt * yb[rout]).sum(0)
+        s_gb = s_gb + ((dt.abs() + dt_sc * 2.0 ** -18) * yb[rout].abs()).sum(0)
+    sums_abs += [s_gb, acc0[3].abs() + dyo_exp.abs().sum(0)]
+    del dt
+    return dict(R=R, D=D, rps=rps, keep=keep, live=live, x=x_d, dy=dy_d, gamma=gamma.float(), mean=mean_d, rstd=rstd_d, dres0=dres0,
+                dyo0=dyo0, accs0=accs0, gb=gb_d, yb=yb_d, rowmask=rm_d, in_map=in_map, out_map=out_map, rin=rin, Ro=Ro,
+                dres_exp=new, dres_sc=sc, dyo_exp=dyo_exp, dyo_sc=dt_sc * gbv.abs(), exp=[exp_g, exp_b, exp_gb],
+                sums_abs=sums_abs, acc0=acc0, has_y=yb is not None, has_gb=gb is not None)
+
+
+def _lnb_run(c):
+    from mem_amd import ops
+    dres, dyo = c["dres0"].clone(), c["dyo0"].clone()
+    accs = [a.clone() for a in c["accs0"]]
+    D = c["D"]
+    ops.layernorm_bwd_branch(c["dy"], c["x"], c["gamma"], c["mean"], c["rstd"], dres, accs[0], accs[1], c["R"], D, c["yb"],
+                             c["gb"], dyo, accs[2] if c["has_y"] else None, accs[3], rowmask=c["rowmask"], keep_prob=c["keep"],
+                             rows_per_sample=c["rps"], in_map=c["in_map"], out_map=c["out_map"])
+    torch.cuda.synchronize()
+    return dres, dyo, accs
+
+
+def _lnb_canaries(c, dres, dyo, accs):
+    R, D = c["R"], c["D"]
+    w = torch.zeros(dres.shape, dtype=torch.bool, device="cuda")
+    w[c["rin"], :D] = True                                   # rows the LayerNorm'ed branch kept, and only those
+    assert _untouched(dres, c["dres0"], w) == 0, "dres written outside the rows of the LayerNorm'ed branch"
+    w = torch.zeros(dyo.shape, dtype=torch.bool, device="cuda")
+    w[:c["Ro"], :D] = True
+    assert _untouched(dyo, c["dyo0"], w) == 0, "dy of the branch written past its kept rows or into ld padding"
+    for a, a0 in zip(accs, c["accs0"]):
+        w = torch.zeros(a.shape, dtype=torch.bool, device="cuda")
+        w[:D] = True
+        assert _untouched(a, a0, w) == 0
+    if not c["has_y"]:
+        assert torch.equal(_bits(accs[2]), _bits(c["accs0"][2]))
+
+
+@pytest.mark.parametrize("D,B,rps", LNB_CASES)
+def test_layernorm_bwd_branch_exact(D, B, rps):
+    """Every mode, every grid: bit-equal to float64 (exact layout), canaries intact."""
+    full = B * rps > 10000
+    for mi, mode in enumerate(LNB_MODES):
+        if full and mode in ("maps_all", "maps_none", "no_gamma_branch", "in_only"):
+            continue                                         # the map / gamma edges are exercised at B = 2 (cheap)
+        c = _lnb_case(D, B, rps, mode, True, 100 + mi)
+        _exact_sums_fit(torch.stack(c["sums_abs"]))
+        rows_bits = None
+        for gr in GRIDS:
+            with _Grid(gr):
+                dres, dyo, accs = _lnb_run(c)
+            R = c["R"]
+            lv = c["live"]                                   # (rows of samples both branches dropped are canaries)
+            assert torch.equal(dres[:R, :D][lv].double(), c["dres_exp"][lv]), (mode, gr, "dres")
+            assert torch.equal(dyo[:c["Ro"], :D].double(), c["dyo_exp"]), (mode, gr, "dy of the branch")
+            assert torch.equal(accs[0][:D].double(), c["exp"][0]), (mode, gr, "dgamma")
+            assert torch.equal(accs[1][:D].double(), c["exp"][1]), (mode, gr, "dbeta")
+            if c["has_y"]:
+                assert torch.equal(accs[2][:D].double(), c["exp"][2]), (mode, gr, "dgamma of the branch")
+            dbias = c["acc0"][3] + dyo[:c["Ro"], :D].double().sum(0)
+            assert torch.equal(accs[3][:D].double(), dbias), (mode, gr, "dbias of the branch")
+            _lnb_canaries(c, dres, dyo, accs)
+            bits = (_bits(dres).clone(), _bits(dyo).clone())
+            if rows_bits is None:
+                rows_bits = bits
+            else:
+                assert torch.equal(bits[0], rows_bits[0]) and torch.equal(bits[1], rows_bits[1]), (mode, gr)
+        del c
+
+
+@pytest.mark.parametrize("D,B,rps,gb_scale", [(768, 256, 197, 0.1), (1024, 64, 1201, 1e-5), (260, 300, 5, 0.1),
+                                              (384, 2, 197, 1e-5), (128, 2, 197, 0.1)])
+def test_layernorm_bwd_branch_random(D, B, rps, gb_scale):
+    """Random values vs float64: fp32 row outputs within 2^-18 of their scale, bf16 within one ulp, column sums within
+    2^-14 of the sum of absolute terms."""
+    full = B * rps > 10000
+    for mi, mode in enumerate(["plain", "rowmask", "maps", "y_branch"]):
+        c = _lnb_case(D, B, rps, mode, False, 200 + mi, gb_scale=gb_scale)
+        print("layernorm_bwd_branch D=%d R=%d %s layer scale %g" % (D, c["R"], mode, gb_scale))
+        rows_bits = None
+        for gr in (GRIDS if full or D == 260 else (None,)):
+            with _Grid(gr):
+                dres, dyo, accs = _lnb_run(c)
+            R = c["R"]
+            lv = c["live"]
+            _check_bar(dres[:R, :D][lv], c["dres_exp"][lv], c["dres_sc"][lv], 18, "dres (grid %s)" % gr)
+            _check_bf16(dyo[:c["Ro"], :D], c["dyo_exp"], c["dyo_sc"] * 2.0 ** -18 * 1.01, "dy of the branch")
+            _check_bar(accs[0][:D], c["exp"][0], c["sums_abs"][0], 14, "dgamma")
+            _check_bar(accs[1][:D], c["exp"][1], c["sums_abs"][1], 14, "dbeta")
+            if c["has_y"]:
+                _check_bar(accs[2][:D], c["exp"][2], c["sums_abs"][2], 14, "dgamma of the branch")
+            own = dyo[:c["Ro"], :D].double()
+            _check_bar(accs[3][:D], c["acc0"][3] + own.sum(0), c["acc0"][3].abs() + own.abs().sum(0), 14, "dbias of the branch")
+            _lnb_canaries(c, dres, dyo, accs)
+            bits = (_bits(dres).clone(), _bits(dyo).clone())
+            if rows_bits is None:
+                rows_bits = bits
+            else:                                            # the row arithmetic does not depend on the grid
+                assert torch.equal(bits[0], rows_bits[0]) and torch.equal(bits[1], rows_bits[1]), (mode, gr)
+        del c
+
+
+# ------------------------------------------------------------------------------------------------ layernorm_bwd
+LNB2_CASES = [(768, 256, 197), (1024, 64, 1201), (128, 2, 197), (384, 2, 197), (512, 2, 197), (260, 2, 197),
+              (1280, 2, 197), (2048, 2, 197), (2048, 40, 5)]
+
+
+@pytest.mark.parametrize("D,B,rps", LNB2_CASES)
+@pytest.mark.parametrize("exact", [True, False])
+def test_layernorm_bwd(D, B, rps, exact):
+    """memhip_layernorm_bwd with row_idx as the work-skipping engine passes it (compact row -> residual row of a kept
+    sample), accumulate = 0 and 1, every grid.  Rows outside row_idx, the ld padding and rows >= R are canaries; with
+    accumulate = 0 the written rows start as NaN too (the kernel must not read them)."""
+    from mem_amd import ops
+    g = _gen(300 + D + B)
+    R = B * rps
+    kept = torch.rand(B, generator=g, device="cuda") < 0.9
+    kept[:2] = torch.tensor([True, False], device="cuda")
+    for use_idx in (True, False):
+        rows = _rows_of(kept, rps) if use_idx else torch.arange(R, device="cuda")
+        Rc = rows.numel()
+        dy, xc, gamma, mean, rstd = _ln_inputs(Rc, D, g, exact)
+        d, xh, scale = _ln_ref(dy, xc, gamma, mean, rstd)
+        ldx, ldr, ldd = D + 4, D + 8, D + 12
+        x_d = _canvas(R + 1, ldx, torch.float32)
+        x_d[rows, :D] = xc.float()
+        dy_d = _canvas(Rc + 1, ldd, torch.bfloat16)
+        dy_d[:Rc, :D] = dy.bfloat16()
+        prev = _ri(-4, 4, (Rc, D), g) if exact else _randn((Rc, D), g, 0.01).float().double()
+        a0 = [(_ri(-8, 8, (D,), g) * 0.5 if exact else _randn((D,), g, 0.1).float().double()) for _ in range(2)]
+        exp_g, exp_b = a0[0] + (dy * xh).sum(0), a0[1] + dy.sum(0)
+        abs_g, abs_b = a0[0].abs() + (dy * xh).abs().sum(0), a0[1].abs() + dy.abs().sum(0)
+        if exact:
+            _exact_sums_fit(torch.stack([abs_g, abs_b]))
+        if use_idx:
+            print("layernorm_bwd D=%d R=%d row_idx (%d of %d rows) %s" % (D, Rc, Rc, R, "exact" if exact else "random"))
+        for accumulate in (1, 0):
+            dres0 = _canvas(R + 2, ldr, torch.float32)
+            if accumulate:
+                dres0[rows, :D] = prev.float()
+            acc0 = []
+            for a in a0:
+                t = _canvas(1, D + 4, torch.float32)[0]
+                t[:D] = a.float()
+                acc0.append(t)
+            dres_exp = d + prev if accumulate else d
+            sc = scale + prev.abs() if accumulate else scale
+            ref_bits = None
+            for gr in (GRIDS if (exact or use_idx) else (None,)):
+                dres, dg, db = dres0.clone(), acc0[0].clone(), acc0[1].clone()
+                with _Grid(gr):
+                    ops.layernorm_bwd(dy_d, x_d, gamma.float(), mean.float(), rstd.float(), dres, dg, db, Rc, D,
+                                      accumulate=bool(accumulate), row_idx=rows.int() if use_idx else None)
+                    torch.cuda.synchronize()
+                got = dres[rows, :D].double()
+                if exact:
+                    assert torch.equal(got, dres_exp), (accumulate, gr, "dres")
+                    assert torch.equal(dg[:D].double(), exp_g) and torch.equal(db[:D].double(), exp_b), (accumulate, gr)
+                else:
+                    _check_bar(got, dres_exp, sc, 18, "dres (acc %d, grid %s)" % (accumulate, gr))
+                    _check_bar(dg[:D], exp_g, abs_g, 14, "dgamma")
+                    _check_bar(db[:D], exp_b, abs_b, 14, "dbeta")
+                w = torch.zeros(dres.shape, dtype=torch.bool, device="cuda")
+                w[rows, :D] = True
+                assert _untouched(dres, dres0, w) == 0, "dres written outside row_idx / into ld padding"
+                for t, t0 in ((dg, acc0[0]), (db, acc0[1])):
+                    assert torch.equal(_bits(t[D:]), _bits(t0[D:]))
+                if ref_bits is None:
+                    ref_bits = _bits(dres).clone()
+                else:
+                    assert torch.equal(_bits(dres), ref_bits), (accumulate, gr)
+        del d, xh, scale
+
+
+# ------------------------------------------------------------------------------------------------ branch_bwd
+BRB_CASES = [(768, 255, 197), (1024, 63, 1201), (260, 2, 197), (768, 3, 5)]    # odd M at the step's sizes
+
+
+@pytest.mark.parametrize("D,B,rps", BRB_CASES)
+@pytest.mark.parametrize("exact", [True, False])
+def test_branch_bwd(D, B, rps, exact):
+    """memhip_branch_bwd_map: rowmask with y and gamma, y = None, gamma = None, out_map (mixed, all kept, all dropped).
+    M = B * rps is odd: the last iteration of the two-rows-per-iteration loop has one row."""
+    from mem_amd import ops
+    g = _gen(400 + D + B)
+    M = B * rps
+    keep = 0.5 if exact else 0.9
+    dx = _ri(-16, 16, (M, D), g) if exact else _randn((M, D), g, 0.01).float().double()
+    y = _ri(-2, 2, (M, D), g) * 0.5 if exact else _bf(_randn((M, D), g))
+    gam = _pow2(-1, 1, (D,), g, signed=True) if exact else (0.1 * (1 + _randn((D,), g, 0.1))).float().double()
+    rowmask = (torch.rand(B, generator=g, device="cuda") < 0.7).double()
+    rowmask[:2] = torch.tensor([1.0, 0.0], device="cuda")
+    ldx, ldy, ldo = D + 4, D + 8, D + 12
+    dx_d = _canvas(M + 1, ldx, torch.float32)
+    dx_d[:M, :D] = dx.float()
+    y_d = _canvas(M + 1, ldy, torch.bfloat16)
+    y_d[:M, :D] = y.bfloat16()
+    pats = {"mixed": torch.rand(B, generator=g, device="cuda") < 0.6, "all": torch.ones(B, dtype=torch.bool, device="cuda"),
+            "none": torch.zeros(B, dtype=torch.bool, device="cuda")}
+    pats["mixed"][:2] = torch.tensor([True, False], device="cuda")
+    modes = [("rowmask_y_gamma", True, True, "mask", None), ("plain_y", True, True, None, None),
+             ("no_y", False, True, None, None), ("no_y_no_gamma", False, False, None, None),
+             ("rowmask_no_y", False, True, "mask", None)]
+    modes += [("out_map_" + k, False, True, None, k) for k in pats] + [("out_map_no_gamma", False, False, None, "mixed")]
+    print("branch_bwd D=%d M=%d %s" % (D, M, "exact" if exact else "random"))
+    for name, has_y, has_g, mask, pat in modes:
+        kept = pats[pat] if pat else torch.ones(B, dtype=torch.bool, device="cuda")
+        rows = _rows_of(kept, rps)
+        Ro = rows.numel()
+        if mask:
+            km = rowmask.repeat_interleave(rps)[:, None]
+            dt = dx * km / keep
+        elif pat:
+            dt = dx / keep
+        else:
+            dt = dx
+        dt = dt[rows]
+        gv = gam if has_g else torch.ones(D, dtype=torch.float64, device="cuda")
+        exp_dy = dt * gv
+        a0 = [_ri(-8, 8, (D,), g) * 0.5 if exact else _randn((D,), g, 0.1).float().double() for _ in range(2)]
+        acc0 = []
+        for a in a0:
+            t = _canvas(1, D + 4, torch.float32)[0]
+            t[:D] = a.float()
+            acc0.append(t)
+        dyo0 = _canvas(Ro + 2, ldo, torch.bfloat16)
+        dyo, dg, db = dyo0.clone(), acc0[0].clone(), acc0[1].clone()
+        ops.branch_bwd(dx_d, y_d if has_y else None, gam.float() if has_g else None, dyo, dg if has_y else None, db, M, D,
+                       rowmask=rowmask.float() if mask else None, keep_prob=keep if (mask or pat) else 1.0,
+                       rows_per_sample=rps, out_map=_cmap(kept) if pat else None)
+        torch.cuda.synchronize()
+        got = dyo[:Ro, :D].double()
+        own = a0[1] + got.sum(0)
+        if exact:
+            _exact_sums_fit(a0[1].abs() + exp_dy.abs().sum(0), unit=0.5)
+            if has_y:
+                _exact_sums_fit((dt * y[rows]).abs().sum(0) + a0[0].abs())
+            assert torch.equal(got, exp_dy), name
+            if has_y:
+                assert torch.equal(dg[:D].double(), a0[0] + (dt * y[rows]).sum(0)), name
+            assert torch.equal(db[:D].double(), own), name
+        else:
+            _check_bf16(got, exp_dy, exp_dy.abs() * 2.0 ** -22, name + " dy")
+            if has_y:
+                _check_bar(dg[:D], a0[0] + (dt * y[rows]).sum(0), a0[0].abs() + (dt * y[rows]).abs().sum(0), 14,
+                           name + " dgamma")
+            _check_bar(db[:D], own, a0[1].abs() + got.abs().sum(0), 14, name + " dbias")
+        w = torch.zeros(dyo.shape, dtype=torch.bool, device="cuda")
+        w[:Ro, :D] = True
+        assert _untouched(dyo, dyo0, w) == 0, (name, "dy written past the kept rows / into ld padding")
+        if not has_y:
+            assert torch.equal(_bits(dg), _bits(acc0[0])), name
+        for t, t0 in ((dg, acc0[0]), (db, acc0[1])):
+            assert torch.equal(_bits(t[D:]), _bits(t0[D:])), name
+
+
+# ------------------------------------------------------------------------------------------------ layerscale_grad
+LSG_CASES = [(768, 768), (768, 3072), (3072, 768), (1024, 4096), (1024, 8192), (770, 8192), (770, 768), (1024, 1024)]
+
+
+@pytest.mark.parametrize("N,K", LSG_CASES)
+def test_layerscale_grad(N, K):
+    """dgamma = (sum_k W dW + b db) / gamma: exact layout (bit-equal) and random values (within 2^-16 of
+    (sum |W dW| + |b db|) / |gamma|), bias present or not, gamma < 0 and gamma = 1e-5 included.  K > 4096 runs the k0 loop;
+    N % 4 != 0 leaves a partial workgroup."""
+    from mem_amd import ops
+    g = _gen(500 + N + K)
+    for exact in (True, False):
+        ldw, lddw = K + 8, K + 4
+        if exact:
+            W, dW = _ri(-8, 8, (N, K), g), _ri(-8, 8, (N, K), g) * 0.25
+            b, db = _ri(-8, 8, (N,), g) * 0.5, _ri(-8, 8, (N,), g) * 0.25
+            gam = _pow2(-17, 1, (N,), g, signed=True)
+        else:
+            W, dW = _bf(_randn((N, K), g, 0.02)), _randn((N, K), g, 1e-3).float().double()
+            b, db = _randn((N,), g, 0.02).float().double(), _randn((N,), g, 0.05).float().double()
+            gam = (0.1 * _randn((N,), g)).float().double()
+            gam[: N // 4] = 1e-5 * (1 + 0.1 * _randn((N // 4,), g)).float().double()
+        W_d = _canvas(N, ldw, torch.bfloat16)
+        W_d[:, :K] = W.bfloat16()
+        dW_d = _canvas(N, lddw, torch.float32)
+        dW_d[:, :K] = dW.float()
+        for with_bias in (True, False):
+            t = (W * dW).sum(1) + (b * db if with_bias else 0.0)
+            tabs = (W * dW).abs().sum(1) + ((b * db).abs() if with_bias else 0.0)
+            out = _canvas(1, N + 4, torch.float32)[0]
+            out0 = out.clone()
+            ops.layerscale_grad(W_d, dW_d, b.float() if with_bias else None, db.float() if with_bias else None, gam.float(),
+                                N, K, out)
+            torch.cuda.synchronize()
+            if exact:
+                _exact_sums_fit(tabs)
+                bad = torch.nonzero(out[:N].double() != t / gam).flatten()[:6]
+                assert bad.numel() == 0, (with_bias, "exact", bad.tolist(), out[bad].tolist(), t[bad].tolist(),
+                                          gam[bad].tolist(), int((out[:N].double() != t / gam).sum().item()))
+            else:
+                print("layerscale_grad N=%d K=%d bias %s" % (N, K, with_bias))
+                _check_bar(out[:N], t / gam, tabs / gam.abs(), 16, "dgamma")
+            w = torch.zeros(out.shape, dtype=torch.bool, device="cuda")
+            w[:N] = True
+            assert _untouched(out, out0, w) == 0
+
+
+def _identity_inputs(M, N, K, gamma_scale, seed):
+    """the engine's arithmetic around a layer-scale branch x += gamma * (A W^T + b): returns Σ_m dt y (float64) and the
+    kernel's inputs W (bf16), dW, db (fp32, from dY = bf16(gamma * dt))"""
+    g = torch.Generator().manual_seed(seed)
+    A = torch.randn((M, K), generator=g, dtype=torch.float64).bfloat16().double()
+    W = (torch.randn((N, K), generator=g, dtype=torch.float64) * 0.02).bfloat16().double()
+    b = (torch.randn((N,), generator=g, dtype=torch.float64) * 0.02).float().double()
+    dt = (torch.randn((M, N), generator=g, dtype=torch.float64) * 1e-3).float().double()
+    gam = (gamma_scale * (1 + 0.1 * torch.randn((N,), generator=g, dtype=torch.float64))).float().double()
+    gam[::3] *= -1
+    y = A @ W.T + b
+    dY = (dt.float() * gam.float()).bfloat16().double()            # branch_bwd: bf16(dt * gamma) in fp32
+    dW = (dY.T @ A).float().double()
+    db = dY.sum(0).float().double()
+    want = (dt * y).sum(0)
+    scale = (dt * y).abs().sum(0)
+    return W, dW, b, db, gam, want, scale
+
+
+# Measured (float64 on these inputs, gamma ~ 0.1 and ~ 1e-5): max over channels of |(<W, dW> + b db) / gamma - Σ dt y| /
+# Σ |dt y| = 1.8e-4.  The only rounding between the two forms beyond fp32 is dY = bf16(gamma dt), |ε| <= 2^-9 per element,
+# so the hard bound is 2^-9 Σ |dt y| (2.0e-3); the bar is 2^-11 = 4.9e-4, 2.7 x the measured figure.
+IDENTITY_BAR = 2.0 ** -11
+
+
+@pytest.mark.parametrize("gamma_scale", [0.1, 1e-5])
+def test_layerscale_grad_identity(gamma_scale):
+    """The kernel's dgamma = (<W, dW> + b db) / gamma with dW = dY^T A, db = Σ dY, dY = bf16(gamma dt) (the engine's rounding
+    points) against Σ_m dt y from its definition, y = A W^T + b.  The gap is the bf16 rounding of dY; see IDENTITY_BAR."""
+    from mem_amd import ops
+    M, N, K = 2048, 770, 1024
+    W, dW, b, db, gam, want, scale = _identity_inputs(M, N, K, gamma_scale, 7)
+    out = torch.zeros(N, device="cuda")
+    ops.layerscale_grad(W.bfloat16().cuda(), dW.float().cuda(), b.float().cuda(), db.float().cuda(), gam.float().cuda(), N, K, out)
+    torch.cuda.synchronize()
+    fig = float(((out.double().cpu() - want).abs() / scale).max())
+    print("layerscale identity gamma ~ %g: max |dgamma - Σ dt y| / Σ |dt y| = %.3e (bar %.3e)" % (gamma_scale, fig, IDENTITY_BAR))
+    assert fig <= IDENTITY_BAR
+
+
+def test_layerscale_grad_gamma_zero():
+    """gamma = 0 exactly: the identity cannot recover Σ dt y (dW = dY^T A is 0 when dY = gamma dt is), and the kernel writes
+    0 -- pinned here.  No reference configuration reaches it: a reference model with init_values = 0 builds no gamma at all
+    (modeling_finetune.py), and a trained gamma does not land on exactly 0."""
+    from mem_amd import ops
+    N, K = 6, 1024
+    W = torch.ones((N, K), device="cuda").bfloat16()
+    dW = torch.full((N, K), 0.5, device="cuda")
+    gam = torch.tensor([0.0, 1.0, -0.0, 2.0, 0.0, -1.0], device="cuda")
+    out = torch.full((N,), float("nan"), device="cuda")
+    ops.layerscale_grad(W, dW, None, None, gam, N, K, out)
+    torch.cuda.synchronize()
+    assert out.tolist() == [0.0, 512.0, 0.0, 256.0, 0.0, -512.0]
+
+
+# ------------------------------------------------------------------------------------------------ gemv_acc
+@pytest.mark.parametrize("N,K", [(771, 8), (770, 520), (768, 768), (1023, 1024), (769, 4096), (3, 4096)])
+def test_gemv_acc(N, K):
+    """y[N] += W x; x_acc[K] += x exactly once (not once per workgroup); zero[K] = 0; nothing past N / K is written."""
+    from mem_amd import ops
+    g = _gen(600 + N + K)
+    for exact in (True, False):
+        W = _ri(-8, 8, (N, K), g) if exact else _bf(_randn((N, K), g, 0.02))
+        x = _ri(-8, 8, (K,), g) * 0.25 if exact else _randn((K,), g).float().double()
+        y0 = _ri(-8, 8, (N,), g) if exact else _randn((N,), g).float().double()
+        xa0 = _ri(-8, 8, (K,), g) if exact else _randn((K,), g).float().double()
+        W_d = _canvas(N, K + 8, torch.bfloat16)
+        W_d[:, :K] = W.bfloat16()
+        y = _canvas(1, N + 4, torch.float32)[0]
+        y[:N] = y0.float()
+        xa = _canvas(1, K + 4, torch.float32)[0]
+        xa[:K] = xa0.float()
+        zero = _canvas(1, K + 4, torch.float32)[0]
+        zero[:K] = 3.0
+        b0 = (y.clone(), xa.clone(), zero.clone())
+        ops.gemv_acc(W_d, N, K, x.float(), y, x_acc=xa, zero=zero)
+        torch.cuda.synchronize()
+        want = y0 + W @ x
+        if exact:
+            _exact_sums_fit(y0.abs() + W.abs() @ x.abs())
+            assert torch.equal(y[:N].double(), want)
+        else:
+            print("gemv_acc N=%d K=%d" % (N, K))
+            _check_bar(y[:N], want, y0.abs() + W.abs() @ x.abs(), 16, "y")
+        assert torch.equal(xa[:K].double(), (xa0.float() + x.float()).double()), "x_acc must be added exactly once"
+        assert torch.equal(zero[:K], torch.zeros(K, device="cuda"))
+        for t, t0, n in ((y, b0[0], N), (xa, b0[1], K), (zero, b0[2], K)):
+            assert torch.equal(_bits(t[n:]), _bits(t0[n:]))
+
+
+# ------------------------------------------------------------------------------------------------ embed_bwd
+@pytest.mark.parametrize("B,L,D", [(256, 196, 768), (129, 1200, 1024), (200, 9, 768), (2, 1200, 1024), (2, 9, 1024),
+                                   (129, 196, 768)])
+def test_embed_bwd(B, L, D):
+    """dcls += Σ_b dx[cls row]; dmask_token += Σ dx w; dy = bf16(dx (1 - w)).  B >= 128: several samples per workgroup;
+    L = 196 = 28 x 7 never reaches the unroll tail, 1200 and 9 do."""
+    from mem_amd import ops
+    g = _gen(700 + B + L + D)
+    T = L + 1
+    mask = torch.rand((B, L), generator=g, device="cuda") < 0.75
+    w = mask.double()[..., None]
+    for exact in (True, False):
+        dx = _ri(-64, 64, (B, T, D), g) if exact else _randn((B, T, D), g, 0.01).float().double()
+        dx_d = _canvas(B * T, D + 4, torch.float32)
+        dx_d[:, :D] = dx.view(B * T, D).float()
+        dy0 = _canvas(B * L + 1, D + 8, torch.bfloat16)
+        c0 = [_ri(-8, 8, (D,), g) if exact else _randn((D,), g).float().double() for _ in range(2)]
+        cls0, msk0 = _canvas(1, D + 4, torch.float32)[0], _canvas(1, D + 4, torch.float32)[0]
+        cls0[:D], msk0[:D] = c0[0].float(), c0[1].float()
+        dy, dcls, dmt = dy0.clone(), cls0.clone(), msk0.clone()
+        ops.embed_bwd(dx_d, mask.to(torch.uint8).flatten().contiguous(), B, L, D, dy, dcls, dmt)
+        torch.cuda.synchronize()
+        p = dx[:, 1:]
+        want_dy = (p * (1 - w)).reshape(B * L, D)
+        want_cls, want_m = c0[0] + dx[:, 0].sum(0), c0[1] + (p * w).sum((0, 1))
+        assert torch.equal(dy[:B * L, :D].double(), _bf(want_dy)), "dy"   # one rounding of an exact product
+        if exact:
+            _exact_sums_fit(torch.stack([dx[:, 0].abs().sum(0), (p * w).abs().sum((0, 1))]), unit=1.0)
+            assert torch.equal(dcls[:D].double(), want_cls) and torch.equal(dmt[:D].double(), want_m)
+        else:
+            print("embed_bwd B=%d L=%d D=%d" % (B, L, D))
+            _check_bar(dcls[:D], want_cls, c0[0].abs() + dx[:, 0].abs().sum(0), 14, "dcls")
+            _check_bar(dmt[:D], want_m, c0[1].abs() + (p * w).abs().sum((0, 1)), 14, "dmask_token")
+        wr = torch.zeros(dy.shape, dtype=torch.bool, device="cuda")
+        wr[:B * L, :D] = True
+        assert _untouched(dy, dy0, wr) == 0
+        assert torch.equal(_bits(dcls[D:]), _bits(cls0[D:])) and torch.equal(_bits(dmt[D:]), _bits(msk0[D:]))
+        del dx, dx_d, p, want_dy
+
+
+# ------------------------------------------------------------------------------------------------ cross_entropy
+def test_cross_entropy_step_size():
+    """M = 25 088 masked tokens (256 x 98), V = 8192: row_correct exact against a float64 argmax (one planted maximum per
+    row, no ties), the reduction's mean loss within 1e-7 of the float64 mean of the kernel's own row losses (it reduces in
+    double), accuracy = the exact count / M, row losses within 2e-5 of float64 (fast exp / log in fp32)."""
+    from mem_amd import ops
+    M, V = 25088, 8192
+    g = _gen(800)
+    lg = _randn((M, V), g, 2.0).clamp(-8, 7.9).bfloat16()
+    top = torch.randint(0, V, (M,), generator=g, device="cuda")
+    lg[torch.arange(M, device="cuda"), top] = (8.0 + _ri(0, 8, (M,), g) * 0.5).bfloat16()
+    labels = torch.randint(0, V, (M,), generator=g, device="cuda")
+    hit = torch.rand(M, generator=g, device="cuda") < 0.3
+    labels[hit] = top[hit]
+    l64 = lg.double()
+    am = l64.argmax(1)
+    assert torch.equal(am, top)
+    want_loss = torch.logsumexp(l64, 1) - l64.gather(1, labels[:, None])[:, 0]
+    row_loss, row_correct = torch.zeros(M, device="cuda"), torch.zeros(M, dtype=torch.int32, device="cuda")
+    out2 = torch.zeros(2, device="cuda")
+    work = lg.clone()
+    ops.cross_entropy(work, labels, M, V, 1.0 / M, row_loss, row_correct, out2)
+    torch.cuda.synchronize()
+    k = int((am == labels).sum().item())
+    assert torch.equal(row_correct.long(), (am == labels).long())
+    mean_own = row_loss.double().mean()
+    rel = abs(out2[0].double() - mean_own).item() / mean_own.item()
+    fig = (row_loss.double() - want_loss).abs().max().item()
+    print("cross_entropy M=%d V=%d: mean loss rel %.2e (bar 1e-7), row loss max |err| %.2e (bar 2e-5), correct %d"
+          % (M, V, rel, fig, k))
+    assert rel <= 1e-7
+    assert out2[1].item() == (torch.tensor(float(k)) / torch.tensor(float(M))).item()
+    assert fig <= 2e-5
+
+
+# ------------------------------------------------------------------------------------------------ copy_samples, zero_ranges
+def test_copy_samples():
+    """dst[id] = src[id] for the listed samples (out of order), every other sample bit-unchanged."""
+    from mem_amd import ops
+    g = _gen(900)
+    B, n = 40, 197 * 768                                   # 64 workgroups per sample, each loops
+    src = _randn((B, n), g).float()
+    dst0 = _canvas(B + 1, n, torch.float32)
+    ids = torch.tensor([17, 3, 39, 4, 0, 22, 5], dtype=torch.int32, device="cuda")
+    dst = dst0.clone()
+    ops.copy_samples(src, dst, ids, ids.numel(), n)
+    torch.cuda.synchronize()
+    w = torch.zeros(dst.shape, dtype=torch.bool, device="cuda")
+    w[ids.long()] = True
+    assert torch.equal(_bits(dst[ids.long()]), _bits(src[ids.long()]))
+    assert _untouched(dst, dst0, w) == 0
+
+
+def test_zero_ranges():
+    """Ranges out of order, adjacent ranges, a 16-byte range, more than 1024 x 256 x 16 bytes in all (every workgroup loops):
+    the ranges are zero, every byte between them is unchanged."""
+    from mem_amd import ops
+    nbytes = 12 << 20
+    base = _canvas(1, nbytes // 4, torch.float32)[0]
+    rngs = [(5 << 20, 3 << 20), (16, 16), (4096, 1 << 20), (4096 + (1 << 20), 8192), (64, 4016), (9 << 20, 16),
+            ((9 << 20) + 48, 2 << 20), ((11 << 20) + 64, (1 << 20) - 96)]
+    total = sum(c for _, c in rngs)
+    assert total > 1024 * 256 * 16
+    r = torch.tensor(rngs, dtype=torch.int64, device="cuda").flatten()
+    buf = base.clone()
+    ops.zero_ranges(buf, r, len(rngs), total)
+    torch.cuda.synchronize()
+    w = torch.zeros(buf.shape, dtype=torch.bool, device="cuda")
+    for o, c in rngs:
+        w[o // 4:(o + c) // 4] = True
+    assert int((_bits(buf)[w] != 0).sum().item()) == 0, "a range was not zeroed"
+    assert _untouched(buf, base, w) == 0, "bytes between ranges changed"
+
+
+# ------------------------------------------------------------------------------------------------ refusals
+def test_refusals_do_not_launch():
+    """Arguments the kernels cannot handle are refused through check() before any launch (outputs untouched)."""
+    from mem_amd import _lib, ops
+    D, B, rps = 1028, 2, 5
+    R = B * rps
+    x, dres = torch.zeros((R, D), device="cuda"), _canvas(R, D, torch.float32)
+    dy, dyo = torch.zeros((R, D), device="cuda").bfloat16(), _canvas(R, D, torch.bfloat16)
+    v = torch.zeros(D, device="cuda")
+    acc = _canvas(1, D, torch.float32)[0]
+    keep = torch.ones(B, device="cuda")
+    cm = torch.arange(B, dtype=torch.int32, device="cuda")
+    snap = [_bits(t).clone() for t in (dres, dyo, acc)]
+    with pytest.raises(_lib.MemhipError, match="unsupported"):
+        ops.layernorm_bwd_branch(dy, x, v, v, v, dres, acc, acc, R, D, None, None, dyo, None, acc, rows_per_sample=rps)
+    Dk = 768
+    with pytest.raises(_lib.MemhipError, match="sample maps"):
+        ops.layernorm_bwd_branch(dy, x, v, v, v, dres, acc, acc, R, Dk, None, None, dyo, None, acc, rowmask=keep,
+                                 keep_prob=0.5, rows_per_sample=rps, in_map=cm, out_map=cm)
+    with pytest.raises(_lib.MemhipError, match="sample maps"):
+        ops.layernorm_bwd_branch(dy, x, v, v, v, dres, acc, acc, R, Dk, None, None, dyo, None, acc, rowmask=keep,
+                                 keep_prob=0.5, rows_per_sample=rps, out_map=cm)
+    W = torch.zeros((4, 520), device="cuda").bfloat16()
+    with pytest.raises(_lib.MemhipError, match="multiples of 8"):
+        ops.gemv_acc(W, 4, 516, v, acc, x_acc=acc, zero=acc)
+    torch.cuda.synchronize()
+    for t, s in zip((dres, dyo, acc), snap):
+        assert torch.equal(_bits(t), s)
