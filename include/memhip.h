@@ -35,7 +35,8 @@
 extern "C" {
 #endif
 
-#define MEMHIP_ABI_VERSION 5   /* 5 (round 6): memhip_build_flags, memhip_attn_bwd_ws / _out_ws / _workspace; 4 (round 5): epilogues 6 / 7 carry the stored GELU derivative as FP16 (since round 4), certified-tokenizer entry points */
+#define MEMHIP_ABI_VERSION 6   /* 6: element-wise dropout (memhip_dropout_t, epilogue RESIDUAL_DROP, memhip_gemm_args_t.dropout, the
+                                  *_drop row kernels); 5 (round 6): memhip_build_flags, memhip_attn_bwd_ws / _out_ws / _workspace; 4 (round 5): epilogues 6 / 7 carry the stored GELU derivative as FP16 (since round 4), certified-tokenizer entry points */
 
 #define MEMHIP_OK 0
 #define MEMHIP_EINVAL (-1)   /* bad argument (shape / alignment / null) */
@@ -290,6 +291,42 @@ int memhip_mask_random_location(uint32_t* mt_state, int H, int W, int num_maskin
                                     gelu' lies in [-0.13, 1.13]) instead of h: the GELU backward then is a plain product
                                     (MUL_AUX) -- erf/exp are evaluated once, in the forward epilogue */
 #define MEMHIP_EPI_MUL_AUX 7     /* out0 bf16 = bf16(acc) * aux fp16  (+ colsum)               (GELU backward with stored gelu') */
+#define MEMHIP_EPI_RESIDUAL_DROP 8 /* RESIDUAL with element-wise dropout of the branch (proj_drop / Mlp.drop, mem/modeling_finetune.py:
+                                    70,155,185-188): y = bf16(acc + bias); z = fp32(y * keep * scale) (one fp32 rounding;
+                                    keep = 0 gives +-0); then exactly RESIDUAL's arithmetic with z for y: gamma * z (own rounding),
+                                    drop path (/ keep_prob, * rowmask), + residual input.  `dropout` must be non-NULL, out0 NULL.
+                                    The mask row is the residual-stream row that the RESIDUAL epilogue resolves (sample_map
+                                    included) + dropout->row0; see memhip_dropout_t. */
+
+/* ------------------------------------------------------------------------
+ * Element-wise dropout (nn.Dropout, p = drop_rate of the finetuning model; mem/modeling_finetune.py:64,70,125-126,155,271,343)
+ * ------------------------------------------------------------------------
+ * THE MASK CONTRACT.  An element is (site, row, col):
+ *   row   the row of the fp32 residual stream, sample * T + token, counted with the ORIGINAL sample index (never a compact
+ *         work-skipping index or a row of a split half): masks do not depend on work skipping, stream splits or b0 / b1.
+ *         A call that addresses a buffer whose row 0 is residual-stream row r0 passes row0 = r0.
+ *   col   in [0, D), D a multiple of 8.
+ *   site  block i's attention branch 2i, its MLP branch 2i + 1, pos_drop 2 * depth.
+ * One Philox4x32-10 call per 8 columns: key = (key0, key1), counter = (row, col / 8, site, 0).  Column 8 * (col / 8) + j takes
+ * the 16-bit half (j & 1) of output word (j >> 1), low half first; the element is KEPT iff that half >= thr = round(p * 65536),
+ * and a kept value is multiplied by scale = 1 / (1 - p) (torch's scale).  The keep rate is 1 - thr / 65536 (within 7.6e-6
+ * of 1 - p).  0 <= p < 1; p = 0 (thr = 0) keeps everything.  The masks follow nn.Dropout's law, not torch's stream.
+ * Every kernel below that takes a memhip_dropout_t and memhip_dropout_mask compute the bits with the same device function.
+ * The struct is read on the HOST at the call (its values become kernel arguments); NULL = no dropout where allowed. */
+typedef struct memhip_dropout {
+  uint32_t key0, key1;   /* per-step key */
+  uint32_t site;
+  uint32_t thr;          /* round(p * 65536) */
+  float scale;           /* 1 / (1 - p) */
+  int32_t row0;          /* residual-stream row of row 0 of the addressed buffer */
+} memhip_dropout_t;
+/* out u8 [rows, cols] = keep bit (0/1) of rows row0 .. row0 + rows - 1 (the struct's row0 is added), columns 0 .. cols - 1
+ * (cols % 8 == 0).  For tests and inspection; not on the training step. */
+int memhip_dropout_mask(const memhip_dropout_t* d, int row0, int rows, int cols, uint8_t* out, memhip_stream_t stream);
+/* x f32 [rows, D] (ld ldx) *= keep * scale in place, rows = residual-stream rows row0 .. (pos_drop after the position
+ * embedding, mem/modeling_finetune.py:343; its backward applies the same mask to the gradient). */
+int memhip_dropout_rows_f32(const memhip_dropout_t* d, float* x, int64_t ldx, int rows, int D, memhip_stream_t stream);
+
 typedef struct memhip_gemm_args {
   const void* A; const void* B;
   int64_t lda, ldb;
@@ -320,6 +357,8 @@ typedef struct memhip_gemm_args {
                              +27 us on the 3072-wide GELU' GEMM, +100 us on a 768 x 768 one).  Fold the copies with
                              memhip_colsum_fold.  0 / 1: a single accumulator (the bias gradient itself). */
   int32_t reserved0;
+  const memhip_dropout_t* dropout;  /* RESIDUAL_DROP: the branch's dropout (HOST struct, read at the call); other epilogues:
+                                       must be NULL (ABI 6) */
 } memhip_gemm_args_t;
 int memhip_gemm_bf16_nt(const memhip_gemm_args_t* args, memhip_stream_t stream);
 
@@ -395,6 +434,8 @@ int memhip_layernorm_bwd(const void* dy_bf16, int64_t lddy, const float* x, int6
 /* Layer-scale gradient from the weight gradient of the Linear that produced the branch:
  *   dgamma[c] = (sum_k W[c,k] * dW[c,k] + bias[c] * dbias[c]) / gamma[c]      (0 where gamma[c] == 0)
  * (x += gamma * y with y = A W^T + b: sum_m dt*y = sum_m dY*y / gamma and dW = dY^T A, dbias = colsum dY), so the
+ * identity also holds with dropout of the branch: with z = keep * scale * y, dgamma = sum_m dt*z and dY = dt*gamma*keep*scale,
+ * so sum_m dY*y = gamma * sum_m dt*z on both sides alike.  The
  * forward does not store y and memhip_branch_bwd / memhip_layernorm_bwd_branch run with y = NULL, dgamma = NULL.
  * W bf16 [N, ldw] (the operand the forward used), dW / dbias f32 = the gradients accumulated so far;
  * dgamma is OVERWRITTEN (it is a function of the accumulated dW). */
@@ -437,6 +478,21 @@ int memhip_layernorm_bwd_branch_map(const void* dy_bf16, int64_t lddy, const flo
                                     int rows_per_sample, void* dy_branch_bf16, int64_t lddyb, float* dgamma_branch,
                                     float* dbias_branch, const int32_t* in_map, const int32_t* out_map,
                                     memhip_stream_t stream);
+/* The two _map calls for a branch with element-wise dropout (epilogue RESIDUAL_DROP in the forward): the branch gradient
+ * becomes dy = bf16(dt * keep * scale * gamma) (dt after drop path as above; dt * keep * scale rounded once in fp32, then
+ * * gamma), dbias += sum dy, and dgamma (when y is given) += sum dt * keep * scale * y.  The mask of the branch's site is
+ * regenerated (memhip_dropout_t, row = residual-stream row + row0); `dropout` must not be NULL. */
+int memhip_branch_bwd_drop(const float* dx, int64_t lddx, const void* y_bf16, int64_t ldy, const float* gamma,
+                           const float* rowmask, float keep_prob, int rows_per_sample, int M, int D,
+                           void* dy_bf16, int64_t lddy, float* dgamma, float* dbias, const int32_t* out_map,
+                           const memhip_dropout_t* dropout, memhip_stream_t stream);
+int memhip_layernorm_bwd_branch_drop(const void* dy_bf16, int64_t lddy, const float* x, int64_t ldx, int R, int D,
+                                     const float* gamma, const float* mean, const float* rstd, float* dres,
+                                     int64_t lddres, float* dgamma, float* dbeta, const void* y_branch_bf16, int64_t ldyb,
+                                     const float* gamma_branch, const float* rowmask, float keep_prob,
+                                     int rows_per_sample, void* dy_branch_bf16, int64_t lddyb, float* dgamma_branch,
+                                     float* dbias_branch, const int32_t* in_map, const int32_t* out_map,
+                                     const memhip_dropout_t* dropout, memhip_stream_t stream);
 
 /* Backward of the token assembly (mem/modeling_pretrain.py:101-108): dcls += dx[cls rows],
  * dmask_token += sum dx*w, dy bf16 [B*L, D] = bf16(dx*(1-w)); mask u8 [B*L]. */

@@ -436,7 +436,8 @@ extern "C" int memhip_f32_gemm_nt(const memhip_gemm_args_t* a, memhip_stream_t s
   MEMHIP_REQUIRE(a, "gemm_f32: null args");
   GemmArgs p;
   __builtin_memset(&p, 0, sizeof(p));
-  __builtin_memcpy(&p, a, sizeof(memhip_gemm_args_t));
+  __builtin_memcpy(&p, a, offsetof(memhip_gemm_args_t, dropout));
+  if (a->dropout) return fail(MEMHIP_EUNSUPPORTED, "gemm_f32: dropout is not part of the fp32 parity path");
   MEMHIP_REQUIRE(p.M >= 0 && p.N > 0 && p.K > 0, "gemm_f32: bad shape M=%d N=%d K=%d", p.M, p.N, p.K);
   if (p.M == 0) return MEMHIP_OK;
   MEMHIP_REQUIRE(p.A && p.B && p.K % 4 == 0 && p.lda % 4 == 0 && p.ldb % 4 == 0 && ((uintptr_t)p.A & 15) == 0 &&

@@ -53,7 +53,7 @@ __device__ __forceinline__ void stage_tile(const __bf16* __restrict__ src, long 
 }
 
 template <int EPI>
-__global__ __launch_bounds__(kThreads, 2) void gemm_nt_kernel(GemmArgs p) {
+__global__ __launch_bounds__(kThreads, 2) void gemm_nt_kernel(typename EpiArgs<EPI>::type p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -180,7 +180,9 @@ int launch(const GemmArgs& p, hipStream_t s) {
     if (e != hipSuccess) return fail(MEMHIP_ELAUNCH, "gemm: set smem attr: %s", hipGetErrorString(e));
     attr_done = true;
   }
-  hipLaunchKernelGGL(gemm_nt_kernel<EPI>, dim3(ntm * ntn), dim3(kThreads), 2 * kStageBytes, s, p);
+  // (the dropout epilogue's kernel takes a GemmArgsD: the dispatcher's arguments are one)
+  hipLaunchKernelGGL(gemm_nt_kernel<EPI>, dim3(ntm * ntn), dim3(kThreads), 2 * kStageBytes, s,
+                     static_cast<const typename EpiArgs<EPI>::type&>(p));
   return check_launch("gemm_bf16_nt");
 }
 
@@ -196,11 +198,11 @@ int gemm_p8_pair_dispatch(const GemmArgs& head, const GemmArgs& tail, hipStream_
 
 extern "C" int memhip_gemm_bf16_nt(const memhip_gemm_args_t* a, memhip_stream_t stream) {
   MEMHIP_REQUIRE(a, "gemm: null args");
-  GemmArgs p;
-  static_assert(sizeof(GemmArgs) >= sizeof(memhip_gemm_args_t) && offsetof(GemmArgs, m_base) >= sizeof(memhip_gemm_args_t) - 8,
-                "GemmArgs = ABI struct + internal tail");
+  GemmArgsD p;     // (a GemmArgsD all the way down: the RESIDUAL_DROP launchers read its dropout parameters)
+  static_assert(offsetof(GemmArgs, m_base) == offsetof(memhip_gemm_args_t, dropout),
+                "GemmArgs = the ABI struct up to `dropout` + internal tail");
   __builtin_memset(&p, 0, sizeof(p));
-  __builtin_memcpy(&p, a, sizeof(memhip_gemm_args_t));
+  __builtin_memcpy(&p, a, offsetof(memhip_gemm_args_t, dropout));
   MEMHIP_REQUIRE(p.M >= 0 && p.N > 0 && p.K > 0, "gemm: bad shape M=%d N=%d K=%d", p.M, p.N, p.K);
   if (p.M == 0) return MEMHIP_OK;
   MEMHIP_REQUIRE(p.K % BK == 0, "gemm: K=%d must be a multiple of %d", p.K, BK);
@@ -220,8 +222,17 @@ extern "C" int memhip_gemm_bf16_nt(const memhip_gemm_args_t* a, memhip_stream_t 
     case MEMHIP_EPI_MUL_AUX: MEMHIP_REQUIRE(p.out0 && p.aux, "gemm: mul_aux args"); break;
     case MEMHIP_EPI_F32: MEMHIP_REQUIRE(p.out0, "gemm: out0"); break;
     case MEMHIP_EPI_PATCH_EMBED: MEMHIP_REQUIRE(p.resid && p.vec1 && p.aux, "gemm: patch args"); break;
+    case MEMHIP_EPI_RESIDUAL_DROP:
+      MEMHIP_REQUIRE(p.resid && a->dropout, "gemm: residual-dropout args (resid, dropout)");
+      MEMHIP_REQUIRE(!p.out0, "gemm: the residual-dropout epilogue writes no bf16 branch copy (out0 must be NULL)");
+      MEMHIP_REQUIRE(p.N % 8 == 0, "gemm: residual-dropout epilogue needs N %% 8 == 0 (N=%d)", p.N);
+      MEMHIP_REQUIRE(!p.sample_map || (!p.rowmask && p.rows_per_sample > 0), "gemm: sample_map excludes rowmask");
+      p.drop = drop_params(*a->dropout);
+      break;
     default: return fail(MEMHIP_EINVAL, "gemm: unknown epilogue %d", p.epilogue);
   }
+  MEMHIP_REQUIRE(!a->dropout || p.epilogue == MEMHIP_EPI_RESIDUAL_DROP, "gemm: dropout is taken by epilogue %d only",
+                 MEMHIP_EPI_RESIDUAL_DROP);
   // large token-dimension products: the phase-interleaved persistent kernel (gemm_p8.hip); the lockstep 256x256
   // kernel (gemm256.hip) takes shapes it does not (K a multiple of 64 but not of 128, or MEMHIP_GEMM_P8=0)
   const bool k256_on = opt(OPT_GEMM256) != 0;
@@ -234,8 +245,8 @@ extern "C" int memhip_gemm_bf16_nt(const memhip_gemm_args_t* a, memhip_stream_t 
     const bool split_on = opt(OPT_GEMM_SPLIT) != 0;
     const int split = split_on ? gemm_p8_split_rows(p, s) : 0;
     if (split > 0 && split < p.M && p.epilogue != MEMHIP_EPI_PATCH_EMBED) {
-      const GemmArgs whole = p;
-      GemmArgs head = p;
+      const GemmArgsD whole = p;
+      GemmArgsD head = p;
       head.M = split;
       {
         const long long r = split;
@@ -244,8 +255,8 @@ extern "C" int memhip_gemm_bf16_nt(const memhip_gemm_args_t* a, memhip_stream_t 
         if (p.out1) p.out1 = (char*)p.out1 + r * p.ldo1 * 2;
         // (with a sample map the residual rows are addressed through the map: resid / aux stay where they are)
         if (p.resid && !p.sample_map) p.resid += r * p.ldr;
-        if (p.aux && !(p.sample_map && p.epilogue == MEMHIP_EPI_RESIDUAL))
-          p.aux = (const char*)p.aux + r * p.ldaux * (p.epilogue == MEMHIP_EPI_RESIDUAL ? 4 : 2);
+        if (p.aux && !(p.sample_map && epi_resid(p.epilogue)))
+          p.aux = (const char*)p.aux + r * p.ldaux * (epi_resid(p.epilogue) ? 4 : 2);
         p.M -= split;
         p.m_base = split;
       }
@@ -269,6 +280,7 @@ extern "C" int memhip_gemm_bf16_nt(const memhip_gemm_args_t* a, memhip_stream_t 
           case MEMHIP_EPI_DGELU: return launch<MEMHIP_EPI_DGELU>(p, s);
           case MEMHIP_EPI_BIAS_GELU_DG: return launch<MEMHIP_EPI_BIAS_GELU_DG>(p, s);
           case MEMHIP_EPI_MUL_AUX: return launch<MEMHIP_EPI_MUL_AUX>(p, s);
+          case MEMHIP_EPI_RESIDUAL_DROP: return launch<MEMHIP_EPI_RESIDUAL_DROP>(p, s);
           default: return launch<MEMHIP_EPI_F32>(p, s);
         }
       }
@@ -292,6 +304,7 @@ extern "C" int memhip_gemm_bf16_nt(const memhip_gemm_args_t* a, memhip_stream_t 
     case MEMHIP_EPI_MUL_AUX: return launch<MEMHIP_EPI_MUL_AUX>(p, s);
     case MEMHIP_EPI_F32: MEMHIP_REQUIRE(p.out0, "gemm: out0"); return launch<MEMHIP_EPI_F32>(p, s);
     case MEMHIP_EPI_PATCH_EMBED: MEMHIP_REQUIRE(p.resid && p.vec1 && p.aux, "gemm: patch args"); return launch<MEMHIP_EPI_PATCH_EMBED>(p, s);
+    case MEMHIP_EPI_RESIDUAL_DROP: return launch<MEMHIP_EPI_RESIDUAL_DROP>(p, s);
     default: return fail(MEMHIP_EINVAL, "gemm: unknown epilogue %d", p.epilogue);
   }
 }

@@ -40,7 +40,7 @@ __device__ __forceinline__ void glds16(const void* gsrc, void* lds_dst) {
 }
 
 template <int EPI>
-__global__ __launch_bounds__(kThreads) void gemm256_kernel(GemmArgs p, int ntm, int ntn) {
+__global__ __launch_bounds__(kThreads) void gemm256_kernel(typename EpiArgs<EPI>::type p, int ntm, int ntn) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -178,7 +178,9 @@ int launch256(const GemmArgs& p, hipStream_t s, int num_cu) {
     attr_done = true;
   }
   const int grid = ntm * ntn < num_cu ? ntm * ntn : num_cu;
-  hipLaunchKernelGGL(gemm256_kernel<EPI>, dim3(grid), dim3(kThreads), kSlots * kStage, s, p, ntm, ntn);
+  // (the dropout epilogue's kernel takes a GemmArgsD: the dispatcher's arguments are one)
+  hipLaunchKernelGGL(gemm256_kernel<EPI>, dim3(grid), dim3(kThreads), kSlots * kStage, s,
+                     static_cast<const typename EpiArgs<EPI>::type&>(p), ntm, ntn);
   return check_launch("gemm_bf16_nt(256)");
 }
 
@@ -205,6 +207,7 @@ int gemm256_dispatch(const GemmArgs& p, hipStream_t s) {
     case MEMHIP_EPI_BIAS_BF16: return launch256<MEMHIP_EPI_BIAS_BF16>(p, s, num_cu);
     case MEMHIP_EPI_BIAS_GELU: return launch256<MEMHIP_EPI_BIAS_GELU>(p, s, num_cu);
     case MEMHIP_EPI_RESIDUAL: return launch256<MEMHIP_EPI_RESIDUAL>(p, s, num_cu);
+    case MEMHIP_EPI_RESIDUAL_DROP: return launch256<MEMHIP_EPI_RESIDUAL_DROP>(p, s, num_cu);
     case MEMHIP_EPI_DGELU: return launch256<MEMHIP_EPI_DGELU>(p, s, num_cu);
     case MEMHIP_EPI_F32: return launch256<MEMHIP_EPI_F32>(p, s, num_cu);
     default: return MEMHIP_EUNSUPPORTED;

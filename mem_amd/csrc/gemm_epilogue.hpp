@@ -3,6 +3,7 @@
 // residual stream / layer-scale / mask-token arithmetic that follows runs in fp32.
 #pragma once
 #include "common.h"
+#include "dropout.hpp"
 
 namespace memhip {
 
@@ -29,6 +30,25 @@ struct GemmArgs {   // memhip_gemm_args_t, followed by launcher-internal fields
   int m_base;      // row offset of this launch inside the caller's problem (a GEMM may be launched in two
                    // row ranges): only the per-sample row mask index needs the absolute row
 };
+
+// The arguments of a RESIDUAL_DROP launch: the kernels of that epilogue take this type, every other instantiation keeps
+// GemmArgs (the kernel arguments -- and the code -- of the existing launches do not change).  The launchers carry a
+// GemmArgsD throughout; code of the dropout epilogue reads the parameters through drop_of.
+struct GemmArgsD : GemmArgs {
+  DropParams drop;
+};
+__host__ __device__ __forceinline__ const DropParams& drop_of(const GemmArgs& p) { return static_cast<const GemmArgsD&>(p).drop; }
+
+constexpr bool epi_resid(int e) { return e == MEMHIP_EPI_RESIDUAL || e == MEMHIP_EPI_RESIDUAL_DROP; }
+// the kernel-argument type of an epilogue's instantiation
+template <int EPI> struct EpiArgs { typedef GemmArgs type; };
+template <> struct EpiArgs<MEMHIP_EPI_RESIDUAL_DROP> { typedef GemmArgsD type; };
+
+// residual-stream row of the dropout mask from the row the residual epilogue resolved (relative to resid / aux: with a
+// sample map the caller's rows, without it the rows of this launch's range, which starts m_base rows in)
+__device__ __forceinline__ unsigned drop_row(const GemmArgs& p, long long rr) {
+  return (unsigned)(drop_of(p).row0 + rr + (p.sample_map ? 0 : p.m_base));
+}
 
 __device__ __forceinline__ float bf16_round(float v) { return (float)(__bf16)v; }
 
@@ -96,6 +116,21 @@ __device__ __forceinline__ void epilogue(const GemmArgs& p, int m, int n, float 
       t = __fdiv_rn(t, p.keep_prob);
     }
     // residual input: aux (fp32, ldaux) when given, else in place
+    const float xin = p.aux ? reinterpret_cast<const float*>(p.aux)[rr * p.ldaux + n] : p.resid[rr * p.ldr + n];
+    p.resid[rr * p.ldr + n] = __fadd_rn(xin, t);
+  } else if constexpr (EPI == MEMHIP_EPI_RESIDUAL_DROP) {
+    // RESIDUAL with z = y * keep * scale in place of y (memhip.h); the mask word of the column's 8-column group
+    const __bf16 y = (__bf16)(acc + bias_n);
+    long long rr = m;
+    if (p.sample_map) {
+      const int mm = m + p.m_base, c = mm / p.rows_per_sample;
+      rr = (long long)p.sample_map[c] * p.rows_per_sample + (mm - c * p.rows_per_sample);
+    }
+    const DropParams& d = drop_of(p);
+    const float z = __fmul_rn((float)y, dropout_mul(d, dropout_keep8(d, drop_row(p, rr), (unsigned)(n >> 3)), n & 7));
+    float t = p.vec1 ? __fmul_rn(vec_n, z) : z;
+    if (p.rowmask) t = __fmul_rn(__fdiv_rn(t, p.keep_prob), p.rowmask[(m + p.m_base) / p.rows_per_sample]);
+    if (p.sample_map) t = __fdiv_rn(t, p.keep_prob);
     const float xin = p.aux ? reinterpret_cast<const float*>(p.aux)[rr * p.ldaux + n] : p.resid[rr * p.ldr + n];
     p.resid[rr * p.ldr + n] = __fadd_rn(xin, t);
   } else if constexpr (EPI == MEMHIP_EPI_DGELU) {
@@ -233,7 +268,7 @@ __device__ __forceinline__ void epi_cols_load(const GemmArgs& p, int n, EpiCols&
 #pragma unroll
     for (int k = 0; k < 4; ++k) c.bias[k] = ef32x2{b[2 * k], b[2 * k + 1]};
   }
-  if constexpr (EPI == MEMHIP_EPI_RESIDUAL) {
+  if constexpr (epi_resid(EPI)) {
     ld8g(p.vec1 ? as_global(p.vec1 + n) : as_global(g_epi_one8), c.g);
   }
 }
@@ -249,6 +284,8 @@ template <>
 struct EpiRow<MEMHIP_EPI_MUL_AUX> { uint4 h; };
 template <>
 struct EpiRow<MEMHIP_EPI_RESIDUAL> { float x[8]; float rm; long long row; };   // row: the residual row (sample_map resolved)
+template <>
+struct EpiRow<MEMHIP_EPI_RESIDUAL_DROP> : EpiRow<MEMHIP_EPI_RESIDUAL> {};
 // No vector-memory instruction of a row epilogue sits behind a branch, not even a wave-uniform one: at the join hipcc's
 // waitcnt pass gives up counting and puts s_waitcnt vmcnt(0) in front of the next use of a loaded row, which then also waits
 // for every store issued so far (one store round trip per row).  Optional operands are therefore handled by POINTER selection:
@@ -263,7 +300,7 @@ template <int EPI, bool BIGROWS = true>
 __device__ __forceinline__ void epi_row_load(const GemmArgs& p, int m, int n, EpiRow<EPI>& r) {
   if constexpr (EPI == MEMHIP_EPI_DGELU || EPI == MEMHIP_EPI_MUL_AUX) {
     r.h = *reinterpret_cast<const uint4*>(reinterpret_cast<const __bf16*>(p.aux) + (long long)m * p.ldaux + n);
-  } else if constexpr (EPI == MEMHIP_EPI_RESIDUAL) {
+  } else if constexpr (epi_resid(EPI)) {
     // (base pointer and leading dimension are selected as scalars: one address computation per lane)
     const float* base = p.aux ? reinterpret_cast<const float*>(p.aux) : p.resid;
     const long long ld = p.aux ? p.ldaux : p.ldr;
@@ -300,6 +337,7 @@ template <int EPI> struct EpiPk { static constexpr int W = 4; };                
 template <> struct EpiPk<MEMHIP_EPI_BIAS_GELU> { static constexpr int W = 8; };        // h | gelu(h)
 template <> struct EpiPk<MEMHIP_EPI_BIAS_GELU_DG> { static constexpr int W = 8; };     // gelu'(h) | gelu(h)
 template <> struct EpiPk<MEMHIP_EPI_RESIDUAL> { static constexpr int W = 8; };         // 8 fp32 of the residual stream
+template <> struct EpiPk<MEMHIP_EPI_RESIDUAL_DROP> { static constexpr int W = 8; };
 template <> struct EpiPk<MEMHIP_EPI_F32> { static constexpr int W = 8; };
 template <> struct EpiPk<MEMHIP_EPI_PATCH_EMBED> { static constexpr int W = 8; };
 
@@ -365,7 +403,7 @@ __device__ __forceinline__ void epi8_math(const GemmArgs& p, int m, int n, const
         cs[2 * k + 1] += f.y;
       }
     }
-  } else if constexpr (EPI == MEMHIP_EPI_RESIDUAL) {
+  } else if constexpr (epi_resid(EPI)) {
     unsigned y[4];
     float x[8];
 #pragma unroll
@@ -377,6 +415,12 @@ __device__ __forceinline__ void epi8_math(const GemmArgs& p, int m, int n, const
       const ef32x2 f = unpack_bf16x2(y[k]);
       br[2 * k] = f.x;
       br[2 * k + 1] = f.y;
+    }
+    if constexpr (EPI == MEMHIP_EPI_RESIDUAL_DROP) {   // z = y * keep * scale: one Philox call for the lane's 8 columns
+      const DropParams& d = drop_of(p);
+      const unsigned kb = dropout_keep8(d, drop_row(p, row.row), (unsigned)(n >> 3));
+#pragma unroll
+      for (int k = 0; k < 8; ++k) br[k] = __fmul_rn(br[k], dropout_mul(d, kb, k));
     }
     // layer scale: gamma * branch (own rounding, as the reference); gamma = 1 (exact) when there is none
 #pragma unroll
@@ -449,7 +493,7 @@ __device__ __forceinline__ void epi8_store(const GemmArgs& p, int m, int n, long
     float x[8];
 #pragma unroll
     for (int k = 0; k < 8; ++k) x[k] = __uint_as_float(out[k]);
-    if constexpr (EPI == MEMHIP_EPI_RESIDUAL) {
+    if constexpr (epi_resid(EPI)) {
       st8(p.resid + rrow * p.ldr + n, x);
     } else if constexpr (EPI == MEMHIP_EPI_F32) {
       st8(reinterpret_cast<float*>(p.out0) + (long long)m * p.ldo0 + n, x);
@@ -467,7 +511,7 @@ __device__ __forceinline__ void epilogue8(const GemmArgs& p, int m, int n, const
   unsigned out[EpiPk<EPI>::W];
   epi8_math<EPI, COPY>(p, m, n, acc, cs, c, row, out);
   long long rrow = m;
-  if constexpr (EPI == MEMHIP_EPI_RESIDUAL) rrow = row.row;
+  if constexpr (epi_resid(EPI)) rrow = row.row;
   epi8_store<EPI>(p, m, n, rrow, out);
 }
 

@@ -360,15 +360,15 @@ __device__ __forceinline__ void p8_body(const GemmArgs& p, int ntm, int ntn, int
   //    iteration (per-lane source addresses; the data lands in a scratch slot and is never read): 512 lines per iteration
   //    and workgroup, the whole operand tile within 2 (bf16) or 4 (fp32) of a K = 768 tile's 6 iterations; the epilogue's
   //    own loads then hit L2.
-  constexpr bool kHasAux = EPI == MEMHIP_EPI_DGELU || EPI == MEMHIP_EPI_MUL_AUX || EPI == MEMHIP_EPI_RESIDUAL;
-  constexpr bool kHasBias = EPI == MEMHIP_EPI_BIAS_BF16 || EPI == MEMHIP_EPI_BIAS_GELU || EPI == MEMHIP_EPI_RESIDUAL ||
+  constexpr bool kHasAux = EPI == MEMHIP_EPI_DGELU || EPI == MEMHIP_EPI_MUL_AUX || epi_resid(EPI);
+  constexpr bool kHasBias = EPI == MEMHIP_EPI_BIAS_BF16 || EPI == MEMHIP_EPI_BIAS_GELU || epi_resid(EPI) ||
                             EPI == MEMHIP_EPI_BIAS_GELU_DG;
   constexpr int PX = 1;
   const char* pf_base = reinterpret_cast<const char*>(p.A);
   long long pf_ld = 0;                                     // bytes per row
   int pf_lpr = 1;                                          // 128-byte lines per tile row
   if constexpr (kHasAux) {
-    if constexpr (EPI == MEMHIP_EPI_RESIDUAL) {
+    if constexpr (epi_resid(EPI)) {
       pf_base = p.aux ? reinterpret_cast<const char*>(p.aux) : reinterpret_cast<const char*>(p.resid);
       pf_ld = (p.aux ? p.ldaux : p.ldr) * 4;
       pf_lpr = BN * 4 / 128;
@@ -404,7 +404,7 @@ __device__ __forceinline__ void p8_body(const GemmArgs& p, int ntm, int ntn, int
           dst = smem + G::kColsOff + tile_par * G::kColsSlot;
         }
       }
-      if constexpr (EPI == MEMHIP_EPI_RESIDUAL) {
+      if constexpr (epi_resid(EPI)) {
         if (wave == 1) {
           src = (p.vec1 ? reinterpret_cast<const char*>(p.vec1 + tn * BN) : reinterpret_cast<const char*>(g_epi_one256)) + dlane * 16;
           dst = smem + G::kColsOff + tile_par * G::kColsSlot + 1024;
@@ -437,7 +437,7 @@ __device__ __forceinline__ void p8_body(const GemmArgs& p, int ntm, int ntn, int
 #pragma unroll
       for (int k = 0; k < 4; ++k) c.bias[k] = ef32x2{b[2 * k], b[2 * k + 1]};
     }
-    if constexpr (EPI == MEMHIP_EPI_RESIDUAL) lds_read8(addr + 1024, c.g);
+    if constexpr (epi_resid(EPI)) lds_read8(addr + 1024, c.g);
   };
 
   P8_READ_B0_FIRST();
@@ -485,10 +485,10 @@ __device__ __forceinline__ void p8_body(const GemmArgs& p, int ntm, int ntn, int
       // a CU has 32 KB outstanding, i.e. ~20 GB/s per CU at ~1.5 us latency -- the epilogue was latency
       // bound, not HBM bound.  Row indices are clamped instead of branched, so that nothing orders the loads.
       // (the residual epilogue carries 8 registers per row: no room for a second batch beside 128 accumulators)
-      constexpr int kAhead = (EPI == MEMHIP_EPI_RESIDUAL || EPI == MEMHIP_EPI_PATCH_EMBED) ? 0 : kEpiAhead;
+      constexpr int kAhead = (epi_resid(EPI) || EPI == MEMHIP_EPI_PATCH_EMBED) ? 0 : kEpiAhead;
       // residual epilogue: batch 0 alone; batches 1 and 2 go out together once batch 0 has released its
       // accumulators and row registers (the accumulators are re-zeroed after the loop, not inside it)
-      constexpr bool kLate = (EPI == MEMHIP_EPI_RESIDUAL || EPI == MEMHIP_EPI_PATCH_EMBED) && P8_EPI_RESID_LATE;
+      constexpr bool kLate = (epi_resid(EPI) || EPI == MEMHIP_EPI_PATCH_EMBED) && P8_EPI_RESID_LATE;
       // The row guard (m < M) is a per-lane branch: a basic block per row, and at every block entry hipcc's waitcnt pass
       // falls back to s_waitcnt vmcnt(0) in front of the first use of a loaded row -- which also waits for the STORE of
       // the previous row (one store round trip per row, 16 per tile: the GELU' epilogue spent 22 us per tile that way).
@@ -765,6 +765,11 @@ template <int EPI, int BMT, bool GUARD, bool COPY>
 __global__ __launch_bounds__(kThreads) void gemm_p8_kernel(GemmArgs p, int ntm, int ntn, int stagger, int prefetch) {
   p8_body<EPI, BMT, GUARD, COPY>(p, ntm, ntn, stagger, prefetch, (int)blockIdx.x, (int)gridDim.x);
 }
+// the residual epilogue with element-wise dropout: kernels of their own (GemmArgsD arguments; no bf16 branch copy)
+template <int BMT, bool GUARD>
+__global__ __launch_bounds__(kThreads) void gemm_p8_drop_kernel(GemmArgsD p, int ntm, int ntn, int stagger, int prefetch) {
+  p8_body<MEMHIP_EPI_RESIDUAL_DROP, BMT, GUARD, false>(p, ntm, ntn, stagger, prefetch, (int)blockIdx.x, (int)gridDim.x);
+}
 
 // ONE launch for a product whose last round of 256-row tiles would be poorly filled (N = 768: 591 tiles on 256 CUs): workgroups
 // 0 .. nmain-1 are the persistent 256-row workgroups over the rows of the full rounds (`head`), the remaining workgroups run the
@@ -783,22 +788,31 @@ __global__ __launch_bounds__(kThreads) void gemm_p8_pair_kernel(GemmArgs head, G
 template <int EPI, int BMT, bool GUARD, bool COPY>
 int launch_p8gc(const GemmArgs& p, hipStream_t s, int num_cu) {
   const int ntm = (p.M + BMT - 1) / BMT, ntn = p.N / BN;
+  constexpr bool kDrop = EPI == MEMHIP_EPI_RESIDUAL_DROP;
+  const void* kfn;
+  if constexpr (kDrop) kfn = reinterpret_cast<const void*>(gemm_p8_drop_kernel<BMT, GUARD>);
+  else kfn = reinterpret_cast<const void*>(gemm_p8_kernel<EPI, BMT, GUARD, COPY>);
   static bool attr_done = false;
   if (!attr_done) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_p8_kernel<EPI, BMT, GUARD, COPY>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, P8Geo<BMT>::kLdsAll);
+    hipError_t e = hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, P8Geo<BMT>::kLdsAll);
     if (e != hipSuccess) return fail(MEMHIP_ELAUNCH, "gemm_p8: set smem attr: %s", hipGetErrorString(e));
     attr_done = true;
   }
   const int grid = ntm * ntn < num_cu ? ntm * ntn : num_cu;
-  hipLaunchKernelGGL((gemm_p8_kernel<EPI, BMT, GUARD, COPY>), dim3(grid), dim3(kThreads), P8Geo<BMT>::kLdsAll, s, p, ntm, ntn,
-                     BMT == 256 ? opt(OPT_GEMM_STAGGER) : 0, opt(OPT_GEMM_PREFETCH));
+  if constexpr (kDrop)
+    hipLaunchKernelGGL((gemm_p8_drop_kernel<BMT, GUARD>), dim3(grid), dim3(kThreads), P8Geo<BMT>::kLdsAll, s,
+                       static_cast<const GemmArgsD&>(p), ntm, ntn, BMT == 256 ? opt(OPT_GEMM_STAGGER) : 0, opt(OPT_GEMM_PREFETCH));
+  else
+    hipLaunchKernelGGL((gemm_p8_kernel<EPI, BMT, GUARD, COPY>), dim3(grid), dim3(kThreads), P8Geo<BMT>::kLdsAll, s, p, ntm, ntn,
+                       BMT == 256 ? opt(OPT_GEMM_STAGGER) : 0, opt(OPT_GEMM_PREFETCH));
   return check_launch("gemm_bf16_nt(p8)");
 }
 
 template <int EPI, int BMT, bool GUARD>
 int launch_p8g(const GemmArgs& p, hipStream_t s, int num_cu) {
-  if constexpr (EPI == MEMHIP_EPI_RESIDUAL) {
+  if constexpr (EPI == MEMHIP_EPI_RESIDUAL_DROP) {
+    return launch_p8gc<EPI, BMT, GUARD, false>(p, s, num_cu);       // (out0 is NULL: checked by the dispatcher)
+  } else if constexpr (EPI == MEMHIP_EPI_RESIDUAL) {
     if (!p.out0) return launch_p8gc<EPI, BMT, GUARD, false>(p, s, num_cu);
     // (the bf16 copy of the branch output beside the full-line residual epilogue of the 256-row kernel spills; no engine
     // asks for it on the bf16 path: those calls run on the 128-row form)
@@ -868,6 +882,10 @@ int gemm_p8_dispatch(const GemmArgs& p, hipStream_t s) {
     case MEMHIP_EPI_RESIDUAL:
       if (p.out0) return gemm_p8_half_dispatch(p, s);
       return launch_p8<MEMHIP_EPI_RESIDUAL, 256>(p, s, num_cu);
+    // The residual-dropout epilogue runs on the 128-row form only (here, in the split's head and tail, never paired): the
+    // 256-row residual epilogue loads its rows with hand-counted waits and has no room for the Philox state -- measured:
+    // the 256-row dropout instantiation spilled, and a spill is an uncounted vector-memory operation.
+    case MEMHIP_EPI_RESIDUAL_DROP: return gemm_p8_half_dispatch(p, s);
     case MEMHIP_EPI_DGELU: return launch_p8<MEMHIP_EPI_DGELU, 256>(p, s, num_cu);
     case MEMHIP_EPI_BIAS_GELU_DG: return launch_p8<MEMHIP_EPI_BIAS_GELU_DG, 256>(p, s, num_cu);
     case MEMHIP_EPI_MUL_AUX: return launch_p8<MEMHIP_EPI_MUL_AUX, 256>(p, s, num_cu);
@@ -886,6 +904,7 @@ int gemm_p8_half_dispatch(const GemmArgs& p, hipStream_t s) {
     case MEMHIP_EPI_BIAS_BF16: return launch_p8<MEMHIP_EPI_BIAS_BF16, 128>(p, s, num_cu);
     case MEMHIP_EPI_BIAS_GELU: return launch_p8<MEMHIP_EPI_BIAS_GELU, 128>(p, s, num_cu);
     case MEMHIP_EPI_RESIDUAL: return launch_p8<MEMHIP_EPI_RESIDUAL, 128>(p, s, num_cu);
+    case MEMHIP_EPI_RESIDUAL_DROP: return launch_p8<MEMHIP_EPI_RESIDUAL_DROP, 128>(p, s, num_cu);
     case MEMHIP_EPI_DGELU: return launch_p8<MEMHIP_EPI_DGELU, 128>(p, s, num_cu);
     case MEMHIP_EPI_BIAS_GELU_DG: return launch_p8<MEMHIP_EPI_BIAS_GELU_DG, 128>(p, s, num_cu);
     case MEMHIP_EPI_MUL_AUX: return launch_p8<MEMHIP_EPI_MUL_AUX, 128>(p, s, num_cu);

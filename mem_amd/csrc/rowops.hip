@@ -6,6 +6,7 @@
 // + DropPath residual (mem/modeling_finetune.py:187-188), nn.CrossEntropyLoss + argmax accuracy
 // (mem/engine_for_pretraining.py:152,233).
 #include "common.h"
+#include "dropout.hpp"
 
 namespace {
 
@@ -178,14 +179,17 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const __bf16* __restrict__ 
 // column sums cost gridDim.x atomics per column (same-address atomics are the slow part)
 constexpr int kBrMaxChunks = 8;   // float4 chunks per lane: D <= 2048
 
-template <int NCH>
+// Drop = {DropParams} (memhip_branch_bwd_drop): the branch had element-wise dropout, dt -> dt * keep * scale; empty: no
+// dropout (the kernel arguments and code of that form are those without the parameter)
+template <int NCH, class... Drop>
 __global__ __launch_bounds__(256) void branch_bwd_kernel(const float* __restrict__ dx, long long lddx,
                                                          const __bf16* __restrict__ y, long long ldy,
                                                          const float* __restrict__ gamma,
                                                          const float* __restrict__ rowmask, float keep,
                                                          int rps, int M, int D, __bf16* __restrict__ dyo,
                                                          long long lddy, float* __restrict__ dgamma,
-                                                         float* __restrict__ dbias, const int* __restrict__ out_map) {
+                                                         float* __restrict__ dbias, const int* __restrict__ out_map,
+                                                         Drop... drop) {
   // out_map (work-skipping stochastic depth): sample -> index of the sample among the KEPT ones, or -1.  The rows of a
   // dropped sample are neither read nor written; kept rows land at their compact position and are scaled by 1 / keep.
   extern __shared__ float red[];   // [4][2][D]
@@ -242,6 +246,12 @@ __global__ __launch_bounds__(256) void branch_bwd_kernel(const float* __restrict
             d.x = div_newton(d.x * k, keep, rk); d.y = div_newton(d.y * k, keep, rk);
             d.z = div_newton(d.z * k, keep, rk); d.w = div_newton(d.w * k, keep, rk);
           }
+          if constexpr (sizeof...(Drop) > 0) {   // the lane's 4 columns 4i.. are one half of the 8-column group i / 2
+            const DropParams dp = (drop, ...);
+            const unsigned kb = dropout_keep8(dp, (unsigned)(dp.row0 + m0 + u * stride), (unsigned)(i >> 1)) >> ((i & 1) * 4);
+            d.x = __fmul_rn(d.x, dropout_mul(dp, kb, 0)); d.y = __fmul_rn(d.y, dropout_mul(dp, kb, 1));
+            d.z = __fmul_rn(d.z, dropout_mul(dp, kb, 2)); d.w = __fmul_rn(d.w, dropout_mul(dp, kb, 3));
+          }
           if (y) {
             const bf16x4 yy = yv[u][c];
             ag[c].x += d.x * (float)yy[0]; ag[c].y += d.y * (float)yy[1];
@@ -279,7 +289,8 @@ __global__ __launch_bounds__(256) void branch_bwd_kernel(const float* __restrict
 // dx is produced, stored and consumed in registers -- one pass over the fp32 gradient stream less.
 //   dx[r] += LN'(dy[r]) ;  dt = dx[r] * mask[r / rps] / keep ;  dyb[r] = bf16(dt * gb) ;
 //   dgamma_ln += sum dy*xhat ; dbeta_ln += sum dy ; dgb += sum dt*y ; dbias_b += sum dyb
-template <int NCH, bool HAS_Y>
+// Drop = {DropParams} (memhip_layernorm_bwd_branch_drop): the produced branch gradient carries the branch's dropout mask
+template <int NCH, bool HAS_Y, class... Drop>
 __global__ __launch_bounds__(256) void ln_bwd_branch_kernel(const __bf16* __restrict__ dy, long long lddy,
                                                             const float* __restrict__ x, long long ldx, int R, int D,
                                                             const float* __restrict__ gamma,
@@ -290,7 +301,8 @@ __global__ __launch_bounds__(256) void ln_bwd_branch_kernel(const __bf16* __rest
                                                             const float* __restrict__ gb, const float* __restrict__ rowmask,
                                                             float keep, int rps, __bf16* __restrict__ dyo, long long lddyo,
                                                             float* __restrict__ dgb, float* __restrict__ dbiasb,
-                                                            const int* __restrict__ in_map, const int* __restrict__ out_map) {
+                                                            const int* __restrict__ in_map, const int* __restrict__ out_map,
+                                                            Drop... drop) {
   // Work-skipping stochastic depth: r runs over the rows of the residual stream (x, dres).  in_map: sample -> its index
   // among the samples the LayerNorm'ed branch KEPT (dy, mean, rstd hold those samples only), -1: that branch skipped the
   // sample, its rows get no LayerNorm gradient.  out_map: the same for the branch whose output gradient is produced
@@ -386,6 +398,12 @@ __global__ __launch_bounds__(256) void ln_bwd_branch_kernel(const __bf16* __rest
         if (rowmask || out_map) {
           d.x = div_newton(d.x * km, keep, rk); d.y = div_newton(d.y * km, keep, rk);
           d.z = div_newton(d.z * km, keep, rk); d.w = div_newton(d.w * km, keep, rk);
+        }
+        if constexpr (sizeof...(Drop) > 0) {     // the lane's 4 columns 4i.. are one half of the 8-column group i / 2
+          const DropParams dp = (drop, ...);
+          const unsigned kb = dropout_keep8(dp, (unsigned)(dp.row0 + r), (unsigned)(i >> 1)) >> ((i & 1) * 4);
+          d.x = __fmul_rn(d.x, dropout_mul(dp, kb, 0)); d.y = __fmul_rn(d.y, dropout_mul(dp, kb, 1));
+          d.z = __fmul_rn(d.z, dropout_mul(dp, kb, 2)); d.w = __fmul_rn(d.w, dropout_mul(dp, kb, 3));
         }
         if constexpr (HAS_Y) {
           bg[c].x += d.x * (float)yv[c][0]; bg[c].y += d.y * (float)yv[c][1];
@@ -669,11 +687,13 @@ extern "C" int memhip_layernorm_bwd(const void* dy, int64_t lddy, const float* x
   return check_launch("layernorm_bwd");
 }
 
-extern "C" int memhip_branch_bwd_map(const float* dx, int64_t lddx, const void* y, int64_t ldy,
-                                     const float* gamma, const float* rowmask, float keep_prob,
-                                     int rows_per_sample, int M, int D, void* dy, int64_t lddy,
-                                     float* dgamma, float* dbias, const int32_t* out_map, memhip_stream_t stream) {
+static int branch_bwd_impl(const float* dx, int64_t lddx, const void* y, int64_t ldy,
+                           const float* gamma, const float* rowmask, float keep_prob,
+                           int rows_per_sample, int M, int D, void* dy, int64_t lddy,
+                           float* dgamma, float* dbias, const int32_t* out_map, const memhip_dropout_t* drop,
+                           memhip_stream_t stream) {
   MEMHIP_REQUIRE(M >= 0 && D > 0 && D % 4 == 0, "branch_bwd: bad M=%d D=%d", M, D);
+  MEMHIP_REQUIRE(!drop || D % 8 == 0, "branch_bwd_drop: D=%d must be a multiple of 8", D);
   MEMHIP_REQUIRE(!out_map || (!rowmask && !y && rows_per_sample > 0), "branch_bwd: out_map excludes rowmask / y");
   if (M == 0) return MEMHIP_OK;
   MEMHIP_REQUIRE(dx && dy, "branch_bwd: null pointer");
@@ -683,10 +703,16 @@ extern "C" int memhip_branch_bwd_map(const float* dx, int64_t lddx, const void* 
   int grid = cdiv(M, 4);
   if (grid > 1024) grid = 1024;
 #define BRB_LAUNCH(N)                                                                                    \
+  if (drop) BRB_LAUNCH_D(N); else                                                                        \
   hipLaunchKernelGGL(branch_bwd_kernel<N>, dim3(grid), dim3(256), (size_t)8 * D * sizeof(float), as_stream(stream), \
                      dx, (long long)lddx, (const __bf16*)y, (long long)ldy, gamma, rowmask, keep_prob,    \
                      rows_per_sample > 0 ? rows_per_sample : 1, M, D, (__bf16*)dy, (long long)lddy, dgamma, dbias, \
                      (const int*)out_map)
+#define BRB_LAUNCH_D(N)                                                                                  \
+  hipLaunchKernelGGL((branch_bwd_kernel<N, DropParams>), dim3(grid), dim3(256), (size_t)8 * D * sizeof(float),  \
+                     as_stream(stream), dx, (long long)lddx, (const __bf16*)y, (long long)ldy, gamma, rowmask, keep_prob, \
+                     rows_per_sample > 0 ? rows_per_sample : 1, M, D, (__bf16*)dy, (long long)lddy, dgamma, dbias, \
+                     (const int*)out_map, drop_params(*drop))
   const int nchl = cdiv(D / 4, 64);
   if (nchl <= 1) BRB_LAUNCH(1);
   else if (nchl <= 2) BRB_LAUNCH(2);
@@ -694,7 +720,26 @@ extern "C" int memhip_branch_bwd_map(const float* dx, int64_t lddx, const void* 
   else if (nchl <= 4) BRB_LAUNCH(4);
   else BRB_LAUNCH(8);
 #undef BRB_LAUNCH
+#undef BRB_LAUNCH_D
   return check_launch("branch_bwd");
+}
+
+extern "C" int memhip_branch_bwd_map(const float* dx, int64_t lddx, const void* y, int64_t ldy,
+                                     const float* gamma, const float* rowmask, float keep_prob,
+                                     int rows_per_sample, int M, int D, void* dy, int64_t lddy,
+                                     float* dgamma, float* dbias, const int32_t* out_map, memhip_stream_t stream) {
+  return branch_bwd_impl(dx, lddx, y, ldy, gamma, rowmask, keep_prob, rows_per_sample, M, D, dy, lddy, dgamma, dbias, out_map,
+                         nullptr, stream);
+}
+
+extern "C" int memhip_branch_bwd_drop(const float* dx, int64_t lddx, const void* y, int64_t ldy,
+                                      const float* gamma, const float* rowmask, float keep_prob,
+                                      int rows_per_sample, int M, int D, void* dy, int64_t lddy,
+                                      float* dgamma, float* dbias, const int32_t* out_map, const memhip_dropout_t* dropout,
+                                      memhip_stream_t stream) {
+  MEMHIP_REQUIRE(dropout, "branch_bwd_drop: null dropout");
+  return branch_bwd_impl(dx, lddx, y, ldy, gamma, rowmask, keep_prob, rows_per_sample, M, D, dy, lddy, dgamma, dbias, out_map,
+                         dropout, stream);
 }
 
 extern "C" int memhip_branch_bwd(const float* dx, int64_t lddx, const void* y, int64_t ldy,
@@ -738,14 +783,15 @@ extern "C" int memhip_cross_entropy(void* logits, int64_t ld, const int64_t* lab
   return check_launch("cross_entropy");
 }
 
-extern "C" int memhip_layernorm_bwd_branch_map(const void* dy, int64_t lddy, const float* x, int64_t ldx, int R, int D,
-                                               const float* gamma, const float* mean, const float* rstd, float* dres,
-                                               int64_t lddres, float* dgamma, float* dbeta, const void* y_branch,
-                                               int64_t ldyb, const float* gamma_branch, const float* rowmask,
-                                               float keep_prob, int rows_per_sample, void* dy_branch, int64_t lddyb,
-                                               float* dgamma_branch, float* dbias_branch, const int32_t* in_map,
-                                               const int32_t* out_map, memhip_stream_t stream) {
+static int ln_bwd_branch_impl(const void* dy, int64_t lddy, const float* x, int64_t ldx, int R, int D,
+                              const float* gamma, const float* mean, const float* rstd, float* dres,
+                              int64_t lddres, float* dgamma, float* dbeta, const void* y_branch,
+                              int64_t ldyb, const float* gamma_branch, const float* rowmask,
+                              float keep_prob, int rows_per_sample, void* dy_branch, int64_t lddyb,
+                              float* dgamma_branch, float* dbias_branch, const int32_t* in_map,
+                              const int32_t* out_map, const memhip_dropout_t* drop, memhip_stream_t stream) {
   MEMHIP_REQUIRE(R >= 0 && D > 0 && D % 4 == 0 && D <= 64 * 4 * 4, "layernorm_bwd_branch: D=%d unsupported (<= 1024)", D);
+  MEMHIP_REQUIRE(!drop || D % 8 == 0, "layernorm_bwd_branch_drop: D=%d must be a multiple of 8", D);
   MEMHIP_REQUIRE(!(in_map || out_map) || (!rowmask && !y_branch && rows_per_sample > 0),
                  "layernorm_bwd_branch: sample maps exclude rowmask / y_branch");
   if (R == 0) return MEMHIP_OK;
@@ -764,7 +810,8 @@ extern "C" int memhip_layernorm_bwd_branch_map(const void* dy, int64_t lddy, con
                                                        // 76 864 rows 301 -> 262 us, 19 216 rows 69 -> 64 us)
   if (grid > cap) grid = cap;
 #define LBB_LAUNCH(N)                                                                                    \
-  if (y_branch) LBB_LAUNCH2(N, true); else LBB_LAUNCH2(N, false)
+  if (drop) { if (y_branch) LBB_LAUNCH2D(N, true); else LBB_LAUNCH2D(N, false); }                       \
+  else if (y_branch) LBB_LAUNCH2(N, true); else LBB_LAUNCH2(N, false)
 #define LBB_LAUNCH2(N, Y)                                                                                \
   hipLaunchKernelGGL((ln_bwd_branch_kernel<N, Y>), dim3(grid), dim3(256), (size_t)16 * D * sizeof(float), \
                      as_stream(stream), (const __bf16*)dy, (long long)lddy, x, (long long)ldx, R, D, gamma, mean, \
@@ -772,6 +819,13 @@ extern "C" int memhip_layernorm_bwd_branch_map(const void* dy, int64_t lddy, con
                      gamma_branch, rowmask, keep_prob, rows_per_sample > 0 ? rows_per_sample : 1,         \
                      (__bf16*)dy_branch, (long long)lddyb, dgamma_branch, dbias_branch, (const int*)in_map, \
                      (const int*)out_map)
+#define LBB_LAUNCH2D(N, Y)                                                                               \
+  hipLaunchKernelGGL((ln_bwd_branch_kernel<N, Y, DropParams>), dim3(grid), dim3(256), (size_t)16 * D * sizeof(float), \
+                     as_stream(stream), (const __bf16*)dy, (long long)lddy, x, (long long)ldx, R, D, gamma, mean, \
+                     rstd, dres, (long long)lddres, dgamma, dbeta, (const __bf16*)y_branch, (long long)ldyb, \
+                     gamma_branch, rowmask, keep_prob, rows_per_sample > 0 ? rows_per_sample : 1,         \
+                     (__bf16*)dy_branch, (long long)lddyb, dgamma_branch, dbias_branch, (const int*)in_map, \
+                     (const int*)out_map, drop_params(*drop))
   const int nchl = cdiv(D / 4, 64);
   if (nchl <= 1) LBB_LAUNCH(1);
   else if (nchl <= 2) LBB_LAUNCH(2);
@@ -779,7 +833,34 @@ extern "C" int memhip_layernorm_bwd_branch_map(const void* dy, int64_t lddy, con
   else LBB_LAUNCH(4);
 #undef LBB_LAUNCH
 #undef LBB_LAUNCH2
+#undef LBB_LAUNCH2D
   return check_launch("layernorm_bwd_branch");
+}
+
+extern "C" int memhip_layernorm_bwd_branch_map(const void* dy, int64_t lddy, const float* x, int64_t ldx, int R, int D,
+                                               const float* gamma, const float* mean, const float* rstd, float* dres,
+                                               int64_t lddres, float* dgamma, float* dbeta, const void* y_branch,
+                                               int64_t ldyb, const float* gamma_branch, const float* rowmask,
+                                               float keep_prob, int rows_per_sample, void* dy_branch, int64_t lddyb,
+                                               float* dgamma_branch, float* dbias_branch, const int32_t* in_map,
+                                               const int32_t* out_map, memhip_stream_t stream) {
+  return ln_bwd_branch_impl(dy, lddy, x, ldx, R, D, gamma, mean, rstd, dres, lddres, dgamma, dbeta, y_branch, ldyb,
+                            gamma_branch, rowmask, keep_prob, rows_per_sample, dy_branch, lddyb, dgamma_branch, dbias_branch,
+                            in_map, out_map, nullptr, stream);
+}
+
+extern "C" int memhip_layernorm_bwd_branch_drop(const void* dy, int64_t lddy, const float* x, int64_t ldx, int R, int D,
+                                                const float* gamma, const float* mean, const float* rstd, float* dres,
+                                                int64_t lddres, float* dgamma, float* dbeta, const void* y_branch,
+                                                int64_t ldyb, const float* gamma_branch, const float* rowmask,
+                                                float keep_prob, int rows_per_sample, void* dy_branch, int64_t lddyb,
+                                                float* dgamma_branch, float* dbias_branch, const int32_t* in_map,
+                                                const int32_t* out_map, const memhip_dropout_t* dropout,
+                                                memhip_stream_t stream) {
+  MEMHIP_REQUIRE(dropout, "layernorm_bwd_branch_drop: null dropout");
+  return ln_bwd_branch_impl(dy, lddy, x, ldx, R, D, gamma, mean, rstd, dres, lddres, dgamma, dbeta, y_branch, ldyb,
+                            gamma_branch, rowmask, keep_prob, rows_per_sample, dy_branch, lddyb, dgamma_branch, dbias_branch,
+                            in_map, out_map, dropout, stream);
 }
 
 extern "C" int memhip_layernorm_bwd_branch(const void* dy, int64_t lddy, const float* x, int64_t ldx, int R, int D,

@@ -38,7 +38,8 @@ class Mlp(nn.Module):
         super().__init__()
         out_features = out_features or in_features
         hidden_features = hidden_features or in_features
-        assert act_layer is nn.GELU and drop == 0.0, "fused path: exact-erf GELU, dropout 0 (all reference configs)"
+        assert act_layer is nn.GELU, "fused path: exact-erf GELU"
+        assert 0.0 <= drop < 1.0, "dropout probability in [0, 1)"     # (applied in the fc2 GEMM epilogue: ViTEngine)
         self.fc1 = nn.Linear(in_features, hidden_features)
         self.act = act_layer()
         self.fc2 = nn.Linear(hidden_features, out_features)
@@ -59,7 +60,9 @@ class Attention(nn.Module):
             head_dim = attn_head_dim
         all_head_dim = head_dim * num_heads
         assert head_dim == 64 and all_head_dim == dim, "fused attention kernel: head_dim 64 (ViT-B / ViT-L)"
-        assert attn_drop == 0.0 and proj_drop == 0.0
+        assert attn_drop == 0.0, ("attn_drop_rate > 0 needs dropout masks inside the fused attention kernels, which do not "
+                                  "carry them (no reference config sets it)")
+        assert 0.0 <= proj_drop < 1.0, "dropout probability in [0, 1)"   # (applied in the proj GEMM epilogue: ViTEngine)
         self.scale = qk_scale or head_dim ** -0.5
         self.qkv = nn.Linear(dim, all_head_dim * 3, bias=False)
         if qkv_bias:
@@ -163,10 +166,10 @@ def _trunc_normal_(tensor, mean=0.0, std=1.0):
 
 class _TrunkFunction(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, model, x, dp_masks, anchor):
+    def forward(ctx, model, x, dp_masks, drop_key, anchor):
         ctx.model = model
         eng = model.engine
-        xl = eng.forward_trunk(x, None, dp_masks)
+        xl = eng.forward_trunk(x, None, dp_masks, drop_key=drop_key)
         return xl[: x.shape[0] * eng.T].view(x.shape[0], eng.T, eng.D).clone()
 
     @staticmethod
@@ -174,7 +177,7 @@ class _TrunkFunction(torch.autograd.Function):
         eng = ctx.model.engine
         eng.attach_grads()
         eng.backward_trunk(dxl.float().contiguous())
-        return None, None, None, None
+        return None, None, None, None, None
 
 
 class VisionTransformer(nn.Module):
@@ -186,7 +189,13 @@ class VisionTransformer(nn.Module):
                  use_rel_pos_bias=False, use_shared_rel_pos_bias=False, use_mean_pooling=True, init_scale=0.001,
                  use_batch_norm=False, **kwargs):
         super().__init__()
-        assert qkv_bias and drop_rate == 0.0 and attn_drop_rate == 0.0, "fused path: qkv_bias, no dropout"
+        assert qkv_bias, "fused path: qkv_bias"
+        assert attn_drop_rate == 0.0, ("attn_drop_rate > 0 needs dropout masks inside the fused attention kernels, which do not "
+                                       "carry them (no reference config sets it)")
+        # drop_rate: pos_drop, Attention.proj_drop and Mlp.drop (element-wise dropout, masks from a counter-based generator keyed
+        # per step by the model's own generator: include/memhip.h, memhip_dropout_t)
+        assert 0.0 <= drop_rate < 1.0, "drop_rate in [0, 1)"
+        self.drop_rate = float(drop_rate)
         assert not use_batch_norm, "linear-probe BatchNorm head: not in the fused path"
         self.num_classes = num_classes
         self.num_features = self.embed_dim = embed_dim
@@ -290,19 +299,31 @@ class VisionTransformer(nn.Module):
         return st.uniform(rows, B, device)
 
 
+    def draw_dropout_key(self):
+        """The (key0, key1) of this step's dropout masks, from the model's own generator (the drop-path stream: seeded
+        seed + rank, checkpointed per rank); None when drop_rate == 0 (nothing is drawn: the drop-path stream stays as it is)."""
+        if self.drop_rate == 0.0:
+            return None
+        st = getattr(self, "_dp_stream", None)
+        if st is None:
+            from .utils import DropPathStream
+            st = self._dp_stream = DropPathStream()
+        return st.key()
+
     def _trunk(self, x, drop_path_masks=None):
         eng = self.engine
         x = x.to(device=eng.dev, dtype=torch.float32).contiguous()
         if self.training and drop_path_masks is None:
             drop_path_masks = self.draw_drop_path(x.shape[0])
+        drop_key = self.draw_dropout_key() if self.training else None
         if not self.training:
             drop_path_masks = None
         if torch.is_grad_enabled() and self.training:
             if self._anchor is None:
                 self._anchor = torch.zeros(1, device=x.device, requires_grad=True)
-            return _TrunkFunction.apply(self, x, drop_path_masks, self._anchor)
+            return _TrunkFunction.apply(self, x, drop_path_masks, drop_key, self._anchor)
         B = x.shape[0]
-        return eng.forward_trunk(x, None, drop_path_masks)[: B * eng.T].view(B, eng.T, eng.D).clone()
+        return eng.forward_trunk(x, None, drop_path_masks, drop_key=drop_key)[: B * eng.T].view(B, eng.T, eng.D).clone()
 
     def forward_features(self, x, drop_path_masks=None):
         t = self._trunk(x, drop_path_masks)

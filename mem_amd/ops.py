@@ -10,6 +10,24 @@ import torch
 from ._lib import check, declare, f32, i32, i64, lib, ptr, stream_ptr, sz, vp
 
 EPI_BIAS_BF16, EPI_BIAS_GELU, EPI_RESIDUAL, EPI_DGELU, EPI_F32, EPI_PATCH_EMBED, EPI_BIAS_GELU_DG, EPI_MUL_AUX = range(8)
+EPI_RESIDUAL_DROP = 8
+
+
+class Dropout(C.Structure):
+    """== memhip_dropout_t (the mask contract: include/memhip.h)."""
+    _fields_ = [("key0", C.c_uint32), ("key1", C.c_uint32), ("site", C.c_uint32), ("thr", C.c_uint32), ("scale", f32),
+                ("row0", i32)]
+
+
+def dropout_params(key0, key1, site, p, row0=0):
+    """memhip_dropout_t of element-wise dropout with probability p (0 <= p < 1) at `site` under the key (key0, key1)."""
+    assert 0.0 <= p < 1.0, p
+    return Dropout(int(key0) & 0xFFFFFFFF, int(key1) & 0xFFFFFFFF, int(site), int(round(p * 65536)), 1.0 / (1.0 - p), int(row0))
+
+
+def with_row0(d, row0):
+    """The same dropout addressed from residual-stream row row0 (a buffer whose row 0 is that row)."""
+    return None if d is None else Dropout(d.key0, d.key1, d.site, d.thr, d.scale, int(row0))
 
 
 class GemmArgs(C.Structure):
@@ -20,7 +38,8 @@ class GemmArgs(C.Structure):
                 ("bias", vp), ("vec1", vp), ("resid", vp), ("ldr", i64),
                 ("aux", vp), ("ldaux", i64), ("rowmask", vp), ("keep_prob", f32),
                 ("colscale", f32), ("colscale_n", i32), ("rows_per_sample", i32), ("accumulate", i32),
-                ("colsum", vp), ("sample_map", vp), ("colsum_copies", i32), ("reserved0", i32)]
+                ("colsum", vp), ("sample_map", vp), ("colsum_copies", i32), ("reserved0", i32),
+                ("dropout", vp)]
 
 
 declare({"memhip_gemm_bf16_nt": (i32, [C.POINTER(GemmArgs), vp])})
@@ -44,9 +63,10 @@ def _timer_event():
 
 def gemm_nt(A, B, M, N, K, epi, out0=None, out1=None, bias=None, vec1=None, resid=None, aux=None,
             rowmask=None, keep_prob=1.0, colscale=1.0, colscale_n=0, rows_per_sample=1, accumulate=False, colsum=None,
-            lda=None, ldb=None, ldo0=None, ldo1=None, ldr=None, ldaux=None, sample_map=None, colsum_copies=0):
+            lda=None, ldb=None, ldo0=None, ldo1=None, ldr=None, ldaux=None, sample_map=None, colsum_copies=0, dropout=None):
     """C[M,N] = A[M,K] @ B[N,K]^T with a fused epilogue.  A/B bf16, row-major, K contiguous.
-    colsum_copies > 1: `colsum` is a zeroed [copies, N] workspace, folded into the bias gradient by colsum_fold."""
+    colsum_copies > 1: `colsum` is a zeroed [copies, N] workspace, folded into the bias gradient by colsum_fold.
+    dropout: a Dropout (epilogue EPI_RESIDUAL_DROP only)."""
     a = GemmArgs()
     a.A, a.B = _p(A), _p(B)
     a.lda = A.stride(0) if lda is None else lda
@@ -66,6 +86,7 @@ def gemm_nt(A, B, M, N, K, epi, out0=None, out1=None, bias=None, vec1=None, resi
     a.colsum = _p(colsum)
     a.sample_map = _p(sample_map)
     a.colsum_copies = colsum_copies
+    a.dropout = None if dropout is None else C.addressof(dropout)
     if GEMM_TIMER is None:
         check(lib.memhip_gemm_bf16_nt(C.byref(a), stream_ptr()), "gemm_bf16_nt")
     else:
@@ -125,7 +146,22 @@ declare({
     "memhip_adamw": (i32, [vp, vp, vp, vp, i64, vp, f64, f64, f64, f64, f64, i32, vp, f64, vp]),
     "memhip_transpose_cast_batched": (i32, [vp, vp, i32, i32, vp]),
     "memhip_adamw_groups": (i32, [vp, vp, vp, vp, i64, vp, vp, i32, f64, f64, f64, i32, vp, f64, vp]),
+    "memhip_branch_bwd_drop": (i32, [vp, i64, vp, i64, vp, vp, f32, i32, i32, i32, vp, i64, vp, vp, vp, C.POINTER(Dropout), vp]),
+    "memhip_layernorm_bwd_branch_drop": (i32, [vp, i64, vp, i64, i32, i32, vp, vp, vp, vp, i64, vp, vp, vp, i64, vp, vp, f32,
+                                               i32, vp, i64, vp, vp, vp, vp, C.POINTER(Dropout), vp]),
+    "memhip_dropout_mask": (i32, [C.POINTER(Dropout), i32, i32, i32, vp, vp]),
+    "memhip_dropout_rows_f32": (i32, [C.POINTER(Dropout), vp, i64, i32, i32, vp]),
 })
+
+
+def dropout_mask(d, row0, rows, cols, out):
+    """out u8 [rows, cols] = keep bits of residual-stream rows d.row0 + row0 .. (memhip_dropout_mask)."""
+    check(lib.memhip_dropout_mask(C.byref(d), row0, rows, cols, ptr(out), stream_ptr()), "dropout_mask")
+
+
+def dropout_rows(d, x, rows, D):
+    """x f32 [rows, D] *= keep * scale in place (pos_drop; and its backward on the gradient)."""
+    check(lib.memhip_dropout_rows_f32(C.byref(d), ptr(x), x.stride(0), rows, D, stream_ptr()), "dropout_rows_f32")
 
 
 def layernorm_fwd(x, gamma, beta, y, mean, rstd, R, D, eps=1e-6, row_idx=None):
@@ -140,9 +176,17 @@ def layernorm_bwd(dy, x, gamma, mean, rstd, dres, dgamma, dbeta, R, D, accumulat
 
 
 def layernorm_bwd_branch(dy, x, gamma, mean, rstd, dres, dgamma, dbeta, R, D, y_b, gamma_b, dy_b, dgamma_b, dbias_b,
-                         rowmask=None, keep_prob=1.0, rows_per_sample=1, in_map=None, out_map=None):
+                         rowmask=None, keep_prob=1.0, rows_per_sample=1, in_map=None, out_map=None, dropout=None):
     """layernorm_bwd(accumulate=True) + the branch_bwd that reads the updated dres, in one pass.  in_map / out_map (i32
-    [samples], -1 = dropped): work-skipping stochastic depth, dy / mean / rstd and dy_b then hold kept samples only."""
+    [samples], -1 = dropped): work-skipping stochastic depth, dy / mean / rstd and dy_b then hold kept samples only.
+    dropout: the Dropout of the branch whose gradient dy_b is (memhip_layernorm_bwd_branch_drop)."""
+    if dropout is not None:
+        check(lib.memhip_layernorm_bwd_branch_drop(
+            ptr(dy), dy.stride(0), ptr(x), x.stride(0), R, D, ptr(gamma), ptr(mean), ptr(rstd), ptr(dres), dres.stride(0),
+            ptr(dgamma), ptr(dbeta), ptr(y_b), y_b.stride(0) if y_b is not None else 0, ptr(gamma_b), ptr(rowmask), keep_prob,
+            rows_per_sample, ptr(dy_b), dy_b.stride(0), ptr(dgamma_b), ptr(dbias_b), ptr(in_map), ptr(out_map), C.byref(dropout),
+            stream_ptr()), "layernorm_bwd_branch_drop")
+        return
     check(lib.memhip_layernorm_bwd_branch_map(ptr(dy), dy.stride(0), ptr(x), x.stride(0), R, D, ptr(gamma), ptr(mean),
                                               ptr(rstd), ptr(dres), dres.stride(0), ptr(dgamma), ptr(dbeta), ptr(y_b),
                                               y_b.stride(0) if y_b is not None else 0, ptr(gamma_b), ptr(rowmask), keep_prob,
@@ -156,7 +200,12 @@ def layerscale_grad(W16, dW, bias, dbias, gamma, N, K, dgamma):
                                      N, K, ptr(dgamma), stream_ptr()), "layerscale_grad")
 
 
-def branch_bwd(dx, y, gamma, dy, dgamma, dbias, M, D, rowmask=None, keep_prob=1.0, rows_per_sample=1, out_map=None):
+def branch_bwd(dx, y, gamma, dy, dgamma, dbias, M, D, rowmask=None, keep_prob=1.0, rows_per_sample=1, out_map=None, dropout=None):
+    if dropout is not None:
+        check(lib.memhip_branch_bwd_drop(ptr(dx), dx.stride(0), ptr(y), y.stride(0) if y is not None else 0, ptr(gamma),
+                                         ptr(rowmask), keep_prob, rows_per_sample, M, D, ptr(dy), dy.stride(0), ptr(dgamma),
+                                         ptr(dbias), ptr(out_map), C.byref(dropout), stream_ptr()), "branch_bwd_drop")
+        return
     check(lib.memhip_branch_bwd_map(ptr(dx), dx.stride(0), ptr(y), y.stride(0) if y is not None else 0, ptr(gamma), ptr(rowmask),
                                     keep_prob, rows_per_sample, M, D, ptr(dy), dy.stride(0), ptr(dgamma), ptr(dbias),
                                     ptr(out_map), stream_ptr()), "branch_bwd")

@@ -564,6 +564,11 @@ class DropPathStream:
     def load_state(self, st):
         self._g().set_state(torch.as_tensor(st, dtype=torch.uint8).cpu())
 
+    def key(self):
+        """Two uint32 words: the per-step key of the element-wise dropout masks (memhip_dropout_t)."""
+        k = torch.randint(0, 1 << 32, (2,), dtype=torch.int64, generator=self._g())
+        return int(k[0]), int(k[1])
+
     def uniform(self, rows, B, device=None):
         u = torch.rand((rows, B), generator=self._g())
         if device is None:

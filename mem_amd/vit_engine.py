@@ -53,6 +53,8 @@ class ViTEngine:
         self.Kpe = self.C * self.ph * self.pw
         assert self.D % 64 == 0 and self.hidden % 64 == 0 and self.Kpe % 64 == 0, "GEMM K dims must be multiples of 64"
         self.has_pos = model.pos_embed is not None
+        # element-wise dropout of the finetuning model (pos_drop, proj_drop, Mlp.drop): p, and per step a key (forward_trunk)
+        self.drop_rate = float(getattr(model, "drop_rate", 0.0))
         self.window = tuple(pe.patch_shape)
         self.nrd = (2 * self.window[0] - 1) * (2 * self.window[1] - 1) + 3
         if model.rel_pos_bias is not None:
@@ -416,6 +418,15 @@ class ViTEngine:
         ridx = (dev[:, :B, None] * T + self._dp_ar[None, None, :]).view(J, B * T)
         return dict(n=kept_n, kidx=dev[:, :B + 256], cmap=dev[:, B + 256:2 * B + 256], drop=dev[:, 2 * B + 256:], ridx=ridx, B=B)
 
+    def _drop(self, site, row0=0):
+        """memhip_dropout_t of `site` (2i: attention branch of block i, 2i + 1: its MLP branch, 2 * depth: pos_drop) for this
+        step, addressed from residual-stream row row0; None when the step runs without dropout."""
+        cur = getattr(self, "cur", None)
+        key = cur.get("drop_key") if cur else None
+        if key is None:
+            return None
+        return ops.dropout_params(key[0], key[1], site, self.drop_rate, row0)
+
     def _copy_dropped(self, plan, j, src, dst, B):
         """Rows of the samples branch j dropped pass through unchanged: dst[sample] = src[sample]."""
         nd = B - plan["n"][j]
@@ -500,9 +511,10 @@ class ViTEngine:
         ops.gemm_nt(h1, self.W16(pre + "attn.qkv.weight", 3 * D, D), M, 3 * D, D, ops.EPI_BIAS_BF16,
                     out0=qkv, bias=self.P(pre + "attn.qkvbias3"), colscale=self.scale, colscale_n=D)
         ops.attn_fwd(qkv, Bs, T, D, self.heads, table, self.window, ao, a["lse"][b0:b1])
-        ops.gemm_nt(ao, self.W16(pre + "attn.proj.weight", D, D), M, D, D, ops.EPI_RESIDUAL, out0=None,
-                    bias=self.P(pre + "attn.proj.bias"), vec1=g1, resid=xmid, aux=xin, ldaux=D,
-                    rowmask=dp_masks[2 * i][b0:b1] if use_dp else None, keep_prob=keep, rows_per_sample=T)
+        da, dm = self._drop(2 * i, r0), self._drop(2 * i + 1, r0)        # (rows of the split half: row0 = r0)
+        ops.gemm_nt(ao, self.W16(pre + "attn.proj.weight", D, D), M, D, D, ops.EPI_RESIDUAL if da is None else ops.EPI_RESIDUAL_DROP,
+                    out0=None, bias=self.P(pre + "attn.proj.bias"), vec1=g1, resid=xmid, aux=xin, ldaux=D,
+                    rowmask=dp_masks[2 * i][b0:b1] if use_dp else None, keep_prob=keep, rows_per_sample=T, dropout=da)
         if tail is not None:
             self._mlp_fwd_tail(i, a, self.x[2 * i + 1], g2, keep, tail)
             return
@@ -510,9 +522,9 @@ class ViTEngine:
                           a["rstd2"][r0:r1], M, D)
         ops.gemm_nt(h2, self.W16(pre + "mlp.fc1.weight", Hd, D), M, Hd, D, self.epi_gelu, out0=hpre,
                     out1=aa, bias=self.P(pre + "mlp.fc1.bias"))
-        ops.gemm_nt(aa, self.W16(pre + "mlp.fc2.weight", D, Hd), M, D, Hd, ops.EPI_RESIDUAL, out0=None,
-                    bias=self.P(pre + "mlp.fc2.bias"), vec1=g2, resid=xout, aux=xmid, ldaux=D,
-                    rowmask=dp_masks[2 * i + 1][b0:b1] if use_dp else None, keep_prob=keep, rows_per_sample=T)
+        ops.gemm_nt(aa, self.W16(pre + "mlp.fc2.weight", D, Hd), M, D, Hd, ops.EPI_RESIDUAL if dm is None else ops.EPI_RESIDUAL_DROP,
+                    out0=None, bias=self.P(pre + "mlp.fc2.bias"), vec1=g2, resid=xout, aux=xmid, ldaux=D,
+                    rowmask=dp_masks[2 * i + 1][b0:b1] if use_dp else None, keep_prob=keep, rows_per_sample=T, dropout=dm)
 
     def _mlp_fwd_tail(self, i, a, xmid, g2, keep, tail):
         """MLP branch of the LAST block on the rows that reach the head only (forward(): tail rows): norm2 on the gathered
@@ -522,6 +534,7 @@ class ViTEngine:
         pre = f"blocks.{i}."
         rows, Mm = tail["rows"], tail["Mm"]
         Mp = _pad(Mm, 256)
+        assert self._drop(0) is None, "the tail-row form of the last block is pretraining-only: no element-wise dropout"
         ops.layernorm_fwd(xmid, self.P(pre + "norm2.weight"), self.P(pre + "norm2.bias"), a["h2"], a["mean2"], a["rstd2"],
                           Mm, D, row_idx=rows)
         ops.gemm_nt(a["h2"], self.W16(pre + "mlp.fc1.weight", Hd, D), Mp, Hd, D, self.epi_gelu, out0=a["hpre"],
@@ -550,9 +563,11 @@ class ViTEngine:
             ops.gemm_nt(a["h1"], self.W16(pre + "attn.qkv.weight", 3 * D, D), M1p, 3 * D, D, ops.EPI_BIAS_BF16,
                         out0=a["qkv"], bias=self.P(pre + "attn.qkvbias3"), colscale=self.scale, colscale_n=D)
             ops.attn_fwd(a["qkv"], na, T, D, self.heads, table, self.window, a["ao"], a["lse"])
-            ops.gemm_nt(a["ao"], self.W16(pre + "attn.proj.weight", D, D), M1p, D, D, ops.EPI_RESIDUAL, out0=None,
+            da = self._drop(2 * i)                  # (the epilogue keys the mask on the residual row the sample map resolves)
+            ops.gemm_nt(a["ao"], self.W16(pre + "attn.proj.weight", D, D), M1p, D, D,
+                        ops.EPI_RESIDUAL if da is None else ops.EPI_RESIDUAL_DROP, out0=None,
                         bias=self.P(pre + "attn.proj.bias"), vec1=g1, resid=xmid, aux=xin, ldaux=D,
-                        keep_prob=keep if smap is not None else 1.0, rows_per_sample=T, sample_map=smap)
+                        keep_prob=keep if smap is not None else 1.0, rows_per_sample=T, sample_map=smap, dropout=da)
         if tail is not None:                                  # last block: the rows that reach the head, every sample
             self._mlp_fwd_tail(i, a, self.x[2 * i + 1], g2, keep, tail)      # (dropped samples: keep flag 0 per row)
             return
@@ -568,13 +583,17 @@ class ViTEngine:
                               M2, D, row_idx=ridx)
             ops.gemm_nt(a["h2"], self.W16(pre + "mlp.fc1.weight", Hd, D), M2p, Hd, D, self.epi_gelu, out0=a["hpre"],
                         out1=a["a"], bias=self.P(pre + "mlp.fc1.bias"))
-            ops.gemm_nt(a["a"], self.W16(pre + "mlp.fc2.weight", D, Hd), M2p, D, Hd, ops.EPI_RESIDUAL, out0=None,
+            dm = self._drop(2 * i + 1)
+            ops.gemm_nt(a["a"], self.W16(pre + "mlp.fc2.weight", D, Hd), M2p, D, Hd,
+                        ops.EPI_RESIDUAL if dm is None else ops.EPI_RESIDUAL_DROP, out0=None,
                         bias=self.P(pre + "mlp.fc2.bias"), vec1=g2, resid=xout, aux=xmid, ldaux=D,
-                        keep_prob=keep if smap is not None else 1.0, rows_per_sample=T, sample_map=smap)
+                        keep_prob=keep if smap is not None else 1.0, rows_per_sample=T, sample_map=smap, dropout=dm)
 
-    def forward_trunk(self, x, mask_u8=None, dp_masks=None, tail_rows=None):
+    def forward_trunk(self, x, mask_u8=None, dp_masks=None, tail_rows=None, drop_key=None):
         """Patch embedding (+ mask-token blend, + abs. position embedding) and the blocks: x f32 [B,C,H,W] ->
-        the fp32 residual stream after the last block, [B*T, D] (engine-owned, valid until the next forward)."""
+        the fp32 residual stream after the last block, [B*T, D] (engine-owned, valid until the next forward).
+        drop_key: (key0, key1) of this step's element-wise dropout masks (finetuning model, drop_rate > 0), or None."""
+        assert drop_key is None or (self.drop_rate > 0.0 and tail_rows is None), "dropout: finetuning trunk only"
         assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous()
         B = x.shape[0]
         assert tuple(x.shape[1:]) == (self.C, self.H, self.W), \
@@ -592,7 +611,7 @@ class ViTEngine:
         plan = self._dp_plan(dp_masks, B)
         if plan is not None:
             dp_masks = None                                  # the plan replaces the keep masks everywhere below
-        self.cur = dict(B=B, M=M, Mm=0, mask=mask_u8, rows=None, dp=dp_masks, labels=None, plan=plan, tail=None)
+        self.cur = dict(B=B, M=M, Mm=0, mask=mask_u8, rows=None, dp=dp_masks, labels=None, plan=plan, tail=None, drop_key=drop_key)
         if tail_rows is not None and not self.fwd_two_streams:
             # per compact row: did the last block's MLP branch keep the row's sample?  (stochastic depth of that branch is
             # applied per row in the tail form, in both the masked and the work-skipping mode)
@@ -618,6 +637,9 @@ class ViTEngine:
                     resid=x0, aux=mask_u8, rows_per_sample=L, ldaux=0)
         if self.has_pos:
             x0[:M].view(B, T, D).add_(self.P("pos_embed").view(1, T, D))
+        dpos = self._drop(2 * self.depth)
+        if dpos is not None:                                 # pos_drop (mem/modeling_finetune.py:343)
+            ops.dropout_rows(dpos, x0, M, D)
         # Two sample-halves on two HIP streams (forward ops are independent per sample): the halves' persistent GEMM
         # launches interleave on the CUs, so the workgroups of one launch fill the partial last round of the other and
         # the HBM-bound epilogue phase of one half runs beside the MFMA-bound main loop of the other.  Same kernels on
@@ -836,6 +858,7 @@ class ViTEngine:
         D, Hd = self.D, self.hidden
         rows, Mm, rk = tail["rows"], tail["Mm"], tail["rowkeep"]
         Mp = _pad(Mm, 256)
+        assert self._drop(0) is None, "the tail-row form of the last block is pretraining-only: no element-wise dropout"
         dx, dY = self.dx, self.dY
         self._before_overwrite("dY")
         ops.branch_bwd(self.dxc, None, self.P(pre + "gamma_2") if has_g else None, dY, None, self.G(pre + "mlp.fc2.bias"),
@@ -898,7 +921,7 @@ class ViTEngine:
             if tail is None and (i == self.depth - 1 or not fuse):
                 self._before_overwrite("dY")
                 ops.branch_bwd(dx, None, self.P(pre + "gamma_2") if has_g else None, dY, None, self.G(pre + "mlp.fc2.bias"),
-                               M, D, keep_prob=kp(jm, i), rows_per_sample=T, out_map=cmap(jm))
+                               M, D, keep_prob=kp(jm, i), rows_per_sample=T, out_map=cmap(jm), dropout=self._drop(jm))
             if tail is None and nm == 0 and not self.accumulate_grads:
                 self._zero_grad_of(pre + "mlp.fc1.weight")      # every sample dropped this branch: zero, not last step's
                 self._zero_grad_of(pre + "mlp.fc2.weight")
@@ -923,7 +946,8 @@ class ViTEngine:
                                          self.G(pre + "norm2.weight"), self.G(pre + "norm2.bias"), M, D, None,
                                          self.P(pre + "gamma_1") if has_g else None, dY2, None, scr,
                                          keep_prob=kp(ja, i), rows_per_sample=T,
-                                         in_map=cmap(jm) if cmap(jm) is not None else None, out_map=cmap(ja))
+                                         in_map=cmap(jm) if cmap(jm) is not None else None, out_map=cmap(ja),
+                                         dropout=self._drop(ja))
             else:
                 if nm > 0:
                     ops.layernorm_bwd(self.dh_small, xmid, self.P(pre + "norm2.weight"), a["mean2"], a["rstd2"], dx,
@@ -931,7 +955,7 @@ class ViTEngine:
                                       row_idx=ridx(jm))
                 self._before_overwrite("dY2")
                 ops.branch_bwd(dx, None, self.P(pre + "gamma_1") if has_g else None, dY2, None, scr, M, D,
-                               keep_prob=kp(ja, i), rows_per_sample=T, out_map=cmap(ja))
+                               keep_prob=kp(ja, i), rows_per_sample=T, out_map=cmap(ja), dropout=self._drop(ja))
             # -- attention branch
             if na == 0 and not self.accumulate_grads:
                 self._zero_grad_of(pre + "attn.proj.weight")
@@ -975,7 +999,8 @@ class ViTEngine:
                 ops.layernorm_bwd_branch(self.dh_small, xin, self.P(pre + "norm1.weight"), a["mean1"], a["rstd1"], dx,
                                          self.G(pre + "norm1.weight"), self.G(pre + "norm1.bias"), M, D, None,
                                          self.P(pb + "gamma_2") if has_gb else None, dY, None, self.G(pb + "mlp.fc2.bias"),
-                                         keep_prob=kp(jb, i - 1), rows_per_sample=T, in_map=cmap(ja), out_map=cmap(jb))
+                                         keep_prob=kp(jb, i - 1), rows_per_sample=T, in_map=cmap(ja), out_map=cmap(jb),
+                                         dropout=self._drop(jb))
             elif na > 0:
                 ops.layernorm_bwd(self.dh_small, xin, self.P(pre + "norm1.weight"), a["mean1"], a["rstd1"], dx,
                                   self.G(pre + "norm1.weight"), self.G(pre + "norm1.bias"), M1, D, accumulate=True,
@@ -1023,7 +1048,8 @@ class ViTEngine:
                     self._before_overwrite("dY")
                     ops.branch_bwd(dx, None, self.P(pre + "gamma_2") if has_g else None, dY,
                                    None, self.G(pre + "mlp.fc2.bias"), M, D,
-                                   rowmask=dp_masks[2 * i + 1] if use_dp else None, keep_prob=keep, rows_per_sample=T)
+                                   rowmask=dp_masks[2 * i + 1] if use_dp else None, keep_prob=keep, rows_per_sample=T,
+                                   dropout=self._drop(2 * i + 1))
                 self._before_overwrite("dbig")
                 # fc1 bias grad = column sums of dh, accumulated in CS_COPIES copies (one per XCD: atomics on one address
                 # serialise and would sit in front of the GEMM's operand stream) and folded by a 3 us kernel
@@ -1042,7 +1068,8 @@ class ViTEngine:
                     ops.layernorm_bwd_branch(self.dh_small, xmid, self.P(pre + "norm2.weight"), a["mean2"], a["rstd2"], dx,
                                              self.G(pre + "norm2.weight"), self.G(pre + "norm2.bias"), M, D, None,
                                              self.P(pre + "gamma_1") if has_g else None, dY2, None, scr,
-                                             rowmask=dp_masks[2 * i] if use_dp else None, keep_prob=keep, rows_per_sample=T)
+                                             rowmask=dp_masks[2 * i] if use_dp else None, keep_prob=keep, rows_per_sample=T,
+                                             dropout=self._drop(2 * i))
                 else:
                     ops.layernorm_bwd(self.dh_small, xmid, self.P(pre + "norm2.weight"), a["mean2"], a["rstd2"], dx,
                                       self.G(pre + "norm2.weight"), self.G(pre + "norm2.bias"), M, D, accumulate=True)
@@ -1054,7 +1081,8 @@ class ViTEngine:
                 if not fuse:
                     self._before_overwrite("dY2")
                     ops.branch_bwd(dx, None, self.P(pre + "gamma_1") if has_g else None, dY2, None, scr, M, D,
-                                   rowmask=dp_masks[2 * i] if use_dp else None, keep_prob=keep, rows_per_sample=T)
+                                   rowmask=dp_masks[2 * i] if use_dp else None, keep_prob=keep, rows_per_sample=T,
+                                   dropout=self._drop(2 * i))
             ops.gemm_nt(dY2, self.wT[i]["proj"], M, D, D, ops.EPI_BIAS_BF16, out0=self.dao)
             ops.gemv_acc(self.wT[i]["proj"], D, D, scr, self.G(pre + "attn.v_bias"),
                          x_acc=self.G(pre + "attn.proj.bias"), zero=self.bias_scr[(i & 1) ^ 1])
@@ -1095,7 +1123,7 @@ class ViTEngine:
                                          self.P(pb + "gamma_2") if has_gb else None, dY, None,
                                          self.G(pb + "mlp.fc2.bias"),
                                          rowmask=dp_masks[2 * (i - 1) + 1] if use_dpb else None,
-                                         keep_prob=1.0 - bb_.drop_prob, rows_per_sample=T)
+                                         keep_prob=1.0 - bb_.drop_prob, rows_per_sample=T, dropout=self._drop(2 * (i - 1) + 1))
             else:
                 ops.layernorm_bwd(self.dh_small, xin, self.P(pre + "norm1.weight"), a["mean1"], a["rstd1"], dx,
                                   self.G(pre + "norm1.weight"), self.G(pre + "norm1.bias"), M, D, accumulate=True)
@@ -1106,6 +1134,9 @@ class ViTEngine:
         D, T, L = self.D, self.T, self.L
         dx = self.dx
         # ---- embedding
+        dpos = self._drop(2 * self.depth)
+        if dpos is not None:                                 # pos_drop backward: pos_embed / cls / patch gradients see the mask
+            ops.dropout_rows(dpos, dx, M, D)
         if self.has_pos:
             if self.accumulate_grads:
                 self.G("pos_embed").view(T, D).add_(dx[:M].view(B, T, D).sum(0))

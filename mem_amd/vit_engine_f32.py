@@ -19,6 +19,7 @@ class ViTEngineF32(ViTEngine):
     precision = "fp32"
 
     def __init__(self, model):
+        assert getattr(model, "drop_rate", 0.0) == 0.0, "element-wise dropout is not part of the fp32 parity engine (bf16 engine only)"
         super().__init__(model)
         assert self.head_kind == "mlm", "fp32 parity mode covers the pretraining model"
         m = model
