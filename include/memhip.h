@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define MEMHIP_ABI_VERSION 6   /* 6: element-wise dropout (memhip_dropout_t, epilogue RESIDUAL_DROP, memhip_gemm_args_t.dropout, the
+#define MEMHIP_ABI_VERSION 7   /* 7: the finetuning recipe (memhip_mixup, memhip_mix_targets, memhip_ce_soft, memhip_ema_update); 6: element-wise dropout (memhip_dropout_t, epilogue RESIDUAL_DROP, memhip_gemm_args_t.dropout, the
                                   *_drop row kernels); 5 (round 6): memhip_build_flags, memhip_attn_bwd_ws / _out_ws / _workspace; 4 (round 5): epilogues 6 / 7 carry the stored GELU derivative as FP16 (since round 4), certified-tokenizer entry points */
 
 #define MEMHIP_OK 0
@@ -754,6 +754,39 @@ int memhip_adamw(float* p, const float* g, float* m, float* v, int64_t n, const 
 int memhip_adamw_groups(float* p, const float* g, float* m, float* v, int64_t n, const uint8_t* group_of_chunk,
                         const float* group_table, int n_groups, double beta1, double beta2, double eps, int step,
                         const float* gnorm, double max_norm, memhip_stream_t stream);
+
+/* ------------------------------------------------------------------------
+ * Finetuning recipe around the ViT step (finetune_recipe.hip)
+ * replaces timm.data.Mixup (mixup 0.8 / cutmix 1.0)                  mem/run_class_finetuning.py:504-511
+ *          timm.loss.SoftTargetCrossEntropy / LabelSmoothingCrossEntropy   mem/run_class_finetuning.py:609-613
+ *          timm.utils.ModelEma.update                                 mem/run_class_finetuning.py:519-527, mem/engine_for_finetuning.py:127-128
+ * ------------------------------------------------------------------------
+ * mixup: x f32 [B, C, H, W] mixed IN PLACE with the flipped batch as it was before the call (sample i with sample B-1-i):
+ *   lam f32 [B], box i32 [B, 4] = (yl, yh, xl, xh) per sample (device).  A box without area: out[i] = lam[i] * x[i] +
+ *   (1 - lam[i]) * x[B-1-i] (lam[i] == 1: sample i is left untouched bit for bit); otherwise out[i] = x[B-1-i] inside the box
+ *   and x[i] outside it (exact copies).  One work-item owns the same elements of both samples of a pair, so no scratch copy of
+ *   the batch exists; 16-byte accesses when C*H*W is a multiple of 4 and x is 16-byte aligned (any shape otherwise).
+ *   lam_host / box_host (host, may be NULL): the same values, validated BEFORE the launch (lam in [0, 1],
+ *   0 <= yl <= yh <= H, 0 <= xl <= xh <= W) -- the parameters are drawn on the host, the device arrays are never read back. */
+int memhip_mixup(float* x, int B, int C, int H, int W, const float* lam, const int32_t* box, const float* lam_host,
+                 const int32_t* box_host, memhip_stream_t stream);
+/* timm.data.mixup.mixup_target: t f32 [B, V] (leading dimension ldt), t[i] = lam[i] * onehot(labels[i]) +
+ * (1 - lam[i]) * onehot(labels[B-1-i]), one-hot values off = smoothing / V and on = 1 - smoothing + off.  A label outside
+ * [0, V) is never used as an index; its row (and its partner's) is NaN, which the training loop's non-finite-loss stop reports. */
+int memhip_mix_targets(const int64_t* labels, const float* lam, int B, int V, double smoothing, float* t, int64_t ldt,
+                       memhip_stream_t stream);
+/* Cross-entropy against soft targets; logits [M, V] bf16 (logits_f32 = 0) or fp32 (1), ANY 2 <= V <= 8192, leading dimension ld.
+ *   target f32 [M, V] (ldt) given, labels NULL:   loss_r = -sum_c t_rc * log_softmax(x_r)_c           (SoftTargetCrossEntropy)
+ *   labels i64 [M] given, target NULL:            loss_r = (1 - s) * nll_r + s * mean_c(-log_softmax(x_r)_c), s = smoothing
+ *                                                 (LabelSmoothingCrossEntropy; no dense target is built; label outside [0, V): NaN)
+ * row_loss f32 [M], row_correct i32 [M] scratch; out2 f32 [2] = {mean loss, top-1 accuracy against the label / argmax_c t};
+ * write_grad: dlogits (dtype of the logits, leading dimension lddl, may BE the logits) = grad_scale * (softmax * sum_c t_rc - t_r). */
+int memhip_ce_soft(const void* logits, int logits_f32, int64_t ld, const float* target, int64_t ldt, const int64_t* labels,
+                   float smoothing, int M, int V, float grad_scale, void* dlogits, int64_t lddl, float* row_loss,
+                   int32_t* row_correct, int write_grad, float* out2, memhip_stream_t stream);
+/* ema[i] = decay * ema[i] + (1 - decay) * p[i] over n fp32 values (16-byte aligned buffers, any n): decay and 1 - decay are
+ * each rounded to fp32 from the double (timm's arithmetic: Python scalars times fp32 tensors), the update is fp32. */
+int memhip_ema_update(float* ema, const float* p, int64_t n, double decay, memhip_stream_t stream);
 
 #ifdef __cplusplus
 }

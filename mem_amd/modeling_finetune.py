@@ -188,7 +188,9 @@ class VisionTransformer(nn.Module):
                  drop_path_rate=0.0, norm_layer=nn.LayerNorm, init_values=None, use_abs_pos_emb=True,
                  use_rel_pos_bias=False, use_shared_rel_pos_bias=False, use_mean_pooling=True, init_scale=0.001,
                  use_batch_norm=False, **kwargs):
+        ctor = {k: v for k, v in locals().items() if k not in ("self", "kwargs", "__class__")}
         super().__init__()
+        self._ctor_kwargs = dict(ctor, **kwargs)     # utils.ModelEma builds its twin (own engine, own flat buffer) from these
         assert qkv_bias, "fused path: qkv_bias"
         assert attn_drop_rate == 0.0, ("attn_drop_rate > 0 needs dropout masks inside the fused attention kernels, which do not "
                                        "carry them (no reference config sets it)")

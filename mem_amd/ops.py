@@ -641,3 +641,55 @@ def nchw_to_padded_nhwc4_f16x2(x, out2, mean=None, std=None):
     B, Cc, H, W = x.shape
     check(lib.memhip_nchw_to_padded_nhwc4_f16x2(ptr(x), B, Cc, H, W, ptr(mean), ptr(std), ptr(out2), out2.stride(0), stream_ptr()),
           "nchw_to_padded_nhwc4_f16x2")
+
+
+# ---------------------------------------------------------------- finetuning recipe (csrc/finetune_recipe.hip)
+declare({
+    "memhip_mixup": (i32, [vp, i32, i32, i32, i32, vp, vp, vp, vp, vp]),
+    "memhip_mix_targets": (i32, [vp, vp, i32, i32, C.c_double, vp, i64, vp]),
+    "memhip_ce_soft": (i32, [vp, i32, i64, vp, i64, vp, f32, i32, i32, f32, vp, i64, vp, vp, i32, vp, vp]),
+    "memhip_ema_update": (i32, [vp, vp, i64, C.c_double, vp]),
+})
+
+
+def mixup(x, lam, box, lam_host=None, box_host=None):
+    """x f32 [B, C, H, W] mixed in place with its flipped self; lam f32 [B], box i32 [B, 4] (yl, yh, xl, xh) on the device;
+    lam_host / box_host: numpy copies of the same values, validated before the launch."""
+    assert x.dtype == torch.float32 and x.is_contiguous() and x.dim() == 4, "mixup: contiguous fp32 [B, C, H, W]"
+    assert lam.dtype == torch.float32 and box.dtype == torch.int32 and lam.numel() == x.shape[0] and box.numel() == 4 * x.shape[0]
+    B, Cc, H, W = x.shape
+    check(lib.memhip_mixup(ptr(x), B, Cc, H, W, ptr(lam), ptr(box),
+                           None if lam_host is None else lam_host.ctypes.data_as(vp),
+                           None if box_host is None else box_host.ctypes.data_as(vp), stream_ptr()), "mixup")
+
+
+def mix_targets(labels, lam, V, smoothing, out):
+    """out f32 [B, V] = lam * onehot(labels) + (1 - lam) * onehot(labels.flip(0)), smoothed one-hots (timm mixup_target)."""
+    assert labels.dtype == torch.int64 and labels.is_contiguous() and lam.dtype == torch.float32
+    assert out.dtype == torch.float32 and out.stride(1) == 1 and out.shape == (labels.numel(), V)
+    check(lib.memhip_mix_targets(ptr(labels), ptr(lam), labels.numel(), V, float(smoothing), ptr(out), out.stride(0),
+                                 stream_ptr()), "mix_targets")
+
+
+def ce_soft(logits, row_loss, row_correct, out2, target=None, labels=None, smoothing=0.0, grad_scale=1.0, dlogits=None):
+    """Soft-target (target f32 [M, V]) or label-smoothing (labels i64 [M]) cross-entropy of bf16 / fp32 logits [M, V], any
+    V >= 2; out2 = {mean loss, top-1 accuracy}; dlogits (may be the logits) = grad_scale * d(sum of row losses)/dlogits."""
+    assert logits.dtype in (torch.bfloat16, torch.float32) and logits.dim() == 2 and logits.stride(1) == 1
+    M, V = logits.shape
+    if target is not None:
+        assert target.dtype == torch.float32 and target.shape == (M, V) and target.stride(1) == 1
+    if labels is not None:
+        assert labels.dtype == torch.int64 and labels.numel() == M and labels.is_contiguous()
+    if dlogits is not None:
+        assert dlogits.dtype == logits.dtype and dlogits.shape == (M, V) and dlogits.stride(1) == 1
+    check(lib.memhip_ce_soft(ptr(logits), int(logits.dtype == torch.float32), logits.stride(0), ptr(target),
+                             target.stride(0) if target is not None else 0, ptr(labels), float(smoothing), M, V,
+                             float(grad_scale), ptr(dlogits), dlogits.stride(0) if dlogits is not None else 0,
+                             ptr(row_loss), ptr(row_correct), int(dlogits is not None), ptr(out2), stream_ptr()), "ce_soft")
+
+
+def ema_update(ema, p, decay):
+    """ema = decay * ema + (1 - decay) * p over two flat fp32 buffers of equal length."""
+    assert ema.dtype == torch.float32 and p.dtype == torch.float32 and ema.numel() == p.numel()
+    assert ema.is_contiguous() and p.is_contiguous()
+    check(lib.memhip_ema_update(ptr(ema), ptr(p), ema.numel(), float(decay), stream_ptr()), "ema_update")

@@ -252,6 +252,70 @@ class NativeScalerWithGradNormCount:
         pass
 
 
+class ModelEma:
+    """timm.utils.ModelEma (mem/run_class_finetuning.py:519-527; updated by engine_for_finetuning.train_one_epoch, evaluated and
+    checkpointed as ``model_ema.ema``): an exponential moving average of the model's weights,
+    ``ema = decay * ema + (1 - decay) * model`` after every optimizer step.
+
+    ``.ema`` is a second ``VisionTransformer`` in eval mode with its OWN fused engine; that engine's flat fp32 parameter
+    buffer IS the EMA, so one ``update`` is one ``memhip_ema_update`` launch over the two engines' flat buffers (12 bytes of
+    traffic per parameter) instead of timm's loop over the state dict, after which the EMA engine's bf16 weight shadows
+    are marked stale (they are re-cast when ``.ema`` is next evaluated, not per step).  Integer buffers (the
+    relative-position index tables) are COPIED, not averaged, like timm's ``ema_v.copy_(model_v)`` would leave them.
+    The twin is built from the model's constructor arguments and state dict (torch's RNG is not advanced), so it does not
+    matter whether the model's engine exists yet.  ``device='cpu'`` (timm's --model_ema_force_cpu) has no counterpart: this
+    project has no CPU path.  ``resume``: a checkpoint path whose 'model_ema' (or timm's 'state_dict_ema') entry is loaded."""
+
+    def __init__(self, model, decay=0.9999, device="", resume=""):
+        if device and torch.device(device).type == "cpu":
+            raise NotImplementedError("ModelEma(device='cpu'): the EMA is updated by a HIP kernel on the engine's flat parameter "
+                                      "buffer; mem_amd has no CPU path")
+        src = model.module if hasattr(model, "module") else model
+        if not hasattr(src, "_ctor_kwargs"):
+            raise NotImplementedError("ModelEma needs a modeling_finetune.VisionTransformer (ft_vit), got %s" % type(src).__name__)
+        with torch.random.fork_rng(devices=[]):                   # the twin's init draws must not shift the run's RNG stream
+            self.ema = type(src)(**src._ctor_kwargs)
+        if hasattr(src, "default_cfg"):
+            self.ema.default_cfg = src.default_cfg
+        self.ema.to(next(src.parameters()).device)
+        self.ema.load_state_dict(src.state_dict(), strict=True)
+        self.ema.eval()
+        for p in self.ema.parameters():
+            p.requires_grad_(False)
+        self.decay = decay
+        self.device = device
+        self._int_pairs = None
+        if resume:
+            self._load_checkpoint(resume)
+
+    def _load_checkpoint(self, checkpoint_path):
+        checkpoint = torch.load(checkpoint_path, map_location="cpu", weights_only=False)
+        for key in ("model_ema", "state_dict_ema"):
+            if key in checkpoint:
+                sd = {(k[7:] if k.startswith("module.") else k): v for k, v in checkpoint[key].items()}
+                self.ema.load_state_dict(sd, strict=True)
+                print("Loaded %s from %s" % (key, checkpoint_path))
+                return
+        print("No EMA weights in %s" % checkpoint_path)
+
+    @torch.no_grad()
+    def update(self, model):
+        from . import ops
+        src = model.module if hasattr(model, "module") else model
+        se, ee = src.engine, self.ema.engine
+        assert se.nflat == ee.nflat and se.segs == ee.segs, "ModelEma.update: the model's parameter layout changed"
+        se.wait_optimizer()                                        # (pipelined optimizer: its stream has written flat_p)
+        ops.ema_update(ee.flat_p, se.flat_p, self.decay)
+        ee.weights_dirty = True
+        if self._int_pairs is None:
+            mine = dict(self.ema.named_buffers())
+            self._int_pairs = [(mine[n], b) for n, b in src.named_buffers() if not b.dtype.is_floating_point]
+            floats = [n for n, b in src.named_buffers() if b.dtype.is_floating_point]
+            assert not floats, "ModelEma.update: floating-point buffers outside the flat parameter buffer: %s" % floats
+        if self._int_pairs:
+            torch._foreach_copy_([a for a, _ in self._int_pairs], [b for _, b in self._int_pairs])
+
+
 def get_grad_norm_(parameters, norm_type: float = 2.0) -> torch.Tensor:
     """utils.py:380-392 (generic helper, torch plumbing)."""
     if isinstance(parameters, torch.Tensor):
@@ -296,6 +360,8 @@ def save_model(args, epoch, model, model_without_ddp, optimizer, loss_scaler, mo
     dps = getattr(model_without_ddp, "_dp_stream", None)
     if dps is not None:
         to_save["drop_path_rng"] = gather_rank_states(dps.state())
+    if model_ema is not None:
+        to_save["model_ema"] = model_ema.ema.state_dict()          # the reference's key (utils.py:439-440)
     save_on_master(to_save, output_dir / ("checkpoint-%s.pth" % str(epoch)))
 
 
@@ -360,6 +426,10 @@ def auto_load_model(args, model, model_without_ddp, optimizer, loss_scaler, mode
             if was is not None and now is not None and was != now:
                 print(f"WARNING: checkpoint was trained with numerics {was}, this run uses {now}")
             print("With optim & sched!")
+        # utils.py:515 (timm's _load_checkpoint_for_ema): the EMA twin, when the run keeps one and the checkpoint has it
+        if model_ema is not None and getattr(args, "model_ema", False) and "model_ema" in checkpoint:
+            model_ema.ema.load_state_dict(checkpoint["model_ema"], strict=True)
+            print("Resume EMA weights from %s" % args.resume)
 
 
 def load_state_dict(model, state_dict, prefix="", ignore_missing="relative_position_index"):
