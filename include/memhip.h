@@ -35,7 +35,8 @@
 extern "C" {
 #endif
 
-#define MEMHIP_ABI_VERSION 7   /* 7: the finetuning recipe (memhip_mixup, memhip_mix_targets, memhip_ce_soft, memhip_ema_update); 6: element-wise dropout (memhip_dropout_t, epilogue RESIDUAL_DROP, memhip_gemm_args_t.dropout, the
+#define MEMHIP_ABI_VERSION 7   /* 7: the finetuning recipe (memhip_mixup, memhip_mix_targets, memhip_ce_soft, memhip_ema_update), and -- additive, no
+                                  existing signature changed, so the number stays -- memhip_pool_tokens / memhip_pool_tokens_bwd; 6: element-wise dropout (memhip_dropout_t, epilogue RESIDUAL_DROP, memhip_gemm_args_t.dropout, the
                                   *_drop row kernels); 5 (round 6): memhip_build_flags, memhip_attn_bwd_ws / _out_ws / _workspace; 4 (round 5): epilogues 6 / 7 carry the stored GELU derivative as FP16 (since round 4), certified-tokenizer entry points */
 
 #define MEMHIP_OK 0
@@ -787,6 +788,19 @@ int memhip_ce_soft(const void* logits, int logits_f32, int64_t ld, const float* 
 /* ema[i] = decay * ema[i] + (1 - decay) * p[i] over n fp32 values (16-byte aligned buffers, any n): decay and 1 - decay are
  * each rounded to fp32 from the double (timm's arithmetic: Python scalars times fp32 tensors), the update is fp32. */
 int memhip_ema_update(float* ema, const float* p, int64_t n, double decay, memhip_stream_t stream);
+
+/* ------------------------------------------------------------------------
+ * Token pooling of the finetuning head (pool.hip)
+ * replaces t[:, 1:, :].mean(1) in front of fc_norm                     mem/modeling_finetune.py:349-354
+ * ------------------------------------------------------------------------
+ * x f32 [B*T, ldx] (the residual stream, sample-major, ldx >= D), out f32 [B, D]:
+ *   out[b] = (sum over t = 1 .. T-1 of x[b*T + t]) / (T - 1)        (row 0 of a sample, the cls token, is skipped)
+ * fp32 accumulation in a fixed order (bit-reproducible), one read of x, no workspace, no atomics; T >= 2, any D
+ * (16-byte lane loads when D and ldx are multiples of 4 and both buffers are 16-byte aligned). */
+int memhip_pool_tokens(const float* x, int64_t ldx, int B, int T, int D, float* out, memhip_stream_t stream);
+/* Its backward: dx f32 [B*T, D] (dense), dx[b*T + t] = dout[b] / (T - 1) for t >= 1 (IEEE division) and 0 for t = 0;
+ * every element of dx is written. */
+int memhip_pool_tokens_bwd(const float* dout, int B, int T, int D, float* dx, memhip_stream_t stream);
 
 #ifdef __cplusplus
 }

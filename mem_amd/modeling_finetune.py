@@ -312,7 +312,29 @@ class VisionTransformer(nn.Module):
             st = self._dp_stream = DropPathStream()
         return st.key()
 
-    def _trunk(self, x, drop_path_masks=None):
+    _TAIL_PREFIXES = ("head.", "fc_norm.", "norm.")      # the torch tail behind the engine's trunk
+
+    def freeze_backbone(self):
+        """Linear probing (mem/run_class_finetuning.py:463-471): every parameter whose name contains none of ``pre_logits``,
+        ``head``, ``fc_norm`` stops requiring a gradient; returns the frozen names.  The model stays in ``train()`` mode when
+        trained (drop path and dropout still act, as in the reference); the trunk then runs forward-only (``_trunk_frozen``)."""
+        frozen = []
+        for name, param in self.named_parameters():
+            if all(n not in name for n in ("pre_logits", "head", "fc_norm")):
+                param.requires_grad = False
+                frozen.append(name)
+        return frozen
+
+    def _trunk_frozen(self):
+        """No trunk parameter requires a gradient (host-side, from the parameter flags; once per call)."""
+        return not any(p.requires_grad for n, p in self.named_parameters() if not n.startswith(self._TAIL_PREFIXES))
+
+    def _trunk(self, x, drop_path_masks=None, pool=False):
+        """The engine's trunk: the fp32 residual stream [B, T, D] (a copy).  ``pool`` (the mean-pooling form): a forward-only
+        call returns the patch-token mean [B, D] instead, taken straight from the engine's buffer (``ops.pool_tokens``); a
+        call whose trunk trains still returns the stream, for the caller's differentiable mean.  Forward-only (``ViTEngine.forward_trunk(keep=False)``: no
+        activation stash, no trunk backward) whenever no gradient can reach the trunk: eval mode, grad mode off, or a
+        frozen trunk.  A frozen trunk in train() mode still draws its drop-path masks and dropout key."""
         eng = self.engine
         x = x.to(device=eng.dev, dtype=torch.float32).contiguous()
         if self.training and drop_path_masks is None:
@@ -320,16 +342,29 @@ class VisionTransformer(nn.Module):
         drop_key = self.draw_dropout_key() if self.training else None
         if not self.training:
             drop_path_masks = None
-        if torch.is_grad_enabled() and self.training:
+        B = x.shape[0]
+        if torch.is_grad_enabled() and self.training and not self._trunk_frozen():
             if self._anchor is None:
                 self._anchor = torch.zeros(1, device=x.device, requires_grad=True)
             return _TrunkFunction.apply(self, x, drop_path_masks, drop_key, self._anchor)
-        B = x.shape[0]
-        return eng.forward_trunk(x, None, drop_path_masks, drop_key=drop_key)[: B * eng.T].view(B, eng.T, eng.D).clone()
+        if torch.is_grad_enabled() and self.training and any(
+                p.grad is None for n, p in self.named_parameters(recurse=True) if n.startswith(self._TAIL_PREFIXES)):
+            eng.attach_grads()               # the tail's autograd accumulates into the flat gradient buffer's views
+        xl = eng.forward_trunk(x, None, drop_path_masks, drop_key=drop_key, keep=False)
+        if pool:
+            from . import ops
+            return ops.pool_tokens(xl, B, eng.T)
+        return xl[: B * eng.T].view(B, eng.T, eng.D).clone()
 
     def forward_features(self, x, drop_path_masks=None):
-        t = self._trunk(x, drop_path_masks)
+        """Features in front of the head: [B, D] (fc_norm of the patch-token mean, or the normed cls token).  Under
+        ``eval()`` this is the supported feature-extraction call (frozen-backbone probing on stored features, retrieval):
+        the trunk runs forward-only and the mean is taken by ``memhip_pool_tokens`` on the engine's buffer -- no activation
+        stash, no copy of the residual stream."""
+        t = self._trunk(x, drop_path_masks, pool=self.fc_norm is not None)
         with torch.autocast("cuda", dtype=torch.bfloat16):
+            if t.dim() == 2:                       # already pooled (mean pooling: self.norm is the identity)
+                return self.fc_norm(t)
             t = self.norm(t)
             if self.fc_norm is not None:
                 return self.fc_norm(t[:, 1:, :].mean(1))

@@ -693,3 +693,33 @@ def ema_update(ema, p, decay):
     assert ema.dtype == torch.float32 and p.dtype == torch.float32 and ema.numel() == p.numel()
     assert ema.is_contiguous() and p.is_contiguous()
     check(lib.memhip_ema_update(ptr(ema), ptr(p), ema.numel(), float(decay), stream_ptr()), "ema_update")
+
+
+# ---------------------------------------------------------------- token pooling of the finetuning head (csrc/pool.hip)
+declare({
+    "memhip_pool_tokens": (i32, [vp, i64, i32, i32, i32, vp, vp]),
+    "memhip_pool_tokens_bwd": (i32, [vp, i32, i32, i32, vp, vp]),
+})
+
+
+def pool_tokens(x, B, T, out=None):
+    """x f32 [>= B*T, D] (row stride >= D) -> out f32 [B, D]: mean of each sample's rows 1 .. T-1 (the cls row is skipped;
+    modeling_finetune.py:349-354), fixed summation order."""
+    assert x.dtype == torch.float32 and x.dim() == 2 and x.stride(1) == 1 and x.shape[0] >= B * T
+    D = x.shape[1]
+    if out is None:
+        out = torch.empty((B, D), dtype=torch.float32, device=x.device)
+    assert out.dtype == torch.float32 and out.shape == (B, D) and out.is_contiguous()
+    check(lib.memhip_pool_tokens(ptr(x), x.stride(0), B, T, D, ptr(out), stream_ptr()), "pool_tokens")
+    return out
+
+
+def pool_tokens_bwd(dout, T, dx=None):
+    """dout f32 [B, D] -> dx f32 [B*T, D]: dout[b] / (T - 1) on the token rows, 0 on the cls rows (every element written)."""
+    assert dout.dtype == torch.float32 and dout.dim() == 2 and dout.is_contiguous()
+    B, D = dout.shape
+    if dx is None:
+        dx = torch.empty((B * T, D), dtype=torch.float32, device=dout.device)
+    assert dx.dtype == torch.float32 and dx.is_contiguous() and dx.numel() == B * T * D
+    check(lib.memhip_pool_tokens_bwd(ptr(dout), B, T, D, ptr(dx), stream_ptr()), "pool_tokens_bwd")
+    return dx

@@ -86,6 +86,11 @@ class FlatAdamW:
         # chunk -> group map for the grouped update (layer-wise lr decay); built lazily on the first step that needs it
         self._group_of_chunk = None
         self._group_table = None
+        # Frozen backbone (every parameter of the groups lies in the engine's head bucket, the front of the flat buffer): the
+        # update, the gradient norm and the bf16 re-cast run on [0, head_end) only -- the trunk's masters, moments and
+        # shadows are never read or written by a step
+        self._active_end, self._active_key = e.nflat, None
+        self._refresh_active_range()
         self.exp_avg = torch.zeros(e.nflat, dtype=torch.float32, device=e.dev)
         self.exp_avg_sq = torch.zeros(e.nflat, dtype=torch.float32, device=e.dev)
         self.steps = 0
@@ -96,9 +101,40 @@ class FlatAdamW:
         from . import ops
         if hasattr(self.engine, "wait_optimizer"):
             self.engine.wait_optimizer()          # a pipelined update may still be reading the gradients
-        ops.zero_(self.engine.flat_g)
+        # (a frozen trunk: nothing ever writes its gradient range, so only the head bucket is cleared)
+        ops.zero_(self.engine.flat_g[: self._active_end])
+
+    def _refresh_active_range(self):
+        """Where the parameters of the groups end in the flat buffer: head_end when all of them lie in the head bucket (a
+        frozen trunk), else everything.  Re-derived whenever the groups' parameter lists change (a parameter added to a
+        group later must not be skipped silently); the chunk -> group map is rebuilt with it."""
+        e = self.engine
+        key = tuple(id(p) for g in self.param_groups for p in g["params"])
+        if key == self._active_key:
+            return
+        self._active_key, self._active_end = key, e.nflat
+        self._group_of_chunk = None
+        if hasattr(self, "_flag_ok"):
+            del self._flag_ok
+        head_end = getattr(e, "head_end", None)
+        if head_end and getattr(e, "head_kind", "") == "cls":
+            assert head_end % 1024 == 0, "the head bucket ends on a chunk boundary (the chunk -> group map is sliced there)"
+            name_of = {id(p): n for n, p in e.named.items()}
+            ends = [sum(e.segs[name_of[id(p)]]) for g in self.param_groups for p in g["params"]]
+            if ends and max(ends) <= head_end:
+                self._active_end = head_end
+                # (a model trained unfrozen before: its trunk gradients are cleared once here; zero_grad() only clears the
+                # head range from now on, and nothing writes the rest)
+                from . import ops
+                ops.zero_(e.flat_g[head_end:])
+
+    def grad_norm(self):
+        e = self.engine
+        self._refresh_active_range()
+        return e.grad_norm() if self._active_end == e.nflat else e.grad_norm(self._active_end)
 
     def step(self):
+        self._refresh_active_range()
         lrs = {g["lr"] for g in self.param_groups}
         wdset = {g["weight_decay"] for g in self.param_groups if g["weight_decay"] > 0}
         g0 = self.param_groups[0]
@@ -148,10 +184,14 @@ class FlatAdamW:
         self._group_table.copy_(torch.from_numpy(tab), non_blocking=True)
         if hasattr(e, "wait_optimizer"):
             e.wait_optimizer()
-        ops.adamw_groups(e.flat_p, e.flat_g, self.exp_avg, self.exp_avg_sq, e.nflat, self._group_of_chunk, self._group_table,
-                         ng + 1, g0["betas"][0], g0["betas"][1], g0["eps"], self.steps, gnorm=e.gnorm,
+        n = self._active_end
+        ops.adamw_groups(e.flat_p[:n], e.flat_g[:n], self.exp_avg[:n], self.exp_avg_sq[:n], n, self._group_of_chunk[:n // 1024],
+                         self._group_table, ng + 1, g0["betas"][0], g0["betas"][1], g0["eps"], self.steps, gnorm=e.gnorm,
                          max_norm=self.max_norm or 0.0)
-        e.weights_dirty = True
+        if n == e.nflat:
+            e.weights_dirty = True
+        else:
+            e.weights_updated(n)
 
     # ---- torch-format state for checkpoints (utils.save_model / auto_load_model)
     def _param_list(self):

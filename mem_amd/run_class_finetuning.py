@@ -8,7 +8,8 @@ fused engine, ``utils.finetune``, layer-wise lr decay, cosine schedules, ``mixup
 
 Data: ``--data_set npy`` reads ``<data_path>/train|val/<class>/*.npy`` (label = index of the sorted class folder) through
 the event transform chain; ``--data_path synthetic`` uses seeded synthetic event streams with ``label = index % nb_classes``.
-Flags of the reference that this path does not carry PARSE and then raise a one-line NotImplementedError naming the flag
+``--freeze_backbone 1`` is the reference's linear-probing protocol: only ``head`` / ``fc_norm`` train and the engine runs
+the trunk forward-only (no activation stash, no backward).  Flags of the reference that this path does not carry PARSE and then raise a one-line NotImplementedError naming the flag
 when set away from the value that turns them off (``REFUSED``); nothing is silently ignored.  Three defaults therefore
 differ from the reference's, whose own defaults select torchvision-side features: ``--aa`` (None instead of
 rand-m9-mstd0.5-inc1), ``--reprob`` (0 instead of 0.25) and ``--num_workers`` (0: the event chain runs on the GPU in this
@@ -30,8 +31,7 @@ from .run_mem_pretraining import _config_file_args
 # flag -> (value that turns it off, why it is refused)
 REFUSED = {
     "enable_deepspeed": (False, "the deepspeed branch is not part of the fused path"),
-    "linear_probe": (False, "the linear-probe / batch-norm head is not carried"),
-    "freeze_backbone": (0, "the linear-probe / batch-norm head is not carried"),
+    "linear_probe": (False, "the BatchNorm head it stands for (use_batch_norm) is not carried"),
     "attn_drop_rate": (0.0, "the fused attention kernels carry no dropout masks"),
     "model_ema_force_cpu": (False, "the EMA lives in the engine's flat device buffer; there is no CPU path"),
     "aa": (None, "torchvision / timm auto-augment belongs to the image dataset builders"),
@@ -270,6 +270,13 @@ def main(args):
     args.window_size = model.patch_embed.patch_shape
     if args.finetune:
         utils.finetune(args, model)
+    if args.freeze_backbone:
+        # linear probing (mem/run_class_finetuning.py:463-471): head / fc_norm train, the trunk runs forward-only.  Applied from
+        # args on every start, so a resumed run comes back frozen; nothing about it is stored in the checkpoint.
+        frozen = set(model.freeze_backbone())
+        for name, _ in model.named_parameters():
+            print(f"{'froze' if name in frozen else 'kept'} {name}")
+        print("Linear probing: the backbone is frozen (%d tensors), the trunk runs forward-only" % len(frozen))
     model.to(device)
     model_ema = None
     if args.model_ema:

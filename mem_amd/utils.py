@@ -235,7 +235,7 @@ class NativeScalerWithGradNormCount:
             if poison is not None and hasattr(reducer, "sync_flag"):
                 reducer.sync_flag(poison)          # the flag is GLOBAL before it gates the update (every rank skips, every rank raises)
             reducer.finish()
-        norm = optimizer.engine.grad_norm()
+        norm = optimizer.grad_norm() if hasattr(optimizer, "grad_norm") else optimizer.engine.grad_norm()
         if poison is not None:
             # a sample of this batch was flagged by the transform chain (the reference raises inside the transform, before
             # the sample reaches the model): a non-finite norm makes the update kernel skip this step on the device

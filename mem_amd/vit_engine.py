@@ -69,6 +69,7 @@ class ViTEngine:
         if hasattr(model, "register_state_dict_pre_hook"):
             model.register_state_dict_pre_hook(lambda *_a, **_k: self.wait_optimizer())
         self.B = 0
+        self.B_stash = 0                 # batch size the backward-only buffers are allocated for (_alloc_stash)
         self.step_masks = None
         self.weights_dirty = True
         self._zero_plans = {}
@@ -256,12 +257,19 @@ class ViTEngine:
         self.epi_gelu, self.epi_dgelu = (ops.EPI_BIAS_GELU_DG, ops.EPI_MUL_AUX) if on else (ops.EPI_BIAS_GELU, ops.EPI_DGELU)
 
     # ------------------------------------------------------------------ buffers per batch size
-    def ensure_batch(self, B, Mm_max):
+    def ensure_batch(self, B, Mm_max, keep=True):
         """Buffers for a batch of B samples with Mm_max rows reaching the head.  The two grow independently: the number of
         masked rows differs from step to step (block-wise masks), and a new maximum must not re-allocate (and zero-fill) the
-        ~100 per-block buffers of the batch -- found in the round-4 step trace as ~80 torch fill kernels inside a step."""
+        ~100 per-block buffers of the batch -- found in the round-4 step trace as ~80 torch fill kernels inside a step.
+        keep: the forward is followed by a backward, which also needs the per-block stash and the backward temporaries
+        (_alloc_stash); a model that only ever runs forward-only (forward_trunk(keep=False)) never allocates them.  Both sets
+        are sized for the LARGEST batch seen so far (self.B), as the single set was before: a training run that evaluates
+        at 1.5 x its batch size carries a stash of 1.5 x the training batch from the first training forward after that
+        evaluation on."""
         if B > self.B:
-            self._alloc_batch(B)
+            self._alloc_forward(B)
+        if keep and self.B_stash < self.B:
+            self._alloc_stash()
         if Mm_max > getattr(self, "Mm_cap", 0) or (self.head_kind == "mlm" and not hasattr(self, "hN")):
             # headroom: a few per cent above the largest count seen, whole 256-row tiles, never more than every patch
             self._alloc_head(min(self.B * self.L, _pad(Mm_max + Mm_max // 16 + 1, 256)))
@@ -282,27 +290,50 @@ class ViTEngine:
             self.y_tail = torch.zeros((_pad(max(Mm_cap, 1), 256), D), dtype=bf, device=dev)
         self.Mm_cap = Mm_cap
 
-    def _alloc_batch(self, B):
+    def _act_set(self, B):
+        """One block's activations for B samples (36 bytes per token-feature with Hd = 4 D): what a forward writes."""
         dev, bf, f32 = self.dev, torch.bfloat16, torch.float32
-        D, Hd, T = self.D, self.hidden, self.T
+        D, Hd, M = self.D, self.hidden, B * self.T
+        Ma = M + 256
+        e = lambda *s, dt=bf: torch.empty(s, dtype=dt, device=dev)   # noqa: E731
+        z = lambda *s, dt=bf: torch.zeros(s, dtype=dt, device=dev)   # noqa: E731
+        return dict(h1=z(Ma, D), qkv=z(Ma, 3 * D), ao=z(Ma, D), h2=z(Ma, D), hpre=z(Ma, Hd),
+                    a=z(Ma, Hd), lse=e(B, self.heads, self.TP, dt=f32),
+                    mean1=e(M, dt=f32), rstd1=e(M, dt=f32), mean2=e(M, dt=f32), rstd2=e(M, dt=f32))
+
+    def _alloc_forward(self, B):
+        """What a forward of B samples needs and nothing else: the patch matrix, THREE residual buffers (a block reads
+        x_in, writes x_mid and x_out) and ONE activation set.  A forward-only run (forward_trunk(keep=False)) rotates
+        all blocks through them; a training forward uses them as the first three snapshots and block 0's set of the stash
+        (_alloc_stash), so nothing is held twice."""
+        dev, f32 = self.dev, torch.float32
+        D, T = self.D, self.T
         M = B * T
         # Work-skipping stochastic depth runs the GEMMs of a branch on its kept samples' rows ROUNDED UP to whole 256-row
         # tiles (a ragged row count costs every product an extra launch on the 128-row kernel): the token-major buffers
         # carry 256 rows of slack (zero-initialised, only ever finite), and the residual snapshots one dummy sample that the
         # padded rows' residual updates go to (sample index B in the sample map)
+        self.patches = torch.empty((B * self.L, self.Kpe), dtype=torch.bfloat16, device=dev)
+        self.x = [torch.zeros((M + T, D), dtype=f32, device=dev) for _ in range(3)]
+        self.act = [self._act_set(B)]
+        if self.head_kind != "mlm":
+            self.zero_mask = torch.zeros(B * self.L, dtype=torch.uint8, device=dev)
+        for name in ("dx", "dY", "dh_small", "dY2", "dbig", "dqkv", "dao", "delta_ws", "_tn_ws", "bias_scr", "cs_ws", "dYpe"):
+            if hasattr(self, name):          # the smaller batch's backward temporaries: freed now, re-made by _alloc_stash
+                delattr(self, name)
+        self.B, self.B_stash = B, 0
+
+    def _alloc_stash(self):
+        """What only a backward needs, on the first training forward of a batch size: the other 2 * depth - 2 residual
+        snapshots and depth - 1 activation sets (the stash), and the backward temporaries shared by all blocks."""
+        dev, bf, f32 = self.dev, torch.bfloat16, torch.float32
+        D, Hd, T, B = self.D, self.hidden, self.T, self.B
+        M = B * T
         Ma = M + 256
         e = lambda *s, dt=bf: torch.empty(s, dtype=dt, device=dev)   # noqa: E731
         z = lambda *s, dt=bf: torch.zeros(s, dtype=dt, device=dev)   # noqa: E731
-        self.patches = e(B * self.L, self.Kpe)
-        self.x = [torch.zeros((M + T, D), dtype=f32, device=dev) for _ in range(2 * self.depth + 1)]
-        self.act = []
-        for _ in range(self.depth):
-            self.act.append(dict(h1=z(Ma, D), qkv=z(Ma, 3 * D), ao=z(Ma, D), h2=z(Ma, D), hpre=z(Ma, Hd),
-                                 a=z(Ma, Hd), lse=e(B, self.heads, self.TP, dt=f32),
-                                 mean1=e(M, dt=f32), rstd1=e(M, dt=f32), mean2=e(M, dt=f32), rstd2=e(M, dt=f32)))
-        if self.head_kind != "mlm":
-            self.zero_mask = torch.zeros(B * self.L, dtype=torch.uint8, device=dev)
-        # backward temporaries (shared by all blocks)
+        self.x += [torch.zeros((M + T, D), dtype=f32, device=dev) for _ in range(2 * self.depth + 1 - len(self.x))]
+        self.act += [self._act_set(B) for _ in range(self.depth - len(self.act))]
         self.dx = torch.zeros((M, D), dtype=f32, device=dev)
         self.dY, self.dh_small = z(Ma, D), z(Ma, D)
         self.dY2 = z(Ma, D)                                   # attention-branch twin of dY (the side stream reads both)
@@ -314,7 +345,7 @@ class ViTEngine:
         self.bias_scr = torch.zeros(2, D, dtype=f32, device=dev)   # ping-pong colsum(dY) of the proj branch
         self.cs_ws = torch.zeros(self.CS_COPIES, self.hidden, dtype=f32, device=dev)   # column-sum accumulator copies (zero between uses)
         self.dYpe = e(B * self.L, D)
-        self.B = B
+        self.B_stash = B
 
     # ------------------------------------------------------------------ weights
     def sync_weights(self):
@@ -491,12 +522,13 @@ class ViTEngine:
         r0, r1 = b0 * T, b1 * T
         M, Bs = r1 - r0, b1 - b0
         pre = f"blocks.{i}."
-        a = self.act[i]
+        xs = self.cur["x"]
+        a = self.cur["act"][i]
         table = self.table(i)
         blk = self.model.blocks[i]
         keep = 1.0 - blk.drop_prob
         use_dp = dp_masks is not None and blk.drop_prob > 0.0
-        xin, xmid, xout = self.x[2 * i][r0:r1], self.x[2 * i + 1][r0:r1], self.x[2 * i + 2][r0:r1]
+        xin, xmid, xout = xs[2 * i][r0:r1], xs[2 * i + 1][r0:r1], xs[2 * i + 2][r0:r1]
         g1 = self.P(pre + "gamma_1") if (pre + "gamma_1") in self.segs else None
         g2 = self.P(pre + "gamma_2") if (pre + "gamma_2") in self.segs else None
         h1, qkv, ao, h2, hpre, aa = (a[k][r0:r1] for k in ("h1", "qkv", "ao", "h2", "hpre", "a"))
@@ -516,7 +548,7 @@ class ViTEngine:
                     out0=None, bias=self.P(pre + "attn.proj.bias"), vec1=g1, resid=xmid, aux=xin, ldaux=D,
                     rowmask=dp_masks[2 * i][b0:b1] if use_dp else None, keep_prob=keep, rows_per_sample=T, dropout=da)
         if tail is not None:
-            self._mlp_fwd_tail(i, a, self.x[2 * i + 1], g2, keep, tail)
+            self._mlp_fwd_tail(i, a, xs[2 * i + 1], g2, keep, tail)
             return
         ops.layernorm_fwd(xmid, self.P(pre + "norm2.weight"), self.P(pre + "norm2.bias"), h2, a["mean2"][r0:r1],
                           a["rstd2"][r0:r1], M, D)
@@ -569,7 +601,7 @@ class ViTEngine:
                         bias=self.P(pre + "attn.proj.bias"), vec1=g1, resid=xmid, aux=xin, ldaux=D,
                         keep_prob=keep if smap is not None else 1.0, rows_per_sample=T, sample_map=smap, dropout=da)
         if tail is not None:                                  # last block: the rows that reach the head, every sample
-            self._mlp_fwd_tail(i, a, self.x[2 * i + 1], g2, keep, tail)      # (dropped samples: keep flag 0 per row)
+            self._mlp_fwd_tail(i, a, self.cur["x"][2 * i + 1], g2, keep, tail)      # (dropped samples: keep flag 0 per row)
             return
         # -- MLP branch on the nm kept samples
         if plan["n"][jm] is not None:
@@ -589,16 +621,24 @@ class ViTEngine:
                         bias=self.P(pre + "mlp.fc2.bias"), vec1=g2, resid=xout, aux=xmid, ldaux=D,
                         keep_prob=keep if smap is not None else 1.0, rows_per_sample=T, sample_map=smap, dropout=dm)
 
-    def forward_trunk(self, x, mask_u8=None, dp_masks=None, tail_rows=None, drop_key=None):
+    def forward_trunk(self, x, mask_u8=None, dp_masks=None, tail_rows=None, drop_key=None, keep=True):
         """Patch embedding (+ mask-token blend, + abs. position embedding) and the blocks: x f32 [B,C,H,W] ->
         the fp32 residual stream after the last block, [B*T, D] (engine-owned, valid until the next forward).
-        drop_key: (key0, key1) of this step's element-wise dropout masks (finetuning model, drop_rate > 0), or None."""
+        drop_key: (key0, key1) of this step's element-wise dropout masks (finetuning model, drop_rate > 0), or None.
+        keep=False: forward only (evaluation, a frozen trunk).  Nothing is kept for a backward: every block runs through the
+        three residual buffers and the one activation set of _alloc_forward (block i reads buffer 2i mod 3 and writes the
+        other two; all blocks share the activation set, the two sample halves of the two-stream split their own row ranges
+        of it), so the footprint does not grow with the depth.  Same launches on the same rows in the same order as
+        keep=True (stochastic-depth plan, drop-path masks, dropout keys, bias tables, position embedding): the returned
+        stream is bit-identical.  backward_trunk() after it raises.  Finetuning trunk only."""
         assert drop_key is None or (self.drop_rate > 0.0 and tail_rows is None), "dropout: finetuning trunk only"
+        assert keep or (self.head_kind == "cls" and tail_rows is None), \
+            "forward-only mode (keep=False) serves the finetuning trunk: no mlm head, no tail-row form"
         assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous()
         B = x.shape[0]
         assert tuple(x.shape[1:]) == (self.C, self.H, self.W), \
             f"Input image size ({x.shape[2]}*{x.shape[3]}) doesn't match model ({self.H}*{self.W})."
-        self.ensure_batch(B, getattr(self, "Mm_cap", 0))
+        self.ensure_batch(B, getattr(self, "Mm_cap", 0), keep=keep)
         if self.weights_dirty:
             self.sync_weights()
         if self.fwd_two_streams:
@@ -611,7 +651,10 @@ class ViTEngine:
         plan = self._dp_plan(dp_masks, B)
         if plan is not None:
             dp_masks = None                                  # the plan replaces the keep masks everywhere below
-        self.cur = dict(B=B, M=M, Mm=0, mask=mask_u8, rows=None, dp=dp_masks, labels=None, plan=plan, tail=None, drop_key=drop_key)
+        nx = 2 * self.depth + 1
+        self.cur = dict(B=B, M=M, Mm=0, mask=mask_u8, rows=None, dp=dp_masks, labels=None, plan=plan, tail=None, drop_key=drop_key,
+                        keep=bool(keep), x=self.x if keep else [self.x[j % 3] for j in range(nx)],
+                        act=self.act if keep else [self.act[0]] * self.depth)
         if tail_rows is not None and not self.fwd_two_streams:
             # per compact row: did the last block's MLP branch keep the row's sample?  (stochastic depth of that branch is
             # applied per row in the tail form, in both the masked and the work-skipping mode)
@@ -630,6 +673,10 @@ class ViTEngine:
             ops.zero_(self.flat_g[: self.head_end])     # the torch tail accumulates its gradients here before backward_trunk
         ops.im2col(x, B, self.C, self.H, self.W, self.ph, self.pw, self.patches)
         x0 = self.x[0]
+        if not keep and plan is not None:
+            # the dummy sample behind the batch (ensure_batch) takes the residual updates of the padded tile rows; a training
+            # forward starts it from the zeros of snapshot 0, which nothing writes -- the rotation writes every buffer
+            ops.zero_(x0[M:M + T])
         ops.fill_cls(x0, B, T, D, self.P("cls_token"))
         ops.gemm_nt(self.patches, self.W16("patch_embed.proj.weight", D, self.Kpe), B * L, D, self.Kpe,
                     ops.EPI_PATCH_EMBED, bias=self.P("patch_embed.proj.bias"),
@@ -663,7 +710,7 @@ class ViTEngine:
             for i in range(self.depth):
                 self._wait_params(f"block{i}")
                 self._block_fwd(i, 0, B, dp_masks)
-        return self.x[2 * self.depth][:M]
+        return self.cur["x"][2 * self.depth][:M]
 
     # ------------------------------------------------------------------ backward
     def _wgrad(self, dY, X, R, n_out, n_in, gname, bias_grads=()):
@@ -844,6 +891,9 @@ class ViTEngine:
     def backward_trunk(self, dxl):
         """Finetuning: gradient of the loss w.r.t. the trunk output (f32 [B*T, D] or [B,T,D]) -> every trunk parameter."""
         c = self.cur
+        if not c.get("keep", True):
+            raise RuntimeError("backward_trunk after forward_trunk(keep=False): a forward-only pass keeps no activations "
+                               "(the blocks shared one buffer set); run the forward with keep=True to train the trunk")
         M, D = c["M"], self.D
         if not self.accumulate_grads:
             self._zero_small_grads(self.head_end)
@@ -1151,9 +1201,21 @@ class ViTEngine:
             self.grad_hook(self.depth + 1)
 
     # ------------------------------------------------------------------ optimizer primitives
-    def grad_norm(self):
-        ops.grad_norm(self.flat_g, self.nflat, self.gnorm, self.gn_ws)
+    def grad_norm(self, end=None):
+        """Total gradient norm; end: only flat_g[:end] (a frozen trunk: its gradients are never produced and stay zero)."""
+        n = self.nflat if end is None else end
+        ops.grad_norm(self.flat_g[:n], n, self.gnorm, self.gn_ws)
         return self.gnorm
+
+    def weights_updated(self, end=None):
+        """The optimizer has changed flat_p[:end] (None: all of it).  A partial update re-casts that range of the bf16
+        shadows now and leaves the rest -- and the [in,out]-major copies, which lie outside the head bucket -- as they are;
+        a full one marks everything stale for the next forward (sync_weights)."""
+        if end is None or end >= self.nflat:
+            self.weights_dirty = True
+        elif not self.weights_dirty:
+            assert end <= self.head_end, "partial weight update: the head bucket only (no transposed copies to refresh)"
+            ops.cast_f32_bf16(self.flat_p[:end], self.flat_w16[:end], end)
 
     def adamw_step(self, m, v, lr, wd, step, betas=(0.9, 0.95), eps=1e-8, max_norm=0.0):
         if not (self.overlap_optimizer and self.head_kind == "mlm" and not self.fwd_two_streams):
