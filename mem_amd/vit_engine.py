@@ -16,12 +16,19 @@ MI355X-first structure (not an autograd graph):
     fp32 residual stream / LayerNorm statistics / softmax / loss / optimizer.
 """
 import math
+from collections import namedtuple
 
 import torch
 
 from . import ops
 
 ALIGN = 1024
+
+# Branch j of a step (2i: the attention branch of block i, 2i + 1: its MLP branch), built once per step by forward_trunk.
+# n: samples that run it; rows = n * T; gemm_rows: rows padded to whole 256-row tiles when a sample map is in use.
+# Work skipping (dp_skip): ridx compact row -> residual-stream row, smap compact sample -> sample, cmap sample -> compact
+# or -1.  Plain / masked: n = B, no maps, rowmask = the branch's keep mask [B] or None.
+Branch = namedtuple("Branch", "n rows gemm_rows ridx smap cmap rowmask keep_prob")
 
 
 def _pad(n, a):
@@ -69,6 +76,8 @@ class ViTEngine:
         if hasattr(model, "register_state_dict_pre_hook"):
             model.register_state_dict_pre_hook(lambda *_a, **_k: self.wait_optimizer())
         self.B = 0
+        self.Mm_cap = 0                  # rows the head buffers are allocated for (_alloc_head)
+        self.cur = None                  # the step in flight (forward_trunk)
         self.B_stash = 0                 # batch size the backward-only buffers are allocated for (_alloc_stash)
         self.step_masks = None
         self.weights_dirty = True
@@ -270,7 +279,7 @@ class ViTEngine:
             self._alloc_forward(B)
         if keep and self.B_stash < self.B:
             self._alloc_stash()
-        if Mm_max > getattr(self, "Mm_cap", 0) or (self.head_kind == "mlm" and not hasattr(self, "hN")):
+        if Mm_max > self.Mm_cap or (self.head_kind == "mlm" and not hasattr(self, "hN")):
             # headroom: a few per cent above the largest count seen, whole 256-row tiles, never more than every patch
             self._alloc_head(min(self.B * self.L, _pad(Mm_max + Mm_max // 16 + 1, 256)))
 
@@ -449,11 +458,24 @@ class ViTEngine:
         ridx = (dev[:, :B, None] * T + self._dp_ar[None, None, :]).view(J, B * T)
         return dict(n=kept_n, kidx=dev[:, :B + 256], cmap=dev[:, B + 256:2 * B + 256], drop=dev[:, 2 * B + 256:], ridx=ridx, B=B)
 
+    def _branches(self, B, plan, dp_masks):
+        """The step's Branch descriptors: from the work plan where it covers a branch, else plain or masked."""
+        T, out = self.T, []
+        for j in range(2 * self.depth):
+            drop_prob = self.model.blocks[j // 2].drop_prob
+            if plan is not None and plan["n"][j] is not None:
+                n = plan["n"][j]
+                out.append(Branch(n, n * T, _pad(n * T, 256), plan["ridx"][j], plan["kidx"][j], plan["cmap"][j], None,
+                                  1.0 - drop_prob))
+            else:
+                rowmask = dp_masks[j] if (dp_masks is not None and drop_prob > 0.0) else None
+                out.append(Branch(B, B * T, B * T, None, None, None, rowmask, 1.0 - drop_prob))
+        return out
+
     def _drop(self, site, row0=0):
         """memhip_dropout_t of `site` (2i: attention branch of block i, 2i + 1: its MLP branch, 2 * depth: pos_drop) for this
         step, addressed from residual-stream row row0; None when the step runs without dropout."""
-        cur = getattr(self, "cur", None)
-        key = cur.get("drop_key") if cur else None
+        key = self.cur["drop_key"] if self.cur else None
         if key is None:
             return None
         return ops.dropout_params(key[0], key[1], site, self.drop_rate, row0)
@@ -516,47 +538,67 @@ class ViTEngine:
         bs = (rounds * num_cu // ntn) * 256 // self.T
         return bs if 0 < bs < B and (B - bs) * self.T >= 4096 else 0
 
-    def _block_fwd(self, i, b0, b1, dp_masks):
-        """Block i on the samples [b0, b1) (mem/modeling_finetune.py:160-189)."""
+    def _branch(self, j, b0, b1):
+        """Descriptor of branch j for the samples [b0, b1): the step's own for the whole batch, a row slice of a plain or
+        masked one for one part of the two-stream split."""
+        br = self.cur["branch"][j]
+        if b0 == 0 and b1 == self.cur["B"]:
+            return br
+        assert br.smap is None, "stochastic-depth work skipping runs the whole batch on one stream"
+        rows = (b1 - b0) * self.T
+        return br._replace(n=b1 - b0, rows=rows, gemm_rows=rows, rowmask=None if br.rowmask is None else br.rowmask[b0:b1])
+
+    def _block_fwd(self, i, b0, b1):
+        """Block i on the samples [b0, b1) (mem/modeling_finetune.py:160-189).  Each branch runs on the samples it kept: a
+        work-skipping one (see dp_skip) on compact activations, through its gather index and sample map; a plain or masked
+        one on every row, with the keep mask in the residual epilogue."""
         D, Hd, T = self.D, self.hidden, self.T
         r0, r1 = b0 * T, b1 * T
-        M, Bs = r1 - r0, b1 - b0
         pre = f"blocks.{i}."
         xs = self.cur["x"]
         a = self.cur["act"][i]
-        table = self.table(i)
-        blk = self.model.blocks[i]
-        keep = 1.0 - blk.drop_prob
-        use_dp = dp_masks is not None and blk.drop_prob > 0.0
+        B, plan = self.cur["B"], self.cur["plan"]
+        ba, bm = self._branch(2 * i, b0, b1), self._branch(2 * i + 1, b0, b1)
         xin, xmid, xout = xs[2 * i][r0:r1], xs[2 * i + 1][r0:r1], xs[2 * i + 2][r0:r1]
         g1 = self.P(pre + "gamma_1") if (pre + "gamma_1") in self.segs else None
         g2 = self.P(pre + "gamma_2") if (pre + "gamma_2") in self.segs else None
-        h1, qkv, ao, h2, hpre, aa = (a[k][r0:r1] for k in ("h1", "qkv", "ao", "h2", "hpre", "a"))
-        plan = self.cur.get("plan")
-        tail = self.cur.get("tail") if (i == self.depth - 1 and b0 == 0 and b1 == self.cur["B"]) else None
-        if plan is not None and (plan["n"][2 * i] is not None or plan["n"][2 * i + 1] is not None):
-            assert b0 == 0 and b1 == plan["B"], "stochastic-depth work skipping runs the whole batch on one stream"
-            self._block_fwd_skip(i, plan, a, xin, xmid, xout, g1, g2, table, keep, tail=tail)
+        tail = self.cur["tail"] if (i == self.depth - 1 and b0 == 0 and b1 == B) else None
+        # -- attention branch
+        if ba.smap is not None:
+            self._copy_dropped(plan, 2 * i, xin, xmid, B)
+        if ba.n > 0:
+            # compact rows start at row 0 of the activation buffers and their tile padding lies in the buffers' slack
+            rs = slice(r0, r1) if ba.smap is None else slice(None)
+            h1, qkv, ao = a["h1"][rs], a["qkv"][rs], a["ao"][rs]
+            ops.layernorm_fwd(xin, self.P(pre + "norm1.weight"), self.P(pre + "norm1.bias"), h1, a["mean1"][r0:r1],
+                              a["rstd1"][r0:r1], ba.rows, D, row_idx=ba.ridx)
+            ops.gemm_nt(h1, self.W16(pre + "attn.qkv.weight", 3 * D, D), ba.gemm_rows, 3 * D, D, ops.EPI_BIAS_BF16,
+                        out0=qkv, bias=self.P(pre + "attn.qkvbias3"), colscale=self.scale, colscale_n=D)
+            ops.attn_fwd(qkv, ba.n, T, D, self.heads, self.table(i), self.window, ao, a["lse"][b0:b1])
+            # (dropout masks are keyed on the residual row: row0 = r0 for a split part, the row the sample map resolves)
+            da = self._drop(2 * i, r0)
+            ops.gemm_nt(ao, self.W16(pre + "attn.proj.weight", D, D), ba.gemm_rows, D, D,
+                        ops.EPI_RESIDUAL if da is None else ops.EPI_RESIDUAL_DROP, out0=None,
+                        bias=self.P(pre + "attn.proj.bias"), vec1=g1, resid=xmid, aux=xin, ldaux=D, rowmask=ba.rowmask,
+                        keep_prob=ba.keep_prob, rows_per_sample=T, sample_map=ba.smap, dropout=da)
+        if tail is not None:            # last block: the rows that reach the head, every sample (dropped: keep flag 0 per row)
+            self._mlp_fwd_tail(i, a, xs[2 * i + 1], g2, bm.keep_prob, tail)
             return
-        ops.layernorm_fwd(xin, self.P(pre + "norm1.weight"), self.P(pre + "norm1.bias"), h1, a["mean1"][r0:r1],
-                          a["rstd1"][r0:r1], M, D)
-        ops.gemm_nt(h1, self.W16(pre + "attn.qkv.weight", 3 * D, D), M, 3 * D, D, ops.EPI_BIAS_BF16,
-                    out0=qkv, bias=self.P(pre + "attn.qkvbias3"), colscale=self.scale, colscale_n=D)
-        ops.attn_fwd(qkv, Bs, T, D, self.heads, table, self.window, ao, a["lse"][b0:b1])
-        da, dm = self._drop(2 * i, r0), self._drop(2 * i + 1, r0)        # (rows of the split half: row0 = r0)
-        ops.gemm_nt(ao, self.W16(pre + "attn.proj.weight", D, D), M, D, D, ops.EPI_RESIDUAL if da is None else ops.EPI_RESIDUAL_DROP,
-                    out0=None, bias=self.P(pre + "attn.proj.bias"), vec1=g1, resid=xmid, aux=xin, ldaux=D,
-                    rowmask=dp_masks[2 * i][b0:b1] if use_dp else None, keep_prob=keep, rows_per_sample=T, dropout=da)
-        if tail is not None:
-            self._mlp_fwd_tail(i, a, xs[2 * i + 1], g2, keep, tail)
-            return
-        ops.layernorm_fwd(xmid, self.P(pre + "norm2.weight"), self.P(pre + "norm2.bias"), h2, a["mean2"][r0:r1],
-                          a["rstd2"][r0:r1], M, D)
-        ops.gemm_nt(h2, self.W16(pre + "mlp.fc1.weight", Hd, D), M, Hd, D, self.epi_gelu, out0=hpre,
-                    out1=aa, bias=self.P(pre + "mlp.fc1.bias"))
-        ops.gemm_nt(aa, self.W16(pre + "mlp.fc2.weight", D, Hd), M, D, Hd, ops.EPI_RESIDUAL if dm is None else ops.EPI_RESIDUAL_DROP,
-                    out0=None, bias=self.P(pre + "mlp.fc2.bias"), vec1=g2, resid=xout, aux=xmid, ldaux=D,
-                    rowmask=dp_masks[2 * i + 1][b0:b1] if use_dp else None, keep_prob=keep, rows_per_sample=T, dropout=dm)
+        # -- MLP branch
+        if bm.smap is not None:
+            self._copy_dropped(plan, 2 * i + 1, xmid, xout, B)
+        if bm.n > 0:
+            rs = slice(r0, r1) if bm.smap is None else slice(None)
+            h2, hpre, aa = a["h2"][rs], a["hpre"][rs], a["a"][rs]
+            ops.layernorm_fwd(xmid, self.P(pre + "norm2.weight"), self.P(pre + "norm2.bias"), h2, a["mean2"][r0:r1],
+                              a["rstd2"][r0:r1], bm.rows, D, row_idx=bm.ridx)
+            ops.gemm_nt(h2, self.W16(pre + "mlp.fc1.weight", Hd, D), bm.gemm_rows, Hd, D, self.epi_gelu, out0=hpre,
+                        out1=aa, bias=self.P(pre + "mlp.fc1.bias"))
+            dm = self._drop(2 * i + 1, r0)
+            ops.gemm_nt(aa, self.W16(pre + "mlp.fc2.weight", D, Hd), bm.gemm_rows, D, Hd,
+                        ops.EPI_RESIDUAL if dm is None else ops.EPI_RESIDUAL_DROP, out0=None,
+                        bias=self.P(pre + "mlp.fc2.bias"), vec1=g2, resid=xout, aux=xmid, ldaux=D, rowmask=bm.rowmask,
+                        keep_prob=bm.keep_prob, rows_per_sample=T, sample_map=bm.smap, dropout=dm)
 
     def _mlp_fwd_tail(self, i, a, xmid, g2, keep, tail):
         """MLP branch of the LAST block on the rows that reach the head only (forward(): tail rows): norm2 on the gathered
@@ -575,52 +617,6 @@ class ViTEngine:
                     bias=self.P(pre + "mlp.fc2.bias"))
         ops.residual_rows(xmid, rows, self.y_tail, g2, tail["rowkeep"], keep, Mm, D, self.x_tail)
 
-    def _block_fwd_skip(self, i, plan, a, xin, xmid, xout, g1, g2, table, keep, tail=None):
-        """Block i with the dropped samples of each branch skipped (see dp_skip): compact activations."""
-        D, Hd, T, B = self.D, self.hidden, self.T, plan["B"]
-        pre = f"blocks.{i}."
-        ja, jm = 2 * i, 2 * i + 1
-        na = B if plan["n"][ja] is None else plan["n"][ja]
-        nm = B if plan["n"][jm] is None else plan["n"][jm]
-        # -- attention branch on the na kept samples
-        if plan["n"][ja] is not None:
-            self._copy_dropped(plan, ja, xin, xmid, B)
-        if na > 0:
-            M1 = na * T
-            ridx = plan["ridx"][ja] if plan["n"][ja] is not None else None
-            smap = plan["kidx"][ja] if plan["n"][ja] is not None else None
-            M1p = _pad(M1, 256) if smap is not None else M1       # GEMM rows: whole 256-row tiles (see ensure_batch)
-            ops.layernorm_fwd(xin, self.P(pre + "norm1.weight"), self.P(pre + "norm1.bias"), a["h1"], a["mean1"], a["rstd1"],
-                              M1, D, row_idx=ridx)
-            ops.gemm_nt(a["h1"], self.W16(pre + "attn.qkv.weight", 3 * D, D), M1p, 3 * D, D, ops.EPI_BIAS_BF16,
-                        out0=a["qkv"], bias=self.P(pre + "attn.qkvbias3"), colscale=self.scale, colscale_n=D)
-            ops.attn_fwd(a["qkv"], na, T, D, self.heads, table, self.window, a["ao"], a["lse"])
-            da = self._drop(2 * i)                  # (the epilogue keys the mask on the residual row the sample map resolves)
-            ops.gemm_nt(a["ao"], self.W16(pre + "attn.proj.weight", D, D), M1p, D, D,
-                        ops.EPI_RESIDUAL if da is None else ops.EPI_RESIDUAL_DROP, out0=None,
-                        bias=self.P(pre + "attn.proj.bias"), vec1=g1, resid=xmid, aux=xin, ldaux=D,
-                        keep_prob=keep if smap is not None else 1.0, rows_per_sample=T, sample_map=smap, dropout=da)
-        if tail is not None:                                  # last block: the rows that reach the head, every sample
-            self._mlp_fwd_tail(i, a, self.cur["x"][2 * i + 1], g2, keep, tail)      # (dropped samples: keep flag 0 per row)
-            return
-        # -- MLP branch on the nm kept samples
-        if plan["n"][jm] is not None:
-            self._copy_dropped(plan, jm, xmid, xout, B)
-        if nm > 0:
-            M2 = nm * T
-            ridx = plan["ridx"][jm] if plan["n"][jm] is not None else None
-            smap = plan["kidx"][jm] if plan["n"][jm] is not None else None
-            M2p = _pad(M2, 256) if smap is not None else M2
-            ops.layernorm_fwd(xmid, self.P(pre + "norm2.weight"), self.P(pre + "norm2.bias"), a["h2"], a["mean2"], a["rstd2"],
-                              M2, D, row_idx=ridx)
-            ops.gemm_nt(a["h2"], self.W16(pre + "mlp.fc1.weight", Hd, D), M2p, Hd, D, self.epi_gelu, out0=a["hpre"],
-                        out1=a["a"], bias=self.P(pre + "mlp.fc1.bias"))
-            dm = self._drop(2 * i + 1)
-            ops.gemm_nt(a["a"], self.W16(pre + "mlp.fc2.weight", D, Hd), M2p, D, Hd,
-                        ops.EPI_RESIDUAL if dm is None else ops.EPI_RESIDUAL_DROP, out0=None,
-                        bias=self.P(pre + "mlp.fc2.bias"), vec1=g2, resid=xout, aux=xmid, ldaux=D,
-                        keep_prob=keep if smap is not None else 1.0, rows_per_sample=T, sample_map=smap, dropout=dm)
-
     def forward_trunk(self, x, mask_u8=None, dp_masks=None, tail_rows=None, drop_key=None, keep=True):
         """Patch embedding (+ mask-token blend, + abs. position embedding) and the blocks: x f32 [B,C,H,W] ->
         the fp32 residual stream after the last block, [B*T, D] (engine-owned, valid until the next forward).
@@ -638,7 +634,7 @@ class ViTEngine:
         B = x.shape[0]
         assert tuple(x.shape[1:]) == (self.C, self.H, self.W), \
             f"Input image size ({x.shape[2]}*{x.shape[3]}) doesn't match model ({self.H}*{self.W})."
-        self.ensure_batch(B, getattr(self, "Mm_cap", 0), keep=keep)
+        self.ensure_batch(B, self.Mm_cap, keep=keep)
         if self.weights_dirty:
             self.sync_weights()
         if self.fwd_two_streams:
@@ -654,7 +650,7 @@ class ViTEngine:
         nx = 2 * self.depth + 1
         self.cur = dict(B=B, M=M, Mm=0, mask=mask_u8, rows=None, dp=dp_masks, labels=None, plan=plan, tail=None, drop_key=drop_key,
                         keep=bool(keep), x=self.x if keep else [self.x[j % 3] for j in range(nx)],
-                        act=self.act if keep else [self.act[0]] * self.depth)
+                        act=self.act if keep else [self.act[0]] * self.depth, branch=self._branches(B, plan, dp_masks))
         if tail_rows is not None and not self.fwd_two_streams:
             # per compact row: did the last block's MLP branch keep the row's sample?  (stochastic depth of that branch is
             # applied per row in the tail form, in both the masked and the work-skipping mode)
@@ -700,16 +696,16 @@ class ViTEngine:
             e0.record()
             self._side.wait_event(e0)
             for i in range(self.depth):
-                self._block_fwd(i, 0, bs, dp_masks)
+                self._block_fwd(i, 0, bs)
                 with torch.cuda.stream(self._side):
-                    self._block_fwd(i, bs, B, dp_masks)
+                    self._block_fwd(i, bs, B)
             e1 = torch.cuda.Event()
             e1.record(self._side)
             torch.cuda.current_stream().wait_event(e1)
         else:
             for i in range(self.depth):
                 self._wait_params(f"block{i}")
-                self._block_fwd(i, 0, B, dp_masks)
+                self._block_fwd(i, 0, B)
         return self.cur["x"][2 * self.depth][:M]
 
     # ------------------------------------------------------------------ backward
@@ -772,14 +768,14 @@ class ViTEngine:
         self._side_reads = {}
         if self._use_side and self._side is None:
             self._side = torch.cuda.Stream(device=self.dev)
-        if self._use_side and getattr(self, "_ws_for", None) != (self.B, getattr(self, "Mm_cap", 0)):
-            self._ws_for = (self.B, getattr(self, "Mm_cap", 0))
+        if self._use_side and getattr(self, "_ws_for", None) != (self.B, self.Mm_cap):
+            self._ws_for = (self.B, self.Mm_cap)
             # the wgrad workspace is sized once so that it is never reallocated while the side stream uses it
             D, Hd = self.D, self.hidden
             M = self.B * self.T
             need = max(ops.gemm_tn_group_workspace([(M, D, D), (M, 3 * D, D)]), ops.gemm_tn_group_workspace([(M, D, Hd), (M, Hd, D)]),
                        ops.gemm_tn_workspace(M, 3 * D, D), ops.gemm_tn_workspace(M, Hd, D), ops.gemm_tn_workspace(M, D, Hd),
-                       ops.gemm_tn_workspace(M, D, D), ops.gemm_tn_workspace(getattr(self, "Mm_cap", 0) or M, max(self.V, 1), D),
+                       ops.gemm_tn_workspace(M, D, D), ops.gemm_tn_workspace(self.Mm_cap or M, max(self.V, 1), D),
                        ops.gemm_tn_workspace(self.B * self.L, D, self.Kpe))
             if need > self._tn_ws.numel():
                 self._tn_ws = torch.empty(need, dtype=torch.uint8, device=self.dev)
@@ -901,10 +897,20 @@ class ViTEngine:
         self._side_begin()
         self._backward_trunk()
 
-    def _mlp_bwd_tail(self, i, a, pre, has_g, keep, tail, attn_branch_bwd):
+    def _attn_branch_bwd(self, i, scr):
+        """dY2 = gradient of block i's attention branch output, from dx on the samples the branch kept; the proj.bias
+        column sums go to scr."""
+        pre = f"blocks.{i}."
+        ba = self.cur["branch"][2 * i]
+        self._before_overwrite("dY2")
+        ops.branch_bwd(self.dx, None, self.P(pre + "gamma_1") if (pre + "gamma_1") in self.segs else None, self.dY2, None, scr,
+                       self.cur["M"], self.D, rowmask=ba.rowmask, keep_prob=ba.keep_prob, rows_per_sample=self.T,
+                       out_map=ba.cmap, dropout=self._drop(2 * i))
+
+    def _mlp_bwd_tail(self, i, a, pre, has_g, keep, tail, scr):
         """Backward of _mlp_fwd_tail: the MLP branch of the last block on the compact rows that reached the head (their
         gradient is self.dxc; every other row's is zero), norm2 backward scattered into dx, then the attention branch's
-        branch backward over all of dx (attn_branch_bwd: the caller's masked / work-skipping form)."""
+        branch backward over all of dx."""
         D, Hd = self.D, self.hidden
         rows, Mm, rk = tail["rows"], tail["Mm"], tail["rowkeep"]
         Mp = _pad(Mm, 256)
@@ -919,105 +925,93 @@ class ViTEngine:
         ops.gemm_nt(dY, self.wT[i]["fc2"], Mp, Hd, D, self.epi_dgelu, out0=self.dbig, aux=a["hpre"],
                     colsum=self.cs_ws, colsum_copies=self.CS_COPIES)
         ops.colsum_fold(self.cs_ws, self.CS_COPIES, Hd, self.G(pre + "mlp.fc1.bias"))
-
-        def wg_mlp():
-            self._wg_mlp(pre, a, has_g, Mm, dY)
-        self._on_side(wg_mlp)
+        self._on_side(lambda: self._wg_mlp(pre, a, has_g, Mm, dY))
         ops.gemm_nt(self.dbig, self.wT[i]["fc1"], Mp, D, Hd, ops.EPI_BIAS_BF16, out0=self.dh_small)
         ops.layernorm_bwd(self.dh_small, self.x[2 * i + 1], self.P(pre + "norm2.weight"), a["mean2"], a["rstd2"], dx,
                           self.G(pre + "norm2.weight"), self.G(pre + "norm2.bias"), Mm, D, accumulate=True, row_idx=rows)
-        attn_branch_bwd()
+        self._attn_branch_bwd(i, scr)
 
-    def _backward_trunk_skip(self, plan):
-        """_backward_trunk with the dropped samples of every branch skipped (dp_skip): the branch gradients dY / dY2, the
-        dgrad chain and the weight gradients run on the kept samples' rows only; the row kernels move between the compact
-        row sets and the residual-stream gradient dx through sample maps (in_map: who the LayerNorm'ed branch kept,
-        out_map: who the branch whose output gradient is produced kept)."""
+    def _backward_trunk(self):
+        """The blocks in reverse, each branch on the samples it kept (self.cur["branch"]): the branch gradients dY (MLP) /
+        dY2 (attention), the dgrad chain and the weight gradients run on those samples' rows only.  With work skipping the
+        row kernels move between the compact row sets and the residual-stream gradient dx through sample maps (in_map: who
+        the LayerNorm'ed branch kept, out_map: who the branch whose output gradient is produced kept)."""
         c = self.cur
-        B, M = c["B"], c["M"]
-        D, Hd, T, L = self.D, self.hidden, self.T, self.L
-        dx = self.dx
+        B, M, br = c["B"], c["M"], c["branch"]
+        D, Hd, T = self.D, self.hidden, self.T
+        dx, dY, dY2 = self.dx, self.dY, self.dY2
         self._bucket_ready(0)
+        # both ping-pong rows of the proj-bias scratch start clean: block i accumulates into row i&1 and clears the
+        # other one, which leaves row (depth-1)&1 dirty for the next backward when depth is odd
         ops.zero_(self.bias_scr)
         fuse = D <= 1024 and self.fuse_ln_branch
-        nk = lambda j: B if plan["n"][j] is None else plan["n"][j]               # noqa: E731  kept samples of branch j
-        cmap = lambda j: None if plan["n"][j] is None else plan["cmap"][j]       # noqa: E731
-        ridx = lambda j: None if plan["n"][j] is None else plan["ridx"][j]       # noqa: E731
-        kp = lambda j, i: (1.0 - self.model.blocks[i].drop_prob) if plan["n"][j] is not None else 1.0   # noqa: E731
         for i in reversed(range(self.depth)):
             pre = f"blocks.{i}."
             a = self.act[i]
-            ja, jm = 2 * i, 2 * i + 1
-            na, nm = nk(ja), nk(jm)
-            M1, M2 = na * T, nm * T
-            # dgrad GEMM rows: whole 256-row tiles (ensure_batch); the weight gradients take the exact row counts
-            M1p = _pad(M1, 256) if plan["n"][ja] is not None else M1
-            M2p = _pad(M2, 256) if plan["n"][jm] is not None else M2
+            ba, bm = br[2 * i], br[2 * i + 1]
             xin, xmid = self.x[2 * i], self.x[2 * i + 1]
             has_g = (pre + "gamma_1") in self.segs
             table, dtable = self.table(i), self.dtable(i)
-            dY, dY2 = self.dY, self.dY2
             scr = self.bias_scr[i & 1]
-            tail = c.get("tail") if i == self.depth - 1 else None
+            tail = c["tail"] if i == self.depth - 1 else None
+            # -- MLP branch: dY, fc2 / fc1 dgrad, norm2 backward, then the attention branch's dY2
             if tail is not None:
-                # last block, MLP branch on the rows that reached the head only (forward(): tail rows); the helper ends with
-                # the attention branch's branch backward in this loop's form
-                def attn_bb(i=i, pre=pre, has_g=has_g, ja=ja, scr=scr):
-                    self._before_overwrite("dY2")
-                    ops.branch_bwd(dx, None, self.P(pre + "gamma_1") if has_g else None, dY2, None, scr, M, D,
-                                   keep_prob=kp(ja, i), rows_per_sample=T, out_map=cmap(ja))
-                self._mlp_bwd_tail(i, a, pre, has_g, 1.0 - self.model.blocks[i].drop_prob, tail, attn_bb)
-            # -- MLP branch (for every block but the last dY already came out of the fused norm1 backward of block i + 1)
-            if tail is None and (i == self.depth - 1 or not fuse):
-                self._before_overwrite("dY")
-                ops.branch_bwd(dx, None, self.P(pre + "gamma_2") if has_g else None, dY, None, self.G(pre + "mlp.fc2.bias"),
-                               M, D, keep_prob=kp(jm, i), rows_per_sample=T, out_map=cmap(jm), dropout=self._drop(jm))
-            if tail is None and nm == 0 and not self.accumulate_grads:
-                self._zero_grad_of(pre + "mlp.fc1.weight")      # every sample dropped this branch: zero, not last step's
-                self._zero_grad_of(pre + "mlp.fc2.weight")
-            if tail is None and nm > 0:
-                self._before_overwrite("dbig")
-                if M2p > M2:
-                    ops.zero_(dY[M2:M2p])   # rows of the padding: zero in, zero out (the epilogue's column sums see them)
-                ops.gemm_nt(dY, self.wT[i]["fc2"], M2p, Hd, D, self.epi_dgelu, out0=self.dbig, aux=a["hpre"],
-                            colsum=self.cs_ws, colsum_copies=self.CS_COPIES)
-                ops.colsum_fold(self.cs_ws, self.CS_COPIES, Hd, self.G(pre + "mlp.fc1.bias"))
-
-                def wg_mlp(i=i, pre=pre, a=a, has_g=has_g, M2=M2):
-                    self._wg_mlp(pre, a, has_g, M2, dY)
-                self._on_side(wg_mlp)
-                ops.gemm_nt(self.dbig, self.wT[i]["fc1"], M2p, D, Hd, ops.EPI_BIAS_BF16, out0=self.dh_small)
-            if tail is not None:
-                pass
-            elif fuse:
-                # norm2 backward (rows the MLP branch kept) + attention-branch backward (rows it kept) in one pass over dx
-                self._before_overwrite("dY2")
-                ops.layernorm_bwd_branch(self.dh_small, xmid, self.P(pre + "norm2.weight"), a["mean2"], a["rstd2"], dx,
-                                         self.G(pre + "norm2.weight"), self.G(pre + "norm2.bias"), M, D, None,
-                                         self.P(pre + "gamma_1") if has_g else None, dY2, None, scr,
-                                         keep_prob=kp(ja, i), rows_per_sample=T,
-                                         in_map=cmap(jm) if cmap(jm) is not None else None, out_map=cmap(ja),
-                                         dropout=self._drop(ja))
+                # last block, MLP branch on the rows that reached the head only (forward(): tail rows)
+                self._mlp_bwd_tail(i, a, pre, has_g, bm.keep_prob, tail, scr)
             else:
-                if nm > 0:
-                    ops.layernorm_bwd(self.dh_small, xmid, self.P(pre + "norm2.weight"), a["mean2"], a["rstd2"], dx,
-                                      self.G(pre + "norm2.weight"), self.G(pre + "norm2.bias"), M2, D, accumulate=True,
-                                      row_idx=ridx(jm))
-                self._before_overwrite("dY2")
-                ops.branch_bwd(dx, None, self.P(pre + "gamma_1") if has_g else None, dY2, None, scr, M, D,
-                               keep_prob=kp(ja, i), rows_per_sample=T, out_map=cmap(ja), dropout=self._drop(ja))
+                if i == self.depth - 1 or not fuse:
+                    # (every other block's dY came out of the fused norm1 backward of block i + 1, see below)
+                    self._before_overwrite("dY")
+                    ops.branch_bwd(dx, None, self.P(pre + "gamma_2") if has_g else None, dY, None, self.G(pre + "mlp.fc2.bias"),
+                                   M, D, rowmask=bm.rowmask, keep_prob=bm.keep_prob, rows_per_sample=T, out_map=bm.cmap,
+                                   dropout=self._drop(2 * i + 1))
+                if bm.n == 0 and not self.accumulate_grads:
+                    self._zero_grad_of(pre + "mlp.fc1.weight")      # every sample dropped this branch: zero, not last step's
+                    self._zero_grad_of(pre + "mlp.fc2.weight")
+                if bm.n > 0:
+                    self._before_overwrite("dbig")
+                    if bm.gemm_rows > bm.rows:
+                        # rows of the tile padding: zero in, zero out (the epilogue's column sums see them)
+                        ops.zero_(dY[bm.rows:bm.gemm_rows])
+                    # fc1 bias grad = column sums of dh, accumulated in CS_COPIES copies (one per XCD: atomics on one address
+                    # serialise and would sit in front of the GEMM's operand stream) and folded by a 3 us kernel
+                    ops.gemm_nt(dY, self.wT[i]["fc2"], bm.gemm_rows, Hd, D, self.epi_dgelu, out0=self.dbig, aux=a["hpre"],
+                                colsum=self.cs_ws, colsum_copies=self.CS_COPIES)
+                    ops.colsum_fold(self.cs_ws, self.CS_COPIES, Hd, self.G(pre + "mlp.fc1.bias"))
+                    # (the weight gradients take the exact row count, the dgrad GEMMs whole 256-row tiles)
+                    self._on_side(lambda: self._wg_mlp(pre, a, has_g, bm.rows, dY))
+                    ops.gemm_nt(self.dbig, self.wT[i]["fc1"], bm.gemm_rows, D, Hd, ops.EPI_BIAS_BF16, out0=self.dh_small)
+                if fuse:
+                    # norm2 backward (rows the MLP branch kept) + attention-branch backward (rows it kept) in one pass over
+                    # dx (proj.bias column sums -> scr)
+                    self._before_overwrite("dY2")
+                    ops.layernorm_bwd_branch(self.dh_small, xmid, self.P(pre + "norm2.weight"), a["mean2"], a["rstd2"], dx,
+                                             self.G(pre + "norm2.weight"), self.G(pre + "norm2.bias"), M, D, None,
+                                             self.P(pre + "gamma_1") if has_g else None, dY2, None, scr,
+                                             rowmask=ba.rowmask, keep_prob=ba.keep_prob, rows_per_sample=T,
+                                             in_map=bm.cmap, out_map=ba.cmap, dropout=self._drop(2 * i))
+                else:
+                    if bm.n > 0:
+                        ops.layernorm_bwd(self.dh_small, xmid, self.P(pre + "norm2.weight"), a["mean2"], a["rstd2"], dx,
+                                          self.G(pre + "norm2.weight"), self.G(pre + "norm2.bias"), bm.rows, D, accumulate=True,
+                                          row_idx=bm.ridx)
+                    self._attn_branch_bwd(i, scr)
             # -- attention branch
-            if na == 0 and not self.accumulate_grads:
+            # proj.bias gradient (column sums of dY2) goes to a scratch vector first: the v_bias gradient is
+            # derived from it.  sum_k dV[k] = sum_q dO[q] * sum_k P[q,k] and the softmax rows sum to one, so
+            # v_bias.grad = colsum(d attn_out) = colsum(dY2) @ W_proj: one 768x768 GEMV instead of column
+            # sums inside the attention kernel (which cost it 32 VGPRs and its occupancy).
+            if ba.n == 0 and not self.accumulate_grads:
                 self._zero_grad_of(pre + "attn.proj.weight")
                 self._zero_grad_of(pre + "attn.qkv.weight")
-            if na > 0:
-                ops.gemm_nt(dY2, self.wT[i]["proj"], M1p, D, D, ops.EPI_BIAS_BF16, out0=self.dao)
+            if ba.n > 0:
+                ops.gemm_nt(dY2, self.wT[i]["proj"], ba.gemm_rows, D, D, ops.EPI_BIAS_BF16, out0=self.dao)
             ops.gemv_acc(self.wT[i]["proj"], D, D, scr, self.G(pre + "attn.v_bias"),
                          x_acc=self.G(pre + "attn.proj.bias"), zero=self.bias_scr[(i & 1) ^ 1])
-            if na > 0:
-                def wg_proj(pre=pre, a=a, has_g=has_g, M1=M1, grouped=False):
+            if ba.n > 0:
+                def wg_proj(grouped=False):
                     if not grouped:
-                        self._wgrad(dY2, a["ao"], M1, D, D, pre + "attn.proj.weight")
+                        self._wgrad(dY2, a["ao"], ba.rows, D, D, pre + "attn.proj.weight")
                     self._side_read_done("dY2")
                     if has_g:
                         ops.layerscale_grad(self.W16(pre + "attn.proj.weight", D, D), self.G(pre + "attn.proj.weight").view(D, D),
@@ -1027,156 +1021,33 @@ class ViTEngine:
                     self._on_side(wg_proj)
                 self._before_overwrite("dqkv")
                 # (rowsum(dO * O) is computed inside the fused 14 x 14 backward; other windows: a delta pass in the library)
-                ops.attn_bwd(a["qkv"], self.dao, a["lse"], self.delta_ws, table, self.window, na, T, D, self.heads,
-                             self.scale, self.dqkv, dtable, dq_bias=self.G(pre + "attn.q_bias"), out=a["ao"], ws=self._attn_ws(na))
+                ops.attn_bwd(a["qkv"], self.dao, a["lse"], self.delta_ws, table, self.window, ba.n, T, D, self.heads,
+                             self.scale, self.dqkv, dtable, dq_bias=self.G(pre + "attn.q_bias"), out=a["ao"],
+                             ws=self._attn_ws(ba.n))
 
-                def wg_qkv(pre=pre, a=a, M1=M1, wg_proj=wg_proj):
+                def wg_qkv():
                     if self.wgrad_group:
-                        self._wgrad_group([(dY2, a["ao"], M1, D, D, pre + "attn.proj.weight"),
-                                           (self.dqkv, a["h1"], M1, 3 * D, D, pre + "attn.qkv.weight")])
+                        self._wgrad_group([(dY2, a["ao"], ba.rows, D, D, pre + "attn.proj.weight"),
+                                           (self.dqkv, a["h1"], ba.rows, 3 * D, D, pre + "attn.qkv.weight")])
                         wg_proj(grouped=True)
                     else:
-                        self._wgrad(self.dqkv, a["h1"], M1, 3 * D, D, pre + "attn.qkv.weight")
+                        self._wgrad(self.dqkv, a["h1"], ba.rows, 3 * D, D, pre + "attn.qkv.weight")
                     self._side_read_done("dqkv")
                 self._on_side(wg_qkv)
-                ops.gemm_nt(self.dqkv, self.wT[i]["qkv"], M1p, D, 3 * D, ops.EPI_BIAS_BF16, out0=self.dh_small)
+                ops.gemm_nt(self.dqkv, self.wT[i]["qkv"], ba.gemm_rows, D, 3 * D, ops.EPI_BIAS_BF16, out0=self.dh_small)
             if fuse and i > 0:
                 # norm1 backward of block i (rows its attention branch kept) + MLP-branch backward of block i - 1
-                pb = f"blocks.{i - 1}."
-                has_gb = (pb + "gamma_1") in self.segs
-                jb = 2 * (i - 1) + 1
+                pb, bb = f"blocks.{i - 1}.", br[2 * i - 1]
                 self._before_overwrite("dY")
                 ops.layernorm_bwd_branch(self.dh_small, xin, self.P(pre + "norm1.weight"), a["mean1"], a["rstd1"], dx,
                                          self.G(pre + "norm1.weight"), self.G(pre + "norm1.bias"), M, D, None,
-                                         self.P(pb + "gamma_2") if has_gb else None, dY, None, self.G(pb + "mlp.fc2.bias"),
-                                         keep_prob=kp(jb, i - 1), rows_per_sample=T, in_map=cmap(ja), out_map=cmap(jb),
-                                         dropout=self._drop(jb))
-            elif na > 0:
+                                         self.P(pb + "gamma_2") if (pb + "gamma_2") in self.segs else None, dY, None,
+                                         self.G(pb + "mlp.fc2.bias"), rowmask=bb.rowmask, keep_prob=bb.keep_prob,
+                                         rows_per_sample=T, in_map=ba.cmap, out_map=bb.cmap, dropout=self._drop(2 * i - 1))
+            elif ba.n > 0:
                 ops.layernorm_bwd(self.dh_small, xin, self.P(pre + "norm1.weight"), a["mean1"], a["rstd1"], dx,
-                                  self.G(pre + "norm1.weight"), self.G(pre + "norm1.bias"), M1, D, accumulate=True,
-                                  row_idx=ridx(ja))
-            self._bucket_ready(self.depth - i)
-        self._backward_embed(c, B, M)
-
-    def _backward_trunk(self):
-        c = self.cur
-        if c.get("plan") is not None:
-            return self._backward_trunk_skip(c["plan"])
-        B, M = c["B"], c["M"]
-        D, Hd, T, L = self.D, self.hidden, self.T, self.L
-        dp_masks = c["dp"]
-        dx = self.dx
-        self._bucket_ready(0)
-        # both ping-pong rows of the proj-bias scratch start clean: block i accumulates into row i&1 and clears the
-        # other one, which leaves row (depth-1)&1 dirty for the next backward when depth is odd
-        ops.zero_(self.bias_scr)
-        fuse = D <= 1024 and self.fuse_ln_branch
-        for i in reversed(range(self.depth)):
-            pre = f"blocks.{i}."
-            a = self.act[i]
-            blk = self.model.blocks[i]
-            keep = 1.0 - blk.drop_prob
-            use_dp = dp_masks is not None and blk.drop_prob > 0.0
-            xin, xmid = self.x[2 * i], self.x[2 * i + 1]
-            has_g = (pre + "gamma_1") in self.segs
-            table, dtable = self.table(i), self.dtable(i)
-            # -- MLP branch (for every block but the last this already ran fused into the norm1 backward of
-            # block i+1, see below).  dY = gradient of the MLP branch output, dY2 = of the attention branch output.
-            dY, dY2 = self.dY, self.dY2
-            tail = c.get("tail") if i == self.depth - 1 else None
-            if tail is not None:
-                # last block, MLP branch on the rows that reached the head only (forward(): tail rows)
-                scr = self.bias_scr[i & 1]
-
-                def attn_bb(i=i, pre=pre, has_g=has_g, scr=scr, use_dp=use_dp, keep=keep):
-                    self._before_overwrite("dY2")
-                    ops.branch_bwd(dx, None, self.P(pre + "gamma_1") if has_g else None, dY2, None, scr, M, D,
-                                   rowmask=dp_masks[2 * i] if use_dp else None, keep_prob=keep, rows_per_sample=T)
-                self._mlp_bwd_tail(i, a, pre, has_g, keep, tail, attn_bb)
-            else:
-                if i == self.depth - 1 or not fuse:
-                    self._before_overwrite("dY")
-                    ops.branch_bwd(dx, None, self.P(pre + "gamma_2") if has_g else None, dY,
-                                   None, self.G(pre + "mlp.fc2.bias"), M, D,
-                                   rowmask=dp_masks[2 * i + 1] if use_dp else None, keep_prob=keep, rows_per_sample=T,
-                                   dropout=self._drop(2 * i + 1))
-                self._before_overwrite("dbig")
-                # fc1 bias grad = column sums of dh, accumulated in CS_COPIES copies (one per XCD: atomics on one address
-                # serialise and would sit in front of the GEMM's operand stream) and folded by a 3 us kernel
-                ops.gemm_nt(dY, self.wT[i]["fc2"], M, Hd, D, self.epi_dgelu, out0=self.dbig, aux=a["hpre"],
-                            colsum=self.cs_ws, colsum_copies=self.CS_COPIES)
-                ops.colsum_fold(self.cs_ws, self.CS_COPIES, Hd, self.G(pre + "mlp.fc1.bias"))
-
-                def wg_mlp(i=i, pre=pre, a=a, has_g=has_g):
-                    self._wg_mlp(pre, a, has_g, M, dY)
-                self._on_side(wg_mlp)
-                ops.gemm_nt(self.dbig, self.wT[i]["fc1"], M, D, Hd, ops.EPI_BIAS_BF16, out0=self.dh_small)
-                scr = self.bias_scr[i & 1]
-                if fuse:
-                    # norm2 backward + attention-branch backward in one pass over dx (proj.bias column sums -> scr)
-                    self._before_overwrite("dY2")
-                    ops.layernorm_bwd_branch(self.dh_small, xmid, self.P(pre + "norm2.weight"), a["mean2"], a["rstd2"], dx,
-                                             self.G(pre + "norm2.weight"), self.G(pre + "norm2.bias"), M, D, None,
-                                             self.P(pre + "gamma_1") if has_g else None, dY2, None, scr,
-                                             rowmask=dp_masks[2 * i] if use_dp else None, keep_prob=keep, rows_per_sample=T,
-                                             dropout=self._drop(2 * i))
-                else:
-                    ops.layernorm_bwd(self.dh_small, xmid, self.P(pre + "norm2.weight"), a["mean2"], a["rstd2"], dx,
-                                      self.G(pre + "norm2.weight"), self.G(pre + "norm2.bias"), M, D, accumulate=True)
-                # -- attention branch
-                # proj.bias gradient (column sums of dY) goes to a scratch vector first: the v_bias gradient is
-                # derived from it.  sum_k dV[k] = sum_q dO[q] * sum_k P[q,k] and the softmax rows sum to one, so
-                # v_bias.grad = colsum(d attn_out) = colsum(dY) @ W_proj: one 768x768 GEMV instead of column
-                # sums inside the attention kernel (which cost it 32 VGPRs and its occupancy).
-                if not fuse:
-                    self._before_overwrite("dY2")
-                    ops.branch_bwd(dx, None, self.P(pre + "gamma_1") if has_g else None, dY2, None, scr, M, D,
-                                   rowmask=dp_masks[2 * i] if use_dp else None, keep_prob=keep, rows_per_sample=T,
-                                   dropout=self._drop(2 * i))
-            ops.gemm_nt(dY2, self.wT[i]["proj"], M, D, D, ops.EPI_BIAS_BF16, out0=self.dao)
-            ops.gemv_acc(self.wT[i]["proj"], D, D, scr, self.G(pre + "attn.v_bias"),
-                         x_acc=self.G(pre + "attn.proj.bias"), zero=self.bias_scr[(i & 1) ^ 1])
-
-            def wg_proj(pre=pre, a=a, has_g=has_g, grouped=False):
-                if not grouped:
-                    self._wgrad(dY2, a["ao"], M, D, D, pre + "attn.proj.weight")
-                self._side_read_done("dY2")
-                if has_g:
-                    ops.layerscale_grad(self.W16(pre + "attn.proj.weight", D, D), self.G(pre + "attn.proj.weight").view(D, D),
-                                        self.P(pre + "attn.proj.bias"), self.G(pre + "attn.proj.bias"),
-                                        self.P(pre + "gamma_1"), D, D, self.G(pre + "gamma_1"))
-            if not self.wgrad_group:
-                self._on_side(wg_proj)
-            self._before_overwrite("dqkv")
-            # (rowsum(dO * O) is computed inside the fused 14 x 14 backward; other windows: a delta pass in the library)
-            ops.attn_bwd(a["qkv"], self.dao, a["lse"], self.delta_ws, table, self.window, B, T, D, self.heads,
-                         self.scale, self.dqkv, dtable, dq_bias=self.G(pre + "attn.q_bias"), out=a["ao"], ws=self._attn_ws(B))
-
-            def wg_qkv(pre=pre, a=a, wg_proj=wg_proj):
-                if self.wgrad_group:
-                    self._wgrad_group([(dY2, a["ao"], M, D, D, pre + "attn.proj.weight"),
-                                       (self.dqkv, a["h1"], M, 3 * D, D, pre + "attn.qkv.weight")])
-                    wg_proj(grouped=True)
-                else:
-                    self._wgrad(self.dqkv, a["h1"], M, 3 * D, D, pre + "attn.qkv.weight")
-                self._side_read_done("dqkv")
-            self._on_side(wg_qkv)
-            ops.gemm_nt(self.dqkv, self.wT[i]["qkv"], M, D, 3 * D, ops.EPI_BIAS_BF16, out0=self.dh_small)
-            if fuse and i > 0:
-                # norm1 backward of block i + MLP-branch backward of block i-1 in one pass over dx
-                pb, ab_, bb_ = f"blocks.{i - 1}.", self.act[i - 1], self.model.blocks[i - 1]
-                has_gb = (pb + "gamma_1") in self.segs
-                use_dpb = dp_masks is not None and bb_.drop_prob > 0.0
-                self._before_overwrite("dY")
-                ops.layernorm_bwd_branch(self.dh_small, xin, self.P(pre + "norm1.weight"), a["mean1"], a["rstd1"], dx,
-                                         self.G(pre + "norm1.weight"), self.G(pre + "norm1.bias"), M, D, None,
-                                         self.P(pb + "gamma_2") if has_gb else None, dY, None,
-                                         self.G(pb + "mlp.fc2.bias"),
-                                         rowmask=dp_masks[2 * (i - 1) + 1] if use_dpb else None,
-                                         keep_prob=1.0 - bb_.drop_prob, rows_per_sample=T, dropout=self._drop(2 * (i - 1) + 1))
-            else:
-                ops.layernorm_bwd(self.dh_small, xin, self.P(pre + "norm1.weight"), a["mean1"], a["rstd1"], dx,
-                                  self.G(pre + "norm1.weight"), self.G(pre + "norm1.bias"), M, D, accumulate=True)
+                                  self.G(pre + "norm1.weight"), self.G(pre + "norm1.bias"), ba.rows, D, accumulate=True,
+                                  row_idx=ba.ridx)
             self._bucket_ready(self.depth - i)
         self._backward_embed(c, B, M)
 

@@ -387,7 +387,8 @@ def test_drop_path_work_skipping_equals_masked_execution(fuse):
     batches and sample maps) against the masked execution of the same step (all samples computed, dropped ones multiplied
     by zero), at ViT-B width on the persistent 256-row GEMM kernels: same loss, same gradients (sums over fewer rows in
     another split order: fp32 round-off only), same residual stream.  Includes a branch that keeps everything, one that
-    drops most, and a block without stochastic depth."""
+    drops most, an attention and an MLP branch that drop every sample (their weight gradients are zero-filled, their GEMMs
+    skipped), and a block without stochastic depth."""
     from mem_amd.modeling_pretrain import pt_vit
     from oracle.gen_golden import BASE, vit_inputs
     from oracle.vit_ref import fill_by_name
@@ -398,6 +399,8 @@ def test_drop_path_work_skipping_equals_masked_execution(fuse):
     masks = (torch.rand(8, B, generator=g) > 0.25).float()
     masks[2] = 1.0                                             # block 1, attention branch: nothing dropped this step
     masks[5] = (torch.rand(B, generator=g) > 0.8).float()      # block 2, MLP branch: most samples dropped
+    masks[4] = 0.0                                             # block 2, attention branch: every sample dropped
+    masks[7] = 0.0                                             # block 3, MLP branch: every sample dropped
     res = {}
     for skip in (False, True):
         m = pt_vit(**cfg)
