@@ -35,7 +35,73 @@ def _pad(n, a):
     return (n + a - 1) // a * a
 
 
-class ViTEngine:
+def flat_layout(shapes, skip, order, aliases=()):
+    """Offsets of the flat parameter buffer: a pure function of names, shapes and flags (no device).
+
+    shapes: name -> shape of every parameter to place;  skip: names without weight decay (model.no_weight_decay());
+    order: [(bucket, [entries])], an entry being a parameter name (left out when it is not in `shapes`: gamma_* without
+    layer scale) or a synthetic (name, numel) segment without weight decay;  aliases: (alias, segment, offset, numel) names
+    for a part of a segment.  Every segment starts on a multiple of ALIGN; there is one weight-decay flag per ALIGN elements.
+    -> segs {name: (offset, numel)}, buckets [(bucket, begin, end)], nflat, flags, decay_names."""
+    decays = lambda n: not (len(shapes[n]) == 1 or n.endswith(".bias") or n in skip)   # noqa: E731  (optim_factory.py:63)
+    segs, buckets, flags, off = {}, [], [], 0
+    for bname, entries in order:
+        b0 = off
+        for e in entries:
+            if isinstance(e, tuple):
+                (n, k), flag = e, 0
+            elif e in shapes:
+                n, k, flag = e, math.prod(shapes[e]), int(decays(e))
+            else:
+                continue
+            segs[n] = (off, k)
+            size = _pad(k, ALIGN)
+            flags += [flag] * (size // ALIGN)
+            off += size
+        buckets.append((bname, b0, off))
+    for alias, seg, o, k in aliases:
+        segs[alias] = (segs[seg][0] + o, k)
+    missing = [n for n in shapes if n not in segs]
+    assert not missing, f"parameters not placed in the flat buffer: {missing}"
+    return segs, buckets, off, flags, [n for n in shapes if decays(n)]
+
+
+class FlatParams:
+    """The flat fp32 parameter / gradient buffers of an engine and the nn.Parameter views into them: the layout contract
+    (segs / buckets / wd_flags) that FlatAdamW, GradReducer and checkpoints read."""
+
+    def _pack_flat(self, named, skip, order, aliases=()):
+        self.segs, self.buckets, self.nflat, flags, self.decay_names = flat_layout(
+            {n: tuple(p.shape) for n, p in named.items()}, skip, order, aliases)
+        self.flat_p = torch.zeros(self.nflat, dtype=torch.float32, device=self.dev)
+        self.flat_g = torch.zeros(self.nflat, dtype=torch.float32, device=self.dev)
+        self.wd_flags = torch.tensor(flags, dtype=torch.uint8, device=self.dev)
+        self.named = named
+        for n, p in named.items():
+            o, k = self.segs[n]
+            view = self.flat_p[o:o + k].view(p.shape)
+            view.copy_(p.data)
+            p.data = view
+        self.attach_grads()
+
+    def attach_grads(self):
+        """Re-point p.grad at the flat gradient buffer (zero_grad(set_to_none=True) drops them)."""
+        for n, p in self.named.items():
+            o, k = self.segs[n]
+            g = p.grad
+            if g is None or g.data_ptr() != self.flat_g.data_ptr() + 4 * o:
+                p.grad = self.flat_g[o:o + k].view(p.shape)
+
+    def P(self, name):           # fp32 master view
+        o, k = self.segs[name]
+        return self.flat_p[o:o + k]
+
+    def G(self, name):           # fp32 gradient view
+        o, k = self.segs[name]
+        return self.flat_g[o:o + k]
+
+
+class ViTEngine(FlatParams):
     def __init__(self, model):
         self.model = model
         p0 = next(model.parameters())
@@ -123,78 +189,24 @@ class ViTEngine:
 
     # ------------------------------------------------------------------ parameter packing
     def _pack_parameters(self):
-        m = self.model
-        named = dict(m.named_parameters())
-        skip = m.no_weight_decay()
-        order = []                                    # (bucket, [names]) in reverse-layer order
+        m, D = self.model, self.D
+        order, aliases = [], []                       # (bucket, [entries]) in reverse-layer order
         order.append(("head", ["lm_head.weight", "lm_head.bias", "head.weight", "head.bias", "fc_norm.weight", "fc_norm.bias",
                                "norm.weight", "norm.bias"]))
         for i in reversed(range(self.depth)):
             pre = f"blocks.{i}."
+            qkvb = pre + "attn.qkvbias3"                                      # [q_bias | 0 | v_bias]
+            aliases += [(pre + "attn.q_bias", qkvb, 0, D), (pre + "attn.v_bias", qkvb, 2 * D, D)]
             names = [pre + n for n in ("mlp.fc2.weight", "mlp.fc2.bias", "gamma_2", "mlp.fc1.weight", "mlp.fc1.bias",
                                        "norm2.weight", "norm2.bias", "attn.proj.weight", "attn.proj.bias", "gamma_1",
-                                       "attn.qkv.weight", "QKVBIAS", "attn.relative_position_bias_table", "norm1.weight",
-                                       "norm1.bias")]
+                                       "attn.qkv.weight")]
+            names += [(qkvb, 3 * D)] + [pre + n for n in ("attn.relative_position_bias_table", "norm1.weight", "norm1.bias")]
             order.append((f"block{i}", names))
         order.append(("embed", ["rel_pos_bias.relative_position_bias_table", "patch_embed.proj.weight",
                                 "patch_embed.proj.bias", "mask_token", "cls_token", "pos_embed"]))
-        segs, off = {}, 0
-        buckets, flags = [], []
-        for bname, names in order:
-            b0 = off
-            for n in names:
-                if n.endswith("QKVBIAS"):
-                    pre = n[: -len("QKVBIAS")]
-                    D = self.D
-                    segs[pre + "attn.q_bias"] = (off, D)
-                    segs[pre + "attn.v_bias"] = (off + 2 * D, D)
-                    segs[pre + "attn.qkvbias3"] = (off, 3 * D)          # [q_bias | 0 | v_bias]
-                    size = _pad(3 * D, ALIGN)
-                    flags += [0] * (size // ALIGN)
-                    off += size
-                    continue
-                if n not in named:
-                    continue                                           # gamma_* absent when layer scale is off
-                p = named[n]
-                segs[n] = (off, p.numel())
-                size = _pad(p.numel(), ALIGN)
-                decay = not (p.ndim == 1 or n.endswith(".bias") or n in skip)   # optim_factory.py:63
-                flags += [1 if decay else 0] * (size // ALIGN)
-                off += size
-            buckets.append((bname, b0, off))
-        missing = [n for n in named if n not in segs]
-        assert not missing, f"parameters not placed in the flat buffer: {missing}"
-        self.nflat = off
-        self.segs, self.buckets = segs, buckets
-        self.flat_p = torch.zeros(off, dtype=torch.float32, device=self.dev)
-        self.flat_g = torch.zeros(off, dtype=torch.float32, device=self.dev)
-        self.flat_w16 = torch.zeros(off, dtype=torch.bfloat16, device=self.dev)
-        self.wd_flags = torch.tensor(flags, dtype=torch.uint8, device=self.dev)
-        self.decay_names = [n for n, p in named.items() if not (p.ndim == 1 or n.endswith(".bias") or n in skip)]
-        self.no_decay_names = [n for n in named if n not in set(self.decay_names)]
-        for n, p in named.items():
-            o, k = segs[n]
-            view = self.flat_p[o:o + k].view(p.shape)
-            view.copy_(p.data)
-            p.data = view
-            p.grad = self.flat_g[o:o + k].view(p.shape)
-        self.named = named
-
-    def attach_grads(self):
-        """Re-point p.grad at the flat gradient buffer (zero_grad(set_to_none=True) drops them)."""
-        for n, p in self.named.items():
-            o, k = self.segs[n]
-            g = p.grad
-            if g is None or g.data_ptr() != self.flat_g.data_ptr() + 4 * o:
-                p.grad = self.flat_g[o:o + k].view(p.shape)
-
-    def P(self, name):           # fp32 master view
-        o, k = self.segs[name]
-        return self.flat_p[o:o + k]
-
-    def G(self, name):           # fp32 gradient view
-        o, k = self.segs[name]
-        return self.flat_g[o:o + k]
+        self._pack_flat(dict(m.named_parameters()), m.no_weight_decay(), order, aliases)
+        self.flat_w16 = torch.zeros(self.nflat, dtype=torch.bfloat16, device=self.dev)
+        self.no_decay_names = [n for n in self.named if n not in set(self.decay_names)]
 
     def W16(self, name, rows, cols):   # bf16 shadow as a [rows, cols] matrix
         o, k = self.segs[name]

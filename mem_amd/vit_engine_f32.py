@@ -9,10 +9,22 @@ SURVEY.md 8d config #1: <= 1e-5 rel) -- not for speed: GEMMs run on v_mfma_f32_1
 none of the fast path's derived-gradient shortcuts are used (layer-scale gradient from the stored branch output, v_bias /
 q_bias gradients as column sums of dqkv, delta = sum P dP).
 """
+from functools import partial
+
 import torch
 
 from . import ops
 from .vit_engine import ViTEngine, _pad
+
+
+def wgrad_f32(tA, tB, dY, X, R, n_out, n_in, g):
+    """g [n_out * n_in] += dY[:R]^T X[:R] on the fp32 NT GEMM: both operands transposed into tA / tB ([width, rows padded
+    to 32]) first.  The weight-gradient product of both fp32 parity engines (this one and mae_engine.MaeEngineF32)."""
+    Rp = _pad(R, 32)
+    tA, tB = tA[:n_out, :Rp], tB[:n_in, :Rp]
+    ops.f32_transpose(dY, R, n_out, tA)
+    ops.f32_transpose(X, R, n_in, tB)
+    ops.f32_gemm_nt(tA, tB, n_out, n_in, Rp, ops.EPI_F32, out0=g.view(n_out, n_in), accumulate=True)
 
 
 class ViTEngineF32(ViTEngine):
@@ -75,7 +87,7 @@ class ViTEngineF32(ViTEngine):
         self.dYpe = e(B * self.L, D)
         Rp = _pad(max(M, Mm_cap, B * self.L), 32)
         wide = max(3 * D, Hd, V, self.Kpe)
-        self.tA, self.tB = e(wide, Rp), e(wide, Rp)              # transposed operands of the weight-gradient products
+        self._wgrad32 = partial(wgrad_f32, e(wide, Rp), e(wide, Rp))   # (the transposed operands of the product)
         self.B, self.Mm_cap = B, Mm_cap
 
     # ------------------------------------------------------------------ forward
@@ -132,13 +144,6 @@ class ViTEngineF32(ViTEngine):
         return self.logits[:Mm]
 
     # ------------------------------------------------------------------ backward
-    def _wgrad32(self, dY, X, R, n_out, n_in, gname):
-        Rp = _pad(R, 32)
-        tA, tB = self.tA[:n_out, :Rp], self.tB[:n_in, :Rp]
-        ops.f32_transpose(dY, R, n_out, tA)
-        ops.f32_transpose(X, R, n_in, tB)
-        ops.f32_gemm_nt(tA, tB, n_out, n_in, Rp, ops.EPI_F32, out0=self.G(gname).view(n_out, n_in), accumulate=True)
-
     def backward(self, dlogits=None):
         c = self.cur
         B, M, Mm = c["B"], c["M"], c["Mm"]
@@ -152,7 +157,7 @@ class ViTEngineF32(ViTEngine):
         dx[:M].zero_()
         dl = self.logits
         G(dl, self.wT32_lm, Mm, D, V, ops.EPI_BIAS_BF16, out0=self.dhN)
-        self._wgrad32(dl, self.hN, Mm, V, D, "lm_head.weight")
+        self._wgrad32(dl, self.hN, Mm, V, D, Gr("lm_head.weight"))
         ops.f32_colsum(dl, Mm, V, Gr("lm_head.bias"))
         ops.f32_layernorm_bwd(self.dhN, self.x[2 * self.depth], P("norm.weight"), self.meanN, self.rstdN, dx,
                               Gr("norm.weight"), Gr("norm.bias"), Mm, D, accumulate=False, row_idx=c["rows"])
@@ -171,8 +176,8 @@ class ViTEngineF32(ViTEngine):
                                Gr(pre + "gamma_2") if has_g else None, Gr(pre + "mlp.fc2.bias"), M, D,
                                rowmask=dp_masks[2 * i + 1] if use_dp else None, keep_prob=keep, rows_per_sample=T)
             G(self.dY, self.wT32[i]["fc2"], M, Hd, D, ops.EPI_DGELU, out0=self.dbig, aux=a["hpre"], colsum=Gr(pre + "mlp.fc1.bias"))
-            self._wgrad32(self.dY, a["a"], M, D, Hd, pre + "mlp.fc2.weight")
-            self._wgrad32(self.dbig, a["h2"], M, Hd, D, pre + "mlp.fc1.weight")
+            self._wgrad32(self.dY, a["a"], M, D, Hd, Gr(pre + "mlp.fc2.weight"))
+            self._wgrad32(self.dbig, a["h2"], M, Hd, D, Gr(pre + "mlp.fc1.weight"))
             G(self.dbig, self.wT32[i]["fc1"], M, D, Hd, ops.EPI_BIAS_BF16, out0=self.dh_small)
             ops.f32_layernorm_bwd(self.dh_small, xmid, P(pre + "norm2.weight"), a["mean2"], a["rstd2"], dx,
                                   Gr(pre + "norm2.weight"), Gr(pre + "norm2.bias"), M, D, accumulate=True)
@@ -181,12 +186,12 @@ class ViTEngineF32(ViTEngine):
                                Gr(pre + "gamma_1") if has_g else None, Gr(pre + "attn.proj.bias"), M, D,
                                rowmask=dp_masks[2 * i] if use_dp else None, keep_prob=keep, rows_per_sample=T)
             G(self.dY, self.wT32[i]["proj"], M, D, D, ops.EPI_BIAS_BF16, out0=self.dao)
-            self._wgrad32(self.dY, a["ao"], M, D, D, pre + "attn.proj.weight")
+            self._wgrad32(self.dY, a["ao"], M, D, D, Gr(pre + "attn.proj.weight"))
             ops.f32_attn_bwd(a["qkv"], self.dao, B, T, D, self.heads, self.scale,
                              self.table(i) if self.rel_index is not None else None, self.rel_index, self.dqkv, self.dtable(i))
             ops.f32_colsum(self.dqkv[:, :D], M, D, Gr(pre + "attn.q_bias"))
             ops.f32_colsum(self.dqkv[:, 2 * D:], M, D, Gr(pre + "attn.v_bias"))
-            self._wgrad32(self.dqkv, a["h1"], M, 3 * D, D, pre + "attn.qkv.weight")
+            self._wgrad32(self.dqkv, a["h1"], M, 3 * D, D, Gr(pre + "attn.qkv.weight"))
             G(self.dqkv, self.wT32[i]["qkv"], M, D, 3 * D, ops.EPI_BIAS_BF16, out0=self.dh_small)
             ops.f32_layernorm_bwd(self.dh_small, xin, P(pre + "norm1.weight"), a["mean1"], a["rstd1"], dx,
                                   Gr(pre + "norm1.weight"), Gr(pre + "norm1.bias"), M, D, accumulate=True)
@@ -195,7 +200,7 @@ class ViTEngineF32(ViTEngine):
         if self.has_pos:
             Gr("pos_embed").view(T, D).copy_(dx[:M].view(B, T, D).sum(0))
         ops.f32_embed_bwd(dx, c["mask"], B, L, D, self.dYpe, Gr("cls_token"), Gr("mask_token"))
-        self._wgrad32(self.dYpe, self.patches, B * L, D, self.Kpe, "patch_embed.proj.weight")
+        self._wgrad32(self.dYpe, self.patches, B * L, D, self.Kpe, Gr("patch_embed.proj.weight"))
         ops.f32_colsum(self.dYpe, B * L, D, Gr("patch_embed.proj.bias"))
         if self.grad_hook:
             self.grad_hook(self.depth + 1)

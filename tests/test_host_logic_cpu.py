@@ -120,3 +120,67 @@ def test_host_thread_cap_respects_the_container_quota(monkeypatch):
         assert cap_host_threads(64) <= torch.get_num_threads()          # a larger limit does not raise the pool again
     finally:
         torch.set_num_threads(before)
+
+
+def _check_flat_layout(segs, buckets, nflat, flags, placed):
+    """Every placed segment starts on a multiple of 1024 and none overlap; the buckets are contiguous and cover [0, nflat);
+    one weight-decay flag per 1024 elements."""
+    spans = sorted(segs[n] for n in placed)
+    assert all(o % 1024 == 0 and k > 0 for o, k in spans)
+    assert all(o0 + k0 <= o1 for (o0, k0), (o1, _) in zip(spans, spans[1:])) and sum(spans[-1]) <= nflat
+    assert buckets[0][1] == 0 and buckets[-1][2] == nflat and nflat % 1024 == 0
+    assert all(b0[2] == b1[1] for b0, b1 in zip(buckets, buckets[1:])) and all(b[1] < b[2] for b in buckets)
+    assert len(flags) == nflat // 1024 and set(flags) <= {0, 1}
+    return lambda n: set(flags[segs[n][0] // 1024: (sum(segs[n]) + 1023) // 1024])
+
+
+def test_flat_layout_offsets_mae_and_vit_ordering():
+    """vit_engine.flat_layout (the offsets behind every engine's flat buffer; no device) on the names and shapes of the tiny
+    MAE model in the MAE engine's bucket order, and on a 2-block ViT ordering with the synthetic qkv-bias segment."""
+    from mem_amd.modeling_mae import MaskedAutoencoderViT
+    from mem_amd.vit_engine import flat_layout
+    from oracle.mae_ref import TINY_MAE
+    m = _quiet(MaskedAutoencoderViT, **TINY_MAE)
+    shapes = {n: tuple(p.shape) for n, p in m.named_parameters() if p.requires_grad}
+    dec = [n for n in shapes if n.startswith("decoder") or n == "mask_token"]
+    enc = [n for n in shapes if n not in dec]
+    assert "pos_embed" not in shapes and "decoder_pos_embed" not in shapes and len(dec) == 31 and len(enc) == 29
+    segs, buckets, nflat, flags, decay = flat_layout(shapes, {"cls_token"}, [("decoder", dec), ("encoder", enc)])
+    flag = _check_flat_layout(segs, buckets, nflat, flags, list(shapes))
+    assert set(segs) == set(shapes) and all(segs[n][1] == int(np.prod(shapes[n])) for n in shapes)
+    assert [b[0] for b in buckets] == ["decoder", "encoder"]                     # the decoder bucket precedes the encoder's
+    assert all(buckets[0][1] <= segs[n][0] < buckets[0][2] for n in dec)
+    assert all(buckets[1][1] <= segs[n][0] < buckets[1][2] for n in enc)
+    for n, shp in shapes.items():                                                # optim_factory.py:63
+        want = 0 if (len(shp) == 1 or n.endswith(".bias") or n == "cls_token") else 1
+        assert flag(n) == {want}, n
+        assert (n in decay) == bool(want)
+    assert flag("blocks.0.norm1.weight") == {0} and flag("decoder_pred.bias") == {0} and flag("cls_token") == {0}
+    assert flag("blocks.1.mlp.fc1.weight") == {1} and flag("decoder_embed.weight") == {1} and flag("mask_token") == {1}
+    assert decay == [n for n in shapes if n in set(decay)]                       # in the model's parameter order
+    # ---- a 2-block ViT ordering (reverse-layer buckets), D = 128: [q_bias | 0 | v_bias] as one synthetic segment
+    D = 128
+    shapes = {"norm.weight": (D,), "patch_embed.proj.weight": (D, 3, 16, 16), "cls_token": (1, 1, D)}
+    order, aliases = [("head", ["lm_head.weight", "norm.weight"])], []           # (lm_head.weight: absent, left out)
+    for i in (1, 0):
+        pre = f"blocks.{i}."
+        shapes.update({pre + "attn.qkv.weight": (3 * D, D), pre + "attn.q_bias": (D,), pre + "attn.v_bias": (D,),
+                       pre + "gamma_1": (D,), pre + "attn.proj.bias": (D,)})
+        order.append((f"block{i}", [pre + "attn.proj.bias", pre + "gamma_1", pre + "gamma_2", pre + "attn.qkv.weight",
+                                    (pre + "attn.qkvbias3", 3 * D)]))
+        aliases += [(pre + "attn.q_bias", pre + "attn.qkvbias3", 0, D), (pre + "attn.v_bias", pre + "attn.qkvbias3", 2 * D, D)]
+    order.append(("embed", ["patch_embed.proj.weight", "cls_token"]))
+    segs, buckets, nflat, flags, decay = flat_layout(shapes, {"cls_token"}, order, aliases)
+    placed = [n for n in segs if not n.endswith(("q_bias", "v_bias"))]
+    flag = _check_flat_layout(segs, buckets, nflat, flags, placed)
+    assert [b[0] for b in buckets] == ["head", "block1", "block0", "embed"] and "lm_head.weight" not in segs
+    for i in (0, 1):
+        o, k = segs[f"blocks.{i}.attn.qkvbias3"]
+        assert k == 3 * D and segs[f"blocks.{i}.attn.q_bias"] == (o, D) and segs[f"blocks.{i}.attn.v_bias"] == (o + 2 * D, D)
+        assert flag(f"blocks.{i}.attn.qkvbias3") == {0} and flag(f"blocks.{i}.attn.qkv.weight") == {1}
+        assert flag(f"blocks.{i}.gamma_1") == {0} and f"blocks.{i}.gamma_2" not in segs
+    assert flag("patch_embed.proj.weight") == {1} and flag("cls_token") == {0} and flag("norm.weight") == {0}
+    assert decay == ["patch_embed.proj.weight", "blocks.1.attn.qkv.weight", "blocks.0.attn.qkv.weight"]
+    import pytest
+    with pytest.raises(AssertionError, match="not placed"):
+        flat_layout(dict(shapes, stray=(4,)), set(), order, aliases)

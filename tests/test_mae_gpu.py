@@ -1,8 +1,8 @@
 """-m gpu: the MAE variant (mem_amd/modeling_mae.py -> csrc/fp32_path.hip: fp32 GEMMs, generic attention with 64- and
 32-wide heads, token gather / mask-token un-shuffle, per-patch MSE loss) against the REFERENCE's MaskedAutoencoderViT
 (tests/golden/mae_tiny.npz, oracle/gen_golden_mae.py: fp32 CPU, timm Block / PatchEmbed restated): same-seed weights
-equal, loss 2e-6 rel, pred 2e-5, mask equal, every gradient rel-L2 <= 2e-5; both loss modes; a short training run
-through engine_for_pretraining.train_one_epoch(MAE=True); the ViT-B MAE factory shapes.
+equal, loss 2e-6 rel, pred 2e-5, mask equal, every gradient rel-L2 <= 2e-5; both loss modes; the bf16 engine
+(mem_amd/mae_engine.py) against the reference under autocast; a short training run through engine_for_pretraining.train_one_epoch(MAE=True); the ViT-B MAE factory shapes.
 Reference: mem/modeling_mae.py:101-313, mem/run_mem_pretraining.py:231-232,275-276, mem/engine_for_pretraining.py:141-149."""
 import contextlib
 import io
@@ -57,26 +57,38 @@ def _check_bf16(m, g, tag, imgs, noise, sample, grad_tol, pred_tol):
     return checked
 
 
-def test_mae_bf16_engine_vs_reference_autocast_golden():
+@pytest.mark.parametrize("fuse", [True, False])
+def test_mae_bf16_tiny_vs_reference_autocast_golden(fuse):
     """f4 on the fast path: the bf16 MFMA engine (what `--mae 1` trains with) against the REFERENCE MaskedAutoencoderViT under
-    bf16 autocast (tests/golden/mae_bf16.npz, oracle/gen_golden_mae.py): the tiny config (2-wide decoder heads of 32: the
-    padded-head path; every gradient whole) and the ViT-B factory at B = 2 (12 x 768 encoder on 99 tokens, 8 x 512 decoder
-    with 16 heads of 32 on 197 tokens).  Loss 5e-3 rel, prediction, mask equal, every gradient rel-L2 <= 3e-2 (VERDICT
-    bar), per-tensor norms 3 %, pooled cosine >= 0.9995."""
-    from functools import partial
-    from mem_amd.modeling_mae import mae_vit_base_patch16_dec512d8b
-    from oracle.gen_golden_mae import BASE_MAE_B, sample
+    bf16 autocast (tests/golden/mae_bf16.npz, oracle/gen_golden_mae.py), tiny config (2-wide decoder heads of 32: the
+    padded-head path; every gradient whole; two blocks per stack: all three positions of the fused LayerNorm backward), with
+    the LayerNorm backward fused into the branch backward (FUSE_LN_BRANCH, the default) and in the two-kernel form: one
+    golden, one set of bars.  Loss 5e-3 rel, prediction, mask equal, every gradient rel-L2 <= 3e-2 (VERDICT bar), per-tensor
+    norms 3 %, pooled cosine >= 0.9995."""
+    from oracle.gen_golden_mae import sample
     from oracle.mae_ref import TINY_MAE, mae_inputs
     g = np.load(os.path.join(GOLDEN, "mae_bf16.npz"))
     m = _tiny(True, precision="bf16").cuda().train()
     assert type(m.engine).__name__ == "MaeEngineBF16"
+    m.engine.FUSE_LN_BRANCH = fuse                               # on the instance: nothing global to restore
     imgs, noise = mae_inputs(TINY_MAE, 4, 21)
     assert _check_bf16(m, g, "tiny", imgs, noise, sample, 3e-2, 0.03) >= 40
+
+
+def test_mae_bf16_engine_vs_reference_autocast_golden():
+    """The same against the ViT-B factory at B = 2 (12 x 768 encoder on 99 tokens, 8 x 512 decoder with 16 heads of 32 on 197
+    tokens; loss, a block of the prediction, every gradient's norm, small gradients whole, big ones on every 32nd row), same
+    bars; the padded head slots stay exact zeros."""
+    from mem_amd.modeling_mae import mae_vit_base_patch16_dec512d8b
+    from oracle.gen_golden_mae import BASE_MAE_B, sample
+    from oracle.mae_ref import mae_inputs
+    g = np.load(os.path.join(GOLDEN, "mae_bf16.npz"))
     with contextlib.redirect_stdout(io.StringIO()):
         torch.manual_seed(3)
         b = mae_vit_base_patch16_dec512d8b(norm_pix_loss=0, LOSS_ONLY_MASKED_MAE=True, img_size=224)
     assert b.precision == "bf16"
     b = b.cuda().train()
+    assert type(b.engine).__name__ == "MaeEngineBF16"
     cfg = dict(img_size=224, patch_size=16)
     imgs, noise = mae_inputs(cfg, BASE_MAE_B, 33)
     assert _check_bf16(b, g, "base", imgs, noise, sample, 3e-2, 0.05) >= 200

@@ -6,7 +6,11 @@ traces of two checkouts can be compared with diff.  Arguments are bound to the c
 them (positional, keyword, default left out) does not show.  ops.dropout_params / with_row0 build a host-side struct and
 launch nothing: they get no line of their own, the struct's fields appear in the launch that takes it.
 
-    python tools/engine_launch_trace.py OUT.txt        # needs the GPU; prints the line count per scenario
+The MAE engines (second section) launch on one stream and issue plain torch ops besides (copy_ of a bf16 Linear output into its
+fp32 buffer, zero_ / add_ on the padded-head gradients): there every in-place or out= ATen call is recorded as well, as
+"aten.<op>" with the same tensor description, through a TorchDispatchMode around the step.
+
+    python tools/engine_launch_trace.py OUT.txt [vit|mae]    # needs the GPU; prints the line count per scenario
 """
 import ctypes
 import inspect
@@ -15,6 +19,7 @@ import os
 import sys
 
 import torch
+from torch.utils._python_dispatch import TorchDispatchMode
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from mem_amd import ops, vit_engine as VE                      # noqa: E402
@@ -31,8 +36,8 @@ def fmt(v):
         return "{" + " ".join(f"{n}={getattr(v, n)!r}" for n, _ in v._fields_) + "}"
     if isinstance(v, (list, tuple)):
         return "[" + ", ".join(fmt(e) for e in v) + "]"
-    if isinstance(v, VE.ViTEngine) or callable(v):               # self of an engine call; the closure given to _on_side
-        return "."
+    if isinstance(v, VE.ViTEngine) or callable(v) or type(v).__name__.startswith("MaeEngine"):
+        return "."                                                # self of an engine call; the closure given to _on_side
     return repr(v)
 
 
@@ -43,7 +48,7 @@ def traced(name, f):
         ba = sig.bind(*a, **k)
         ba.apply_defaults()
         eng = ENG[0]
-        side = eng is not None and eng._side is not None and torch.cuda.current_stream() == eng._side
+        side = getattr(eng, "_side", None) is not None and torch.cuda.current_stream() == eng._side
         LINES.append(f"{name} {'side' if side else 'main'} " + " ".join(f"{n}={fmt(v)}" for n, v in ba.arguments.items()))
         return f(*a, **k)
     return g
@@ -56,14 +61,26 @@ for n in ENGINE_CALLS:
     setattr(VE.ViTEngine, n, traced(n, getattr(VE.ViTEngine, n)))
 
 
-def run(out, name, eng, step, **switches):
+class TorchWrites(TorchDispatchMode):
+    """Every ATen call that writes into one of its arguments (copy_, zero_, add_, out= forms) as a trace line."""
+    def __torch_dispatch__(self, func, types, args=(), kwargs=None):
+        if func._schema.is_mutable:
+            LINES.append(f"aten.{func._schema.name[6:]} " + " ".join(fmt(a) for a in (*args, *(kwargs or {}).values())))
+        return func(*args, **(kwargs or {}))
+
+
+def run(out, name, eng, step, torch_ops=False, **switches):
     """One scenario: set the switches, run step(), restore them; its lines go behind a header with their count."""
     old = {k: getattr(eng, k) for k in switches}
     for k, v in switches.items():
         setattr(eng, k, v)
     ENG[0], LINES[:] = eng, []
     eng.grad_hook = traced("grad_hook", lambda bucket: None)
-    step()
+    if torch_ops:
+        with TorchWrites():
+            step()
+    else:
+        step()
     torch.cuda.synchronize()
     for k, v in old.items():
         setattr(eng, k, v)
@@ -71,13 +88,12 @@ def run(out, name, eng, step, **switches):
     print(f"{len(LINES):5d}  {name} {switches}")
 
 
-def main(path):
+def vit_section(out):
     from mem_amd.modeling_finetune import ft_vit
     from mem_amd.modeling_pretrain import pt_vit
     torch.manual_seed(0)
     g = torch.Generator().manual_seed(1)
     rnd = lambda *s: (torch.rand(*s, generator=g) > 0.3).float()   # noqa: E731
-    out = open(path, "w")
     # ---- pretraining model: 3 blocks at ViT-B width, drop probabilities 0 / 0.15 / 0.3 (block 0 never drops)
     B = 8
     m = pt_vit(img_size=(224, 224), patch_size=(16, 16), in_chans=2, vocab_size=8192, embed_dim=768, depth=3, num_heads=12,
@@ -130,8 +146,51 @@ def main(path):
         run(out, f"ft masked dropout={dk is not None}", eng, lambda: ft_step(False, dk), fwd_two_streams=True)
     for skip in (False, True):
         run(out, f"ft {'skip' if skip else 'masked'} dropout=True keep=False", eng, lambda: ft_step(skip, key, keep=False))
-    out.close()
+
+
+def mae_section(out):
+    """Two optimizer steps per scenario (forward_loss, backward, grad_norm, FlatAdamW.step): the second one runs sync_weights
+    after an update.  Tiny config: 64-wide encoder heads, 32-wide (padded) decoder heads, two blocks per stack."""
+    import contextlib
+    import io
+    from mem_amd.modeling_mae import MaskedAutoencoderViT, mae_vit_base_patch16_dec512d8b
+    from mem_amd.optim_factory import FlatAdamW, get_parameter_groups
+    from oracle.mae_ref import TINY_MAE, mae_inputs
+
+    def scenario(name, build, precision, imgs, noise, gelu_dg=True, **switches):
+        with contextlib.redirect_stdout(io.StringIO()):
+            torch.manual_seed(3)
+            m = build()
+            m.precision = precision
+            m = m.cuda().train()
+            opt = FlatAdamW(m, get_parameter_groups(m, 0.05, m.no_weight_decay()), lr=1e-4)
+        opt.max_norm = 3.0
+        eng = m.engine
+        if not gelu_dg:
+            eng.set_gelu_dg(False)
+        imgs, noise = imgs.cuda(), noise.cuda()
+
+        def step():
+            for _ in range(2):
+                m.forward_loss(imgs, noise=noise)
+                m.backward()
+                eng.grad_norm()
+                opt.step()
+        run(out, name, eng, step, torch_ops=True, **switches)
+    imgs, noise = mae_inputs(TINY_MAE, 4, 21)
+    for mode in (True, False):
+        scenario(f"mae tiny fp32 masked_only={mode}", lambda: MaskedAutoencoderViT(**dict(TINY_MAE, LOSS_ONLY_MASKED_MAE=mode)),
+                 "fp32", imgs, noise)
+    tiny = lambda: MaskedAutoencoderViT(**dict(TINY_MAE, LOSS_ONLY_MASKED_MAE=True))   # noqa: E731
+    for fuse in (True, False):
+        scenario("mae tiny bf16", tiny, "bf16", imgs, noise, FUSE_LN_BRANCH=fuse)
+    scenario("mae tiny bf16 gelu_dg=False", tiny, "bf16", imgs, noise, gelu_dg=False)
+    imgs, noise = mae_inputs(dict(img_size=224, patch_size=16), 2, 33)
+    scenario("mae base bf16", lambda: mae_vit_base_patch16_dec512d8b(norm_pix_loss=0, LOSS_ONLY_MASKED_MAE=True, img_size=224),
+             "bf16", imgs, noise)
 
 
 if __name__ == "__main__":
-    main(sys.argv[1])
+    with open(sys.argv[1], "w") as out:
+        for section in (sys.argv[2:] or ["vit", "mae"]):
+            {"vit": vit_section, "mae": mae_section}[section](out)
