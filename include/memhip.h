@@ -36,7 +36,7 @@ extern "C" {
 #endif
 
 #define MEMHIP_ABI_VERSION 7   /* 7: the finetuning recipe (memhip_mixup, memhip_mix_targets, memhip_ce_soft, memhip_ema_update), and -- additive, no
-                                  existing signature changed, so the number stays -- memhip_pool_tokens / memhip_pool_tokens_bwd; 6: element-wise dropout (memhip_dropout_t, epilogue RESIDUAL_DROP, memhip_gemm_args_t.dropout, the
+                                  existing signature changed, so the number stays -- memhip_pool_tokens / memhip_pool_tokens_bwd, memhip_gemm_bf16_nt_plan; 6: element-wise dropout (memhip_dropout_t, epilogue RESIDUAL_DROP, memhip_gemm_args_t.dropout, the
                                   *_drop row kernels); 5 (round 6): memhip_build_flags, memhip_attn_bwd_ws / _out_ws / _workspace; 4 (round 5): epilogues 6 / 7 carry the stored GELU derivative as FP16 (since round 4), certified-tokenizer entry points */
 
 #define MEMHIP_OK 0
@@ -362,6 +362,26 @@ typedef struct memhip_gemm_args {
                                        must be NULL (ABI 6) */
 } memhip_gemm_args_t;
 int memhip_gemm_bf16_nt(const memhip_gemm_args_t* args, memhip_stream_t stream);
+
+/* The dispatch of memhip_gemm_bf16_nt as data: which kernel form takes which rows of the product (additive to ABI 7).
+ * memhip_gemm_bf16_nt_plan validates `args` like the GEMM itself and plans with the current option values for a stream
+ * with stream_cus usable CUs on a device of device_cus CUs; it launches nothing and needs no device (pointers are
+ * checked, never read).  The launches cover rows [0, M) once, in order. */
+#define MEMHIP_NT_128 0       /* 128x128 kernel, one workgroup per tile */
+#define MEMHIP_NT_G256 1      /* lockstep persistent 256x256 kernel (grid sized for device_cus) */
+#define MEMHIP_NT_P8_256 2    /* phase-interleaved persistent kernel, 256-row tiles (rows % 256 == 0) */
+#define MEMHIP_NT_P8_128 3    /* the same on 128-row tiles */
+#define MEMHIP_NT_P8_PAIR 4   /* one launch: 256-row tiles on `rows`, 128-row tiles on the `tail_rows` behind them */
+typedef struct memhip_nt_launch {
+  int32_t kind;
+  int32_t row0, rows;
+  int32_t tail_rows;          /* P8_PAIR only */
+  int32_t guard;              /* P8_128 / P8_PAIR: the 128-row range is not a multiple of 128 rows */
+  int32_t copy;               /* P8_*: the kernel form that stores out0 */
+  int32_t grid, tail_grid;    /* workgroups: tiles (NT_128) or min(tiles, CUs); tail_grid: the 128-row part of a pair */
+} memhip_nt_launch_t;
+typedef struct memhip_nt_plan { int32_t count; memhip_nt_launch_t l[2]; } memhip_nt_plan_t;
+int memhip_gemm_bf16_nt_plan(const memhip_gemm_args_t* args, int stream_cus, int device_cus, memhip_nt_plan_t* out);
 
 /* Weight-gradient GEMM  out[N,K] (+)= sum_r A[r,N] * B[r,K]  (A = dY, B = X, both token-major
  * bf16 with the reduction over ROWS): the dY^T @ X that autograd computes for every Linear /

@@ -171,8 +171,7 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_nt_kernel(typename EpiArgs<E
 }
 
 template <int EPI>
-int launch(const GemmArgs& p, hipStream_t s) {
-  const int ntm = (p.M + BM - 1) / BM, ntn = (p.N + BN - 1) / BN;
+int launch(const GemmArgs& p, hipStream_t s, int grid) {
   static bool attr_done = false;
   if (!attr_done) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_nt_kernel<EPI>),
@@ -181,24 +180,15 @@ int launch(const GemmArgs& p, hipStream_t s) {
     attr_done = true;
   }
   // (the dropout epilogue's kernel takes a GemmArgsD: the dispatcher's arguments are one)
-  hipLaunchKernelGGL(gemm_nt_kernel<EPI>, dim3(ntm * ntn), dim3(kThreads), 2 * kStageBytes, s,
+  hipLaunchKernelGGL(gemm_nt_kernel<EPI>, dim3(grid), dim3(kThreads), 2 * kStageBytes, s,
                      static_cast<const typename EpiArgs<EPI>::type&>(p));
   return check_launch("gemm_bf16_nt");
 }
 
-}  // namespace
-
-namespace memhip {
-int gemm256_dispatch(const GemmArgs& p, hipStream_t s);
-int gemm_p8_dispatch(const GemmArgs& p, hipStream_t s);
-int gemm_p8_split_rows(const GemmArgs& p, hipStream_t s);
-int gemm_p8_half_dispatch(const GemmArgs& p, hipStream_t s);
-int gemm_p8_pair_dispatch(const GemmArgs& head, const GemmArgs& tail, hipStream_t s);
-}
-
-extern "C" int memhip_gemm_bf16_nt(const memhip_gemm_args_t* a, memhip_stream_t stream) {
+// The argument checks of memhip_gemm_bf16_nt; `p` = the arguments as the launchers carry them (a GemmArgsD all the way
+// down: the RESIDUAL_DROP launchers read its dropout parameters).
+int validate(const memhip_gemm_args_t* a, GemmArgsD& p) {
   MEMHIP_REQUIRE(a, "gemm: null args");
-  GemmArgsD p;     // (a GemmArgsD all the way down: the RESIDUAL_DROP launchers read its dropout parameters)
   static_assert(offsetof(GemmArgs, m_base) == offsetof(memhip_gemm_args_t, dropout),
                 "GemmArgs = the ABI struct up to `dropout` + internal tail");
   __builtin_memset(&p, 0, sizeof(p));
@@ -209,7 +199,6 @@ extern "C" int memhip_gemm_bf16_nt(const memhip_gemm_args_t* a, memhip_stream_t 
   MEMHIP_REQUIRE(p.A && p.B, "gemm: null operand");
   MEMHIP_REQUIRE(p.lda % 8 == 0 && p.ldb % 8 == 0 && ((uintptr_t)p.A & 15) == 0 && ((uintptr_t)p.B & 15) == 0,
                  "gemm: operands must be 16-byte aligned with ld %% 8 == 0");
-  hipStream_t s = as_stream(stream);
   switch (p.epilogue) {
     case MEMHIP_EPI_BIAS_BF16: MEMHIP_REQUIRE(p.out0, "gemm: out0"); break;
     case MEMHIP_EPI_BIAS_GELU: MEMHIP_REQUIRE(p.out0 && p.out1, "gemm: out0/out1"); break;
@@ -233,78 +222,67 @@ extern "C" int memhip_gemm_bf16_nt(const memhip_gemm_args_t* a, memhip_stream_t 
   }
   MEMHIP_REQUIRE(!a->dropout || p.epilogue == MEMHIP_EPI_RESIDUAL_DROP, "gemm: dropout is taken by epilogue %d only",
                  MEMHIP_EPI_RESIDUAL_DROP);
-  // large token-dimension products: the phase-interleaved persistent kernel (gemm_p8.hip); the lockstep 256x256
-  // kernel (gemm256.hip) takes shapes it does not (K a multiple of 64 but not of 128, or MEMHIP_GEMM_P8=0)
-  const bool k256_on = opt(OPT_GEMM256) != 0;
-  const bool p8_on = opt(OPT_GEMM_P8) != 0;
-  if (p8_on) {
-    // A persistent 256x256-tile launch whose last round would be poorly filled (N = 768: 591 tiles on
-    // 256 CUs) only takes the rows of the full rounds; the remaining rows go to the 128x128 kernel
-    // below (finer tiles, 2-3 workgroups per CU).  Rows are independent, so this is two launches of
-    // the same contract on two row ranges.
-    const bool split_on = opt(OPT_GEMM_SPLIT) != 0;
-    const int split = split_on ? gemm_p8_split_rows(p, s) : 0;
-    if (split > 0 && split < p.M && p.epilogue != MEMHIP_EPI_PATCH_EMBED) {
-      const GemmArgsD whole = p;
-      GemmArgsD head = p;
-      head.M = split;
-      {
-        const long long r = split;
-        p.A += r * p.lda;
-        if (p.out0) p.out0 = (char*)p.out0 + r * p.ldo0 * (p.epilogue == MEMHIP_EPI_F32 ? 4 : 2);
-        if (p.out1) p.out1 = (char*)p.out1 + r * p.ldo1 * 2;
-        // (with a sample map the residual rows are addressed through the map: resid / aux stay where they are)
-        if (p.resid && !p.sample_map) p.resid += r * p.ldr;
-        if (p.aux && !(p.sample_map && epi_resid(p.epilogue)))
-          p.aux = (const char*)p.aux + r * p.ldaux * (epi_resid(p.epilogue) ? 4 : 2);
-        p.M -= split;
-        p.m_base = split;
-      }
-      // one launch for both row ranges (gemm_p8.hip: gemm_p8_pair_kernel) when the epilogue has a paired form
-      if (opt(OPT_GEMM_P8_HALF) != 0 && opt(OPT_GEMM_P8_PAIR) != 0) {
-        const int rcp = gemm_p8_pair_dispatch(head, p, s);
-        if (rcp != MEMHIP_EUNSUPPORTED) return rcp;
-      }
-      const int rc = gemm_p8_dispatch(head, s);
-      if (rc == MEMHIP_OK) {
-        // the left-over rows: the same phase structure on 128-row tiles (MEMHIP_GEMM_P8_HALF=0: 128x128 kernel)
-        const bool half_on = opt(OPT_GEMM_P8_HALF) != 0;
-        if (half_on) {
-          const int rch = gemm_p8_half_dispatch(p, s);
-          if (rch != MEMHIP_EUNSUPPORTED) return rch;
-        }
-        switch (p.epilogue) {
-          case MEMHIP_EPI_BIAS_BF16: return launch<MEMHIP_EPI_BIAS_BF16>(p, s);
-          case MEMHIP_EPI_BIAS_GELU: return launch<MEMHIP_EPI_BIAS_GELU>(p, s);
-          case MEMHIP_EPI_RESIDUAL: return launch<MEMHIP_EPI_RESIDUAL>(p, s);
-          case MEMHIP_EPI_DGELU: return launch<MEMHIP_EPI_DGELU>(p, s);
-          case MEMHIP_EPI_BIAS_GELU_DG: return launch<MEMHIP_EPI_BIAS_GELU_DG>(p, s);
-          case MEMHIP_EPI_MUL_AUX: return launch<MEMHIP_EPI_MUL_AUX>(p, s);
-          case MEMHIP_EPI_RESIDUAL_DROP: return launch<MEMHIP_EPI_RESIDUAL_DROP>(p, s);
-          default: return launch<MEMHIP_EPI_F32>(p, s);
-        }
-      }
-      if (rc != MEMHIP_EUNSUPPORTED) return rc;
-      p = whole;                                   // no persistent form for this call: the paths below take all rows
-    } else {
-      const int rc = gemm_p8_dispatch(p, s);
-      if (rc != MEMHIP_EUNSUPPORTED) return rc;
+  return MEMHIP_OK;
+}
+
+NtPlan plan_now(const GemmArgs& p, int stream_cus, int device_cus) {
+  if (p.M == 0) return NtPlan{};
+  const NtOptions o = {opt(OPT_GEMM_P8), opt(OPT_GEMM256), opt(OPT_GEMM_SPLIT), opt(OPT_GEMM_P8_HALF), opt(OPT_GEMM_P8_PAIR),
+                       opt(OPT_GEMM_P8_MIN_N), opt(OPT_GEMM256_MIN_N)};
+  return gemm_nt_plan(p, stream_cus, device_cus, o);
+}
+
+// Rows [row0, row0 + rows) of the product as a problem of its own.  Rows are independent, so a plan of two launches is the
+// same contract on two row ranges.
+GemmArgsD slice_rows(GemmArgsD p, int row0, int rows) {
+  const long long r = row0;
+  p.A += r * p.lda;
+  if (p.out0) p.out0 = (char*)p.out0 + r * p.ldo0 * (p.epilogue == MEMHIP_EPI_F32 ? 4 : 2);
+  if (p.out1) p.out1 = (char*)p.out1 + r * p.ldo1 * 2;
+  // (with a sample map the residual rows are addressed through the map: resid / aux stay where they are)
+  if (p.resid && !p.sample_map) p.resid += r * p.ldr;
+  if (p.aux && !(p.sample_map && epi_resid(p.epilogue)))
+    p.aux = (const char*)p.aux + r * p.ldaux * (epi_resid(p.epilogue) ? 4 : 2);
+  p.M = rows;
+  p.m_base = row0;
+  return p;
+}
+
+}  // namespace
+
+namespace memhip {
+int gemm256_launch(const GemmArgs& p, const NtLaunch& l, hipStream_t s);
+int gemm_p8_launch(const GemmArgs& p, const NtLaunch& l, hipStream_t s);
+int gemm_p8_pair_launch(const GemmArgs& head, const GemmArgs& tail, const NtLaunch& l, hipStream_t s);
+}
+
+// validate -> plan -> launch
+extern "C" int memhip_gemm_bf16_nt(const memhip_gemm_args_t* a, memhip_stream_t stream) {
+  GemmArgsD p;
+  if (const int rc = validate(a, p)) return rc;
+  hipStream_t s = as_stream(stream);
+  const NtPlan plan = plan_now(p, usable_cus(s), max_cus());
+  for (int i = 0; i < plan.count; ++i) {
+    const NtLaunch& l = plan.l[i];
+    const GemmArgsD part = slice_rows(p, l.row0, l.rows);
+    int rc;
+    switch (l.kind) {
+      case MEMHIP_NT_P8_PAIR: rc = gemm_p8_pair_launch(part, slice_rows(p, l.row0 + l.rows, l.tail_rows), l, s); break;
+      case MEMHIP_NT_P8_256:
+      case MEMHIP_NT_P8_128: rc = gemm_p8_launch(part, l, s); break;
+      case MEMHIP_NT_G256: rc = gemm256_launch(part, l, s); break;
+      default:             // MEMHIP_NT_128: all nine epilogues
+        rc = dispatch_epilogue(part.epilogue, [&](auto E) { return launch<decltype(E)::value>(part, s, l.grid); });
     }
+    if (rc != MEMHIP_OK) return rc;
   }
-  if (k256_on) {
-    const int rc = gemm256_dispatch(p, s);
-    if (rc != MEMHIP_EUNSUPPORTED) return rc;
-  }
-  switch (p.epilogue) {
-    case MEMHIP_EPI_BIAS_BF16: MEMHIP_REQUIRE(p.out0, "gemm: out0"); return launch<MEMHIP_EPI_BIAS_BF16>(p, s);
-    case MEMHIP_EPI_BIAS_GELU: MEMHIP_REQUIRE(p.out0 && p.out1, "gemm: out0/out1"); return launch<MEMHIP_EPI_BIAS_GELU>(p, s);
-    case MEMHIP_EPI_RESIDUAL: return launch<MEMHIP_EPI_RESIDUAL>(p, s);
-    case MEMHIP_EPI_DGELU: MEMHIP_REQUIRE(p.out0 && p.aux, "gemm: dgelu args"); return launch<MEMHIP_EPI_DGELU>(p, s);
-    case MEMHIP_EPI_BIAS_GELU_DG: return launch<MEMHIP_EPI_BIAS_GELU_DG>(p, s);
-    case MEMHIP_EPI_MUL_AUX: return launch<MEMHIP_EPI_MUL_AUX>(p, s);
-    case MEMHIP_EPI_F32: MEMHIP_REQUIRE(p.out0, "gemm: out0"); return launch<MEMHIP_EPI_F32>(p, s);
-    case MEMHIP_EPI_PATCH_EMBED: MEMHIP_REQUIRE(p.resid && p.vec1 && p.aux, "gemm: patch args"); return launch<MEMHIP_EPI_PATCH_EMBED>(p, s);
-    case MEMHIP_EPI_RESIDUAL_DROP: return launch<MEMHIP_EPI_RESIDUAL_DROP>(p, s);
-    default: return fail(MEMHIP_EINVAL, "gemm: unknown epilogue %d", p.epilogue);
-  }
+  return MEMHIP_OK;
+}
+
+extern "C" int memhip_gemm_bf16_nt_plan(const memhip_gemm_args_t* a, int stream_cus, int device_cus, memhip_nt_plan_t* out) {
+  MEMHIP_REQUIRE(out && stream_cus >= 0 && device_cus >= 0, "gemm plan: bad arguments");
+  GemmArgsD p;
+  if (const int rc = validate(a, p)) return rc;
+  *out = plan_now(p, stream_cus, device_cus);
+  return MEMHIP_OK;
 }

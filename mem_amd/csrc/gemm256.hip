@@ -168,7 +168,7 @@ __global__ __launch_bounds__(kThreads) void gemm256_kernel(typename EpiArgs<EPI>
 }
 
 template <int EPI>
-int launch256(const GemmArgs& p, hipStream_t s, int num_cu) {
+int launch256(const GemmArgs& p, hipStream_t s, int grid) {
   const int ntm = (p.M + BM - 1) / BM, ntn = p.N / BN;
   static bool attr_done = false;
   if (!attr_done) {
@@ -177,7 +177,6 @@ int launch256(const GemmArgs& p, hipStream_t s, int num_cu) {
     if (e != hipSuccess) return fail(MEMHIP_ELAUNCH, "gemm256: set smem attr: %s", hipGetErrorString(e));
     attr_done = true;
   }
-  const int grid = ntm * ntn < num_cu ? ntm * ntn : num_cu;
   // (the dropout epilogue's kernel takes a GemmArgsD: the dispatcher's arguments are one)
   hipLaunchKernelGGL(gemm256_kernel<EPI>, dim3(grid), dim3(kThreads), kSlots * kStage, s,
                      static_cast<const typename EpiArgs<EPI>::type&>(p), ntm, ntn);
@@ -188,30 +187,13 @@ int launch256(const GemmArgs& p, hipStream_t s, int num_cu) {
 
 namespace memhip {
 
-// Returns MEMHIP_EUNSUPPORTED when the shape does not fit this structure (caller falls back).
-int gemm256_dispatch(const GemmArgs& p, hipStream_t s) {
-  const bool vec = ((p.ldo0 | p.ldo1 | p.ldr | p.ldaux | p.colscale_n) & 7) == 0;      // host twin of vec_ok()
-  // N = 768 (3 tiles wide) leaves the third round of 591 tiles 31 % full on 256 CUs and measures
-  // 5-10 % below the 128x128 kernel (tools/bench_gemm.py); wide N gains 12-25 %.  MEMHIP_GEMM256_MIN_N
-  // overrides the threshold for experiments.
-  const int min_n = opt(OPT_GEMM256_MIN_N);
-  if (p.M < 4096 || p.N < min_n || p.N % BN != 0 || p.K % BK != 0 || !vec) return MEMHIP_EUNSUPPORTED;
-  static int num_cu = 0;
-  if (!num_cu) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return MEMHIP_EUNSUPPORTED;
-    num_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-  }
-  switch (p.epilogue) {
-    case MEMHIP_EPI_BIAS_BF16: return launch256<MEMHIP_EPI_BIAS_BF16>(p, s, num_cu);
-    case MEMHIP_EPI_BIAS_GELU: return launch256<MEMHIP_EPI_BIAS_GELU>(p, s, num_cu);
-    case MEMHIP_EPI_RESIDUAL: return launch256<MEMHIP_EPI_RESIDUAL>(p, s, num_cu);
-    case MEMHIP_EPI_RESIDUAL_DROP: return launch256<MEMHIP_EPI_RESIDUAL_DROP>(p, s, num_cu);
-    case MEMHIP_EPI_DGELU: return launch256<MEMHIP_EPI_DGELU>(p, s, num_cu);
-    case MEMHIP_EPI_F32: return launch256<MEMHIP_EPI_F32>(p, s, num_cu);
-    default: return MEMHIP_EUNSUPPORTED;
-  }
+// A MEMHIP_NT_G256 launch of the plan (gemm_nt_plan.cpp decides where this kernel runs): the epilogues of nt_g256_has.
+int gemm256_launch(const GemmArgs& p, const NtLaunch& l, hipStream_t s) {
+  return dispatch_epilogue(p.epilogue, [&](auto E) {
+    constexpr int EPI = decltype(E)::value;
+    if constexpr (nt_g256_has(EPI)) return launch256<EPI>(p, s, l.grid);
+    else return fail(MEMHIP_EINVAL, "gemm256: no kernel for epilogue %d", EPI);
+  });
 }
 
 }  // namespace memhip

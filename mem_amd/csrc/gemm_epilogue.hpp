@@ -2,34 +2,12 @@
 // autocast: every Linear/Conv output is rounded to bf16 first (fp32 accumulate + fp32 bias), the
 // residual stream / layer-scale / mask-token arithmetic that follows runs in fp32.
 #pragma once
+#include <type_traits>
 #include "common.h"
 #include "dropout.hpp"
+#include "gemm_nt_plan.hpp"   // GemmArgs
 
 namespace memhip {
-
-struct GemmArgs {   // memhip_gemm_args_t, followed by launcher-internal fields
-  const __bf16* A; const __bf16* B;
-  long long lda, ldb;
-  int M, N, K, epilogue;
-  void* out0; long long ldo0;
-  void* out1; long long ldo1;
-  const float* bias;
-  const float* vec1;
-  float* resid; long long ldr;
-  const void* aux; long long ldaux;
-  const float* rowmask;
-  float keep_prob;
-  float colscale; int colscale_n;
-  int rows_per_sample;
-  int accumulate;
-  float* colsum;   // optional: += column sums of the (rounded) primary output
-  const int* sample_map;   // RESIDUAL: compact sample -> sample whose residual rows this output row updates (NULL: identity)
-  int colsum_copies;       // > 1: colsum holds that many accumulator copies of N floats; a workgroup uses copy blockIdx % copies
-  int reserved0;
-  // ---- internal (not part of the C ABI; zero when the struct is copied from memhip_gemm_args_t)
-  int m_base;      // row offset of this launch inside the caller's problem (a GEMM may be launched in two
-                   // row ranges): only the per-sample row mask index needs the absolute row
-};
 
 // The arguments of a RESIDUAL_DROP launch: the kernels of that epilogue take this type, every other instantiation keeps
 // GemmArgs (the kernel arguments -- and the code -- of the existing launches do not change).  The launchers carry a
@@ -43,6 +21,29 @@ constexpr bool epi_resid(int e) { return e == MEMHIP_EPI_RESIDUAL || e == MEMHIP
 // the kernel-argument type of an epilogue's instantiation
 template <int EPI> struct EpiArgs { typedef GemmArgs type; };
 template <> struct EpiArgs<MEMHIP_EPI_RESIDUAL_DROP> { typedef GemmArgsD type; };
+
+// The one switch over the epilogues: f(std::integral_constant<int, EPI>) with the epilogue as a compile-time constant.  A
+// launcher instantiates its kernels under `if constexpr` of its form's predicate (gemm_nt_plan.hpp).
+template <class F>
+int dispatch_epilogue(int epi, F&& f) {
+  switch (epi) {
+#define MEMHIP_EPI_CASE(E) case E: return f(std::integral_constant<int, E>{})
+    MEMHIP_EPI_CASE(MEMHIP_EPI_BIAS_BF16);
+    MEMHIP_EPI_CASE(MEMHIP_EPI_BIAS_GELU);
+    MEMHIP_EPI_CASE(MEMHIP_EPI_RESIDUAL);
+    MEMHIP_EPI_CASE(MEMHIP_EPI_DGELU);
+    MEMHIP_EPI_CASE(MEMHIP_EPI_F32);
+    MEMHIP_EPI_CASE(MEMHIP_EPI_PATCH_EMBED);
+    MEMHIP_EPI_CASE(MEMHIP_EPI_BIAS_GELU_DG);
+    MEMHIP_EPI_CASE(MEMHIP_EPI_MUL_AUX);
+    MEMHIP_EPI_CASE(MEMHIP_EPI_RESIDUAL_DROP);
+#undef MEMHIP_EPI_CASE
+    default: return fail(MEMHIP_EINVAL, "gemm: unknown epilogue %d", epi);
+  }
+}
+// (for the template flags of a launch: f(std::true_type) / f(std::false_type))
+template <class F>
+int dispatch_bool(bool b, F&& f) { return b ? f(std::true_type{}) : f(std::false_type{}); }
 
 // residual-stream row of the dropout mask from the row the residual epilogue resolved (relative to resid / aux: with a
 // sample map the caller's rows, without it the rows of this launch's range, which starts m_base rows in)

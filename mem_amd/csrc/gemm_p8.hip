@@ -786,7 +786,7 @@ __global__ __launch_bounds__(kThreads) void gemm_p8_pair_kernel(GemmArgs head, G
 }
 
 template <int EPI, int BMT, bool GUARD, bool COPY>
-int launch_p8gc(const GemmArgs& p, hipStream_t s, int num_cu) {
+int launch_p8(const GemmArgs& p, hipStream_t s, int grid) {
   const int ntm = (p.M + BMT - 1) / BMT, ntn = p.N / BN;
   constexpr bool kDrop = EPI == MEMHIP_EPI_RESIDUAL_DROP;
   const void* kfn;
@@ -798,7 +798,6 @@ int launch_p8gc(const GemmArgs& p, hipStream_t s, int num_cu) {
     if (e != hipSuccess) return fail(MEMHIP_ELAUNCH, "gemm_p8: set smem attr: %s", hipGetErrorString(e));
     attr_done = true;
   }
-  const int grid = ntm * ntn < num_cu ? ntm * ntn : num_cu;
   if constexpr (kDrop)
     hipLaunchKernelGGL((gemm_p8_drop_kernel<BMT, GUARD>), dim3(grid), dim3(kThreads), P8Geo<BMT>::kLdsAll, s,
                        static_cast<const GemmArgsD&>(p), ntm, ntn, BMT == 256 ? opt(OPT_GEMM_STAGGER) : 0, opt(OPT_GEMM_PREFETCH));
@@ -808,25 +807,19 @@ int launch_p8gc(const GemmArgs& p, hipStream_t s, int num_cu) {
   return check_launch("gemm_bf16_nt(p8)");
 }
 
-template <int EPI, int BMT, bool GUARD>
-int launch_p8g(const GemmArgs& p, hipStream_t s, int num_cu) {
-  if constexpr (EPI == MEMHIP_EPI_RESIDUAL_DROP) {
-    return launch_p8gc<EPI, BMT, GUARD, false>(p, s, num_cu);       // (out0 is NULL: checked by the dispatcher)
-  } else if constexpr (EPI == MEMHIP_EPI_RESIDUAL) {
-    if (!p.out0) return launch_p8gc<EPI, BMT, GUARD, false>(p, s, num_cu);
-    // (the bf16 copy of the branch output beside the full-line residual epilogue of the 256-row kernel spills; no engine
-    // asks for it on the bf16 path: those calls run on the 128-row form)
-    if constexpr (BMT == 256) return MEMHIP_EUNSUPPORTED;
-    else return launch_p8gc<EPI, BMT, GUARD, true>(p, s, num_cu);
-  } else {
-    return launch_p8gc<EPI, BMT, GUARD, true>(p, s, num_cu);
+template <int EPI, bool GUARD_T, bool COPY>
+int launch_pair(const GemmArgs& head, const GemmArgs& tail, hipStream_t s, int nmain, int ntail) {
+  const int ntn = head.N / BN, ntm_h = head.M / BM, ntm_t = (tail.M + 127) / 128;
+  static bool attr_done = false;
+  if (!attr_done) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_p8_pair_kernel<EPI, GUARD_T, COPY>),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, P8Geo<256>::kLdsAll);
+    if (e != hipSuccess) return fail(MEMHIP_ELAUNCH, "gemm_p8(pair): set smem attr: %s", hipGetErrorString(e));
+    attr_done = true;
   }
-}
-
-template <int EPI, int BMT>
-int launch_p8(const GemmArgs& p, hipStream_t s, int num_cu) {
-  if constexpr (BMT == 256) return launch_p8g<EPI, 256, false>(p, s, num_cu);
-  else return p.M % 128 == 0 ? launch_p8g<EPI, 128, false>(p, s, num_cu) : launch_p8g<EPI, 128, true>(p, s, num_cu);
+  hipLaunchKernelGGL((gemm_p8_pair_kernel<EPI, GUARD_T, COPY>), dim3(nmain + ntail), dim3(kThreads), P8Geo<256>::kLdsAll, s, head, tail,
+                     ntm_h, ntm_t, ntn, nmain, opt(OPT_GEMM_STAGGER), opt(OPT_GEMM_PREFETCH));
+  return check_launch("gemm_bf16_nt(p8 pair)");
 }
 
 }  // namespace
@@ -842,113 +835,36 @@ extern "C" int memhip_debug_p8_stamps_rt(unsigned long long* host_out) {
 
 namespace memhip {
 
-static int p8_num_cu(hipStream_t s) { return usable_cus(s); }
-
-static bool p8_fits(const GemmArgs& p) {
-  const bool vec = ((p.ldo0 | p.ldo1 | p.ldr | p.ldaux | p.colscale_n) & 7) == 0;      // host twin of vec_ok()
-  // Narrow outputs (N = 768: 591 tiles on 256 CUs) are taken too: the launcher hands the rows of a
-  // poorly filled last round to the 128x128 kernel (gemm_p8_split_rows).  MEMHIP_GEMM_P8_MIN_N overrides.
-  const int min_n = opt(OPT_GEMM_P8_MIN_N);
-  const bool wide = p.N >= min_n;
-  // (the residual epilogue of the 256-row kernel finds a row's sample without an integer division: rows below 2^21)
-  // (a 256-row tile touches at most four samples of a sample map: rows_per_sample >= 86)
-  const bool rows_ok = (!(p.rowmask || p.sample_map) || (long long)p.M + p.m_base < (1 << 21)) &&
-                       (!p.sample_map || p.rows_per_sample >= 86);
-  return p.M >= 4096 && wide && p.N % BN == 0 && p.K % (2 * BK) == 0 && vec && rows_ok;
+// The launches of the plan (gemm_nt_plan.cpp decides which rows run on which form; nothing here looks at shapes).
+// MEMHIP_NT_P8_256 / MEMHIP_NT_P8_128 on the rows of `p`: the instantiations of nt_p8_has.
+int gemm_p8_launch(const GemmArgs& p, const NtLaunch& l, hipStream_t s) {
+  return dispatch_epilogue(p.epilogue, [&](auto E) {
+    return dispatch_bool(l.kind == MEMHIP_NT_P8_256, [&](auto Big) {
+      return dispatch_bool(l.guard != 0, [&](auto Guard) {
+        return dispatch_bool(l.copy != 0, [&](auto Copy) {
+          constexpr int EPI = decltype(E)::value, BMT = decltype(Big)::value ? 256 : 128;
+          constexpr bool G = decltype(Guard)::value, C = decltype(Copy)::value;
+          if constexpr (nt_p8_has(EPI, BMT, G, C)) return launch_p8<EPI, BMT, G, C>(p, s, l.grid);
+          else return fail(MEMHIP_EINVAL, "gemm_p8: no %d-row kernel for epilogue %d (guard %d, copy %d)", BMT, EPI, G, C);
+        });
+      });
+    });
+  });
 }
 
-// Rows the persistent launch should take when its last round of tiles would be less than half full
-// (0 = take everything): full rounds only, the caller runs the remaining rows on finer tiles.
-int gemm_p8_split_rows(const GemmArgs& p, hipStream_t s) {
-  if (!p8_fits(p)) return 0;
-  const int num_cu = p8_num_cu(s);
-  if (!num_cu) return 0;
-  const int ntm = (p.M + BM - 1) / BM, ntn = p.N / BN;
-  const int tiles = ntm * ntn, rounds = tiles / num_cu, rem = tiles % num_cu;
-  const int whole = (p.M / BM) * BM;                       // the 256-row kernel takes whole tiles only
-  if (rounds < 1 || rem == 0 || rem * 2 > num_cu) return whole == p.M ? 0 : whole;
-  return (rounds * num_cu / ntn) * BM;
-}
-
-// Returns MEMHIP_EUNSUPPORTED when the shape does not fit this structure (caller falls back).
-int gemm_p8_half_dispatch(const GemmArgs& p, hipStream_t s);
-int gemm_p8_dispatch(const GemmArgs& p, hipStream_t s) {
-  if (!p8_fits(p) || p.M % BM != 0) return MEMHIP_EUNSUPPORTED;   // whole 256-row tiles only (no row guard in the epilogue)
-  const int num_cu = p8_num_cu(s);
-  if (!num_cu) return MEMHIP_EUNSUPPORTED;
-  switch (p.epilogue) {
-    case MEMHIP_EPI_BIAS_BF16: return launch_p8<MEMHIP_EPI_BIAS_BF16, 256>(p, s, num_cu);
-    case MEMHIP_EPI_BIAS_GELU: return launch_p8<MEMHIP_EPI_BIAS_GELU, 256>(p, s, num_cu);
-    case MEMHIP_EPI_RESIDUAL:
-      if (p.out0) return gemm_p8_half_dispatch(p, s);
-      return launch_p8<MEMHIP_EPI_RESIDUAL, 256>(p, s, num_cu);
-    // The residual-dropout epilogue runs on the 128-row form only (here, in the split's head and tail, never paired): the
-    // 256-row residual epilogue loads its rows with hand-counted waits and has no room for the Philox state -- measured:
-    // the 256-row dropout instantiation spilled, and a spill is an uncounted vector-memory operation.
-    case MEMHIP_EPI_RESIDUAL_DROP: return gemm_p8_half_dispatch(p, s);
-    case MEMHIP_EPI_DGELU: return launch_p8<MEMHIP_EPI_DGELU, 256>(p, s, num_cu);
-    case MEMHIP_EPI_BIAS_GELU_DG: return launch_p8<MEMHIP_EPI_BIAS_GELU_DG, 256>(p, s, num_cu);
-    case MEMHIP_EPI_MUL_AUX: return launch_p8<MEMHIP_EPI_MUL_AUX, 256>(p, s, num_cu);
-    case MEMHIP_EPI_F32: return launch_p8<MEMHIP_EPI_F32, 256>(p, s, num_cu);
-    default: return MEMHIP_EUNSUPPORTED;
-  }
-}
-
-// The 128-row-tile form for the rows that gemm_p8_split_rows leaves over (any M; same N / K rules).
-int gemm_p8_half_dispatch(const GemmArgs& p, hipStream_t s) {
-  const bool vec = ((p.ldo0 | p.ldo1 | p.ldr | p.ldaux | p.colscale_n) & 7) == 0;
-  if (p.M < 128 || p.N % BN != 0 || p.K % (2 * BK) != 0 || !vec) return MEMHIP_EUNSUPPORTED;
-  const int num_cu = p8_num_cu(s);
-  if (!num_cu) return MEMHIP_EUNSUPPORTED;
-  switch (p.epilogue) {
-    case MEMHIP_EPI_BIAS_BF16: return launch_p8<MEMHIP_EPI_BIAS_BF16, 128>(p, s, num_cu);
-    case MEMHIP_EPI_BIAS_GELU: return launch_p8<MEMHIP_EPI_BIAS_GELU, 128>(p, s, num_cu);
-    case MEMHIP_EPI_RESIDUAL: return launch_p8<MEMHIP_EPI_RESIDUAL, 128>(p, s, num_cu);
-    case MEMHIP_EPI_RESIDUAL_DROP: return launch_p8<MEMHIP_EPI_RESIDUAL_DROP, 128>(p, s, num_cu);
-    case MEMHIP_EPI_DGELU: return launch_p8<MEMHIP_EPI_DGELU, 128>(p, s, num_cu);
-    case MEMHIP_EPI_BIAS_GELU_DG: return launch_p8<MEMHIP_EPI_BIAS_GELU_DG, 128>(p, s, num_cu);
-    case MEMHIP_EPI_MUL_AUX: return launch_p8<MEMHIP_EPI_MUL_AUX, 128>(p, s, num_cu);
-    case MEMHIP_EPI_F32: return launch_p8<MEMHIP_EPI_F32, 128>(p, s, num_cu);
-    default: return MEMHIP_EUNSUPPORTED;
-  }
-}
-
-
-template <int EPI, bool GUARD_T>
-static int launch_pair(const GemmArgs& head, const GemmArgs& tail, hipStream_t s, int num_cu) {
-  constexpr bool COPY = EPI != MEMHIP_EPI_RESIDUAL;
-  const int ntn = head.N / BN, ntm_h = head.M / BM, ntm_t = (tail.M + 127) / 128;
-  static bool attr_done = false;
-  if (!attr_done) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_p8_pair_kernel<EPI, GUARD_T, COPY>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, P8Geo<256>::kLdsAll);
-    if (e != hipSuccess) return fail(MEMHIP_ELAUNCH, "gemm_p8(pair): set smem attr: %s", hipGetErrorString(e));
-    attr_done = true;
-  }
-  const int nmain = ntm_h * ntn < num_cu ? ntm_h * ntn : num_cu;
-  const int ntail = ntm_t * ntn < num_cu ? ntm_t * ntn : num_cu;
-  hipLaunchKernelGGL((gemm_p8_pair_kernel<EPI, GUARD_T, COPY>), dim3(nmain + ntail), dim3(kThreads), P8Geo<256>::kLdsAll, s, head, tail,
-                     ntm_h, ntm_t, ntn, nmain, opt(OPT_GEMM_STAGGER), opt(OPT_GEMM_PREFETCH));
-  return check_launch("gemm_bf16_nt(p8 pair)");
-}
-
-// head: whole 256-row tiles of the full rounds; tail: the left-over rows (any count >= 128).  MEMHIP_EUNSUPPORTED when this
-// epilogue / shape has no paired form (the caller launches the two kernels one after the other).
-int gemm_p8_pair_dispatch(const GemmArgs& head, const GemmArgs& tail, hipStream_t s) {
-  if (!p8_fits(head) || head.M % BM != 0 || tail.M < 128) return MEMHIP_EUNSUPPORTED;
-  if (head.epilogue == MEMHIP_EPI_RESIDUAL && head.out0) return MEMHIP_EUNSUPPORTED;     // (the COPY form lives on the 128-row kernel only)
-  const int num_cu = p8_num_cu(s);
-  if (!num_cu || num_cu % 8 != 0) return MEMHIP_EUNSUPPORTED;
-  const bool g = tail.M % 128 != 0;
-#define P8_PAIR(E) return g ? launch_pair<E, true>(head, tail, s, num_cu) : launch_pair<E, false>(head, tail, s, num_cu)
-  switch (head.epilogue) {
-    case MEMHIP_EPI_BIAS_BF16: P8_PAIR(MEMHIP_EPI_BIAS_BF16);
-    case MEMHIP_EPI_RESIDUAL: P8_PAIR(MEMHIP_EPI_RESIDUAL);
-    case MEMHIP_EPI_BIAS_GELU_DG: P8_PAIR(MEMHIP_EPI_BIAS_GELU_DG);
-    case MEMHIP_EPI_MUL_AUX: P8_PAIR(MEMHIP_EPI_MUL_AUX);
-    default: return MEMHIP_EUNSUPPORTED;
-  }
-#undef P8_PAIR
+// MEMHIP_NT_P8_PAIR: ONE launch for the whole 256-row tiles of the full rounds (`head`) and the left-over rows (`tail`, any
+// count >= 128): the instantiations of nt_pair_has.
+int gemm_p8_pair_launch(const GemmArgs& head, const GemmArgs& tail, const NtLaunch& l, hipStream_t s) {
+  return dispatch_epilogue(head.epilogue, [&](auto E) {
+    return dispatch_bool(l.guard != 0, [&](auto Guard) {
+      return dispatch_bool(l.copy != 0, [&](auto Copy) {
+        constexpr int EPI = decltype(E)::value;
+        constexpr bool G = decltype(Guard)::value, C = decltype(Copy)::value;
+        if constexpr (nt_pair_has(EPI, C)) return launch_pair<EPI, G, C>(head, tail, s, l.grid, l.tail_grid);
+        else return fail(MEMHIP_EINVAL, "gemm_p8: no paired kernel for epilogue %d (copy %d)", EPI, C);
+      });
+    });
+  });
 }
 
 }  // namespace memhip

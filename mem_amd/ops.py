@@ -42,7 +42,18 @@ class GemmArgs(C.Structure):
                 ("dropout", vp)]
 
 
-declare({"memhip_gemm_bf16_nt": (i32, [C.POINTER(GemmArgs), vp])})
+class NtLaunch(C.Structure):
+    """== memhip_nt_launch_t."""
+    _fields_ = [(n, i32) for n in ("kind", "row0", "rows", "tail_rows", "guard", "copy", "grid", "tail_grid")]
+
+
+class NtPlan(C.Structure):
+    """== memhip_nt_plan_t."""
+    _fields_ = [("count", i32), ("l", NtLaunch * 2)]
+
+
+declare({"memhip_gemm_bf16_nt": (i32, [C.POINTER(GemmArgs), vp]),
+         "memhip_gemm_bf16_nt_plan": (i32, [C.POINTER(GemmArgs), i32, i32, C.POINTER(NtPlan)])})
 
 
 def _p(t):
@@ -61,12 +72,10 @@ def _timer_event():
     return GEMM_EVENT_POOL.pop() if GEMM_EVENT_POOL else torch.cuda.Event(enable_timing=True)
 
 
-def gemm_nt(A, B, M, N, K, epi, out0=None, out1=None, bias=None, vec1=None, resid=None, aux=None,
-            rowmask=None, keep_prob=1.0, colscale=1.0, colscale_n=0, rows_per_sample=1, accumulate=False, colsum=None,
-            lda=None, ldb=None, ldo0=None, ldo1=None, ldr=None, ldaux=None, sample_map=None, colsum_copies=0, dropout=None):
-    """C[M,N] = A[M,K] @ B[N,K]^T with a fused epilogue.  A/B bf16, row-major, K contiguous.
-    colsum_copies > 1: `colsum` is a zeroed [copies, N] workspace, folded into the bias gradient by colsum_fold.
-    dropout: a Dropout (epilogue EPI_RESIDUAL_DROP only)."""
+def gemm_args(A, B, M, N, K, epi, out0=None, out1=None, bias=None, vec1=None, resid=None, aux=None,
+              rowmask=None, keep_prob=1.0, colscale=1.0, colscale_n=0, rows_per_sample=1, accumulate=False, colsum=None,
+              lda=None, ldb=None, ldo0=None, ldo1=None, ldr=None, ldaux=None, sample_map=None, colsum_copies=0, dropout=None):
+    """The memhip_gemm_args_t of gemm_nt (same parameters)."""
     a = GemmArgs()
     a.A, a.B = _p(A), _p(B)
     a.lda = A.stride(0) if lda is None else lda
@@ -87,6 +96,14 @@ def gemm_nt(A, B, M, N, K, epi, out0=None, out1=None, bias=None, vec1=None, resi
     a.sample_map = _p(sample_map)
     a.colsum_copies = colsum_copies
     a.dropout = None if dropout is None else C.addressof(dropout)
+    return a
+
+
+def gemm_nt(A, B, M, N, K, epi, *args, **kw):
+    """C[M,N] = A[M,K] @ B[N,K]^T with a fused epilogue (keywords: gemm_args).  A/B bf16, row-major, K contiguous.
+    colsum_copies > 1: `colsum` is a zeroed [copies, N] workspace, folded into the bias gradient by colsum_fold.
+    dropout: a Dropout (epilogue EPI_RESIDUAL_DROP only)."""
+    a = gemm_args(A, B, M, N, K, epi, *args, **kw)
     if GEMM_TIMER is None:
         check(lib.memhip_gemm_bf16_nt(C.byref(a), stream_ptr()), "gemm_bf16_nt")
     else:
@@ -95,6 +112,22 @@ def gemm_nt(A, B, M, N, K, epi, out0=None, out1=None, bias=None, vec1=None, resi
         check(lib.memhip_gemm_bf16_nt(C.byref(a), stream_ptr()), "gemm_bf16_nt")
         e1.record()
         GEMM_TIMER.append((e0, e1, 2.0 * M * N * K, epi))
+
+
+NT_128, NT_G256, NT_P8_256, NT_P8_128, NT_P8_PAIR = range(5)
+
+
+def gemm_nt_plan(a, stream_cus=None, device_cus=None):
+    """The launches memhip_gemm_bf16_nt makes for the GemmArgs `a` under the current options, as a list of NtLaunch (kind
+    NT_*, rows [row0, row0 + rows), tail_rows, guard, copy, grid, tail_grid).  Nothing is launched; no device is needed
+    when both CU counts are given (default: the current device's, no reservation)."""
+    if stream_cus is None or device_cus is None:
+        cus = torch.cuda.get_device_properties(torch.cuda.current_device()).multi_processor_count
+        stream_cus = cus if stream_cus is None else stream_cus
+        device_cus = cus if device_cus is None else device_cus
+    plan = NtPlan()
+    check(lib.memhip_gemm_bf16_nt_plan(C.byref(a), stream_cus, device_cus, C.byref(plan)), "gemm_bf16_nt_plan")
+    return [plan.l[i] for i in range(plan.count)]
 
 
 f64 = C.c_double

@@ -6,6 +6,13 @@ import torch
 pytestmark = pytest.mark.gpu
 
 
+def _forms(ops, *args, **kw):
+    """The kernel forms memhip_gemm_bf16_nt takes for a gemm_nt call on this device, as a set: every (kind, guard) of the plan,
+    and ("then", kind, kind) for a plan of two launches."""
+    p = ops.gemm_nt_plan(ops.gemm_args(*args, **kw))
+    return {(l.kind, bool(l.guard)) for l in p} | ({("then", p[0].kind, p[1].kind)} if len(p) == 2 else set())
+
+
 def _rand(shape, seed, scale=1.0):
     g = torch.Generator(device="cuda").manual_seed(seed)
     return (torch.randn(shape, generator=g, device="cuda") * scale)
@@ -210,9 +217,12 @@ def test_gemm_tn_group_equals_single_calls(shapes):
         torch.testing.assert_close(o, s1, rtol=1e-4, atol=1e-5 * float(s1.abs().max()))
 
 
-@pytest.mark.parametrize("M,N,K", [(2048, 128, 64), (4000, 768, 768), (2304 + 17, 2304, 768), (5000, 384, 3072),
-                                   (4096, 256, 64), (4096 + 100, 768, 768), (9000, 2304, 128), (4500, 512, 3072),
-                                   (25600 + 13, 768, 1536)])       # last: 303 tiles -> row-split launch (p8 + 128x128)
+_ALL_EPI_SHAPES = [(2048, 128, 64), (4000, 768, 768), (2304 + 17, 2304, 768), (5000, 384, 3072),
+                   (4096, 256, 64), (4096 + 100, 768, 768), (9000, 2304, 128), (4500, 512, 3072),
+                   (25600 + 13, 768, 1536)]       # last: 303 tiles -> row-split launch (full rounds + 128-row tiles)
+
+
+@pytest.mark.parametrize("M,N,K", _ALL_EPI_SHAPES)
 def test_persistent_gemm_large_m_all_epilogues(M, N, K):
     """Large-M shapes dispatch to the persistent 256-row-tile kernels (gemm_p8.hip, row-split launches with 128-row
     tiles for the left-over rows; gemm256.hip when K is not a multiple of 128; the 128x128 kernel otherwise):
@@ -230,6 +240,10 @@ def test_persistent_gemm_large_m_all_epilogues(M, N, K):
     ref = A.float() @ B.float().t() + bias
     out = torch.full((M + 5, N), 7.0, dtype=torch.bfloat16, device="cuda")
     ops.gemm_nt(A, B, M, N, K, ops.EPI_BIAS_BF16, out0=out, bias=bias, colscale=0.125, colscale_n=N // 2)
+    # the shape list reaches the paired launch (gemm_p8_pair_kernel) on this device's CU count; the plan looks at no pointer,
+    # so this case's tensors stand in for every shape of the list
+    assert any(f[0] == ops.NT_P8_PAIR for m, n, kk in _ALL_EPI_SHAPES
+               for f in _forms(ops, A, B, m, n, kk, ops.EPI_BIAS_BF16, out0=out, bias=bias, lda=kk, ldb=kk, ldo0=n))
     r = ref.bfloat16()
     r[:, : N // 2] = (r[:, : N // 2].float() * 0.125).bfloat16()
     torch.testing.assert_close(out[:M].float(), r.float(), rtol=2e-2, atol=2e-2)
@@ -310,7 +324,8 @@ def test_gelu_with_stored_derivative(M, N, K):
 
 def test_gemm_dispatch_fuzz_exact():
     """Randomised shapes across every dispatch boundary (128x128 kernel, gemm256, gemm_p8 full launches, row-split
-    launches with 128-row tiles, weight-gradient kernels with and without the workspace): small-integer operands, so
+    launches with 128-row tiles -- asserted through the plan query --, weight-gradient kernels with and without the
+    workspace): small-integer operands, so
     fp32 accumulation is exact and any mis-addressed tile / dropped row / double-counted split shows as a bit
     difference."""
     from mem_amd import ops
@@ -320,7 +335,9 @@ def test_gemm_dispatch_fuzz_exact():
     for _ in range(14):
         shapes.append((int(rng.integers(1, 9000)), 8 * int(rng.integers(1, 200)), 64 * int(rng.integers(1, 20))))
     shapes += [(4096, 256, 128), (4095, 1024, 192), (12289, 1024, 1024), (19216, 4096, 1024), (19216, 1024, 4096),
-               (8193, 768, 64), (50432, 256, 128), (4097, 3072, 320)]
+               (8193, 768, 64), (50432, 256, 128), (4097, 3072, 320),
+               (4224, 512, 128)]            # 256-row tiles + one whole 128-row tile (the 128-row form without row guard)
+    reached = set()
     for (M, N, K) in shapes:
         A = torch.randint(-2, 3, (M, K), generator=g, device="cuda").float()
         B = torch.randint(-2, 3, (N, K), generator=g, device="cuda").float()
@@ -328,6 +345,10 @@ def test_gemm_dispatch_fuzz_exact():
         ops.gemm_nt(A.bfloat16(), B.bfloat16(), M, N, K, ops.EPI_F32, out0=C)
         assert torch.equal(C[:M], A @ B.t()), (M, N, K)
         assert (C[M:] == 5.0).all(), (M, N, K)
+        reached |= _forms(ops, A.bfloat16(), B.bfloat16(), M, N, K, ops.EPI_F32, out0=C)
+    # the list walks the rows of the dispatch table (gemm_nt_plan) on this device's CU count
+    assert reached >= {(ops.NT_128, False), (ops.NT_G256, False), (ops.NT_P8_256, False), (ops.NT_P8_128, True),
+                       (ops.NT_P8_128, False), ("then", ops.NT_P8_256, ops.NT_128)}, reached
     for _ in range(10):
         R, N, K = int(rng.integers(1, 9000)), 8 * int(rng.integers(1, 160)), 8 * int(rng.integers(1, 160))
         dY = torch.randint(-2, 3, (R, N), generator=g, device="cuda").float()
