@@ -36,7 +36,7 @@ extern "C" {
 #endif
 
 #define MEMHIP_ABI_VERSION 7   /* 7: the finetuning recipe (memhip_mixup, memhip_mix_targets, memhip_ce_soft, memhip_ema_update), and -- additive, no
-                                  existing signature changed, so the number stays -- memhip_pool_tokens / memhip_pool_tokens_bwd, memhip_gemm_bf16_nt_plan; 6: element-wise dropout (memhip_dropout_t, epilogue RESIDUAL_DROP, memhip_gemm_args_t.dropout, the
+                                  existing signature changed, so the number stays -- memhip_pool_tokens / memhip_pool_tokens_bwd, memhip_gemm_bf16_nt_plan, memhip_tokens_to_maps / memhip_maps_to_tokens_add; 6: element-wise dropout (memhip_dropout_t, epilogue RESIDUAL_DROP, memhip_gemm_args_t.dropout, the
                                   *_drop row kernels); 5 (round 6): memhip_build_flags, memhip_attn_bwd_ws / _out_ws / _workspace; 4 (round 5): epilogues 6 / 7 carry the stored GELU derivative as FP16 (since round 4), certified-tokenizer entry points */
 
 #define MEMHIP_OK 0
@@ -821,6 +821,24 @@ int memhip_pool_tokens(const float* x, int64_t ldx, int B, int T, int D, float* 
 /* Its backward: dx f32 [B*T, D] (dense), dx[b*T + t] = dout[b] / (T - 1) for t >= 1 (IEEE division) and 0 for t = 0;
  * every element of dx is written. */
 int memhip_pool_tokens_bwd(const float* dout, int B, int T, int D, float* dx, memhip_stream_t stream);
+
+/* ------------------------------------------------------------------------
+ * Dense per-block feature maps (dense.hip; additive to ABI 7)
+ * replaces x[:, 1:, :].permute(0, 2, 1).reshape(B, -1, Hp, Wp).contiguous()   mem/semantic_segmentation/backbone/mem.py:439-441
+ *          (and its autograd backward); the streams of get_intermediate_layers  mem/modeling_finetune.py:361-378
+ * ------------------------------------------------------------------------
+ * x f32 [B*T, ldx] (the residual stream, sample-major, ldx >= D), out f32 [B, D, T-1] contiguous (= [B, D, Hp, Wp]):
+ *   out[b, d, l] = x[b*T + 1 + l, d]   for the samples b0 <= b < b1    (row 0 of a sample, the cls token, is skipped)
+ * A batched [L, D] -> [D, L] transpose through a padded LDS tile, 16-byte lane accesses and whole 128-byte lines on both
+ * sides; samples outside [b0, b1) are neither read nor written.  T >= 2, D % 64 == 0, ldx % 4 == 0, x 16-byte aligned; any
+ * T (the map side moves 16 bytes per lane when (T-1) % 4 == 0 and `out` is 16-byte aligned, 4 otherwise); at most 65535
+ * samples per call. */
+int memhip_tokens_to_maps(const float* x, int64_t ldx, int b0, int b1, int T, int D, float* out, memhip_stream_t stream);
+/* Its backward INTO a gradient that already holds other terms: dx f32 [B*T, lddx], dmap f32 [B, D, T-1] contiguous:
+ *   dx[b*T + 1 + l, d] += dmap[b, d, l]   for b0 <= b < b1
+ * exactly one fp32 add per element, no atomics (every dx element has one writer: the result is deterministic); cls rows,
+ * columns >= D and other samples are untouched.  Same shape rules (dx 16-byte aligned, lddx % 4 == 0). */
+int memhip_maps_to_tokens_add(const float* dmap, int b0, int b1, int T, int D, float* dx, int64_t lddx, memhip_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -180,6 +180,26 @@ class _TrunkFunction(torch.autograd.Function):
         return None, None, None, None, None
 
 
+class _DenseFunction(torch.autograd.Function):
+    """The trunk with dense-map exits (VisionTransformer.forward_dense): returns the engine's maps of the blocks
+    ``out_indices`` and feeds their gradients back at those depths (ViTEngine.backward_trunk(None, dmaps))."""
+
+    @staticmethod
+    def forward(ctx, model, x, dp_masks, drop_key, out_indices, anchor):
+        ctx.model, ctx.out_indices = model, out_indices
+        ctx.set_materialize_grads(False)              # a map nothing reads arrives as None and is skipped
+        eng = model.engine
+        eng.forward_trunk(x, None, dp_masks, drop_key=drop_key, export=out_indices)
+        return tuple(eng.cur["maps"][i] for i in out_indices)
+
+    @staticmethod
+    def backward(ctx, *dmaps):
+        eng = ctx.model.engine
+        eng.attach_grads()
+        eng.backward_trunk(None, {i: g.float().contiguous() for i, g in zip(ctx.out_indices, dmaps) if g is not None})
+        return None, None, None, None, None, None
+
+
 class VisionTransformer(nn.Module):
     """modeling_finetune.py:250-369: same constructor keywords, state-dict keys, init order and forward()."""
 
@@ -329,6 +349,30 @@ class VisionTransformer(nn.Module):
         """No trunk parameter requires a gradient (host-side, from the parameter flags; once per call)."""
         return not any(p.requires_grad for n, p in self.named_parameters() if not n.startswith(self._TAIL_PREFIXES))
 
+    def _step_inputs(self, x, drop_path_masks):
+        """The input on the engine's device and this call's draws: (x, drop-path masks, dropout key); none in eval()."""
+        x = x.to(device=self.engine.dev, dtype=torch.float32).contiguous()
+        if self.training and drop_path_masks is None:
+            drop_path_masks = self.draw_drop_path(x.shape[0])
+        drop_key = self.draw_dropout_key() if self.training else None
+        if not self.training:
+            drop_path_masks = None
+        return x, drop_path_masks, drop_key
+
+    def _trunk_trains(self):
+        """A gradient can reach the trunk: train(), grad mode on, trunk not frozen (then the autograd anchor exists)."""
+        if not (torch.is_grad_enabled() and self.training and not self._trunk_frozen()):
+            return False
+        if self._anchor is None:
+            self._anchor = torch.zeros(1, device=self.engine.dev, requires_grad=True)
+        return True
+
+    def _attach_tail_grads(self):
+        """Forward-only trunk under a training tail: the tail's autograd accumulates into the flat gradient buffer's views."""
+        if torch.is_grad_enabled() and self.training and any(
+                p.grad is None for n, p in self.named_parameters(recurse=True) if n.startswith(self._TAIL_PREFIXES)):
+            self.engine.attach_grads()
+
     def _trunk(self, x, drop_path_masks=None, pool=False):
         """The engine's trunk: the fp32 residual stream [B, T, D] (a copy).  ``pool`` (the mean-pooling form): a forward-only
         call returns the patch-token mean [B, D] instead, taken straight from the engine's buffer (``ops.pool_tokens``); a
@@ -336,20 +380,11 @@ class VisionTransformer(nn.Module):
         activation stash, no trunk backward) whenever no gradient can reach the trunk: eval mode, grad mode off, or a
         frozen trunk.  A frozen trunk in train() mode still draws its drop-path masks and dropout key."""
         eng = self.engine
-        x = x.to(device=eng.dev, dtype=torch.float32).contiguous()
-        if self.training and drop_path_masks is None:
-            drop_path_masks = self.draw_drop_path(x.shape[0])
-        drop_key = self.draw_dropout_key() if self.training else None
-        if not self.training:
-            drop_path_masks = None
+        x, drop_path_masks, drop_key = self._step_inputs(x, drop_path_masks)
         B = x.shape[0]
-        if torch.is_grad_enabled() and self.training and not self._trunk_frozen():
-            if self._anchor is None:
-                self._anchor = torch.zeros(1, device=x.device, requires_grad=True)
+        if self._trunk_trains():
             return _TrunkFunction.apply(self, x, drop_path_masks, drop_key, self._anchor)
-        if torch.is_grad_enabled() and self.training and any(
-                p.grad is None for n, p in self.named_parameters(recurse=True) if n.startswith(self._TAIL_PREFIXES)):
-            eng.attach_grads()               # the tail's autograd accumulates into the flat gradient buffer's views
+        self._attach_tail_grads()
         xl = eng.forward_trunk(x, None, drop_path_masks, drop_key=drop_key, keep=False)
         if pool:
             from . import ops
@@ -376,7 +411,34 @@ class VisionTransformer(nn.Module):
             return self.head(x)
 
     def get_intermediate_layers(self, x):
-        raise NotImplementedError("per-block features are not exported by the fused engine")
+        """modeling_finetune.py:361-378: the list of the fp32 residual streams [B, T, D] behind every block, cls row
+        included.  Forward-only (``forward_trunk(keep=False)``: three rotating buffers, one copy per block as the block
+        finishes); the streams carry no autograd graph -- train through ``forward_dense``."""
+        eng = self.engine
+        x, drop_path_masks, drop_key = self._step_inputs(x, None)
+        B, T, D = x.shape[0], eng.T, eng.D
+        streams = torch.empty((eng.depth, B * T, D), dtype=torch.float32, device=eng.dev)
+        eng.forward_trunk(x, None, drop_path_masks, drop_key=drop_key, keep=False, streams=streams)
+        return [streams[i].view(B, T, D) for i in range(eng.depth)]
+
+    def forward_dense(self, x, out_indices=(3, 5, 7, 11), drop_path_masks=None):
+        """Dense feature maps of the blocks ``out_indices`` (ascending, distinct): a tuple of fp32 [B, D, Hp, Wp], the
+        block's output tokens without the cls row (semantic_segmentation/backbone/mem.py:439-441), written by
+        ``memhip_tokens_to_maps`` from the engine's buffer as the block finishes.  A training call with an unfrozen trunk is
+        differentiable: the maps' gradients enter the trunk backward at their depths (``memhip_maps_to_tokens_add``; a map
+        without gradient is skipped, blocks behind the deepest gradient run on a zero gradient).  Every other call (eval(),
+        no_grad, frozen trunk) runs forward-only.  The maps are the engine's buffers: valid until this model's next forward."""
+        from .vit_engine import check_export
+        out_indices = check_export(out_indices, len(self.blocks), "out_indices")      # host-side, before any GPU work
+        if not out_indices:
+            raise ValueError("out_indices: no block index given")
+        eng = self.engine
+        x, drop_path_masks, drop_key = self._step_inputs(x, drop_path_masks)
+        if self._trunk_trains():
+            return _DenseFunction.apply(self, x, drop_path_masks, drop_key, out_indices, self._anchor)
+        self._attach_tail_grads()
+        eng.forward_trunk(x, None, drop_path_masks, drop_key=drop_key, keep=False, export=out_indices)
+        return tuple(eng.cur["maps"][i] for i in out_indices)
 
 
 def ft_vit(pretrained=False, **kwargs):

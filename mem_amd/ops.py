@@ -756,3 +756,36 @@ def pool_tokens_bwd(dout, T, dx=None):
     assert dx.dtype == torch.float32 and dx.is_contiguous() and dx.numel() == B * T * D
     check(lib.memhip_pool_tokens_bwd(ptr(dout), B, T, D, ptr(dx), stream_ptr()), "pool_tokens_bwd")
     return dx
+
+
+# ---------------------------------------------------------------- dense per-block feature maps (csrc/dense.hip)
+declare({
+    "memhip_tokens_to_maps": (i32, [vp, i64, i32, i32, i32, i32, vp, vp]),
+    "memhip_maps_to_tokens_add": (i32, [vp, i32, i32, i32, i32, vp, i64, vp]),
+})
+
+
+def tokens_to_maps(x, B, T, out=None, b0=0, b1=None):
+    """x f32 [>= B*T, D] (row stride >= D) -> out f32 [B, D, T-1]: out[b, d, l] = x[b*T + 1 + l, d] for the samples
+    b0 <= b < b1 (default: all B); the cls row is skipped (semantic_segmentation/backbone/mem.py:439-441)."""
+    assert x.dtype == torch.float32 and x.dim() == 2 and x.stride(1) == 1 and x.shape[0] >= B * T
+    D = x.shape[1]
+    if out is None:
+        out = torch.empty((B, D, T - 1), dtype=torch.float32, device=x.device)
+    assert out.dtype == torch.float32 and out.is_contiguous() and out.numel() == B * D * (T - 1)
+    b1 = B if b1 is None else b1
+    assert 0 <= b0 < b1 <= B, (b0, b1, B)
+    check(lib.memhip_tokens_to_maps(ptr(x), x.stride(0), b0, b1, T, D, ptr(out), stream_ptr()), "tokens_to_maps")
+    return out
+
+
+def maps_to_tokens_add(dmap, dx, B, T, b0=0, b1=None):
+    """dx f32 [>= B*T, D] (row stride >= D): dx[b*T + 1 + l, d] += dmap[b, d, l] (dmap f32 [B, D, T-1] contiguous, any
+    trailing shape of T-1 elements) for b0 <= b < b1; cls rows untouched, one fp32 add per element."""
+    assert dx.dtype == torch.float32 and dx.dim() == 2 and dx.stride(1) == 1 and dx.shape[0] >= B * T
+    D = dx.shape[1]
+    assert dmap.dtype == torch.float32 and dmap.is_contiguous() and dmap.numel() == B * D * (T - 1)
+    b1 = B if b1 is None else b1
+    assert 0 <= b0 < b1 <= B, (b0, b1, B)
+    check(lib.memhip_maps_to_tokens_add(ptr(dmap), b0, b1, T, D, ptr(dx), dx.stride(0), stream_ptr()), "maps_to_tokens_add")
+    return dx

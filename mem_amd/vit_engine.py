@@ -66,6 +66,22 @@ def flat_layout(shapes, skip, order, aliases=()):
     return segs, buckets, off, flags, [n for n in shapes if decays(n)]
 
 
+def check_export(export, depth, what="export"):
+    """Block indices of a per-block export -> tuple, validated on the host (no device): inside the trunk, distinct,
+    ascending.  None -> ()."""
+    if export is None:
+        return ()
+    export = tuple(int(i) for i in export)
+    for k, i in enumerate(export):
+        if not 0 <= i < depth:
+            raise ValueError(f"{what}: block index {i} outside [0, {depth})")
+        if i in export[:k]:
+            raise ValueError(f"{what}: block index {i} given twice")
+        if k and i < export[k - 1]:
+            raise ValueError(f"{what}: block indices must ascend, {i} follows {export[k - 1]}")
+    return export
+
+
 class FlatParams:
     """The flat fp32 parameter / gradient buffers of an engine and the nn.Parameter views into them: the layout contract
     (segs / buckets / wd_flags) that FlatAdamW, GradReducer and checkpoints read."""
@@ -191,8 +207,12 @@ class ViTEngine(FlatParams):
     def _pack_parameters(self):
         m, D = self.model, self.D
         order, aliases = [], []                       # (bucket, [entries]) in reverse-layer order
-        order.append(("head", ["lm_head.weight", "lm_head.bias", "head.weight", "head.bias", "fc_norm.weight", "fc_norm.bias",
-                               "norm.weight", "norm.bias"]))
+        # (the head bucket also takes the parameters of a model's own torch tail behind the trunk -- the necks of
+        # semseg_backbone.EvBEiT: every name under the model's _TAIL_PREFIXES that is not listed here)
+        head = ["lm_head.weight", "lm_head.bias", "head.weight", "head.bias", "fc_norm.weight", "fc_norm.bias", "norm.weight",
+                "norm.bias"]
+        head += [n for n, _ in m.named_parameters() if n.startswith(tuple(getattr(m, "_TAIL_PREFIXES", ()))) and n not in head]
+        order.append(("head", head))
         for i in reversed(range(self.depth)):
             pre = f"blocks.{i}."
             qkvb = pre + "attn.qkvbias3"                                      # [q_bias | 0 | v_bias]
@@ -342,7 +362,16 @@ class ViTEngine(FlatParams):
         for name in ("dx", "dY", "dh_small", "dY2", "dbig", "dqkv", "dao", "delta_ws", "_tn_ws", "bias_scr", "cs_ws", "dYpe"):
             if hasattr(self, name):          # the smaller batch's backward temporaries: freed now, re-made by _alloc_stash
                 delattr(self, name)
+        self._maps = []                  # dense feature maps of exported blocks (_map_buffers), sized for B like the set above
         self.B, self.B_stash = B, 0
+
+    def _map_buffers(self, n, B):
+        """n engine-owned map buffers [B, D, Hp, Wp] (views of buffers sized for the largest batch, like the forward set;
+        valid until the next forward that exports)."""
+        D, L = self.D, self.L
+        while len(self._maps) < n:
+            self._maps.append(torch.empty(self.B * D * L, dtype=torch.float32, device=self.dev))
+        return [m[: B * D * L].view(B, D, *self.window) for m in self._maps[:n]]
 
     def _alloc_stash(self):
         """What only a backward needs, on the first training forward of a batch size: the other 2 * depth - 2 residual
@@ -629,7 +658,8 @@ class ViTEngine(FlatParams):
                     bias=self.P(pre + "mlp.fc2.bias"))
         ops.residual_rows(xmid, rows, self.y_tail, g2, tail["rowkeep"], keep, Mm, D, self.x_tail)
 
-    def forward_trunk(self, x, mask_u8=None, dp_masks=None, tail_rows=None, drop_key=None, keep=True):
+    def forward_trunk(self, x, mask_u8=None, dp_masks=None, tail_rows=None, drop_key=None, keep=True, export=None,
+                      streams=None):
         """Patch embedding (+ mask-token blend, + abs. position embedding) and the blocks: x f32 [B,C,H,W] ->
         the fp32 residual stream after the last block, [B*T, D] (engine-owned, valid until the next forward).
         drop_key: (key0, key1) of this step's element-wise dropout masks (finetuning model, drop_rate > 0), or None.
@@ -638,7 +668,17 @@ class ViTEngine(FlatParams):
         other two; all blocks share the activation set, the two sample halves of the two-stream split their own row ranges
         of it), so the footprint does not grow with the depth.  Same launches on the same rows in the same order as
         keep=True (stochastic-depth plan, drop-path masks, dropout keys, bias tables, position embedding): the returned
-        stream is bit-identical.  backward_trunk() after it raises.  Finetuning trunk only."""
+        stream is bit-identical.  backward_trunk() after it raises.  Finetuning trunk only.
+        export: sorted tuple of distinct block indices whose OUTPUT is also written as a dense map [B, D, Hp, Wp] (cls row
+        skipped; ops.tokens_to_maps) right after the block, on the stream that ran it and for the rows it ran (each half of
+        the two-stream split exports its own samples) -- with keep=False the block's output buffer is overwritten two blocks
+        later, so the export cannot wait for the end of the trunk.  The maps are self.cur["maps"] (block index -> map),
+        engine-owned, valid until the next forward.  streams: f32 [depth, >= B*T, D] (caller-owned) that receives a copy of
+        every block's output stream, cls row included, the same way.  Both None: nothing new is launched.  Finetuning
+        trunk only."""
+        export = check_export(export, self.depth)
+        assert (not export and streams is None) or (self.head_kind == "cls" and tail_rows is None), \
+            "per-block exports serve the finetuning trunk: no mlm head, no tail-row form"
         assert drop_key is None or (self.drop_rate > 0.0 and tail_rows is None), "dropout: finetuning trunk only"
         assert keep or (self.head_kind == "cls" and tail_rows is None), \
             "forward-only mode (keep=False) serves the finetuning trunk: no mlm head, no tail-row form"
@@ -662,7 +702,8 @@ class ViTEngine(FlatParams):
         nx = 2 * self.depth + 1
         self.cur = dict(B=B, M=M, Mm=0, mask=mask_u8, rows=None, dp=dp_masks, labels=None, plan=plan, tail=None, drop_key=drop_key,
                         keep=bool(keep), x=self.x if keep else [self.x[j % 3] for j in range(nx)],
-                        act=self.act if keep else [self.act[0]] * self.depth, branch=self._branches(B, plan, dp_masks))
+                        act=self.act if keep else [self.act[0]] * self.depth, branch=self._branches(B, plan, dp_masks),
+                        maps=dict(zip(export, self._map_buffers(len(export), B))) if export else None, streams=streams, dmaps=None)
         if tail_rows is not None and not self.fwd_two_streams:
             # per compact row: did the last block's MLP branch keep the row's sample?  (stochastic depth of that branch is
             # applied per row in the tail form, in both the masked and the work-skipping mode)
@@ -677,7 +718,7 @@ class ViTEngine(FlatParams):
             if keepvec is not None:
                 rowkeep = keepvec.index_select(0, torch.div(tail_rows, T, rounding_mode="floor").long()).contiguous()
             self.cur["tail"] = dict(rows=tail_rows, Mm=tail_rows.numel(), rowkeep=rowkeep)
-        if self.head_kind == "cls" and not self.accumulate_grads:
+        if self.head_kind == "cls" and not self.accumulate_grads and self.head_end:
             ops.zero_(self.flat_g[: self.head_end])     # the torch tail accumulates its gradients here before backward_trunk
         ops.im2col(x, B, self.C, self.H, self.W, self.ph, self.pw, self.patches)
         x0 = self.x[0]
@@ -709,8 +750,10 @@ class ViTEngine(FlatParams):
             self._side.wait_event(e0)
             for i in range(self.depth):
                 self._block_fwd(i, 0, bs)
+                self._export_block(i, 0, bs)
                 with torch.cuda.stream(self._side):
                     self._block_fwd(i, bs, B)
+                    self._export_block(i, bs, B)
             e1 = torch.cuda.Event()
             e1.record(self._side)
             torch.cuda.current_stream().wait_event(e1)
@@ -718,7 +761,19 @@ class ViTEngine(FlatParams):
             for i in range(self.depth):
                 self._wait_params(f"block{i}")
                 self._block_fwd(i, 0, B)
+                self._export_block(i, 0, B)
         return self.cur["x"][2 * self.depth][:M]
+
+    def _export_block(self, i, b0, b1):
+        """Block i has just written its output for the samples [b0, b1) on the current stream: export it (forward_trunk)."""
+        c = self.cur
+        if c["maps"] is None and c["streams"] is None:
+            return
+        xout, T = c["x"][2 * i + 2], self.T
+        if c["maps"] is not None and i in c["maps"]:
+            ops.tokens_to_maps(xout, c["B"], T, out=c["maps"][i], b0=b0, b1=b1)
+        if c["streams"] is not None:
+            c["streams"][i][b0 * T:b1 * T].copy_(xout[b0 * T:b1 * T])
 
     # ------------------------------------------------------------------ backward
     def _wgrad(self, dY, X, R, n_out, n_in, gname, bias_grads=()):
@@ -896,8 +951,11 @@ class ViTEngine(FlatParams):
                               self.G("norm.weight"), self.G("norm.bias"), Mm, D, accumulate=False, row_idx=c["rows"])
         self._backward_trunk()
 
-    def backward_trunk(self, dxl):
-        """Finetuning: gradient of the loss w.r.t. the trunk output (f32 [B*T, D] or [B,T,D]) -> every trunk parameter."""
+    def backward_trunk(self, dxl, dmaps=None):
+        """Finetuning: gradient of the loss w.r.t. the trunk output (f32 [B*T, D] or [B,T,D]; None = zero) -> every trunk
+        parameter.  dmaps: {block index: f32 [B, D, Hp, Wp] contiguous}, the gradients w.r.t. the dense maps of those blocks'
+        outputs (forward_trunk(export=...)); each is added into the token gradient once (ops.maps_to_tokens_add), on the
+        main stream, where dx is the gradient w.r.t. that block's output (_inject_dmap).  None: the path is unchanged."""
         c = self.cur
         if not c.get("keep", True):
             raise RuntimeError("backward_trunk after forward_trunk(keep=False): a forward-only pass keeps no activations "
@@ -905,9 +963,30 @@ class ViTEngine(FlatParams):
         M, D = c["M"], self.D
         if not self.accumulate_grads:
             self._zero_small_grads(self.head_end)
-        self.dx[:M].copy_(dxl.reshape(M, D))
+        if dxl is None:
+            ops.zero_(self.dx[:M])
+        else:
+            self.dx[:M].copy_(dxl.reshape(M, D))
+        if dmaps is not None:
+            B, n = c["B"], c["B"] * D * self.L
+            for i, g in dmaps.items():
+                if not 0 <= i < self.depth:
+                    raise ValueError(f"dmaps: block index {i} outside [0, {self.depth})")
+                assert g.is_cuda and g.dtype == torch.float32 and g.is_contiguous() and g.numel() == n, \
+                    f"dmaps[{i}]: contiguous fp32 [{B}, {D}, {self.window[0]}, {self.window[1]}]"
+        c["dmaps"] = dmaps or None
         self._side_begin()
         self._backward_trunk()
+
+    def _inject_dmap(self, i):
+        """dx += the gradient w.r.t. block i's dense map (backward_trunk(dmaps=...)).  Called once per block on the main
+        stream where dx is about to become the gradient w.r.t. block i's OUTPUT and nothing has read it as such: for the
+        last block in front of the loop; for block i < depth - 1 in front of block i + 1's norm1 backward, which ACCUMULATES
+        its term into dx and (fused form) derives block i's MLP-branch gradient from the sum in the same pass -- the two
+        terms commute, and the side stream never reads dx."""
+        dm = self.cur.get("dmaps")
+        if dm is not None and i in dm:
+            ops.maps_to_tokens_add(dm[i], self.dx, self.cur["B"], self.T)
 
     def _attn_branch_bwd(self, i, scr):
         """dY2 = gradient of block i's attention branch output, from dx on the samples the branch kept; the proj.bias
@@ -957,6 +1036,7 @@ class ViTEngine(FlatParams):
         # other one, which leaves row (depth-1)&1 dirty for the next backward when depth is odd
         ops.zero_(self.bias_scr)
         fuse = D <= 1024 and self.fuse_ln_branch
+        self._inject_dmap(self.depth - 1)
         for i in reversed(range(self.depth)):
             pre = f"blocks.{i}."
             a = self.act[i]
@@ -1047,6 +1127,8 @@ class ViTEngine(FlatParams):
                     self._side_read_done("dqkv")
                 self._on_side(wg_qkv)
                 ops.gemm_nt(self.dqkv, self.wT[i]["qkv"], ba.gemm_rows, D, 3 * D, ops.EPI_BIAS_BF16, out0=self.dh_small)
+            if i > 0:
+                self._inject_dmap(i - 1)
             if fuse and i > 0:
                 # norm1 backward of block i (rows its attention branch kept) + MLP-branch backward of block i - 1
                 pb, bb = f"blocks.{i - 1}.", br[2 * i - 1]
