@@ -585,6 +585,48 @@ int memhip_attn_bwd_out_ws(const void* qkv, int64_t ldqkv, const void* dout, int
                            int D, int heads, float scale, void* dqkv, int64_t lddqkv, float* dtable, float* dq_bias,
                            float* dv_bias, void* ws, int64_t ws_bytes, memhip_stream_t stream);
 
+/* The dispatch of memhip_attn_fwd / memhip_attn_bwd* as data (additive to ABI 7): the kernel family, its template arguments,
+ * the samples-per-workgroup numbers the kernels take and the ordered launches, auxiliary ones included.
+ * memhip_attn_plan_fwd / _bwd validate the shape like the calls themselves and plan with the current option values for a
+ * stream with stream_cus usable CUs; they launch nothing and need no device.  has_dtable / has_dv_bias: the call gives
+ * dtable / dv_bias; has_out: the call gives the forward output (memhip_attn_bwd_out*); ws / ws_bytes: the workspace of the
+ * *_ws calls (checked for NULL and alignment, never read).  A shape no family takes: MEMHIP_EUNSUPPORTED, as from the call. */
+#define MEMHIP_ATTN_16 1        /* attn16.hip: the 14 x 14 window, fused backward */
+#define MEMHIP_ATTN_SMALL 2     /* attn.hip: up to 256 tokens held on chip */
+#define MEMHIP_ATTN_WIN 3       /* attn_win.hip: slot layout, windows 40 / 20 wide; backward recomputes the scores */
+#define MEMHIP_ATTN_WIN_DS 4    /* attn_win.hip, backward only: the dS-storing pair over the caller's workspace */
+#define MEMHIP_ATTN_STREAM 5    /* attn_stream.hip: any longer sequence */
+enum { MEMHIP_ATTN_K_STATS_ZERO, MEMHIP_ATTN_K_DELTA, MEMHIP_ATTN_K_FWD, MEMHIP_ATTN_K_BWD_KV, MEMHIP_ATTN_K_BWD_Q,
+       MEMHIP_ATTN_K_FWD16, MEMHIP_ATTN_K_BWD16,
+       MEMHIP_ATTN_K_WIN_STATS, MEMHIP_ATTN_K_FWD_WIN, MEMHIP_ATTN_K_BWD_KV_WIN, MEMHIP_ATTN_K_BWD_Q_WIN,
+       MEMHIP_ATTN_K_BWD_KVS_WIN, MEMHIP_ATTN_K_BWD_QS_WIN,
+       MEMHIP_ATTN_K_FWD_STREAM, MEMHIP_ATTN_K_BWD_KV_STREAM, MEMHIP_ATTN_K_BWD_Q_STREAM };
+typedef struct memhip_attn_launch {
+  int32_t kernel;             /* MEMHIP_ATTN_K_* */
+  int32_t grid_x, grid_y, grid_z;
+  int32_t block;              /* workgroup size */
+  int32_t lds;                /* dynamic LDS bytes */
+} memhip_attn_launch_t;
+typedef struct memhip_attn_plan {
+  int32_t family;             /* MEMHIP_ATTN_* (0: nothing to do, B = 0) */
+  int32_t n;                  /* SMALL: kernel template argument, 32-token blocks */
+  int32_t ww;                 /* WIN / WIN_DS: kernel template argument, window width */
+  int32_t vb, dt, fd;         /* backward template choices: v_bias gradient, table gradient, delta inside the kernel (ATTN_16) */
+  int32_t spb;                /* SMALL: samples per workgroup */
+  int32_t nwg;                /* ATTN_16: workgroups per head */
+  int32_t groups;             /* WIN / WIN_DS / STREAM: workgroups per (head, sample): groups of 8 token blocks */
+  int32_t nbz, nbq, nbs;      /* WIN / WIN_DS: sample slots of the grids (nbq: the kernel that owns the table gradient, nbs: the
+                                 streaming dQ kernel of WIN_DS) */
+  int32_t qgroups, qs;        /* WIN_DS: workgroups per (head, sample) of the streaming dQ kernel; slots per row of stored dS */
+  int32_t stream_spb;         /* STREAM backward: samples per workgroup of the dQ kernel */
+  int32_t lds_over;           /* internal: LDS bytes of the last family tried when none fits (the query fails instead) */
+  int32_t count;
+  memhip_attn_launch_t l[5];
+} memhip_attn_plan_t;
+int memhip_attn_plan_fwd(int B, int T, int D, int heads, int window_h, int window_w, int stream_cus, memhip_attn_plan_t* out);
+int memhip_attn_plan_bwd(int B, int T, int D, int heads, int window_h, int window_w, int has_dtable, int has_dv_bias,
+                         int has_out, const void* ws, int64_t ws_bytes, int stream_cus, memhip_attn_plan_t* out);
+
 /* ------------------------------------------------------------------------
  * fp32 PARITY MODE (`--precision fp32`): the ViT path with fp32 operands / accumulation and no bf16 rounding points --
  * the reference's arithmetic without autocast (same reference lines as the bf16 entry points above).  For loss-curve

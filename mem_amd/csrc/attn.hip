@@ -1,7 +1,11 @@
 // Fused multi-head attention with the shared additive relative-position bias, forward and
 // backward (reference: Attention.forward, mem/modeling_finetune.py:137-154, with the bias of
-// RelativePositionBias :213-247 broadcast over the batch).  head_dim = 64 (ViT-B and ViT-L),
-// up to 256 tokens (longer sequences: attn_stream.hip).
+// RelativePositionBias :213-247 broadcast over the batch).  head_dim = 64 (ViT-B and ViT-L).
+//
+// This file holds the entry points of every bf16 attention call -- validate -> plan -> launch: attn_plan.cpp decides the
+// kernel family, template arguments, grids and LDS sizes, and the launches of the plan run on the family's launcher
+// (attn16.hip: the 14 x 14 window; attn_win.hip: long windows 40 / 20 wide; attn_stream.hip: any other sequence longer than
+// 256 tokens) -- and the kernels of the general family: up to 256 tokens, the whole sequence on chip.
 //
 // CDNA4 mapping.  The whole 197-token problem of one (sample, head) stays on chip; nothing of the
 // [B,H,N,N] score tensor ever reaches HBM.  Scores are computed TRANSPOSED (S^T = K Q^T,
@@ -572,95 +576,177 @@ __global__ void attn_stats_zero_kernel(float* stats, int n) {
   for (int i = threadIdx.x; i < n; i += blockDim.x) stats[i] = 0.f;
 }
 
-// Samples per workgroup.  One workgroup is resident per CU (LDS), so a grid of more than #CUs
-// workgroups runs a second, nearly empty round: ceil(256*12/256) = 12 samples per workgroup gives
-// 22 * 12 = 264 workgroups on 256 CUs, i.e. T(12) + T(4) -- 13 gives 240 workgroups and T(13)
-// (measured: forward 156 -> 130 us, backward 603 -> 503 us per layer).  Dealing (head, sample) pairs
-// perfectly evenly (12 per workgroup, runs crossing into the next head) was tried and is no faster:
-// the crossing workgroups pay the per-head setup twice.  Smallest count for which the grid fits one
-// round, capped at 16 (the table-gradient buckets are sized for that).
-int pick_spb(int B, int heads, hipStream_t s) {
-  int num_cu = memhip::usable_cus(s);
-  if (num_cu <= 0) num_cu = 256;
-  for (int spb = 1; spb <= 16; ++spb)
-    if ((long long)((B + spb - 1) / spb) * heads <= num_cu) return spb;
-  return 16;
-}
-
-}  // namespace
-
-namespace memhip {   // attn_stream.hip: sequences longer than 256 tokens
-int attn_fwd_stream(const void* qkv, int64_t ldqkv, int B, int T, int D, int heads, const float* table, int window_h,
-                    int window_w, void* out, int64_t ldo, float* lse, hipStream_t s);
-int attn_bwd_stream(const void* qkv, int64_t ldqkv, const void* dout, int64_t ldo, const float* lse, float* delta,
-                    float* stats, const float* table, int window_h, int window_w, int B, int T, int D, int heads,
-                    float scale, void* dqkv, int64_t lddqkv, float* dtable, float* dq_bias, float* dv_bias,
-                    hipStream_t s);
-// attn_win.hip: long windows 40 / 20 wide in the slot layout (round 5)
-bool attn_win_fits(int T, int window_h, int window_w);
-int attn_fwd_win(const void* qkv, int64_t ldqkv, int B, int T, int D, int heads, const float* table, int window_h, int window_w,
-                 void* out, int64_t ldo, float* lse, hipStream_t s);
-int attn_bwd_win(const void* qkv, int64_t ldqkv, const void* dout, int64_t ldo, const float* lse, float* delta, float* stats,
-                 const float* table, int window_h, int window_w, int B, int T, int D, int heads, float scale, void* dqkv,
-                 int64_t lddqkv, float* dtable, float* dq_bias, float* dv_bias, void* ws, int64_t ws_bytes, hipStream_t s);
-int64_t attn_bwd_win_workspace(int B, int T, int heads, int window_h, int window_w);
-// attn16.hip: the 14 x 14 window (197 tokens) -- key-slot layout, fused backward
-bool attn16_fits(int T, int window_h, int window_w);
-int attn16_fwd(const void* qkv, int64_t ldqkv, int B, int D, int heads, const float* table, void* out, int64_t ldo,
-               float* lse, hipStream_t s);
-int attn16_bwd(const void* qkv, int64_t ldqkv, const void* dout, int64_t ldo, const void* out, int64_t ldout, const float* lse,
-               const float* delta, const float* table, int B, int D, int heads, float scale, void* dqkv, int64_t lddqkv,
-               float* dtable, float* dq_bias, hipStream_t s);
-}
-
 #define ATTN_DISPATCH(NKB_EXPR, MACRO)                                    \
   switch (NKB_EXPR) {                                                     \
     case 1: MACRO(1); break; case 2: MACRO(2); break; case 3: MACRO(3); break; \
     case 4: MACRO(4); break; case 5: MACRO(5); break; case 6: MACRO(6); break; \
     case 7: MACRO(7); break; case 8: MACRO(8); break;                     \
-    default: return fail(MEMHIP_EUNSUPPORTED, "attention: %d tokens: internal dispatch error", T); \
   }
+
+// the launch text of the three kernels at N token blocks (bodies of launch_small)
+#define FWD(N)                                                                                                       \
+  {                                                                                                                  \
+    static bool done = false;                                                                                        \
+    return launch_planned(attn_fwd_kernel<N>, &done, l, s, qkv, ldq, a.B, a.T, a.D, a.heads, a.table, nrd, a.window_h, \
+                          a.window_w, (__bf16*)a.out, (long long)a.ldout, a.lse, p.spb);                             \
+  }
+#define BWD_KV(N)                                                                                                    \
+  return dispatch_bool(p.vb, [&](auto VB) {                                                                          \
+    static bool done = false;                                                                                        \
+    return launch_planned(attn_bwd_kv_kernel<N, decltype(VB)::value>, &done, l, s, qkv, ldq, dout, ldo, lse, delta,  \
+                          a.dtable ? a.stats : (float*)nullptr, a.table, nrd, a.window_h, a.window_w, dqkv, lddq,    \
+                          a.dv_bias, a.B, a.T, a.D, a.heads, p.spb);                                                 \
+  })
+#define BWD_Q(N)                                                                                                     \
+  return dispatch_bool(p.dt, [&](auto DT) {                                                                          \
+    static bool done = false;                                                                                        \
+    return launch_planned(attn_bwd_q_kernel<N, decltype(DT)::value>, &done, l, s, qkv, ldq, dout, ldo, lse, delta,   \
+                          (const float*)a.stats, a.table, nrd, a.window_h, a.window_w, dqkv, lddq, a.dtable,         \
+                          a.dq_bias, a.B, a.T, a.D, a.heads, a.scale, p.spb);                                        \
+  })
+
+// one launch of a MEMHIP_ATTN_SMALL plan (p.n token blocks, p.spb samples per workgroup), or one of the auxiliary launches in
+// front of any family but the 14 x 14 one
+int launch_small(const AttnArgs& a, const AttnPlan& p, const AttnLaunch& l, hipStream_t s) {
+  const int nrd = (2 * a.window_h - 1) * (2 * a.window_w - 1) + 3;
+  const __bf16 *qkv = (const __bf16*)a.qkv, *dout = (const __bf16*)a.dout;
+  const long long ldq = a.ldqkv, ldo = a.ldo, lddq = a.lddqkv;
+  const float *lse = a.lse, *delta = a.delta;
+  __bf16* dqkv = (__bf16*)a.dqkv;
+  switch (l.kernel) {
+    case MEMHIP_ATTN_K_DELTA:           // rowsum(dout * out) from the forward output (dout and out share ldo here)
+      return launch_planned(attn_delta_kernel, nullptr, l, s, dout, (const __bf16*)a.out, ldo, (long long)a.B * a.T, a.heads,
+                            a.delta);
+    case MEMHIP_ATTN_K_STATS_ZERO:      // per-head bounds, written by the family's first kernel for the one that owns dtable
+      return launch_planned(attn_stats_zero_kernel, nullptr, l, s, a.stats, 4 * a.heads);
+    case MEMHIP_ATTN_K_FWD: ATTN_DISPATCH(p.n, FWD) break;
+    case MEMHIP_ATTN_K_BWD_KV: ATTN_DISPATCH(p.n, BWD_KV) break;
+    case MEMHIP_ATTN_K_BWD_Q: ATTN_DISPATCH(p.n, BWD_Q) break;
+  }
+  return fail(MEMHIP_EINVAL, "attention: kernel %d with %d token blocks: internal dispatch error", l.kernel, p.n);
+}
+
+#undef FWD
+#undef BWD_KV
+#undef BWD_Q
+
+AttnOptions options_now() { return AttnOptions{opt(OPT_ATTN16), opt(OPT_ATTN_WIN)}; }
+
+int validate_shape(bool fwd, int B, int T, int D, int heads, int window_h, int window_w) {
+  if (!(B >= 0 && T > 0 && heads > 0 && D == heads * HD))
+    return fwd ? fail(MEMHIP_EINVAL, "attn_fwd: head_dim must be 64 (D=%d heads=%d)", D, heads)
+               : fail(MEMHIP_EINVAL, "attn_bwd: head_dim must be 64");
+  MEMHIP_REQUIRE(window_h > 0 && window_w > 0 && window_h * window_w + 1 == T, "%s: T must be window_h*window_w + 1",
+                 fwd ? "attn_fwd" : "attn_bwd");
+  return MEMHIP_OK;
+}
+
+// the plan found no family: small or stream over the LDS budget
+int unsupported(const AttnPlan& p, bool fwd, int T, int window_h, int window_w) {
+  if (!fwd)
+    return fail(MEMHIP_EUNSUPPORTED, "attn_bwd: %d tokens with a %dx%d window exceed the LDS budget", T, window_h, window_w);
+  if (p.family == MEMHIP_ATTN_SMALL) return fail(MEMHIP_EUNSUPPORTED, "attn_fwd: LDS budget exceeded");
+  return fail(MEMHIP_EUNSUPPORTED, "attn_fwd: a %dx%d window needs %zu bytes of LDS", window_h, window_w, (size_t)p.lds_over);
+}
+
+// the launches of the plan, in order, each on its family's launcher
+int run(const AttnArgs& a, const AttnPlan& p, bool fwd, hipStream_t s) {
+  static const char* const what[2][6] = {
+      {"", "attn_bwd(14x14)", "attn_bwd", "attn_bwd(win)", "attn_bwd(win, dS-storing)", "attn_bwd(stream)"},
+      {"", "attn_fwd(14x14)", "attn_fwd", "attn_fwd(win)", "", "attn_fwd(stream)"}};
+  for (int i = 0; i < p.count; ++i) {
+    const AttnLaunch& l = p.l[i];
+    int rc;
+    switch (l.kernel) {
+      case MEMHIP_ATTN_K_FWD16:
+      case MEMHIP_ATTN_K_BWD16: rc = attn16_launch(a, p, l, s); break;
+      case MEMHIP_ATTN_K_WIN_STATS:
+      case MEMHIP_ATTN_K_FWD_WIN:
+      case MEMHIP_ATTN_K_BWD_KV_WIN:
+      case MEMHIP_ATTN_K_BWD_Q_WIN:
+      case MEMHIP_ATTN_K_BWD_KVS_WIN:
+      case MEMHIP_ATTN_K_BWD_QS_WIN: rc = attn_win_launch(a, p, l, s); break;
+      case MEMHIP_ATTN_K_FWD_STREAM:
+      case MEMHIP_ATTN_K_BWD_KV_STREAM:
+      case MEMHIP_ATTN_K_BWD_Q_STREAM: rc = attn_stream_launch(a, p, l, s); break;
+      default: rc = launch_small(a, p, l, s);
+    }
+    if (rc != MEMHIP_OK) return rc;
+  }
+  return check_launch(what[fwd][p.family]);
+}
+
+AttnBwdFlags bwd_flags(bool dtable, bool dv_bias, bool out, const void* ws, int64_t ws_bytes) {
+  return AttnBwdFlags{dtable, dv_bias, out, ws && ((uintptr_t)ws & 15) == 0, ws_bytes};
+}
+
+// The four backward entry points are this one call: validate -> plan -> launch.  from_out: a memhip_attn_bwd_out* call -- `out`
+// is required, and rowsum(dout * out) is computed by the library (inside the fused 14 x 14 kernel when it applies, otherwise
+// by attn_delta_kernel into `delta`); ws / ws_bytes: the caller-owned workspace of the *_ws calls.
+int attn_bwd(bool from_out, const void* qkv, int64_t ldqkv, const void* dout, int64_t ldo, const void* out, int64_t ldout,
+             const float* lse, float* delta, const float* table, int window_h, int window_w, int B, int T, int D, int heads,
+             float scale, void* dqkv, int64_t lddqkv, float* dtable, float* dq_bias, float* dv_bias, void* ws, int64_t ws_bytes,
+             memhip_stream_t stream) {
+  if (const int rc = validate_shape(false, B, T, D, heads, window_h, window_w)) return rc;
+  if (B == 0) return MEMHIP_OK;
+  MEMHIP_REQUIRE(qkv && dout && (out || !from_out) && lse && delta && table && dqkv, "attn_bwd: null pointer");
+  MEMHIP_REQUIRE(ldqkv % 8 == 0 && ldo % 8 == 0 && ldout % 8 == 0 && lddqkv % 8 == 0, "attn_bwd: ld must be a multiple of 8");
+  hipStream_t s = as_stream(stream);
+  AttnArgs a = {};
+  a.qkv = qkv; a.ldqkv = ldqkv; a.table = table; a.out = const_cast<void*>(out); a.ldout = ldout;
+  a.lse = const_cast<float*>(lse); a.dout = dout; a.ldo = ldo; a.delta = delta;
+  a.stats = delta + 2LL * B * T * heads;
+  a.scale = scale; a.dqkv = dqkv; a.lddqkv = lddqkv; a.dtable = dtable; a.dq_bias = dq_bias; a.dv_bias = dv_bias; a.ws = ws;
+  a.B = B; a.T = T; a.D = D; a.heads = heads; a.window_h = window_h; a.window_w = window_w;
+  const AttnPlan p = attn_plan_bwd(AttnShape{B, T, heads, window_h, window_w}, bwd_flags(dtable, dv_bias, out, ws, ws_bytes),
+                                   usable_cus(s), options_now());
+  // attn_delta_kernel reads dout and out with one leading dimension
+  MEMHIP_REQUIRE(!out || p.family == MEMHIP_ATTN_16 || ldo == ldout,
+                 "attn_bwd: dout and out must share a leading dimension on this path");
+  if (!p.count) return unsupported(p, false, T, window_h, window_w);
+  return run(a, p, false, s);
+}
+
+}  // namespace
 
 extern "C" int memhip_attn_tokens_padded(int T) { return ((T + 31) / 32) * 32; }
 
+// validate -> plan -> launch
 extern "C" int memhip_attn_fwd(const void* qkv, int64_t ldqkv, int B, int T, int D, int heads, const float* table,
                                int window_h, int window_w, void* out, int64_t ldo, float* lse,
                                memhip_stream_t stream) {
-  MEMHIP_REQUIRE(B >= 0 && T > 0 && heads > 0 && D == heads * HD, "attn_fwd: head_dim must be 64 (D=%d heads=%d)", D, heads);
-  MEMHIP_REQUIRE(window_h > 0 && window_w > 0 && window_h * window_w + 1 == T, "attn_fwd: T must be window_h*window_w + 1");
+  if (const int rc = validate_shape(true, B, T, D, heads, window_h, window_w)) return rc;
   if (B == 0) return MEMHIP_OK;
   MEMHIP_REQUIRE(qkv && table && out && lse, "attn_fwd: null pointer");
   MEMHIP_REQUIRE(ldqkv % 8 == 0 && ldo % 8 == 0, "attn_fwd: ld must be a multiple of 8");
   hipStream_t s = as_stream(stream);
-  if (opt(OPT_ATTN16) && memhip::attn16_fits(T, window_h, window_w))
-    return memhip::attn16_fwd(qkv, ldqkv, B, D, heads, table, out, ldo, lse, s);
-  const int nkb = (T + 31) / 32;
-  const int nrd = (2 * window_h - 1) * (2 * window_w - 1) + 3;
-  if (nkb > 8) {
-    if (opt(OPT_ATTN_WIN) && memhip::attn_win_fits(T, window_h, window_w)) {
-      const int rc = memhip::attn_fwd_win(qkv, ldqkv, B, T, D, heads, table, window_h, window_w, out, ldo, lse, s);
-      if (rc != MEMHIP_EUNSUPPORTED) return rc;
-    }
-    return memhip::attn_fwd_stream(qkv, ldqkv, B, T, D, heads, table, window_h, window_w, out, ldo, lse, s);
-  }
-  const int spb = pick_spb(B, heads, s);
-#define FWD(N)                                                                                          \
-  {                                                                                                     \
-    const size_t sm = (size_t)4 * N * 32 * 128 + (size_t)(rel_geom(window_h, window_w).len + 2 * N * 32) * 4 + 32; \
-    if (sm > (size_t)kMaxLds) return fail(MEMHIP_EUNSUPPORTED, "attn_fwd: LDS budget exceeded");         \
-    static bool attr_done = false;                                                                      \
-    if (!attr_done) {                                                                                   \
-      MEMHIP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fwd_kernel<N>),                 \
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds));             \
-      attr_done = true;                                                                                 \
-    }                                                                                                   \
-    hipLaunchKernelGGL(attn_fwd_kernel<N>, dim3(((B + spb - 1) / spb) * heads), dim3(512), sm, s,       \
-                       (const __bf16*)qkv, (long long)ldqkv, B, T, D, heads, table, nrd, window_h,      \
-                       window_w, (__bf16*)out, (long long)ldo, lse, spb);                               \
-  }
-  ATTN_DISPATCH(nkb, FWD)
-#undef FWD
-  return check_launch("attn_fwd");
+  AttnArgs a = {};
+  a.qkv = qkv; a.ldqkv = ldqkv; a.table = table; a.out = out; a.ldout = ldo; a.lse = lse;
+  a.B = B; a.T = T; a.D = D; a.heads = heads; a.window_h = window_h; a.window_w = window_w;
+  const AttnPlan p = attn_plan_fwd(AttnShape{B, T, heads, window_h, window_w}, usable_cus(s), options_now());
+  if (!p.count) return unsupported(p, true, T, window_h, window_w);
+  return run(a, p, true, s);
+}
+
+extern "C" int memhip_attn_plan_fwd(int B, int T, int D, int heads, int window_h, int window_w, int stream_cus,
+                                    memhip_attn_plan_t* out) {
+  MEMHIP_REQUIRE(out && stream_cus >= 0, "attn plan: bad arguments");
+  if (const int rc = validate_shape(true, B, T, D, heads, window_h, window_w)) return rc;
+  *out = AttnPlan{};
+  if (B == 0) return MEMHIP_OK;
+  *out = attn_plan_fwd(AttnShape{B, T, heads, window_h, window_w}, stream_cus, options_now());
+  return out->count ? MEMHIP_OK : unsupported(*out, true, T, window_h, window_w);
+}
+
+extern "C" int memhip_attn_plan_bwd(int B, int T, int D, int heads, int window_h, int window_w, int has_dtable, int has_dv_bias,
+                                    int has_out, const void* ws, int64_t ws_bytes, int stream_cus, memhip_attn_plan_t* out) {
+  MEMHIP_REQUIRE(out && stream_cus >= 0, "attn plan: bad arguments");
+  if (const int rc = validate_shape(false, B, T, D, heads, window_h, window_w)) return rc;
+  *out = AttnPlan{};
+  if (B == 0) return MEMHIP_OK;
+  *out = attn_plan_bwd(AttnShape{B, T, heads, window_h, window_w}, bwd_flags(has_dtable, has_dv_bias, has_out, ws, ws_bytes),
+                       stream_cus, options_now());
+  return out->count ? MEMHIP_OK : unsupported(*out, false, T, window_h, window_w);
 }
 
 extern "C" int memhip_attn_delta(const void* dout, const void* out, int64_t ldo, int64_t rows, int heads,
@@ -668,125 +754,44 @@ extern "C" int memhip_attn_delta(const void* dout, const void* out, int64_t ldo,
   MEMHIP_REQUIRE(rows >= 0 && heads > 0 && ldo % 8 == 0, "attn_delta: bad arguments");
   if (rows == 0) return MEMHIP_OK;
   MEMHIP_REQUIRE(dout && out && delta, "attn_delta: null pointer");
-  const long long pairs = rows * heads;
-  hipLaunchKernelGGL(attn_delta_kernel, dim3((unsigned)((pairs + 31) / 32)), dim3(256), 0, as_stream(stream),
+  hipLaunchKernelGGL(attn_delta_kernel, dim3(attn_delta_grid(rows, heads)), dim3(256), 0, as_stream(stream),
                      (const __bf16*)dout, (const __bf16*)out, (long long)ldo, (long long)rows, heads, delta);
   return check_launch("attn_delta");
-}
-
-// Attention backward from the forward OUTPUT: rowsum(dout * out) is computed by the library -- inside the fused 14 x 14
-// kernel when it applies (no separate pass), otherwise by memhip_attn_delta into `delta` in front of memhip_attn_bwd.
-extern "C" int memhip_attn_bwd_out(const void* qkv, int64_t ldqkv, const void* dout, int64_t ldo, const void* out, int64_t ldout,
-                                   const float* lse, float* delta, const float* table, int window_h, int window_w, int B,
-                                   int T, int D, int heads, float scale, void* dqkv, int64_t lddqkv, float* dtable,
-                                   float* dq_bias, float* dv_bias, memhip_stream_t stream) {
-  return memhip_attn_bwd_out_ws(qkv, ldqkv, dout, ldo, out, ldout, lse, delta, table, window_h, window_w, B, T, D, heads, scale, dqkv,
-                                lddqkv, dtable, dq_bias, dv_bias, nullptr, 0, stream);
-}
-
-extern "C" int memhip_attn_bwd_out_ws(const void* qkv, int64_t ldqkv, const void* dout, int64_t ldo, const void* out, int64_t ldout,
-                                      const float* lse, float* delta, const float* table, int window_h, int window_w, int B,
-                                      int T, int D, int heads, float scale, void* dqkv, int64_t lddqkv, float* dtable,
-                                      float* dq_bias, float* dv_bias, void* ws, int64_t ws_bytes, memhip_stream_t stream) {
-  MEMHIP_REQUIRE(B >= 0 && T > 0 && heads > 0 && D == heads * HD, "attn_bwd: head_dim must be 64");
-  MEMHIP_REQUIRE(window_h > 0 && window_w > 0 && window_h * window_w + 1 == T, "attn_bwd: T must be window_h*window_w + 1");
-  if (B == 0) return MEMHIP_OK;
-  MEMHIP_REQUIRE(qkv && dout && out && lse && delta && table && dqkv, "attn_bwd: null pointer");
-  MEMHIP_REQUIRE(ldqkv % 8 == 0 && ldo % 8 == 0 && ldout % 8 == 0 && lddqkv % 8 == 0, "attn_bwd: ld must be a multiple of 8");
-  if (opt(OPT_ATTN16) && !dv_bias && memhip::attn16_fits(T, window_h, window_w))
-    return memhip::attn16_bwd(qkv, ldqkv, dout, ldo, out, ldout, lse, delta, table, B, D, heads, scale, dqkv, lddqkv, dtable,
-                              dq_bias, as_stream(stream));
-  MEMHIP_REQUIRE(ldo == ldout, "attn_bwd: dout and out must share a leading dimension on this path");
-  const int rc = memhip_attn_delta(dout, out, ldo, (int64_t)B * T, heads, delta, stream);
-  if (rc != MEMHIP_OK) return rc;
-  return memhip_attn_bwd_ws(qkv, ldqkv, dout, ldo, lse, delta, table, window_h, window_w, B, T, D, heads, scale, dqkv, lddqkv, dtable,
-                            dq_bias, dv_bias, ws, ws_bytes, stream);
 }
 
 extern "C" int memhip_attn_bwd(const void* qkv, int64_t ldqkv, const void* dout, int64_t ldo, const float* lse,
                                float* delta, const float* table, int window_h, int window_w, int B,
                                int T, int D, int heads, float scale, void* dqkv, int64_t lddqkv, float* dtable,
                                float* dq_bias, float* dv_bias, memhip_stream_t stream) {
-  return memhip_attn_bwd_ws(qkv, ldqkv, dout, ldo, lse, delta, table, window_h, window_w, B, T, D, heads, scale, dqkv, lddqkv, dtable,
-                            dq_bias, dv_bias, nullptr, 0, stream);
-}
-
-extern "C" int64_t memhip_attn_bwd_workspace(int B, int T, int heads, int window_h, int window_w) {
-  if (B <= 0 || T <= 0 || heads <= 0) return 0;
-  return memhip::attn_bwd_win_workspace(B, T, heads, window_h, window_w);
+  return attn_bwd(false, qkv, ldqkv, dout, ldo, nullptr, 0, lse, delta, table, window_h, window_w, B, T, D, heads, scale, dqkv,
+                  lddqkv, dtable, dq_bias, dv_bias, nullptr, 0, stream);
 }
 
 extern "C" int memhip_attn_bwd_ws(const void* qkv, int64_t ldqkv, const void* dout, int64_t ldo, const float* lse,
                                   float* delta, const float* table, int window_h, int window_w, int B,
                                   int T, int D, int heads, float scale, void* dqkv, int64_t lddqkv, float* dtable,
                                   float* dq_bias, float* dv_bias, void* ws, int64_t ws_bytes, memhip_stream_t stream) {
-  MEMHIP_REQUIRE(B >= 0 && T > 0 && heads > 0 && D == heads * HD, "attn_bwd: head_dim must be 64");
-  MEMHIP_REQUIRE(window_h > 0 && window_w > 0 && window_h * window_w + 1 == T, "attn_bwd: T must be window_h*window_w + 1");
-  if (B == 0) return MEMHIP_OK;
-  MEMHIP_REQUIRE(qkv && dout && lse && delta && table && dqkv, "attn_bwd: null pointer");
-  MEMHIP_REQUIRE(ldqkv % 8 == 0 && ldo % 8 == 0 && lddqkv % 8 == 0, "attn_bwd: ld must be a multiple of 8");
-  hipStream_t s = as_stream(stream);
-  // the fused kernel has no v_bias-gradient output (the engine derives it from the proj dgrad: vit_engine.py)
-  if (opt(OPT_ATTN16) && !dv_bias && memhip::attn16_fits(T, window_h, window_w))
-    return memhip::attn16_bwd(qkv, ldqkv, dout, ldo, nullptr, 0, lse, delta, table, B, D, heads, scale, dqkv, lddqkv, dtable,
-                              dq_bias, s);
-  const int nkb = (T + 31) / 32;
-  const int nrd = (2 * window_h - 1) * (2 * window_w - 1) + 3;
-  const int spb = pick_spb(B, heads, s);
-  const int grid = ((B + spb - 1) / spb) * heads;
-  const int glen = rel_geom(window_h, window_w).len;
-  float* stats = delta + 2LL * B * T * heads;             // per-head bounds, written by the kv kernel for the q kernel
-  if (dtable) hipLaunchKernelGGL(attn_stats_zero_kernel, dim3(1), dim3(64), 0, s, stats, 4 * heads);
-  if (nkb > 8) {
-    if (opt(OPT_ATTN_WIN) && memhip::attn_win_fits(T, window_h, window_w)) {
-      const int rc = memhip::attn_bwd_win(qkv, ldqkv, dout, ldo, lse, delta, stats, table, window_h, window_w, B, T, D, heads,
-                                          scale, dqkv, lddqkv, dtable, dq_bias, dv_bias, ws, ws_bytes, s);
-      if (rc != MEMHIP_EUNSUPPORTED) return rc;
-    }
-    return memhip::attn_bwd_stream(qkv, ldqkv, dout, ldo, lse, delta, stats, table, window_h, window_w, B, T, D, heads,
-                                   scale, dqkv, lddqkv, dtable, dq_bias, dv_bias, s);
-  }
-#define BWD(N)                                                                                          \
-  {                                                                                                     \
-    static bool attr_done = false;                                                                      \
-    if (!attr_done) {                                                                                   \
-      MEMHIP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_kv_kernel<N, true>),        \
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds));             \
-      MEMHIP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_kv_kernel<N, false>),       \
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds));             \
-      MEMHIP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_q_kernel<N, true>),         \
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds));             \
-      MEMHIP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_q_kernel<N, false>),        \
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds));             \
-      attr_done = true;                                                                                 \
-    }                                                                                                   \
-    const size_t sm_kv = (size_t)4 * N * 32 * 128 + (size_t)(glen + 6 * N * 32 + HD) * 4 + 32;          \
-    const size_t sm_q = (size_t)4 * N * 32 * 128 + (size_t)(2 * glen + HD + 2 * N * 32) * 4 + 32;       \
-    if (sm_kv > (size_t)kMaxLds || sm_q > (size_t)kMaxLds)                                              \
-      return fail(MEMHIP_EUNSUPPORTED, "attn_bwd: %d tokens with a %dx%d window exceed the LDS budget", T, window_h, \
-                  window_w);                                                                            \
-    if (dv_bias)                                                                                        \
-      hipLaunchKernelGGL((attn_bwd_kv_kernel<N, true>), dim3(grid), dim3(512), sm_kv, s, (const __bf16*)qkv, \
-                         (long long)ldqkv, (const __bf16*)dout, (long long)ldo, lse, delta,             \
-                         dtable ? stats : (float*)nullptr, table, nrd, window_h, window_w, (__bf16*)dqkv, \
-                         (long long)lddqkv, dv_bias, B, T, D, heads, spb);                              \
-    else                                                                                                \
-      hipLaunchKernelGGL((attn_bwd_kv_kernel<N, false>), dim3(grid), dim3(512), sm_kv, s, (const __bf16*)qkv, \
-                         (long long)ldqkv, (const __bf16*)dout, (long long)ldo, lse, delta,             \
-                         dtable ? stats : (float*)nullptr, table, nrd, window_h, window_w, (__bf16*)dqkv, \
-                         (long long)lddqkv, dv_bias, B, T, D, heads, spb);                              \
-    if (dtable)                                                                                         \
-      hipLaunchKernelGGL((attn_bwd_q_kernel<N, true>), dim3(grid), dim3(512), sm_q, s, (const __bf16*)qkv, \
-                         (long long)ldqkv, (const __bf16*)dout, (long long)ldo, lse, delta, stats,      \
-                         table, nrd, window_h, window_w, (__bf16*)dqkv, (long long)lddqkv, dtable,      \
-                         dq_bias, B, T, D, heads, scale, spb);                                          \
-    else                                                                                                \
-      hipLaunchKernelGGL((attn_bwd_q_kernel<N, false>), dim3(grid), dim3(512), sm_q, s, (const __bf16*)qkv, \
-                         (long long)ldqkv, (const __bf16*)dout, (long long)ldo, lse, delta, stats,      \
-                         table, nrd, window_h, window_w, (__bf16*)dqkv, (long long)lddqkv, dtable,      \
-                         dq_bias, B, T, D, heads, scale, spb);                                          \
-  }
-  ATTN_DISPATCH(nkb, BWD)
-#undef BWD
-  return check_launch("attn_bwd");
+  return attn_bwd(false, qkv, ldqkv, dout, ldo, nullptr, 0, lse, delta, table, window_h, window_w, B, T, D, heads, scale, dqkv,
+                  lddqkv, dtable, dq_bias, dv_bias, ws, ws_bytes, stream);
+}
+
+extern "C" int memhip_attn_bwd_out(const void* qkv, int64_t ldqkv, const void* dout, int64_t ldo, const void* out, int64_t ldout,
+                                   const float* lse, float* delta, const float* table, int window_h, int window_w, int B,
+                                   int T, int D, int heads, float scale, void* dqkv, int64_t lddqkv, float* dtable,
+                                   float* dq_bias, float* dv_bias, memhip_stream_t stream) {
+  return attn_bwd(true, qkv, ldqkv, dout, ldo, out, ldout, lse, delta, table, window_h, window_w, B, T, D, heads, scale, dqkv,
+                  lddqkv, dtable, dq_bias, dv_bias, nullptr, 0, stream);
+}
+
+extern "C" int memhip_attn_bwd_out_ws(const void* qkv, int64_t ldqkv, const void* dout, int64_t ldo, const void* out, int64_t ldout,
+                                      const float* lse, float* delta, const float* table, int window_h, int window_w, int B,
+                                      int T, int D, int heads, float scale, void* dqkv, int64_t lddqkv, float* dtable,
+                                      float* dq_bias, float* dv_bias, void* ws, int64_t ws_bytes, memhip_stream_t stream) {
+  return attn_bwd(true, qkv, ldqkv, dout, ldo, out, ldout, lse, delta, table, window_h, window_w, B, T, D, heads, scale, dqkv,
+                  lddqkv, dtable, dq_bias, dv_bias, ws, ws_bytes, stream);
+}
+
+extern "C" int64_t memhip_attn_bwd_workspace(int B, int T, int heads, int window_h, int window_w) {
+  if (B <= 0 || T <= 0 || heads <= 0) return 0;
+  return memhip::attn_bwd_win_workspace(B, T, heads, window_h, window_w);
 }

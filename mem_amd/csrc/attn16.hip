@@ -1,7 +1,7 @@
 // Attention for the 14 x 14 token grid (197 tokens: ViT-B/16 and ViT-L/16 at 224 x 224, the BASELINE configuration):
 // forward, and a FUSED backward that computes the probabilities once.  Same contract, rounding points and outputs as the
 // general kernels in attn.hip (reference: Attention.forward, mem/modeling_finetune.py:137-154, bias of RelativePositionBias
-// :213-247); attn.hip dispatches here when the window is 14 x 14.
+// :213-247); the family MEMHIP_ATTN_16 of the plan (attn_plan.cpp).
 //
 // What the general kernels spend their time on (profiles/r02: 9-15 % MFMA-busy, VALU-issue bound): per score element one
 // integer subtract + one LDS gather for the bias bucket, 1.5 instructions to unpack the bf16-rounded score, and -- in
@@ -40,7 +40,6 @@
 //     time, was 23 % of the seven-wave kernel), and waves 4-6 run half a sample behind waves 0-3 so that the two waves of a
 //     SIMD alternate between their MFMA and VALU phases; K and V are double-buffered separately.
 #include "attn_common.hpp"
-#include <type_traits>
 
 #define ATTN16_FD_POS 0   // where the fused-delta loads of the next sample are issued: 0 = in front of the Q / dO DMA (B = 256:
                           // 300.5 us per layer), 1 = behind dQ's LDS staging (306.5 us); attn_delta + unfused backward: 314.4 us
@@ -1011,57 +1010,32 @@ __global__ __launch_bounds__(kThreads16) void attn16_bwd_kernel(const __bf16* __
   }
 }
 
-int num_cu16(hipStream_t s) { const int n = memhip::usable_cus(s); return n > 0 ? n : 256; }
-// workgroups per head: one workgroup per CU (LDS), as many as fit in one round
-int nwg16(int B, int heads, hipStream_t s) {
-  const int n = num_cu16(s) / heads;
-  return n < 1 ? 1 : (n > B ? B : n);
-}
+static_assert(kThreadsFwd16 == kAttn16ThreadsFwd && kThreads16 == kAttn16ThreadsBwd, "attn_plan.hpp: workgroup sizes");
+static_assert(TAB2LEN16 * 4 + 4 * IMG16 + NB16 * 4096 == kAttn16LdsFwd && kLdsBwd16 == kAttn16LdsBwd, "attn_plan.hpp: LDS bytes");
 
 }  // namespace
 
 namespace memhip {
 
-bool attn16_fits(int T, int window_h, int window_w) { return window_h == W16 && window_w == W16 && T == T16; }
-
-int attn16_fwd(const void* qkv, int64_t ldqkv, int B, int D, int heads, const float* table, void* out, int64_t ldo,
-               float* lse, hipStream_t s) {
-  const size_t sm = (size_t)TAB2LEN16 * 4 + 4 * IMG16 + NB16 * 4096;
-  static bool attr_done = false;
-  if (!attr_done) {
-    MEMHIP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(attn16_fwd_kernel),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds));
-    attr_done = true;
+// one launch of a MEMHIP_ATTN_16 plan (p.nwg workgroups per head); arguments already validated
+int attn16_launch(const AttnArgs& a, const AttnPlan& p, const AttnLaunch& l, hipStream_t s) {
+  if (l.kernel == MEMHIP_ATTN_K_FWD16) {
+    static bool done = false;
+    return launch_planned(attn16_fwd_kernel, &done, l, s, (const __bf16*)a.qkv, (long long)a.ldqkv, a.B, a.D, a.heads, a.table,
+                          (__bf16*)a.out, (long long)a.ldout, a.lse, p.nwg, opt(OPT_ATTN16_STAGGER_FWD));
   }
-  const int nwg = nwg16(B, heads, s);
-  hipLaunchKernelGGL(attn16_fwd_kernel, dim3(nwg * heads), dim3(kThreadsFwd16), sm, s, (const __bf16*)qkv,
-                     (long long)ldqkv, B, D, heads, table, (__bf16*)out, (long long)ldo, lse, nwg, opt(OPT_ATTN16_STAGGER_FWD));
-  return check_launch("attn_fwd(14x14)");
-}
-
-int attn16_bwd(const void* qkv, int64_t ldqkv, const void* dout, int64_t ldo, const void* out, int64_t ldout, const float* lse,
-               const float* delta, const float* table, int B, int D, int heads, float scale, void* dqkv, int64_t lddqkv,
-               float* dtable, float* dq_bias, hipStream_t s) {
-  static bool attr_done = false;
-  if (!attr_done) {
-#define A16_ATTR(DT, FD) MEMHIP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(attn16_bwd_kernel<DT, FD>), \
-                                                       hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds))
-    A16_ATTR(true, true); A16_ATTR(true, false); A16_ATTR(false, true); A16_ATTR(false, false);
-#undef A16_ATTR
-    attr_done = true;
-  }
-  const int nwg = nwg16(B, heads, s), stagger = opt(OPT_ATTN16_STAGGER);
-  const int grid = nwg * heads;
-#define A16_LAUNCH(DT, FD)                                                                                          \
-  hipLaunchKernelGGL((attn16_bwd_kernel<DT, FD>), dim3(grid), dim3(kThreads16), kLdsBwd16, s, (const __bf16*)qkv,     \
-                     (long long)ldqkv, (const __bf16*)dout, (long long)ldo, (const __bf16*)out, (long long)ldout, lse, \
-                     delta, table, (__bf16*)dqkv, (long long)lddqkv, dtable, dq_bias, B, D, heads, scale, nwg, stagger)
-  // out != NULL: delta is computed inside the kernel (the `delta` workspace is not read)
-  if (dtable) { if (out) A16_LAUNCH(true, true); else A16_LAUNCH(true, false); }
-  else { if (out) A16_LAUNCH(false, true); else A16_LAUNCH(false, false); }
-#undef A16_LAUNCH
-  return check_launch("attn_bwd(14x14)");
+  if (l.kernel != MEMHIP_ATTN_K_BWD16) return fail(MEMHIP_EINVAL, "attention (14x14): kernel %d is not of this family", l.kernel);
+  // FD (the forward output is given): delta is computed inside the kernel (the `delta` workspace is not read)
+  return dispatch_bool(p.dt, [&](auto DT) {
+    return dispatch_bool(p.fd, [&](auto FD) {
+      static bool done = false;
+      return launch_planned(attn16_bwd_kernel<decltype(DT)::value, decltype(FD)::value>, &done, l, s, (const __bf16*)a.qkv,
+                            (long long)a.ldqkv, (const __bf16*)a.dout, (long long)a.ldo, (const __bf16*)a.out,
+                            (long long)a.ldout, (const float*)a.lse, (const float*)a.delta, a.table, (__bf16*)a.dqkv,
+                            (long long)a.lddqkv, a.dtable, a.dq_bias, a.B, a.D, a.heads, a.scale, p.nwg,
+                            opt(OPT_ATTN16_STAGGER));
+    });
+  });
 }
 
 }  // namespace memhip
-

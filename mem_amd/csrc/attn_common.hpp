@@ -2,6 +2,8 @@
 // sequences streamed in chunks): LDS image layout + LDS-DMA staging, MFMA fragment reads, the extended
 // relative-position table.  Everything has internal linkage (each translation unit gets its own copy).
 #pragma once
+#include <type_traits>
+#include "attn_plan.hpp"
 #include "common.h"
 
 namespace {
@@ -14,7 +16,6 @@ typedef __attribute__((ext_vector_type(16))) float f32x16;
 typedef __attribute__((ext_vector_type(4))) short s16x4;
 
 constexpr int HD = 64;   // head dim
-constexpr int kMaxLds = 160 * 1024;   // bytes of LDS one workgroup may use on gfx950
 
 __device__ __forceinline__ float bfr(float v) { return (float)(__bf16)v; }
 // round two fp32 values to bf16 precision with one packed convert (v_cvt_pk_bf16_f32 + shift + and)
@@ -143,11 +144,7 @@ __device__ __forceinline__ bf16x8 col_frag_o(const char* img, const LaneOffs& o,
 //   5off+3              both cls       (= table[nrd-1])
 // Codes are stored pre-multiplied by 4 (byte offsets).  The table is stored times log2(e) so that
 // the softmax runs on exp2.
-struct RelGeom { int off, len; };
-__device__ __host__ __forceinline__ RelGeom rel_geom(int Wh, int Ww) {
-  const int off = (Wh - 1) * (2 * Ww - 1) + (Ww - 1);
-  return RelGeom{off, (5 * off + 4 + 3) & ~3};   // padded to 16 bytes: the arrays laid out behind it are read as b128
-}
+// (RelGeom / rel_geom: attn_plan.hpp -- the host-only plan sizes the LDS from the same arithmetic)
 // target bucket of extended index i
 __device__ __forceinline__ int rel_target(int i, int off, int nrd) {
   if (i <= 2 * off) return i;
@@ -191,4 +188,34 @@ __device__ __forceinline__ float lds_f32_at(const float* base, int byte_off) {
   return *reinterpret_cast<const float*>(reinterpret_cast<const char*>(base) + byte_off);
 }
 
+// ---- host side: the launchers obey the plan (attn_plan.hpp) and test nothing themselves.
+// a runtime boolean as a template argument: f(std::true_type{}) or f(std::false_type{})
+template <typename F>
+int dispatch_bool(bool b, F&& f) { return b ? f(std::true_type{}) : f(std::false_type{}); }
+
+template <typename K>
+int set_lds_attr(K kernel, bool* done) {
+  if (!*done) {
+    MEMHIP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds));
+    *done = true;
+  }
+  return MEMHIP_OK;
+}
+// Launch `kernel` as the plan's launch `l` says.  `done`: a static of the call site, one per kernel instantiation (the
+// dynamic-LDS limit is raised once); null for kernels without dynamic LDS.
+template <typename K, typename... A>
+int launch_planned(K kernel, bool* done, const AttnLaunch& l, hipStream_t s, A... args) {
+  if (done)
+    if (int rc = set_lds_attr(kernel, done)) return rc;
+  hipLaunchKernelGGL(kernel, dim3(l.grid_x, l.grid_y, l.grid_z), dim3(l.block), l.lds, s, args...);
+  return MEMHIP_OK;
+}
+
 }  // namespace
+
+namespace memhip {
+// one launch `l` of the plan `p` on its family's kernels (attn.hip holds the small family and the loop over the plan)
+int attn16_launch(const AttnArgs& a, const AttnPlan& p, const AttnLaunch& l, hipStream_t s);
+int attn_win_launch(const AttnArgs& a, const AttnPlan& p, const AttnLaunch& l, hipStream_t s);
+int attn_stream_launch(const AttnArgs& a, const AttnPlan& p, const AttnLaunch& l, hipStream_t s);
+}

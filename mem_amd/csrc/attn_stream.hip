@@ -12,7 +12,6 @@
 // The head's extended bias table (5*off+4 floats, 46.6 KB for a 30 x 40 window) stays in LDS for the
 // whole workgroup; bucket indices are code differences (attn_common.hpp), no [H,N,N] tensor exists.
 #include "attn_common.hpp"
-#include <type_traits>
 
 namespace {
 
@@ -538,80 +537,44 @@ __global__ __launch_bounds__(512) void attn_bwd_q_stream_kernel(
   }
 }
 
-constexpr int kFwdCKB = 4, kKvCKB = 4, kQCKB = 2;
-
-template <typename K>
-int set_lds_attr(K kernel, bool* done) {
-  if (!*done) {
-    MEMHIP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   kMaxLds));
-    *done = true;
-  }
-  return MEMHIP_OK;
-}
+constexpr int kFwdCKB = 4, kKvCKB = 4, kQCKB = 2;   // (attn_plan.cpp sizes LDS and grids for these)
 
 }  // namespace
 
 namespace memhip {
 
-// called by memhip_attn_fwd / memhip_attn_bwd (attn.hip) when T > 256; arguments already validated
-int attn_fwd_stream(const void* qkv, int64_t ldqkv, int B, int T, int D, int heads, const float* table, int window_h,
-                    int window_w, void* out, int64_t ldo, float* lse, hipStream_t s) {
-  constexpr int CT = kFwdCKB * 32;
-  const int TP = ((T + 31) / 32) * 32, TPc = ((T + CT - 1) / CT) * CT;
-  const int nrd = (2 * window_h - 1) * (2 * window_w - 1) + 3;
-  const size_t sm = (size_t)4 * CT * 128 + (size_t)(rel_geom(window_h, window_w).len + 2 * TPc) * 4 + 32;
-  if (sm > (size_t)kMaxLds)
-    return fail(MEMHIP_EUNSUPPORTED, "attn_fwd: a %dx%d window needs %zu bytes of LDS", window_h, window_w, sm);
-  static bool done = false;
-  if (int rc = set_lds_attr(attn_fwd_stream_kernel<kFwdCKB>, &done)) return rc;
-  hipLaunchKernelGGL(attn_fwd_stream_kernel<kFwdCKB>, dim3((TP / 32 + 7) / 8, heads, B), dim3(512), sm, s,
-                     (const __bf16*)qkv, (long long)ldqkv, T, TP, TPc, D, heads, table, nrd, window_h, window_w,
-                     (__bf16*)out, (long long)ldo, lse);
-  return check_launch("attn_fwd(stream)");
-}
-
-int attn_bwd_stream(const void* qkv, int64_t ldqkv, const void* dout, int64_t ldo, const float* lse, float* delta,
-                    float* stats, const float* table, int window_h, int window_w, int B, int T, int D, int heads,
-                    float scale, void* dqkv, int64_t lddqkv, float* dtable, float* dq_bias, float* dv_bias,
-                    hipStream_t s) {
-  const int TP = ((T + 31) / 32) * 32;
-  const int nrd = (2 * window_h - 1) * (2 * window_w - 1) + 3;
-  const int glen = rel_geom(window_h, window_w).len;
-  constexpr int CTK = kKvCKB * 32, CTQ = kQCKB * 32;
-  const int TPcK = ((T + CTK - 1) / CTK) * CTK, TPcQ = ((T + CTQ - 1) / CTQ) * CTQ;
-  const size_t sm_kv = (size_t)4 * CTK * 128 + (size_t)(glen + 2 * TPcK + 4 * CTK + HD) * 4 + 32;
-  const size_t sm_q = (size_t)4 * CTQ * 128 + (size_t)(2 * glen + HD + 2 * TPcQ) * 4 + 32;
-  if (sm_kv > (size_t)kMaxLds || sm_q > (size_t)kMaxLds)
-    return fail(MEMHIP_EUNSUPPORTED, "attn_bwd: %d tokens with a %dx%d window exceed the LDS budget", T, window_h, window_w);
-  static bool d0 = false, d1 = false, d2 = false, d3 = false;
-  if (int rc = set_lds_attr(attn_bwd_kv_stream_kernel<kKvCKB, true>, &d0)) return rc;
-  if (int rc = set_lds_attr(attn_bwd_kv_stream_kernel<kKvCKB, false>, &d1)) return rc;
-  if (int rc = set_lds_attr(attn_bwd_q_stream_kernel<kQCKB, true>, &d2)) return rc;
-  if (int rc = set_lds_attr(attn_bwd_q_stream_kernel<kQCKB, false>, &d3)) return rc;
-  const int groups = (TP / 32 + 7) / 8;
-  const dim3 gkv(groups, heads, B);
-  if (dv_bias)
-    hipLaunchKernelGGL((attn_bwd_kv_stream_kernel<kKvCKB, true>), gkv, dim3(512), sm_kv, s, (const __bf16*)qkv,
-                       (long long)ldqkv, (const __bf16*)dout, (long long)ldo, lse, delta, dtable ? stats : (float*)nullptr,
-                       table, nrd, window_h, window_w, (__bf16*)dqkv, (long long)lddqkv, dv_bias, B, T, TP, TPcK, D, heads);
-  else
-    hipLaunchKernelGGL((attn_bwd_kv_stream_kernel<kKvCKB, false>), gkv, dim3(512), sm_kv, s, (const __bf16*)qkv,
-                       (long long)ldqkv, (const __bf16*)dout, (long long)ldo, lse, delta, dtable ? stats : (float*)nullptr,
-                       table, nrd, window_h, window_w, (__bf16*)dqkv, (long long)lddqkv, dv_bias, B, T, TP, TPcK, D, heads);
-  // samples per workgroup of the dQ kernel: amortise the bucket flush once the grid is a few rounds deep
-  long long spb = (long long)B * heads * groups / 1024;
-  spb = spb < 1 ? 1 : (spb > 16 ? 16 : spb);
-  const dim3 gq(groups, heads, (unsigned)((B + spb - 1) / spb));
-  if (dtable)
-    hipLaunchKernelGGL((attn_bwd_q_stream_kernel<kQCKB, true>), gq, dim3(512), sm_q, s, (const __bf16*)qkv,
-                       (long long)ldqkv, (const __bf16*)dout, (long long)ldo, lse, delta, stats, table, nrd, window_h,
-                       window_w, (__bf16*)dqkv, (long long)lddqkv, dtable, dq_bias, B, T, TP, TPcQ, D, heads, scale, (int)spb);
-  else
-    hipLaunchKernelGGL((attn_bwd_q_stream_kernel<kQCKB, false>), gq, dim3(512), sm_q, s, (const __bf16*)qkv,
-                       (long long)ldqkv, (const __bf16*)dout, (long long)ldo, lse, delta, stats, table, nrd, window_h,
-                       window_w, (__bf16*)dqkv, (long long)lddqkv, dtable, dq_bias, B, T, TP, TPcQ, D, heads, scale, (int)spb);
-  return check_launch("attn_bwd(stream)");
+// one launch of a MEMHIP_ATTN_STREAM plan; arguments already validated
+int attn_stream_launch(const AttnArgs& a, const AttnPlan& p, const AttnLaunch& l, hipStream_t s) {
+  const int T = a.T, TP = ((T + 31) / 32) * 32;
+  const int nrd = (2 * a.window_h - 1) * (2 * a.window_w - 1) + 3;
+  auto padded = [&](int ckb) { return ((T + ckb * 32 - 1) / (ckb * 32)) * (ckb * 32); };   // T in whole chunks
+  switch (l.kernel) {
+    case MEMHIP_ATTN_K_FWD_STREAM: {
+      static bool done = false;
+      return launch_planned(attn_fwd_stream_kernel<kFwdCKB>, &done, l, s, (const __bf16*)a.qkv, (long long)a.ldqkv, T, TP,
+                            padded(kFwdCKB), a.D, a.heads, a.table, nrd, a.window_h, a.window_w, (__bf16*)a.out,
+                            (long long)a.ldout, a.lse);
+    }
+    case MEMHIP_ATTN_K_BWD_KV_STREAM:
+      return dispatch_bool(p.vb, [&](auto VB) {
+        static bool done = false;
+        return launch_planned(attn_bwd_kv_stream_kernel<kKvCKB, decltype(VB)::value>, &done, l, s, (const __bf16*)a.qkv,
+                              (long long)a.ldqkv, (const __bf16*)a.dout, (long long)a.ldo, (const float*)a.lse,
+                              (const float*)a.delta, a.dtable ? a.stats : (float*)nullptr, a.table, nrd, a.window_h,
+                              a.window_w, (__bf16*)a.dqkv, (long long)a.lddqkv, a.dv_bias, a.B, T, TP, padded(kKvCKB), a.D,
+                              a.heads);
+      });
+    case MEMHIP_ATTN_K_BWD_Q_STREAM:
+      return dispatch_bool(p.dt, [&](auto DT) {
+        static bool done = false;
+        return launch_planned(attn_bwd_q_stream_kernel<kQCKB, decltype(DT)::value>, &done, l, s, (const __bf16*)a.qkv,
+                              (long long)a.ldqkv, (const __bf16*)a.dout, (long long)a.ldo, (const float*)a.lse,
+                              (const float*)a.delta, (const float*)a.stats, a.table, nrd, a.window_h, a.window_w,
+                              (__bf16*)a.dqkv, (long long)a.lddqkv, a.dtable, a.dq_bias, a.B, T, TP, padded(kQCKB), a.D,
+                              a.heads, a.scale, p.stream_spb);
+      });
+  }
+  return fail(MEMHIP_EINVAL, "attention (stream): kernel %d is not of this family", l.kernel);
 }
 
 }  // namespace memhip

@@ -20,7 +20,7 @@
 //   * the cls ROW reads a constant strip (stride 0), the cls COLUMN is one static register of chunk 0.
 // Table in LDS: (2Wh-1)(2Ww-1) floats (18.6 KB for 30 x 40) instead of the 46.6 KB extended table.
 // Instantiated for the window widths the engine meets (40: config #5; 20: the 16 x 20 parity fixture); every other
-// long window stays on attn_stream.hip.
+// long window stays on attn_stream.hip (attn_plan.cpp names this family, MEMHIP_ATTN_WIN / _WIN_DS, only for these widths).
 #include "attn_win_common.hpp"
 
 namespace {
@@ -1228,121 +1228,55 @@ __global__ __launch_bounds__(512) void attn_bwd_q_win_kernel(
   }
 }
 
+// one launch of a MEMHIP_ATTN_WIN / MEMHIP_ATTN_WIN_DS plan at window width WW
 template <int WW>
-size_t win_lds_fwd(int Wh) {
-  using G = WinGeo<WW>;
-  const int NB = (2 * Wh - 1) * G::P;
-  return (size_t)(((NB + 3) & ~3) + G::CQ) * 4 + (size_t)4 * G::CT * 128;
-}
-
-template <int WW>
-int launch_fwd(const void* qkv, int64_t ldqkv, int B, int T, int D, int heads, const float* table, int Wh, void* out,
-               int64_t ldo, float* lse, hipStream_t s) {
-  const int TP = ((T + 31) / 32) * 32;
+int launch_win(const AttnArgs& a, const AttnPlan& p, const AttnLaunch& l, hipStream_t s) {
+  const int Wh = a.window_h, T = a.T, TP = ((T + 31) / 32) * 32, H = a.heads;
   const int nrd = (2 * Wh - 1) * (2 * WW - 1) + 3;
-  const size_t sm = win_lds_fwd<WW>(Wh);
-  if (sm > (size_t)kMaxLds) return MEMHIP_EUNSUPPORTED;
-  static bool done = false;
-  if (int rc = set_lds_attr(attn_fwd_win_kernel<WW>, &done)) return rc;
-  const int groups = (TP / 32 + 7) / 8;
-  // samples per workgroup: the table set-up is paid once per workgroup; keep the grid a few rounds of the chip deep
-  int nbz = B;
-  const long long per = (long long)groups * heads;
-  const int cus = usable_cus(s);
-  while (nbz > 1 && per * nbz > 6LL * cus) nbz = (nbz + 1) / 2;
-  const int grid = 8 * ((heads * nbz + 7) / 8) * groups;
-  hipLaunchKernelGGL((attn_fwd_win_kernel<WW>), dim3(grid), dim3(512), sm, s, (const __bf16*)qkv, (long long)ldqkv,
-                     B, T, TP, D, heads, table, nrd, Wh, (__bf16*)out, (long long)ldo, lse, groups, nbz);
-  return check_launch("attn_fwd(win)");
-}
-
-template <int WW>
-int launch_bwd(const void* qkv, int64_t ldqkv, const void* dout, int64_t ldo, const float* lse, float* delta, float* stats,
-               const float* table, int Wh, int B, int T, int D, int heads, float scale, void* dqkv, int64_t lddqkv, float* dtable,
-               float* dq_bias, float* dv_bias, void* ws, int64_t ws_bytes, hipStream_t s) {
-  using G = WinGeo<WW>;
-  const int TP = ((T + 31) / 32) * 32;
-  const int nrd = (2 * Wh - 1) * (2 * WW - 1) + 3;
-  const int NBP = ((2 * Wh - 1) * G::P + 3) & ~3;
-  const int groups = (TP / 32 + 7) / 8;
-  int nbz = B;
-  const long long per = (long long)groups * heads;
-  const int cus = usable_cus(s);
-  while (nbz > 1 && per * nbz > 6LL * cus) nbz = (nbz + 1) / 2;
-  // the kernel that owns the table gradient is persistent over at most 16 samples per workgroup (the fixed-point bound of the buckets)
-  int nbq = nbz;
-  while ((B + nbq - 1) / nbq > 16) ++nbq;
-  // ---- dS-storing form: needs the caller's workspace (memhip_attn_bwd_workspace)
-  const int QS = G::CT * ((Wh + G::RPC - 1) / G::RPC);
-  const int64_t need = (int64_t)B * heads * TP * QS * 2;
-  if (opt(OPT_ATTN_WIN) == 1 && ws && ws_bytes >= need && ((uintptr_t)ws & 15) == 0) {
-    const size_t sm_kvs = (size_t)(2 * (NBP + 2 * G::CQ) + 16 + 4 * G::CT + 8 * HD) * 4 + (size_t)4 * G::CT * 128;
-    const size_t sm_kvs0 = (size_t)((NBP + 2 * G::CQ) + 16 + 4 * G::CT + 8 * HD) * 4 + (size_t)4 * G::CT * 128;
-    const size_t sm_qs = (size_t)8 * HD * 4 + (size_t)3 * 5 * 64 * 128;
-    if (sm_kvs <= (size_t)kMaxLds) {
-      static bool a0 = false, a1 = false, a2 = false, a3 = false, a4 = false;
-      if (int rc = set_lds_attr(attn_bwd_kvs_win_kernel<WW, true, true>, &a0)) return rc;
-      if (int rc = set_lds_attr(attn_bwd_kvs_win_kernel<WW, false, true>, &a1)) return rc;
-      if (int rc = set_lds_attr(attn_bwd_kvs_win_kernel<WW, true, false>, &a2)) return rc;
-      if (int rc = set_lds_attr(attn_bwd_kvs_win_kernel<WW, false, false>, &a3)) return rc;
-      if (int rc = set_lds_attr(attn_bwd_qs_win_kernel<WW>, &a4)) return rc;
-      if (dtable) {            // max |dO_q|^2, max |delta_q| per head (the caller has zeroed stats)
-        const int sg = heads * ((256 + heads - 1) / heads);       // a multiple of the head count (see the kernel), ~256 blocks
-        hipLaunchKernelGGL(attn_win_stats_kernel, dim3(sg), dim3(256), 0, s, (const float*)delta, (long long)B * T, heads, stats);
-      }
-      const int nb = dtable ? nbq : nbz;
-      const dim3 gk(8 * ((heads * nb + 7) / 8) * groups);
-#define KVS_LAUNCH(VBF, DTF, SM)                                                                                              \
-      hipLaunchKernelGGL((attn_bwd_kvs_win_kernel<WW, VBF, DTF>), gk, dim3(512), SM, s, (const __bf16*)qkv, (long long)ldqkv,   \
-                         (const __bf16*)dout, (long long)ldo, lse, (const float*)delta, (const float*)stats, table, nrd, Wh,   \
-                         (__bf16*)dqkv, (long long)lddqkv, dv_bias, dtable, (__bf16*)ws, QS, B, T, TP, D, heads, groups, nb)
-      if (dtable) { if (dv_bias) KVS_LAUNCH(true, true, sm_kvs); else KVS_LAUNCH(false, true, sm_kvs); }
-      else { if (dv_bias) KVS_LAUNCH(true, false, sm_kvs0); else KVS_LAUNCH(false, false, sm_kvs0); }
-#undef KVS_LAUNCH
-      const int qgroups = (QS + 255) / 256;
-      int nbs = B;
-      while (nbs > 1 && (long long)qgroups * heads * nbs > 6LL * cus) nbs = (nbs + 1) / 2;
-      const dim3 gq2(8 * ((heads * nbs + 7) / 8) * qgroups);
-      hipLaunchKernelGGL((attn_bwd_qs_win_kernel<WW>), gq2, dim3(512), sm_qs, s, (const __bf16*)qkv, (long long)ldqkv,
-                         (const __bf16*)ws, QS, Wh, (__bf16*)dqkv, (long long)lddqkv, dq_bias, B, T, TP, D, heads, scale, qgroups, nbs);
-      return check_launch("attn_bwd(win, dS-storing)");
+  const __bf16 *qkv = (const __bf16*)a.qkv, *dout = (const __bf16*)a.dout;
+  const long long ldq = a.ldqkv, ldo = a.ldo, lddq = a.lddqkv;
+  const float *lse = a.lse, *delta = a.delta;
+  __bf16* dqkv = (__bf16*)a.dqkv;
+  switch (l.kernel) {
+    case MEMHIP_ATTN_K_FWD_WIN: {
+      static bool done = false;
+      return launch_planned(attn_fwd_win_kernel<WW>, &done, l, s, qkv, ldq, a.B, T, TP, a.D, H, a.table, nrd, Wh, (__bf16*)a.out,
+                            (long long)a.ldout, a.lse, p.groups, p.nbz);
+    }
+    // ---- recomputing form (no workspace)
+    case MEMHIP_ATTN_K_BWD_KV_WIN:
+      return dispatch_bool(p.vb, [&](auto VB) {
+        static bool done = false;
+        return launch_planned(attn_bwd_kv_win_kernel<WW, decltype(VB)::value>, &done, l, s, qkv, ldq, dout, ldo, lse, delta,
+                              a.dtable ? a.stats : (float*)nullptr, a.table, nrd, Wh, dqkv, lddq, a.dv_bias, a.B, T, TP, a.D, H,
+                              p.groups, p.nbz);
+      });
+    case MEMHIP_ATTN_K_BWD_Q_WIN:
+      return dispatch_bool(p.dt, [&](auto DT) {
+        static bool done = false;
+        return launch_planned(attn_bwd_q_win_kernel<WW, decltype(DT)::value>, &done, l, s, qkv, ldq, dout, ldo, lse, delta,
+                              (const float*)a.stats, a.table, nrd, Wh, dqkv, lddq, a.dtable, a.dq_bias, a.B, T, TP, a.D, H,
+                              a.scale, p.groups, p.nbq);
+      });
+    // ---- dS-storing form: the caller's workspace (memhip_attn_bwd_workspace)
+    case MEMHIP_ATTN_K_WIN_STATS:        // max |dO_q|^2, max |delta_q| per head (stats zeroed by the launch in front)
+      return launch_planned(attn_win_stats_kernel, nullptr, l, s, delta, (long long)a.B * T, H, a.stats);
+    case MEMHIP_ATTN_K_BWD_KVS_WIN:
+      return dispatch_bool(p.vb, [&](auto VB) {
+        return dispatch_bool(p.dt, [&](auto DT) {
+          static bool done = false;
+          return launch_planned(attn_bwd_kvs_win_kernel<WW, decltype(VB)::value, decltype(DT)::value>, &done, l, s, qkv, ldq,
+                                dout, ldo, lse, delta, (const float*)a.stats, a.table, nrd, Wh, dqkv, lddq, a.dv_bias, a.dtable,
+                                (__bf16*)a.ws, p.qs, a.B, T, TP, a.D, H, p.groups, p.nbq);
+        });
+      });
+    case MEMHIP_ATTN_K_BWD_QS_WIN: {
+      static bool done = false;
+      return launch_planned(attn_bwd_qs_win_kernel<WW>, &done, l, s, qkv, ldq, (const __bf16*)a.ws, p.qs, Wh, dqkv, lddq,
+                            a.dq_bias, a.B, T, TP, a.D, H, a.scale, p.qgroups, p.nbs);
     }
   }
-  // ---- recomputing form (no workspace)
-  const size_t sm_kv = (size_t)(NBP + G::CQ + 4 * G::CT + 8 * HD) * 4 + (size_t)4 * G::CT * 128;
-  const size_t sm_q = (size_t)(2 * (NBP + G::CQ) + 8 * HD) * 4 + (size_t)4 * G::CT * 128;
-  if (sm_kv > (size_t)kMaxLds || sm_q > (size_t)kMaxLds) return MEMHIP_EUNSUPPORTED;
-  static bool d0 = false, d1 = false, d2 = false, d3 = false;
-  if (int rc = set_lds_attr(attn_bwd_kv_win_kernel<WW, true>, &d0)) return rc;
-  if (int rc = set_lds_attr(attn_bwd_kv_win_kernel<WW, false>, &d1)) return rc;
-  if (int rc = set_lds_attr(attn_bwd_q_win_kernel<WW, true>, &d2)) return rc;
-  if (int rc = set_lds_attr(attn_bwd_q_win_kernel<WW, false>, &d3)) return rc;
-  const dim3 grid(8 * ((heads * nbz + 7) / 8) * groups);
-  if (dv_bias)
-    hipLaunchKernelGGL((attn_bwd_kv_win_kernel<WW, true>), grid, dim3(512), sm_kv, s, (const __bf16*)qkv, (long long)ldqkv,
-                       (const __bf16*)dout, (long long)ldo, lse, delta, dtable ? stats : (float*)nullptr, table, nrd, Wh,
-                       (__bf16*)dqkv, (long long)lddqkv, dv_bias, B, T, TP, D, heads, groups, nbz);
-  else
-    hipLaunchKernelGGL((attn_bwd_kv_win_kernel<WW, false>), grid, dim3(512), sm_kv, s, (const __bf16*)qkv, (long long)ldqkv,
-                       (const __bf16*)dout, (long long)ldo, lse, delta, dtable ? stats : (float*)nullptr, table, nrd, Wh,
-                       (__bf16*)dqkv, (long long)lddqkv, dv_bias, B, T, TP, D, heads, groups, nbz);
-  const dim3 gq(8 * ((heads * nbq + 7) / 8) * groups);
-  if (dtable)
-    hipLaunchKernelGGL((attn_bwd_q_win_kernel<WW, true>), gq, dim3(512), sm_q, s, (const __bf16*)qkv, (long long)ldqkv,
-                       (const __bf16*)dout, (long long)ldo, lse, delta, stats, table, nrd, Wh, (__bf16*)dqkv, (long long)lddqkv,
-                       dtable, dq_bias, B, T, TP, D, heads, scale, groups, nbq);
-  else
-    hipLaunchKernelGGL((attn_bwd_q_win_kernel<WW, false>), gq, dim3(512), sm_q, s, (const __bf16*)qkv, (long long)ldqkv,
-                       (const __bf16*)dout, (long long)ldo, lse, delta, stats, table, nrd, Wh, (__bf16*)dqkv, (long long)lddqkv,
-                       dtable, dq_bias, B, T, TP, D, heads, scale, groups, nbq);
-  return check_launch("attn_bwd(win)");
-}
-
-template <int WW>
-int64_t win_ws_bytes(int B, int T, int heads, int Wh) {
-  using G = WinGeo<WW>;
-  const int TP = ((T + 31) / 32) * 32;
-  return (int64_t)B * heads * TP * (G::CT * ((Wh + G::RPC - 1) / G::RPC)) * 2;
+  return fail(MEMHIP_EINVAL, "attention (win): kernel %d is not of this family", l.kernel);
 }
 
 }  // namespace
@@ -1356,36 +1290,9 @@ extern "C" int memhip_debug_win_stamps(unsigned long long* host_out) {
 
 namespace memhip {
 
-bool attn_win_fits(int T, int window_h, int window_w) {
-  return T > 256 && (window_w == 40 || window_w == 20) && T == window_h * window_w + 1;
-}
-
-int attn_fwd_win(const void* qkv, int64_t ldqkv, int B, int T, int D, int heads, const float* table, int window_h, int window_w,
-                 void* out, int64_t ldo, float* lse, hipStream_t s) {
-  if (window_w == 40) return launch_fwd<40>(qkv, ldqkv, B, T, D, heads, table, window_h, out, ldo, lse, s);
-  if (window_w == 20) return launch_fwd<20>(qkv, ldqkv, B, T, D, heads, table, window_h, out, ldo, lse, s);
-  return MEMHIP_EUNSUPPORTED;
-}
-
-
-int attn_bwd_win(const void* qkv, int64_t ldqkv, const void* dout, int64_t ldo, const float* lse, float* delta, float* stats,
-                 const float* table, int window_h, int window_w, int B, int T, int D, int heads, float scale, void* dqkv,
-                 int64_t lddqkv, float* dtable, float* dq_bias, float* dv_bias, void* ws, int64_t ws_bytes, hipStream_t s) {
-  if (window_w == 40)
-    return launch_bwd<40>(qkv, ldqkv, dout, ldo, lse, delta, stats, table, window_h, B, T, D, heads, scale, dqkv, lddqkv, dtable,
-                          dq_bias, dv_bias, ws, ws_bytes, s);
-  if (window_w == 20)
-    return launch_bwd<20>(qkv, ldqkv, dout, ldo, lse, delta, stats, table, window_h, B, T, D, heads, scale, dqkv, lddqkv, dtable,
-                          dq_bias, dv_bias, ws, ws_bytes, s);
-  return MEMHIP_EUNSUPPORTED;
-}
-
-// bytes of the dS workspace the dS-storing backward wants (0: no such form for this window)
-int64_t attn_bwd_win_workspace(int B, int T, int heads, int window_h, int window_w) {
-  if (!attn_win_fits(T, window_h, window_w)) return 0;
-  if (window_w == 40) return win_ws_bytes<40>(B, T, heads, window_h);
-  if (window_w == 20) return win_ws_bytes<20>(B, T, heads, window_h);
-  return 0;
+// one launch of a slot-layout plan (p.ww: 40 or 20, the widths the plan names this family for); arguments already validated
+int attn_win_launch(const AttnArgs& a, const AttnPlan& p, const AttnLaunch& l, hipStream_t s) {
+  return p.ww == 40 ? launch_win<40>(a, p, l, s) : launch_win<20>(a, p, l, s);
 }
 
 }  // namespace memhip

@@ -3,24 +3,10 @@
 // Internal linkage: each translation unit gets its own copy.
 #pragma once
 #include "attn_common.hpp"
-#include <type_traits>
 
 namespace {
 
-template <int WW> struct WinGeo {
-  static constexpr int WS = (WW + 7) & ~7;        // slots per grid row
-  static constexpr int CT = 128;                   // slots per chunk
-  static constexpr int RPC = CT / WS;              // grid rows per chunk
-  static constexpr int PAD0 = RPC * WS;            // first padding slot of a chunk (the cls token in chunk 0)
-  static constexpr int P = 2 * WW - 1;
-  static_assert(PAD0 < CT && PAD0 % 8 == 0, "the window width needs at least one padding slot per chunk");
-  static constexpr int CLS_KB = PAD0 / 32, CLS_G = (PAD0 % 32) / 8;
-  static constexpr int CQ = ((RPC - 1) * P + WS + 8 + 3) & ~3;     // floats of the constant strip of the cls row
-  // (slot s of a chunk, s a multiple of 4) -> constant part of the bucket index; s + 4 stays in the same grid row
-  static constexpr int imm(int s) { return (s / WS) * P + (s % WS); }
-  static constexpr bool valid(int s) { return s < PAD0 && (s % WS) < WW; }
-  static constexpr int row(int s) { return s / WS; }
-};
+// (WinGeo<WW>, the slot geometry: attn_plan.hpp -- the host-only plan sizes LDS and workspace from it)
 
 // the slots of chunk c of a head slice -> chunk image (rows indexed by the slot; zero rows for padding slots)
 template <int WW>
@@ -145,16 +131,6 @@ __device__ __forceinline__ void colsum_add4(float* row64, int r, int hh, int db,
     t.x += a0; t.y += a1; t.z += a2; t.w += a3;
     *p = t;
   }
-}
-
-
-template <typename K>
-int set_lds_attr(K kernel, bool* done) {
-  if (!*done) {
-    MEMHIP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds));
-    *done = true;
-  }
-  return MEMHIP_OK;
 }
 
 }  // namespace

@@ -353,6 +353,52 @@ def attn_bwd_workspace(B, T, heads, window):
     return int(lib.memhip_attn_bwd_workspace(B, T, heads, window[0], window[1]))
 
 
+ATTN_16, ATTN_SMALL, ATTN_WIN, ATTN_WIN_DS, ATTN_STREAM = range(1, 6)
+# kernel names of AttnLaunch.kernel (MEMHIP_ATTN_K_*), as they appear in a kernel trace
+ATTN_KERNELS = ("attn_stats_zero_kernel", "attn_delta_kernel", "attn_fwd_kernel", "attn_bwd_kv_kernel", "attn_bwd_q_kernel",
+                "attn16_fwd_kernel", "attn16_bwd_kernel", "attn_win_stats_kernel", "attn_fwd_win_kernel", "attn_bwd_kv_win_kernel",
+                "attn_bwd_q_win_kernel", "attn_bwd_kvs_win_kernel", "attn_bwd_qs_win_kernel", "attn_fwd_stream_kernel",
+                "attn_bwd_kv_stream_kernel", "attn_bwd_q_stream_kernel")
+
+
+class AttnLaunch(C.Structure):
+    """== memhip_attn_launch_t."""
+    _fields_ = [(n, i32) for n in ("kernel", "grid_x", "grid_y", "grid_z", "block", "lds")]
+
+
+class AttnPlan(C.Structure):
+    """== memhip_attn_plan_t."""
+    _fields_ = [(n, i32) for n in ("family", "n", "ww", "vb", "dt", "fd", "spb", "nwg", "groups", "nbz", "nbq", "nbs", "qgroups",
+                                   "qs", "stream_spb", "lds_over", "count")] + [("l", AttnLaunch * 5)]
+
+    @property
+    def launches(self):
+        """[(kernel name, (grid x, y, z), workgroup size, dynamic LDS bytes)], in launch order."""
+        return [(ATTN_KERNELS[l.kernel], (l.grid_x, l.grid_y, l.grid_z), l.block, l.lds) for l in self.l[:self.count]]
+
+
+declare({"memhip_attn_plan_fwd": (i32, [i32, i32, i32, i32, i32, i32, i32, C.POINTER(AttnPlan)]),
+         "memhip_attn_plan_bwd": (i32, [i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, i64, i32, C.POINTER(AttnPlan)])})
+
+
+def attn_plan(B, T, heads, window, backward=False, dtable=True, dv_bias=False, out=False, ws=None, ws_bytes=0, stream_cus=None):
+    """The AttnPlan of attn_fwd (backward=False) or attn_bwd for this shape under the current options: family ATTN_*, template
+    choices, samples-per-workgroup numbers and `.launches`.  dtable / dv_bias / out: the call gives them; ws: a tensor, or an
+    address with ws_bytes.  Nothing is launched; no device is needed when stream_cus is given (default: the current
+    device's CU count, no reservation)."""
+    if stream_cus is None:
+        stream_cus = torch.cuda.get_device_properties(torch.cuda.current_device()).multi_processor_count
+    plan = AttnPlan()
+    if not backward:
+        check(lib.memhip_attn_plan_fwd(B, T, 64 * heads, heads, window[0], window[1], stream_cus, C.byref(plan)), "attn_plan_fwd")
+        return plan
+    if ws is not None and not isinstance(ws, int):
+        ws, ws_bytes = ptr(ws), ws.numel() * ws.element_size()
+    check(lib.memhip_attn_plan_bwd(B, T, 64 * heads, heads, window[0], window[1], int(dtable), int(dv_bias), int(out), ws, ws_bytes,
+                                   stream_cus, C.byref(plan)), "attn_plan_bwd")
+    return plan
+
+
 def attn_bwd(qkv, dout, lse, delta, table, window, B, T, D, heads, scale, dqkv, dtable, dq_bias=None, dv_bias=None, out=None, ws=None):
     """out = the forward output: rowsum(dout * out) is computed by the library (inside the fused 14 x 14 kernel when it
     applies); without it `delta` must have been filled by attn_delta.  ws = a uint8 scratch tensor of at least

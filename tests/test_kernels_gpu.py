@@ -173,6 +173,11 @@ def test_attention_bwd_ds_storing_form(B, T, H, win):
     assert nbytes == B * H * ops.attn_tokens_padded(T) * 128 * -(-win[0] // (128 // ((win[1] + 7) // 8 * 8))) * 2
     ws = torch.empty(nbytes, dtype=torch.uint8, device="cuda")
     ws.fill_(0xFF)                                  # NaN patterns: every word the dQ kernel reads must have been written
+    # the call below (table gradient, v_bias gradient, this workspace) runs the dS-storing pair; one byte less would not
+    plan = ops.attn_plan(B, T, H, win, backward=True, dtable=True, dv_bias=True, ws=ws)
+    assert plan.family == ops.ATTN_WIN_DS and [l[0] for l in plan.launches][-2:] == ["attn_bwd_kvs_win_kernel", "attn_bwd_qs_win_kernel"]
+    assert ops.attn_plan(B, T, H, win, backward=True, dtable=True, dv_bias=True, ws=ws.data_ptr(),
+                         ws_bytes=nbytes - 1).family == ops.ATTN_WIN
     _attention_case(B, T, H, win, ws=ws)
 
 
@@ -180,7 +185,12 @@ def test_attention_bwd_workspace_is_optional():
     """No workspace form for the short windows (0 bytes); a workspace that is too small falls back to the recomputing kernels."""
     from mem_amd import ops
     assert ops.attn_bwd_workspace(4, 197, 12, (14, 14)) == 0 and ops.attn_bwd_workspace(4, 325, 4, (18, 18)) == 0
-    _attention_case(2, 321, 2, (16, 20), ws=torch.empty(1024, dtype=torch.uint8, device="cuda"))
+    small = torch.empty(1024, dtype=torch.uint8, device="cuda")
+    plan = ops.attn_plan(2, 321, 2, (16, 20), backward=True, dtable=True, dv_bias=True, ws=small)
+    assert plan.family == ops.ATTN_WIN and [l[0] for l in plan.launches][-2:] == ["attn_bwd_kv_win_kernel", "attn_bwd_q_win_kernel"]
+    assert ops.attn_plan(2, 321, 2, (16, 20), backward=True, dtable=True, dv_bias=True, ws=small.data_ptr(),
+                         ws_bytes=ops.attn_bwd_workspace(2, 321, 2, (16, 20))).family == ops.ATTN_WIN_DS
+    _attention_case(2, 321, 2, (16, 20), ws=small)
 
 
 def test_attn_win_equals_stream_kernels():
@@ -204,6 +214,10 @@ def test_attn_win_equals_stream_kernels():
         try:
             for mode in (0, 1):
                 _lib.set_option("attn_win", mode)
+                # what the calls below dispatch to: the two settings must not run the same kernels
+                fams = (ops.attn_plan(B, T, H, win).family,
+                        ops.attn_plan(B, T, H, win, backward=True, dtable=True, dv_bias=True).family)
+                assert fams == ((ops.ATTN_WIN, ops.ATTN_WIN) if mode else (ops.ATTN_STREAM, ops.ATTN_STREAM)), (B, H, win, mode, fams)
                 out = torch.zeros(B * T, D, dtype=torch.bfloat16, device="cuda"); lse = torch.zeros(B, H, TP, device="cuda")
                 dqkv = torch.full((B * T, 3 * D), 3.0, dtype=torch.bfloat16, device="cuda")
                 dtable = torch.zeros(nrd, H, device="cuda"); dqb = torch.zeros(D, device="cuda"); dvb = torch.zeros(D, device="cuda")
@@ -223,9 +237,13 @@ def test_attn_win_equals_stream_kernels():
 
 def test_attention_general_kernels_at_14x14():
     """The 14 x 14 window dispatches to attn16.hip; with the switch off the general kernels of attn.hip take it."""
-    from mem_amd import _lib
+    from mem_amd import _lib, ops
+    assert ops.attn_plan(29, 197, 3, (14, 14)).family == ops.ATTN_16
+    assert ops.attn_plan(29, 197, 3, (14, 14), backward=True).family == ops.ATTN_16
     _lib.set_option("attn16", 0)
     try:
+        assert ops.attn_plan(29, 197, 3, (14, 14)).family == ops.ATTN_SMALL
+        assert ops.attn_plan(29, 197, 3, (14, 14), backward=True).family == ops.ATTN_SMALL
         _attention_case(29, 197, 3, (14, 14))
     finally:
         _lib.set_option("attn16", 1)
