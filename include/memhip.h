@@ -36,7 +36,7 @@ extern "C" {
 #endif
 
 #define MEMHIP_ABI_VERSION 7   /* 7: the finetuning recipe (memhip_mixup, memhip_mix_targets, memhip_ce_soft, memhip_ema_update), and -- additive, no
-                                  existing signature changed, so the number stays -- memhip_pool_tokens / memhip_pool_tokens_bwd, memhip_gemm_bf16_nt_plan, memhip_tokens_to_maps / memhip_maps_to_tokens_add; 6: element-wise dropout (memhip_dropout_t, epilogue RESIDUAL_DROP, memhip_gemm_args_t.dropout, the
+                                  existing signature changed, so the number stays -- memhip_pool_tokens / memhip_pool_tokens_bwd, memhip_gemm_bf16_nt_plan, memhip_tokens_to_maps / memhip_maps_to_tokens_add, memhip_conv_plan; 6: element-wise dropout (memhip_dropout_t, epilogue RESIDUAL_DROP, memhip_gemm_args_t.dropout, the
                                   *_drop row kernels); 5 (round 6): memhip_build_flags, memhip_attn_bwd_ws / _out_ws / _workspace; 4 (round 5): epilogues 6 / 7 carry the stored GELU derivative as FP16 (since round 4), certified-tokenizer entry points */
 
 #define MEMHIP_OK 0
@@ -753,6 +753,37 @@ int memhip_conv2d_nhwc_f16x2(const void* in, int64_t in_plane, const void* weigh
                              memhip_stream_t stream);
 int memhip_nchw_to_padded_nhwc4_f16x2(const float* x, int B, int C, int H, int W, const float* mean, const float* stdv,
                                       void* out, int64_t out_plane, memhip_stream_t stream);
+
+/* The dispatch of the four conv2d entry points above as data (additive to ABI 7): the layer's geometry and the ordered
+ * launches.  memhip_conv_plan validates the shape like the call of that mode (same messages, same return codes) and plans
+ * with the current value of the "conv_waves" option for a device of device_cus CUs (< 0: the current device's); it launches
+ * nothing and needs no device when device_cus is given.  has_add: the call gives `add`; out_f32: MEMHIP_CONV_F16X2 only;
+ * dynamic: MEMHIP_CONV_F32 only, the plan of memhip_conv2d_nhwc_f32_dyn -- two launches, of which the one whose
+ * [dyn_lo, dyn_hi) holds *n_active works. */
+enum { MEMHIP_CONV_BF16, MEMHIP_CONV_F32, MEMHIP_CONV_F16X2 };
+enum { MEMHIP_CONV_K_BF16,          /* conv_gemm_kernel */
+       MEMHIP_CONV_K_F32,           /* conv_gemm_f32_kernel: 128-row tiles */
+       MEMHIP_CONV_K_F32_M32,       /* conv_gemm_f32_m32_kernel: 32-row tiles, dynamic batch only */
+       MEMHIP_CONV_K_F16X2_W4,      /* conv_gemm_f16x2_kernel<4> */
+       MEMHIP_CONV_K_F16X2_W8,      /* conv_gemm_f16x2_kernel<8> */
+       MEMHIP_CONV_K_F16X2_WIDE,    /* conv_gemm_f16x2_wide_kernel: 256 x 128 tile */
+       MEMHIP_CONV_K_F16X2_FIRST }; /* conv_gemm_f16x2_first_kernel: C_in = 4, persistent */
+typedef struct memhip_conv_launch {
+  int32_t kernel;             /* MEMHIP_CONV_K_* */
+  int32_t grid;               /* workgroups */
+  int32_t block;              /* workgroup size */
+  int32_t lds;                /* dynamic LDS bytes */
+  int32_t dyn_lo, dyn_hi;     /* dynamic batch: works when dyn_lo <= *n_active < dyn_hi (otherwise 0, 2^30) */
+} memhip_conv_launch_t;
+typedef struct memhip_conv_plan {
+  int32_t Hp, Wp, Ho, Wo;     /* padded input, output */
+  int32_t K, off;             /* GEMM depth k*k*C_in; first tap = 1 - pad */
+  int64_t M;                  /* GEMM rows B*Ho*Wo (0: nothing to do) */
+  int32_t count;
+  memhip_conv_launch_t l[2];
+} memhip_conv_plan_t;
+int memhip_conv_plan(int mode, int B, int H, int W, int Cin, int Cout, int ksize, int stride, int pad, int has_add,
+                     int out_f32, int out_padded, int dynamic, int device_cus, memhip_conv_plan_t* out);
 
 /* ------------------------------------------------------------------------
  * Layout / dtype movers

@@ -14,7 +14,7 @@
 // pixels x 4 channels.  Epilogue (16-byte accesses after an LDS transposition): + bias, optional
 // ReLU, optional residual add (ResBlock: net(x) + x), bf16, written into the interior of the padded
 // output (or densely, for the token logits).
-#include "common.h"
+#include "conv_common.hpp"
 
 namespace {
 
@@ -40,11 +40,6 @@ struct ConvArgs {
   int out_padded, relu, cin4;
 };
 
-__device__ __forceinline__ int swz_slot(int row, int chunk) { return row * 8 + (chunk ^ ((row >> 1) & 7)); }
-__device__ __forceinline__ void glds16(const void* gsrc, void* lds_dst) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc,
-                                   (__attribute__((address_space(3))) void*)lds_dst, 16, 0, 0);
-}
 __device__ __forceinline__ unsigned pack2(float a, float b) {
   return __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{a, b}, bf16x2));
 }
@@ -214,13 +209,6 @@ __global__ __launch_bounds__(256) void nchw_to_padded_nhwc4_kernel(const float* 
   *reinterpret_cast<uint2*>(out + (((long long)b * (H + 2) + y + 1) * (W + 2) + xw + 1) * 4) = o;
 }
 
-// torch.argmax's order: NaN above every number, ties to the smallest index (all -inf -> 0): always a valid id
-__device__ __forceinline__ bool argmax_better(float a, int ai, float b, int bi) {
-  const bool an = a != a, bn = b != b;
-  if (an || bn) return an && (!bn || ai < bi);
-  return a > b || (a == b && ai < bi);
-}
-
 // ids[m] = argmax_n logits[m, n] (first maximum, NaN wins like torch.argmax), one wave per row, 16-byte loads
 __global__ __launch_bounds__(256) void argmax_rows_kernel(const __bf16* __restrict__ logits, long long ld, int M, int N,
                                                           long long* __restrict__ ids) {
@@ -247,35 +235,22 @@ __global__ __launch_bounds__(256) void argmax_rows_kernel(const __bf16* __restri
 
 }  // namespace
 
+static_assert(BM == kConvTileM && BN == kConvTileN && BK == kConvBK16 && 2 * kStageBytes == kConvLdsBf16, "conv_plan.hpp: tile, LDS bytes");
+
+// validate -> plan -> launch (conv_plan.cpp holds the rules)
 extern "C" int memhip_conv2d_nhwc_bf16(const void* in, const void* weight, const float* bias, const void* add,
                                        void* out, int B, int H, int W, int Cin, int Cout, int ksize, int stride,
                                        int pad, int relu, int out_padded, memhip_stream_t stream) {
-  MEMHIP_REQUIRE(B >= 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0, "conv2d: bad shape");
-  if (B == 0) return MEMHIP_OK;
-  MEMHIP_REQUIRE(in && weight && out, "conv2d: null pointer");
-  MEMHIP_REQUIRE((ksize == 4 && stride == 2 && pad == 1) || (ksize == 3 && stride == 1 && pad == 1) ||
-                     (ksize == 1 && stride == 1 && pad == 0),
-                 "conv2d: only the encoder's shapes (4x4/s2/p1, 3x3/s1/p1, 1x1) are provided");
-  const bool cin4 = Cin == 4;
-  MEMHIP_REQUIRE(cin4 ? (ksize == 4) : (Cin % 64 == 0), "conv2d: C_in must be 4 (first layer, 4x4) or a multiple of 64");
-  MEMHIP_REQUIRE(Cout % 8 == 0, "conv2d: C_out must be a multiple of 8");
+  const ConvFlags f = {add != nullptr, false, out_padded != 0, false};
+  ConvGeom g;
+  if (int rc = conv_validate(MEMHIP_CONV_BF16, B, H, W, Cin, Cout, ksize, stride, pad, f, in && weight && out, &g)) return rc;
+  const ConvPlan plan = conv_plan(MEMHIP_CONV_BF16, g, f, ConvOptions{0}, 0);
+  if (!plan.count) return MEMHIP_OK;
   ConvArgs p;
   p.in = (const __bf16*)in; p.w = (const __bf16*)weight; p.bias = bias; p.add = (const __bf16*)add; p.out = (__bf16*)out;
-  p.B = B; p.Hp = H + 2; p.Wp = W + 2; p.Cin = Cin;
-  p.Ho = (H + 2 * pad - ksize) / stride + 1; p.Wo = (W + 2 * pad - ksize) / stride + 1;
-  p.Cout = Cout; p.kh = ksize; p.kw = ksize; p.stride = stride; p.off = 1 - pad; p.K = ksize * ksize * Cin;
-  p.out_padded = out_padded; p.relu = relu; p.cin4 = cin4 ? 1 : 0;
-  MEMHIP_REQUIRE(p.K % BK == 0, "conv2d: K = %d must be a multiple of 64", p.K);
-  const long long M = (long long)B * p.Ho * p.Wo;
-  MEMHIP_REQUIRE(M < (1LL << 31), "conv2d: too many output pixels");
-  const int grid = cdiv(M, BM) * cdiv(Cout, BN);
-  static bool attr_done = false;
-  if (!attr_done) {
-    MEMHIP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_gemm_kernel),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, 2 * kStageBytes));
-    attr_done = true;
-  }
-  hipLaunchKernelGGL(conv_gemm_kernel, dim3(grid), dim3(kThreads), 2 * kStageBytes, as_stream(stream), p);
+  fill_geom(p, g);
+  p.kh = ksize; p.out_padded = out_padded; p.relu = relu; p.cin4 = Cin == 4 ? 1 : 0;
+  if (int rc = conv_launch<conv_gemm_kernel>(plan.l[0], as_stream(stream), p)) return rc;
   return check_launch("conv2d_nhwc_bf16");
 }
 

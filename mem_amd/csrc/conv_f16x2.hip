@@ -11,7 +11,7 @@
 // Layout: as conv.hip (NHWC with a one-pixel zero border, weights [C_out][ky][kx][c]) with two PLANES per tensor
 // (hi plane, lo plane; plane stride passed in); the structure is conv.hip's 128x128x64 tile with an LDS-DMA-gathered A
 // operand, doubled: {A_hi, A_lo, B_hi, B_lo} x 16 KiB per stage, two stages = 128 KiB (one workgroup per CU).
-#include "common.h"
+#include "conv_common.hpp"
 
 namespace {
 
@@ -36,11 +36,6 @@ struct ConvArgsH {
   int out_padded, relu, cin4, out_f32;
 };
 
-__device__ __forceinline__ int swz_slot(int row, int chunk) { return row * 8 + (chunk ^ ((row >> 1) & 7)); }
-__device__ __forceinline__ void glds16(const void* gsrc, void* lds_dst) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc,
-                                   (__attribute__((address_space(3))) void*)lds_dst, 16, 0, 0);
-}
 __device__ __forceinline__ void split16(float v, _Float16& hi, _Float16& lo) {
   hi = (_Float16)v;
   lo = (_Float16)((v - (float)hi) * kLoScale);
@@ -595,72 +590,36 @@ __global__ __launch_bounds__(256) void nchw_to_padded_nhwc4_f16x2_kernel(const f
 
 }  // namespace
 
+static_assert(BM == kConvTileM && BN == kConvTileN && WBM == kConvWideM && WBN == kConvTileN && BK == kConvBK16, "conv_plan.hpp: tiles");
+static_assert(2 * kStageBytes == kConvLdsF16x2 && 3 * kWStage == kConvLdsF16x2Wide &&
+                  2 * kTileBytes + 2 * 2 * kTileBytes + 8 * 16 * 72 * 4 == kConvLdsF16x2First, "conv_plan.hpp: LDS bytes");
+
+// validate -> plan -> launch (conv_plan.cpp holds the rules: which layer gets the first-layer kernel, the wide tile, <4> or <8>)
 extern "C" int memhip_conv2d_nhwc_f16x2(const void* in, int64_t in_plane, const void* weight, int64_t w_plane, const float* bias,
                                         const void* add, int64_t add_plane, void* out, int64_t out_plane, int B, int H, int W,
                                         int Cin, int Cout, int ksize, int stride, int pad, int relu, int out_padded,
                                         int out_f32, memhip_stream_t stream) {
-  MEMHIP_REQUIRE(B >= 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0, "conv2d_f16x2: bad shape");
-  if (B == 0) return MEMHIP_OK;
-  MEMHIP_REQUIRE(in && weight && out, "conv2d_f16x2: null pointer");
-  MEMHIP_REQUIRE((ksize == 4 && stride == 2 && pad == 1) || (ksize == 3 && stride == 1 && pad == 1) ||
-                     (ksize == 1 && stride == 1 && pad == 0),
-                 "conv2d_f16x2: only the encoder's shapes (4x4/s2/p1, 3x3/s1/p1, 1x1) are provided");
-  const bool cin4 = Cin == 4;
-  MEMHIP_REQUIRE(cin4 ? (ksize == 4) : (Cin % 64 == 0), "conv2d_f16x2: C_in must be 4 (first layer, 4x4) or a multiple of 64");
-  MEMHIP_REQUIRE(Cout % 8 == 0, "conv2d_f16x2: C_out must be a multiple of 8");
-  MEMHIP_REQUIRE(!(out_f32 && out_padded), "conv2d_f16x2: the fp32 output is the dense token-logit matrix");
+  const ConvFlags f = {add != nullptr, out_f32 != 0, out_padded != 0, false};
+  ConvGeom g;
+  if (int rc = conv_validate(MEMHIP_CONV_F16X2, B, H, W, Cin, Cout, ksize, stride, pad, f, in && weight && out, &g)) return rc;
+  const ConvPlan plan = conv_plan(MEMHIP_CONV_F16X2, g, f, ConvOptions{opt(OPT_CONV_WAVES)}, max_cus());
+  if (!plan.count) return MEMHIP_OK;
   ConvArgsH p;
   p.in = (const _Float16*)in; p.in_plane = in_plane; p.w = (const _Float16*)weight; p.w_plane = w_plane; p.bias = bias;
   p.add = (const _Float16*)add; p.add_plane = add_plane; p.out = out; p.out_plane = out_plane;
-  p.B = B; p.Hp = H + 2; p.Wp = W + 2; p.Cin = Cin;
-  p.Ho = (H + 2 * pad - ksize) / stride + 1; p.Wo = (W + 2 * pad - ksize) / stride + 1;
-  p.Cout = Cout; p.kh = ksize; p.kw = ksize; p.stride = stride; p.off = 1 - pad; p.K = ksize * ksize * Cin;
-  p.out_padded = out_padded; p.relu = relu; p.cin4 = cin4 ? 1 : 0; p.out_f32 = out_f32;
-  MEMHIP_REQUIRE(p.K % BK == 0, "conv2d_f16x2: K = %d must be a multiple of 64", p.K);
-  const long long M = (long long)B * p.Ho * p.Wo;
-  MEMHIP_REQUIRE(M < (1LL << 31), "conv2d_f16x2: too many output pixels");
-  const int grid = cdiv(M, BM) * cdiv(Cout, BN);
-  static bool attr_done = false;
-  if (!attr_done) {
-    MEMHIP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_gemm_f16x2_kernel<4>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, 2 * kStageBytes));
-    MEMHIP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_gemm_f16x2_kernel<8>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, 2 * kStageBytes));
-    attr_done = true;
+  fill_geom(p, g);
+  p.kh = ksize; p.out_padded = out_padded; p.relu = relu; p.cin4 = Cin == 4 ? 1 : 0; p.out_f32 = out_f32;
+  const ConvLaunch& l = plan.l[0];
+  const hipStream_t s = as_stream(stream);
+  int rc = MEMHIP_EINVAL;
+  switch (l.kernel) {
+    case MEMHIP_CONV_K_F16X2_FIRST: rc = conv_launch<conv_gemm_f16x2_first_kernel>(l, s, p); break;
+    case MEMHIP_CONV_K_F16X2_WIDE: rc = conv_launch<conv_gemm_f16x2_wide_kernel>(l, s, p); break;
+    case MEMHIP_CONV_K_F16X2_W4: rc = conv_launch<conv_gemm_f16x2_kernel<4>>(l, s, p); break;
+    case MEMHIP_CONV_K_F16X2_W8: rc = conv_launch<conv_gemm_f16x2_kernel<8>>(l, s, p); break;
   }
-  // the 256 x 128 tile where its grid is at least two full rounds of the chip: every layer of the encoder at batch 256 but the first
-  // (the 14 x 14 layers are 588 workgroups = 2.3 rounds and still gain: forward 18.55 -> 18.30 ms against the finer 128 x 128 tiles)
-  const int wgrid = cdiv(M, WBM) * cdiv(Cout, WBN);
-  if (cin4 && opt(OPT_CONV_WAVES) >= 16 && p.K == BK && !add && !out_f32 && M % BM == 0 && Cout % BN == 0) {
-    // the first layer, persistent (whole tiles only: every lane then issues every store, which the kernel's counted waits rely on)
-    const int ntn = Cout / BN;
-    int cols = max_cus() / ntn;
-    cols = cols < 1 ? 1 : cols;
-    const int nmt = (int)(M / BM);
-    cols = cols > nmt ? nmt : cols;
-    constexpr int kFirstLds = 2 * kTileBytes + 2 * 2 * kTileBytes + 8 * 16 * 72 * 4;
-    static bool fattr_done = false;
-    if (!fattr_done) {
-      MEMHIP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_gemm_f16x2_first_kernel),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, kFirstLds));
-      fattr_done = true;
-    }
-    hipLaunchKernelGGL(conv_gemm_f16x2_first_kernel, dim3(cols * ntn), dim3(512), kFirstLds, as_stream(stream), p);
-    return check_launch("conv2d_nhwc_f16x2(first)");
-  }
-  if (!cin4 && (opt(OPT_CONV_WAVES) == 32 || (opt(OPT_CONV_WAVES) == 16 && wgrid >= 2 * max_cus()))) {     // 32: the wide tile at any size (tests)
-    static bool wattr_done = false;
-    if (!wattr_done) {
-      MEMHIP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_gemm_f16x2_wide_kernel),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, 3 * kWStage));
-      wattr_done = true;
-    }
-    hipLaunchKernelGGL(conv_gemm_f16x2_wide_kernel, dim3(wgrid), dim3(512), 3 * kWStage, as_stream(stream), p);
-  } else if (opt(OPT_CONV_WAVES) == 4)
-    hipLaunchKernelGGL(conv_gemm_f16x2_kernel<4>, dim3(grid), dim3(256), 2 * kStageBytes, as_stream(stream), p);
-  else
-    hipLaunchKernelGGL(conv_gemm_f16x2_kernel<8>, dim3(grid), dim3(512), 2 * kStageBytes, as_stream(stream), p);
-  return check_launch("conv2d_nhwc_f16x2");
+  if (rc) return rc;
+  return check_launch(l.kernel == MEMHIP_CONV_K_F16X2_FIRST ? "conv2d_nhwc_f16x2(first)" : "conv2d_nhwc_f16x2");
 }
 
 extern "C" int memhip_nchw_to_padded_nhwc4_f16x2(const float* x, int B, int C, int H, int W, const float* mean,

@@ -10,7 +10,7 @@
 // C_in % 4 == 0: a 16-byte chunk never straddles a tap).  128x128x32 tiles, 4 waves of 64x64 (4x4 MFMA blocks),
 // register-staged double buffer; LDS rows have a pitch of 34 floats so that the fragment reads (16 rows x 2 k per
 // 32-lane group) touch 32 distinct banks.  Epilogue: + bias, ReLU, residual add, fp32 float4 stores.
-#include "common.h"
+#include "conv_common.hpp"
 
 namespace {
 
@@ -346,14 +346,6 @@ __global__ __launch_bounds__(256) void nchw_to_padded_nhwc4_f32_kernel(const flo
       make_float4(v[0], v[1], v[2], v[3]);
 }
 
-// torch.argmax's order: a NaN is greater than every number, ties (and several NaNs) go to the smallest index; so a row of
-// all -inf gives 0 and a row with a NaN gives the first NaN's index -- always a valid id (it is used as a label next).
-__device__ __forceinline__ bool argmax_better(float a, int ai, float b, int bi) {
-  const bool an = a != a, bn = b != b;
-  if (an || bn) return an && (!bn || ai < bi);
-  return a > b || (a == b && ai < bi);
-}
-
 // ids[m] = argmax_n logits[m, n] (first maximum, NaN wins like torch.argmax), one wave per row
 // (rms, optional: sqrt(mean_n logits[m, n]^2), the scale of the row the certified tokenizer compares the gap with;
 //  rows_dyn, optional device int: only the first min(M, *rows_dyn) rows exist)
@@ -497,62 +489,32 @@ __global__ __launch_bounds__(256) void scatter_ids_kernel(const long long* __res
 
 }  // namespace
 
+static_assert(BM == kConvTileM && BN == kConvTileN && SBM == kConvF32SmallM && BK == kConvBK32, "conv_plan.hpp: tiles");
+static_assert(2 * kStageFloats * sizeof(float) == kConvLdsF32 && 2 * (SBM * PITCH + kTileFloats) * sizeof(float) == kConvLdsF32M32,
+              "conv_plan.hpp: LDS bytes");
+
+// validate -> plan -> launch (conv_plan.cpp holds the rules).  Dynamic batch (n_active): the plan names both tile forms, each
+// with the range of live-sample counts it works for.
 static int conv2d_nhwc_f32_impl(const float* in, const float* weight, const float* bias, const float* add, float* out,
                                 int B, int H, int W, int Cin, int Cout, int ksize, int stride, int pad, int relu,
                                 int out_padded, const int* n_active, memhip_stream_t stream) {
-  MEMHIP_REQUIRE(B >= 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0, "conv2d_f32: bad shape");
-  if (B == 0) return MEMHIP_OK;
-  MEMHIP_REQUIRE(in && weight && out, "conv2d_f32: null pointer");
-  MEMHIP_REQUIRE(ksize >= 1 && ksize <= 4 && stride >= 1 && pad >= 0 && pad <= 1,
-                 "conv2d_f32: kernel size 1..4, padding 0 or 1 (one-pixel border layout)");
-  MEMHIP_REQUIRE(Cin % 4 == 0 && Cout % 4 == 0, "conv2d_f32: C_in and C_out must be multiples of 4");
+  const ConvFlags f = {add != nullptr, false, out_padded != 0, n_active != nullptr};
+  ConvGeom g;
+  if (int rc = conv_validate(MEMHIP_CONV_F32, B, H, W, Cin, Cout, ksize, stride, pad, f, in && weight && out, &g)) return rc;
+  const ConvPlan plan = conv_plan(MEMHIP_CONV_F32, g, f, ConvOptions{0}, 0);
+  if (!plan.count) return MEMHIP_OK;
   ConvArgsF32 p;
   p.in = in; p.w = weight; p.bias = bias; p.add = add; p.out = out;
-  p.B = B; p.Hp = H + 2; p.Wp = W + 2; p.Cin = Cin;
-  p.Ho = (H + 2 * pad - ksize) / stride + 1; p.Wo = (W + 2 * pad - ksize) / stride + 1;
-  p.Cout = Cout; p.kw = ksize; p.stride = stride; p.off = 1 - pad; p.K = ksize * ksize * Cin;
+  fill_geom(p, g);
   p.out_padded = out_padded; p.relu = relu; p.n_active = n_active;
-  p.dyn_lo = 0; p.dyn_hi = 1 << 30;
-  MEMHIP_REQUIRE(p.Ho > 0 && p.Wo > 0, "conv2d_f32: empty output");
-  MEMHIP_REQUIRE(p.K % BK == 0, "conv2d_f32: K = %d must be a multiple of %d", p.K, BK);
-  const long long M = (long long)B * p.Ho * p.Wo;
-  MEMHIP_REQUIRE(M < (1LL << 31), "conv2d_f32: too many output pixels");
-  const size_t lds = 2 * kStageFloats * sizeof(float);
-  static bool attr_done = false;
-  if (!attr_done) {
-    MEMHIP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_gemm_f32_kernel),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    attr_done = true;
+  for (int i = 0; i < plan.count; ++i) {
+    const ConvLaunch& l = plan.l[i];
+    p.dyn_lo = l.dyn_lo; p.dyn_hi = l.dyn_hi;
+    const int rc = l.kernel == MEMHIP_CONV_K_F32_M32 ? conv_launch<conv_gemm_f32_m32_kernel>(l, as_stream(stream), p)
+                                                     : conv_launch<conv_gemm_f32_kernel>(l, as_stream(stream), p);
+    if (rc) return rc;
   }
-  if (n_active) {
-    // dynamic batch: BOTH tile forms are launched with fixed grids of persistent workgroups; the device-side count selects
-    // one (fewer than kDynSwitch live samples: 32-row tiles, a layer is otherwise one under-filled round of 128-row tiles;
-    // from kDynSwitch on: the 128-row tiles at their better rate per FLOP).  The other launch returns at its first instruction.
-    // (per layer: the 128-row form pays once its live tiles fill the chip's 2 x 256 workgroup slots -- 7 samples at the 56 x 56
-    // level, 111 at the 14 x 14 level with 384 output channels)
-    const int ntn_ = cdiv(Cout, BN), hw_ = p.Ho * p.Wo;
-    int kDynSwitch = (int)((512LL * BM + (long long)hw_ * ntn_ - 1) / ((long long)hw_ * ntn_));
-    kDynSwitch = kDynSwitch < 1 ? 1 : kDynSwitch;
-    const size_t lds_s = (size_t)2 * (SBM * PITCH + kTileFloats) * sizeof(float);
-    int grid_s = cdiv(M, SBM) * cdiv(Cout, BN);
-    grid_s = grid_s > 2048 ? 2048 : grid_s;
-    static bool attr_s = false;
-    if (!attr_s) {
-      MEMHIP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_gemm_f32_m32_kernel),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_s));
-      attr_s = true;
-    }
-    p.dyn_lo = 0; p.dyn_hi = kDynSwitch;
-    hipLaunchKernelGGL(conv_gemm_f32_m32_kernel, dim3(grid_s), dim3(kThreads), lds_s, as_stream(stream), p);
-    int grid_b = cdiv(M, BM) * cdiv(Cout, BN);
-    grid_b = grid_b > 1024 ? 1024 : grid_b;
-    p.dyn_lo = kDynSwitch; p.dyn_hi = 1 << 30;
-    hipLaunchKernelGGL(conv_gemm_f32_kernel, dim3(grid_b), dim3(kThreads), lds, as_stream(stream), p);
-    return check_launch("conv2d_nhwc_f32(dyn)");
-  }
-  const int grid = cdiv(M, BM) * cdiv(Cout, BN);
-  hipLaunchKernelGGL(conv_gemm_f32_kernel, dim3(grid), dim3(kThreads), lds, as_stream(stream), p);
-  return check_launch("conv2d_nhwc_f32");
+  return check_launch(n_active ? "conv2d_nhwc_f32(dyn)" : "conv2d_nhwc_f32");
 }
 
 extern "C" int memhip_conv2d_nhwc_f32(const float* in, const float* weight, const float* bias, const float* add, float* out,

@@ -722,6 +722,47 @@ def nchw_to_padded_nhwc4_f16x2(x, out2, mean=None, std=None):
           "nchw_to_padded_nhwc4_f16x2")
 
 
+# ---------------------------------------------------------------- the dispatch of the tokenizer convolutions (csrc/conv_plan.cpp)
+CONV_MODES = ("bf16", "fp32", "fp16x2")                  # MEMHIP_CONV_*; the precisions of HipTokenizer
+# kernel names of ConvLaunch.kernel (MEMHIP_CONV_K_*), as they appear in a kernel trace
+CONV_KERNELS = ("conv_gemm_kernel", "conv_gemm_f32_kernel", "conv_gemm_f32_m32_kernel", "conv_gemm_f16x2_kernel<4>",
+                "conv_gemm_f16x2_kernel<8>", "conv_gemm_f16x2_wide_kernel", "conv_gemm_f16x2_first_kernel")
+
+
+class ConvLaunch(C.Structure):
+    """== memhip_conv_launch_t."""
+    _fields_ = [(n, i32) for n in ("kernel", "grid", "block", "lds", "dyn_lo", "dyn_hi")]
+
+    @property
+    def name(self):
+        return CONV_KERNELS[self.kernel]
+
+
+class ConvPlan(C.Structure):
+    """== memhip_conv_plan_t."""
+    _fields_ = [(n, i32) for n in ("Hp", "Wp", "Ho", "Wo", "K", "off")] + [("M", i64), ("count", i32), ("l", ConvLaunch * 2)]
+
+    @property
+    def launches(self):
+        """[(kernel name, grid, workgroup size, dynamic LDS bytes, dyn_lo, dyn_hi)], in launch order."""
+        return [(l.name, l.grid, l.block, l.lds, l.dyn_lo, l.dyn_hi) for l in self.l[:self.count]]
+
+
+declare({"memhip_conv_plan": (i32, [i32] * 14 + [C.POINTER(ConvPlan)])})
+
+
+def conv_plan(mode, B, H, W, Cin, Cout, ksize, stride, pad, add=False, out_f32=False, out_padded=True, dynamic=False,
+              device_cus=None):
+    """The ConvPlan of conv2d_nhwc (mode "bf16" / "fp32"; dynamic: with n_active) or conv2d_nhwc_f16x2 (mode "fp16x2") for this
+    layer under the current `conv_waves` option: geometry and `.launches`.  Validates like the call (fp16x2: out_f32 goes with out_padded=False, the dense logit matrix).  Nothing is launched; no
+    device is needed when device_cus is given (default: the library asks the current device)."""
+    plan = ConvPlan()
+    check(lib.memhip_conv_plan(CONV_MODES.index(mode), B, H, W, Cin, Cout, ksize, stride, pad, int(add), int(out_f32),
+                               int(out_padded), int(dynamic), -1 if device_cus is None else device_cus,
+                               C.byref(plan)), "conv_plan")
+    return plan
+
+
 # ---------------------------------------------------------------- finetuning recipe (csrc/finetune_recipe.hip)
 declare({
     "memhip_mixup": (i32, [vp, i32, i32, i32, i32, vp, vp, vp, vp, vp]),

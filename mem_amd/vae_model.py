@@ -4,6 +4,8 @@ mem/engine_for_pretraining.py:144).  SURVEY.md section 8 row a22 / f1: v1 runs t
 through stock PyTorch-ROCm (MIOpen convs); a hand-written implicit-GEMM version is the next row.
 Same module tree => same state-dict keys as the reference checkpoints ('hparams' / 'weights').
 Training the dVAE (gumbel-softmax path, losses) is a different stage and not provided."""
+from typing import NamedTuple, Optional
+
 import torch
 from torch import nn
 
@@ -72,6 +74,21 @@ class DiscreteVAE(nn.Module):
         return self.decoder(emb.transpose(1, 2).reshape(b, d, h, w))
 
 
+class ConvLayer(NamedTuple):
+    """One packed convolution of the encoder: weight [Cout, k*k*cin] ((ky, kx, c)-major; fp16x2: two planes), fp32 bias."""
+    w: torch.Tensor
+    b: Optional[torch.Tensor]
+    cin: int
+    cout: int
+    k: int
+    stride: int
+    pad: int
+
+    def out_hw(self, h, w):
+        """Output size of this convolution on an h x w input -- the one place that computes it."""
+        return (h + 2 * self.pad - self.k) // self.stride + 1, (w + 2 * self.pad - self.k) // self.stride + 1
+
+
 class HipTokenizer:
     """`DiscreteVAE.get_codebook_indices` on the hand-written HIP path: NHWC activations with a one-pixel zero
     border, implicit-GEMM convolutions on MFMA tiles with fused bias / ReLU / residual, argmax over the token logits.
@@ -118,6 +135,12 @@ class HipTokenizer:
         self._exact = None
         self.dt = {"fp32": torch.float32, "bf16": torch.bfloat16, "fp16x2": torch.float16}[precision]
         self.planes = 2 if precision == "fp16x2" else 1
+        # the convolution and the input conversion of this precision, chosen once; the two conv callables spell the residual
+        # keyword differently (ops.conv2d_nhwc: add, ops.conv2d_nhwc_f16x2: add2)
+        if self.planes == 2:
+            self._conv, self._add_kw, self._to_nhwc = ops.conv2d_nhwc_f16x2, "add2", ops.nchw_to_padded_nhwc4_f16x2
+        else:
+            self._conv, self._add_kw, self._to_nhwc = ops.conv2d_nhwc, "add", ops.nchw_to_padded_nhwc4
         dev = next(vae.parameters()).device
         assert dev.type == "cuda", "HipTokenizer needs the model on the GPU"
         self.dev, self.H, self.W = dev, vae.input_H, vae.input_W
@@ -126,20 +149,18 @@ class HipTokenizer:
         if vae.normalization is not None:
             m, s = (torch.as_tensor(t, dtype=torch.float32, device=dev).contiguous() for t in vae.normalization)
             self.norm = (m, s)
-        self.layers = []                                   # (kind, weight, bias, Cin, Cout, k, stride, pad, relu)
-        mods = list(vae.encoder)
+        # the encoder in order: ("conv", ConvLayer) = strided conv + ReLU, ("res", (ConvLayer,) * 3) = ResBlock, ("head", ConvLayer)
+        self.layers = []
         self.cin0 = None
-        for m in mods:
+        for m in vae.encoder:
             if isinstance(m, nn.Sequential):               # Conv2d(4, s2, p1) + ReLU
-                conv = m[0]
-                self.layers.append(("conv",) + self._pack(conv) + (True,))
+                self.layers.append(("conv", self._pack(m[0])))
                 if self.cin0 is None:
-                    self.cin0 = conv.in_channels
+                    self.cin0 = m[0].in_channels
             elif isinstance(m, ResBlock):
-                c1, c2, c3 = m.net[0], m.net[2], m.net[4]
-                self.layers.append(("res", self._pack(c1), self._pack(c2), self._pack(c3)))
+                self.layers.append(("res", tuple(self._pack(m.net[i]) for i in (0, 2, 4))))
             else:                                          # final Conv2d(hidden, num_tokens, 1)
-                self.layers.append(("head",) + self._pack(m) + (False,))
+                self.layers.append(("head", self._pack(m)))
         assert self.cin0 is not None and self.cin0 <= 4, "first layer must have <= 4 input channels"
         self.max_batch = 0
         self.kappa = float(kappa) if kappa is not None else self.CERT_KAPPA
@@ -164,7 +185,7 @@ class HipTokenizer:
         M = n * self.hw_out[0] * self.hw_out[1]
         certify, self.certify = self.certify, False
         try:
-            self._forward_f16x2(images, n)
+            self.get_codebook_indices(images)
         finally:
             self.certify = certify
         ex.get_codebook_indices(images)
@@ -187,7 +208,7 @@ class HipTokenizer:
         else:
             wp = wp.to(self.dt).contiguous()
         b = conv.bias.detach().float().contiguous() if conv.bias is not None else None
-        return (wp, b, ci, co, k, conv.stride[0], conv.padding[0])
+        return ConvLayer(wp, b, ci, co, k, conv.stride[0], conv.padding[0])
 
     def _alloc(self, B):
         """Zero-bordered activation buffers for batch B (allocated once; only interiors are written)."""
@@ -200,19 +221,15 @@ class HipTokenizer:
         self.x0 = torch.zeros(pl + (B, H + 2, W + 2, 4), dtype=bf, device=dev)
         self.bufs = {}
         h, w = H, W
-        for L in self.layers:
-            if L[0] == "conv":
-                _, wp, b, ci, co, k, s, p, _ = L
-                h, w = (h + 2 * p - k) // s + 1, (w + 2 * p - k) // s + 1
-                key = (h, w, co)
-                if key not in self.bufs:                  # one buffer per strided level; the ResBlocks' level gets 3 below
-                    self.bufs[key] = [torch.zeros(pl + (B, h + 2, w + 2, co), dtype=bf, device=dev)]
-            elif L[0] == "res":
-                key = (h, w, L[1][3])
-                if key not in self.bufs:
-                    self.bufs[key] = [torch.zeros(pl + (B, h + 2, w + 2, L[1][3]), dtype=bf, device=dev) for _ in range(3)]
-                while len(self.bufs[key]) < 3:
-                    self.bufs[key].append(torch.zeros_like(self.bufs[key][0]))
+        for kind, L in self.layers:                       # one buffer per strided level; the ResBlocks' level gets 3
+            if kind == "head":
+                continue
+            if kind == "conv":
+                h, w = L.out_hw(h, w)
+            cout = L.cout if kind == "conv" else L[0].cout
+            pool = self.bufs.setdefault((h, w, cout), [])
+            while len(pool) < (1 if kind == "conv" else 3):
+                pool.append(torch.zeros(pl + (B, h + 2, w + 2, cout), dtype=bf, device=dev))
         self.hw_out = (h, w)
         lt = torch.float32 if self.precision in ("fp32", "fp16x2") else bf
         self.logits = torch.empty((B * h * w, self.num_tokens), dtype=lt, device=dev)
@@ -231,6 +248,32 @@ class HipTokenizer:
             if self._exact is None or self._exact.max_batch < R:
                 self._exact = HipTokenizer(self._vae, max_batch=R, precision="fp32")
 
+    def _walk(self, n, **kw):
+        """The encoder from self.x0 to self.logits on `n` samples (the batch, or the capacity of a dynamic-batch call); kw goes
+        to every convolution (n_active).  Owns the ResBlock buffer rotation: t1, t2 = the first pool buffers that are not
+        the block's input.  Returns the output size (h, w)."""
+        conv = self._conv
+        cur, h, w = self.x0, self.H, self.W
+        for kind, L in self.layers:
+            if kind == "conv":
+                ho, wo = L.out_hw(h, w)
+                out = self.bufs[(ho, wo, L.cout)][0]
+                conv(cur, L.w, L.b, out, n, h, w, L.cin, L.cout, L.k, L.stride, L.pad, relu=True, **kw)
+                cur, h, w = out, ho, wo
+            elif kind == "res":
+                c1, c2, c3 = L
+                pool = self.bufs[(h, w, c1.cout)]
+                t1 = next(t for t in pool if t is not cur)
+                t2 = next(t for t in pool if t is not cur and t is not t1)
+                conv(cur, c1.w, c1.b, t1, n, h, w, c1.cin, c1.cout, c1.k, c1.stride, c1.pad, relu=True, **kw)
+                conv(t1, c2.w, c2.b, t2, n, h, w, c2.cin, c2.cout, c2.k, c2.stride, c2.pad, relu=True, **kw)
+                conv(t2, c3.w, c3.b, t1, n, h, w, c3.cin, c3.cout, c3.k, c3.stride, c3.pad, relu=False,
+                     **{self._add_kw: cur}, **kw)                                                     # net(x) + x
+                cur = t1
+            else:
+                conv(cur, L.w, L.b, self.logits, n, h, w, L.cin, L.cout, L.k, L.stride, L.pad, relu=False, out_padded=False, **kw)
+        return h, w
+
     @torch.no_grad()
     def get_codebook_indices(self, images):
         """images f32 [B, C, H, W] on the GPU -> i64 [B, h*w] token ids."""
@@ -239,63 +282,13 @@ class HipTokenizer:
         images = images.contiguous()
         B = images.shape[0]
         self._alloc(B)
-        if self.planes == 2:
-            return self._forward_f16x2(images, B)
-        ops.nchw_to_padded_nhwc4(images, self.x0, *(self.norm or (None, None)))
-        cur, h, w = self.x0, self.H, self.W
-        for L in self.layers:
-            if L[0] == "conv":
-                _, wp, b, ci, co, k, s, p, relu = L
-                ho, wo = (h + 2 * p - k) // s + 1, (w + 2 * p - k) // s + 1
-                out = self.bufs[(ho, wo, co)][0]
-                ops.conv2d_nhwc(cur, wp, b, out, B, h, w, ci, co, k, s, p, relu=relu)
-                cur, h, w = out, ho, wo
-            elif L[0] == "res":
-                (w1, b1, ci, co, k1, s1, p1), (w2, b2, _, _, k2, s2, p2), (w3, b3, _, _, k3, s3, p3) = L[1], L[2], L[3]
-                pool = self.bufs[(h, w, co)]
-                t1 = next(t for t in pool if t is not cur)
-                t2 = next(t for t in pool if t is not cur and t is not t1)
-                ops.conv2d_nhwc(cur, w1, b1, t1, B, h, w, ci, co, k1, s1, p1, relu=True)
-                ops.conv2d_nhwc(t1, w2, b2, t2, B, h, w, co, co, k2, s2, p2, relu=True)
-                ops.conv2d_nhwc(t2, w3, b3, t1, B, h, w, co, co, k3, s3, p3, relu=False, add=cur)   # net(x) + x
-                cur = t1
-            else:
-                _, wp, b, ci, co, k, s, p, _ = L
-                ops.conv2d_nhwc(cur, wp, b, self.logits, B, h, w, ci, co, k, s, p, relu=False, out_padded=False)
-        M = B * h * w
-        ops.argmax_rows(self.logits, M, self.num_tokens, self.ids, self.gap)
-        return self.ids[:M].view(B, h * w).clone()
-
-    def _forward_f16x2(self, images, B):
-        ops = self.ops
-        conv = ops.conv2d_nhwc_f16x2
-        ops.nchw_to_padded_nhwc4_f16x2(images, self.x0, *(self.norm or (None, None)))
-        cur, h, w = self.x0, self.H, self.W
-        for L in self.layers:
-            if L[0] == "conv":
-                _, wp, b, ci, co, k, s, p, relu = L
-                ho, wo = (h + 2 * p - k) // s + 1, (w + 2 * p - k) // s + 1
-                out = self.bufs[(ho, wo, co)][0]
-                conv(cur, wp, b, out, B, h, w, ci, co, k, s, p, relu=relu)
-                cur, h, w = out, ho, wo
-            elif L[0] == "res":
-                (w1, b1, ci, co, k1, s1, p1), (w2, b2, _, _, k2, s2, p2), (w3, b3, _, _, k3, s3, p3) = L[1], L[2], L[3]
-                pool = self.bufs[(h, w, co)]
-                t1 = next(t for t in pool if t is not cur)
-                t2 = next(t for t in pool if t is not cur and t is not t1)
-                conv(cur, w1, b1, t1, B, h, w, ci, co, k1, s1, p1, relu=True)
-                conv(t1, w2, b2, t2, B, h, w, co, co, k2, s2, p2, relu=True)
-                conv(t2, w3, b3, t1, B, h, w, co, co, k3, s3, p3, relu=False, add2=cur)             # net(x) + x
-                cur = t1
-            else:
-                _, wp, b, ci, co, k, s, p, _ = L
-                conv(cur, wp, b, self.logits, B, h, w, ci, co, k, s, p, relu=False, out_padded=False)
-        M = B * h * w
+        self._to_nhwc(images, self.x0, *(self.norm or (None, None)))
+        h, w = self._walk(B)
+        M, hw = B * h * w, h * w
         if not self.certify:
             ops.argmax_rows(self.logits, M, self.num_tokens, self.ids, self.gap)
-            return self.ids[:M].view(B, h * w).clone()
+            return self.ids[:M].view(B, hw).clone()
         # ---- certification: margins on the device, flagged samples recomputed in fp32 (no host synchronisation)
-        hw = h * w
         ops.argmax_rows(self.logits, M, self.num_tokens, self.ids, self.gap, rms=self.rms)
         ops.tok_flag_samples(self.gap, self.rms, B, hw, self.kappa, self.flag_list, self.flag_count, self.cert_stats)
         ex = self._exact
@@ -303,7 +296,7 @@ class HipTokenizer:
         for off in range(0, B, R):                   # ceil(B / R) rounds cover ANY number of flagged samples
             ex._forward_dyn(images, self.norm, self.flag_list, self.flag_count, off, self.n_round)
             ops.tok_scatter_ids(ex.ids, self.flag_list, self.n_round, off, R, hw, self.ids)
-        out = self.ids[:M].view(B, h * w).clone()
+        out = self.ids[:M].view(B, hw).clone()
         # run-time audit of the certification claim: one sample of every audit_every-th call is recomputed by the fp32 kernels
         # (whether it was flagged or not) and label mismatches are counted on the device -- no host synchronisation
         self._calls += 1
@@ -321,26 +314,7 @@ class HipTokenizer:
         assert self.precision == "fp32"
         R = self.max_batch
         ops.tok_gather_images(images, norm[0] if norm else None, norm[1] if norm else None, lst, count, off, R, self.x0, n_round)
-        cur, h, w = self.x0, self.H, self.W
-        for L in self.layers:
-            if L[0] == "conv":
-                _, wp, b, ci, co, k, s, p, relu = L
-                ho, wo = (h + 2 * p - k) // s + 1, (w + 2 * p - k) // s + 1
-                out = self.bufs[(ho, wo, co)][0]
-                ops.conv2d_nhwc(cur, wp, b, out, R, h, w, ci, co, k, s, p, relu=relu, n_active=n_round)
-                cur, h, w = out, ho, wo
-            elif L[0] == "res":
-                (w1, b1, ci, co, k1, s1, p1), (w2, b2, _, _, k2, s2, p2), (w3, b3, _, _, k3, s3, p3) = L[1], L[2], L[3]
-                pool = self.bufs[(h, w, co)]
-                t1 = next(t for t in pool if t is not cur)
-                t2 = next(t for t in pool if t is not cur and t is not t1)
-                ops.conv2d_nhwc(cur, w1, b1, t1, R, h, w, ci, co, k1, s1, p1, relu=True, n_active=n_round)
-                ops.conv2d_nhwc(t1, w2, b2, t2, R, h, w, co, co, k2, s2, p2, relu=True, n_active=n_round)
-                ops.conv2d_nhwc(t2, w3, b3, t1, R, h, w, co, co, k3, s3, p3, relu=False, add=cur, n_active=n_round)
-                cur = t1
-            else:
-                _, wp, b, ci, co, k, s, p, _ = L
-                ops.conv2d_nhwc(cur, wp, b, self.logits, R, h, w, ci, co, k, s, p, relu=False, out_padded=False, n_active=n_round)
+        h, w = self._walk(R, n_active=n_round)
         ops.argmax_rows(self.logits, R * h * w, self.num_tokens, self.ids, self.gap, n_samples=n_round, rows_per_sample=h * w)
 
     def certification_stats(self):

@@ -93,6 +93,17 @@ def test_conv_f32_layers_vs_torch(k, s, p, cin, cout, h):
     ops.conv2d_nhwc(xp, wp, None, dense, B, h, h, cin, cout, k, s, p, relu=False, out_padded=False)
     want = ref - b.double().view(1, -1, 1, 1)
     assert (dense.view(B, ho, ho, cout).permute(0, 3, 1, 2).double() - want).abs().max().item() <= tol
+    if (k, s, p, cin, cout, h) == (1, 1, 0, 64, 256, 14):
+        # dynamic batch: capacity 3, two live samples.  The plan names both tile forms, their live-count ranges partition
+        # [0, 2^30); the live samples equal the static result bit for bit, the slot behind them is not written
+        plan = ops.conv_plan("fp32", B, h, h, cin, cout, k, s, p, out_padded=False, dynamic=True)
+        (n0, _, _, _, lo0, hi0), (n1, _, _, _, lo1, hi1) = plan.launches
+        assert (n0, n1) == ("conv_gemm_f32_m32_kernel", "conv_gemm_f32_kernel") and lo0 == 0 and hi0 == lo1 and hi1 == 1 << 30
+        assert lo0 <= 2 < hi0                                                   # two live samples: the 32-row form works
+        dyn = torch.full_like(dense, 7.0)
+        ops.conv2d_nhwc(xp, wp, None, dyn, B, h, h, cin, cout, k, s, p, relu=False, out_padded=False,
+                        n_active=torch.tensor([2], dtype=torch.int32, device="cuda"))
+        assert torch.equal(dyn[: 2 * ho * ho], dense[: 2 * ho * ho]) and (dyn[2 * ho * ho:] == 7.0).all()
 
 
 def test_argmax_rows_f32_first_maximum_and_gap():
@@ -241,6 +252,11 @@ def test_tokenizer_fp16x2_mode():
         tok = HipTokenizer(m, max_batch=B, precision="fp16x2")
         ids = tok.get_codebook_indices(img.cuda()).cpu().numpy()
         assert np.array_equal(ids, g["ids"]), fix
+        if cfg is BASE_VAE:                      # its first layer (whole tiles at B = 2) runs on the persistent first-layer kernel
+            first = tok.layers[0][1]
+            assert (tok.H, tok.W, first.cin, first.cout) == (224, 224, 4, 384)
+            plan = ops.conv_plan("fp16x2", B, 224, 224, 4, 384, first.k, first.stride, first.pad)
+            assert [l[0] for l in plan.launches] == ["conv_gemm_f16x2_first_kernel"]
         lg2 = tok.logits.clone()
         tok32 = HipTokenizer(m, max_batch=B)
         tok32.get_codebook_indices(img.cuda())
@@ -338,6 +354,9 @@ def test_fp16x2_wide_tile_equals_the_128_tile_bit_for_bit():
         outs = {}
         for w in (8, 32):
             _lib.set_option("conv_waves", w)
+            # what the option selects for this ragged layer (588 rows, 192 channels): the plan names it
+            plan = ops.conv_plan("fp16x2", Bn, h, h, cin, cout, k, s, p)
+            assert [l[0] for l in plan.launches] == [{8: "conv_gemm_f16x2_kernel<8>", 32: "conv_gemm_f16x2_wide_kernel"}[w]]
             dense = torch.full((Bn * h * h, cout), 7.0, device="cuda")
             ops.conv2d_nhwc_f16x2(x2, w2, b, dense, Bn, h, h, cin, cout, k, s, p, relu=False, out_padded=False)
             o_relu = torch.zeros(2, Bn, h + 2, h + 2, cout, dtype=torch.float16, device="cuda")

@@ -10,7 +10,11 @@ The MAE engines (second section) launch on one stream and issue plain torch ops 
 fp32 buffer, zero_ / add_ on the padded-head gradients): there every in-place or out= ATen call is recorded as well, as
 "aten.<op>" with the same tensor description, through a TorchDispatchMode around the step.
 
-    python tools/engine_launch_trace.py OUT.txt [vit|mae]    # needs the GPU; prints the line count per scenario
+The tokenizer (third section, `tok`) is traced through HipTokenizer's public calls only, construction included; every
+scenario ends with a line holding the SHA-256 of the bytes of its ids and logits (the kernels use no atomics: the hashes are
+reproducible, and equal between two checkouts that compute the same).
+
+    python tools/engine_launch_trace.py OUT.txt [vit|mae|tok]    # needs the GPU; prints the line count per scenario
 """
 import ctypes
 import inspect
@@ -190,7 +194,32 @@ def mae_section(out):
              "bf16", imgs, noise)
 
 
+def tok_section(out):
+    """HipTokenizer on the tiny tokenizer config at B = 6, every precision: fp32, bf16, fp16x2 raw, fp16x2 certified with a kappa
+    that flags every sample and a recompute capacity of 4 (two dynamic-batch rounds), and one audited call."""
+    import hashlib
+    from mem_amd.vae_model import DiscreteVAE, HipTokenizer
+    from oracle.vae_ref import TINY_VAE, fill_vae_by_name, vae_inputs
+    B = 6
+    m = DiscreteVAE(**TINY_VAE).eval()
+    m.load_state_dict(fill_vae_by_name(m.state_dict(), seed=0))
+    m = m.cuda()
+    img = vae_inputs(TINY_VAE, B, 11).cuda()
+    sha = lambda t: hashlib.sha256(t.contiguous().view(torch.uint8).cpu().numpy().tobytes()).hexdigest()   # noqa: E731
+    for name, kw in (("fp32", {}), ("bf16", dict(precision="bf16")), ("fp16x2 raw", dict(precision="fp16x2", certify=False)),
+                     ("fp16x2 certified, every sample flagged", dict(precision="fp16x2", kappa=1e9, exact_capacity=4, audit_every=0)),
+                     ("fp16x2 audited", dict(precision="fp16x2", audit_every=1))):
+        ENG[0], LINES[:] = None, []
+        tok = HipTokenizer(m, max_batch=B, **kw)
+        tok.get_codebook_indices(img)
+        torch.cuda.synchronize()
+        M = B * tok.hw_out[0] * tok.hw_out[1]
+        LINES.append(f"sha256 ids={sha(tok.ids[:M])} logits={sha(tok.logits[:M])}")
+        out.write(f"## tok {name} {kw}: {len(LINES)} lines\n" + "\n".join(LINES) + "\n")
+        print(f"{len(LINES):5d}  tok {name}")
+
+
 if __name__ == "__main__":
     with open(sys.argv[1], "w") as out:
-        for section in (sys.argv[2:] or ["vit", "mae"]):
-            {"vit": vit_section, "mae": mae_section}[section](out)
+        for section in (sys.argv[2:] or ["vit", "mae", "tok"]):
+            {"vit": vit_section, "mae": mae_section, "tok": tok_section}[section](out)
