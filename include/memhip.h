@@ -36,7 +36,7 @@ extern "C" {
 #endif
 
 #define MEMHIP_ABI_VERSION 7   /* 7: the finetuning recipe (memhip_mixup, memhip_mix_targets, memhip_ce_soft, memhip_ema_update), and -- additive, no
-                                  existing signature changed, so the number stays -- memhip_pool_tokens / memhip_pool_tokens_bwd, memhip_gemm_bf16_nt_plan, memhip_tokens_to_maps / memhip_maps_to_tokens_add, memhip_conv_plan; 6: element-wise dropout (memhip_dropout_t, epilogue RESIDUAL_DROP, memhip_gemm_args_t.dropout, the
+                                  existing signature changed, so the number stays -- memhip_pool_tokens / memhip_pool_tokens_bwd, memhip_gemm_bf16_nt_plan, memhip_tokens_to_maps / memhip_maps_to_tokens_add, memhip_conv_plan, memhip_gemm_bf16_tn_plan / memhip_gemm_bf16_tn_plan_workspace; 6: element-wise dropout (memhip_dropout_t, epilogue RESIDUAL_DROP, memhip_gemm_args_t.dropout, the
                                   *_drop row kernels); 5 (round 6): memhip_build_flags, memhip_attn_bwd_ws / _out_ws / _workspace; 4 (round 5): epilogues 6 / 7 carry the stored GELU derivative as FP16 (since round 4), certified-tokenizer entry points */
 
 #define MEMHIP_OK 0
@@ -400,13 +400,14 @@ int memhip_gemm_bf16_tn_ws(const void* A, int64_t lda, const void* B, int64_t ld
                            float* out, int64_t ldo, int accumulate, void* workspace, size_t workspace_bytes,
                            memhip_stream_t stream);
 /* The weight gradients of up to 4 Linear layers whose operands are ready at the same time (fc2 + fc1, proj + qkv of a
- * Block: mem/modeling_finetune.py:160-189 backward) as ONE launch: the products share one grid and one split count (the fewest rounds of workgroups that keep >= 80 % of the CUs busy), so a
- * small product (768 x 768: 9 tiles) runs with the 7 row slices of its neighbour instead of the 28 it needs alone to fill
- * the chip, and the group has one reduction pass.  Each product has the contract of memhip_gemm_bf16_tn_ws (fixed sum order:
- * run-to-run deterministic; the order differs from the single call's, so the two agree to fp32 rounding, not bitwise).
- * workspace: memhip_gemm_bf16_tn_group_workspace(problems, count) bytes (also >= what each product needs alone).  When the
- * group cannot run as one grid (count == 1, a shape outside the 256 x 256 tile kernel, workspace too small, option
- * "tn_group" = 0) the products are computed one after the other by memhip_gemm_bf16_tn_ws -- same results contract. */
+ * Block: mem/modeling_finetune.py:160-189 backward) as ONE launch: the products share one grid and one common count of row
+ * slices, so a small product (768 x 768: 9 tiles) runs with the 7 row slices of its neighbour instead of the 27 it plans
+ * alone to fill the chip, and the group has one reduction pass.  Each product has the contract of memhip_gemm_bf16_tn_ws
+ * (fixed sum order: run-to-run deterministic; the order differs from the single call's, so the two agree to fp32 rounding,
+ * not bitwise).  workspace: memhip_gemm_bf16_tn_group_workspace(problems, count) bytes (also >= what each product needs
+ * alone).  Whether a group runs as one grid is decided by tn_plan (mem_amd/csrc/gemm_tn_plan.cpp; memhip_gemm_bf16_tn_plan
+ * shows the decision); a group that does not is computed product by product, each exactly as memhip_gemm_bf16_tn_ws would
+ * -- same results contract. */
 typedef struct memhip_tn_problem {
   const void* A; int64_t lda;       /* dY  bf16 [R, N] */
   const void* B; int64_t ldb;       /* X   bf16 [R, K] */
@@ -417,6 +418,37 @@ typedef struct memhip_tn_problem {
 size_t memhip_gemm_bf16_tn_group_workspace(const memhip_tn_problem_t* problems, int count);
 int memhip_gemm_bf16_tn_group(const memhip_tn_problem_t* problems, int count, int accumulate, void* workspace,
                               size_t workspace_bytes, memhip_stream_t stream);
+
+/* The dispatch of memhip_gemm_bf16_tn / _tn_ws / _tn_group as data (additive to ABI 7): the ordered launches with their row
+ * slices, grids and workspace layout.  memhip_gemm_bf16_tn_plan validates `problems` like memhip_gemm_bf16_tn_group (a single
+ * call is a group of one) and plans with the current option values for a stream of stream_cus usable CUs (>= 0: no device
+ * is needed; < 0: what the default stream has on the current device).  Nothing is launched; of the pointers only the address
+ * bits are read (null, 16-byte alignment).  Products with R == 0 appear in no launch. */
+#define MEMHIP_TN_128 0        /* gemm_tn_kernel: 128x128 tiles, row slices added with atomics (one slice, overwrite: plain stores) */
+#define MEMHIP_TN_P8_ATOMIC 1  /* gemm_tn_p8_kernel<false>: 256x256 tiles, row slices added with atomics */
+#define MEMHIP_TN_P8_WS 2      /* gemm_tn_p8_kernel<true> + tn_reduce_kernel: slices stored to the workspace, then summed */
+#define MEMHIP_TN_P8_GROUP 3   /* gemm_tn_p8_group_kernel + tn_reduce_group_kernel: several products, one grid */
+typedef struct memhip_tn_part {   /* one product inside a launch */
+  int32_t problem;                /* index into `problems` */
+  int32_t tiles, splits, rows_per_split;   /* the product runs tiles * splits workgroups; slice s takes rows [s, s + 1) * rows_per_split */
+  int32_t wg_begin, quad_begin;   /* group: first workgroup id of the product, first float4 of it in the reduction pass */
+  int64_t ws_offset;              /* floats: where the product's slabs [splits][N][K] start in the workspace */
+} memhip_tn_part_t;
+typedef struct memhip_tn_launch {
+  int32_t kind;                   /* MEMHIP_TN_* */
+  int32_t count;                  /* products covered (1 unless MEMHIP_TN_P8_GROUP) */
+  int32_t grid, reduce_grid;      /* workgroups of the main kernel and of the reduction pass (0: none) */
+  int32_t memset_first;           /* `out` is cleared in front of the launch */
+  int32_t use_atomics;            /* the main kernel adds into `out` with atomics */
+  int64_t ws_bytes;               /* workspace bytes the launch uses (0: none) */
+  memhip_tn_part_t p[4];
+} memhip_tn_launch_t;
+typedef struct memhip_tn_plan { int32_t count; int32_t reserved0; memhip_tn_launch_t l[4]; } memhip_tn_plan_t;
+int memhip_gemm_bf16_tn_plan(const memhip_tn_problem_t* problems, int count, int accumulate, const void* workspace,
+                             size_t workspace_bytes, int stream_cus, memhip_tn_plan_t* out_plan);
+/* memhip_gemm_bf16_tn_group_workspace as it answers on a device of device_cus CUs (count == 1: memhip_gemm_bf16_tn_workspace
+ * of that shape); needs no device. */
+size_t memhip_gemm_bf16_tn_plan_workspace(const memhip_tn_problem_t* problems, int count, int device_cus);
 /* out f32 [C] += column sums of in bf16 [R, C]  (Linear bias gradients = grad_output.sum(0)) */
 int memhip_colsum_bf16(const void* in, int64_t ld, int R, int C, float* out, memhip_stream_t stream);
 /* out[n] += sum_k ws[k * N + n] for the `copies` accumulator copies a GEMM with colsum_copies > 1 filled; the copies

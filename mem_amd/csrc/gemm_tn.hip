@@ -16,12 +16,13 @@
 // split-K: S slices of the token range per output tile, combined with fp32 atomics into the
 // (pre-zeroed) gradient buffer -- S is chosen so that tiles * S fills the 256 CUs.
 #include "common.h"
+#include "gemm_tn_plan.hpp"
 
 namespace {
 
 using namespace memhip;
 
-constexpr int BM = 128, BN = 128, BR = 64;       // output tile (BM x BN), reduction rows per stage
+constexpr int BM = kTn128Tile, BN = kTn128Tile, BR = kTnStageRows;   // output tile (BM x BN), reduction rows per stage
 constexpr int kThreads = 256;
 constexpr int kTileBytes = BR * 128 * 2;        // 16 KiB
 constexpr int kStageBytes = 2 * kTileBytes;
@@ -195,24 +196,66 @@ __global__ __launch_bounds__(256) void colsum_kernel(const __bf16* __restrict__ 
 }  // namespace
 
 namespace memhip {
-int gemm_tn_p8_dispatch(const void* A, long long lda, const void* B, long long ldb, int R, int N, int K, float* out,
-                        long long ldo, int accumulate, float* ws, size_t ws_bytes, hipStream_t s);
-size_t gemm_tn_p8_workspace(int R, int N, int K);
-size_t gemm_tn_p8_group_workspace(const memhip_tn_problem_t* pr, int count);
-int gemm_tn_p8_group_dispatch(const memhip_tn_problem_t* pr, int count, int accumulate, float* ws, size_t ws_bytes,
-                              hipStream_t s);
+int tn_p8_launch_atomic(const TnLaunch& l, const memhip_tn_problem_t& q, hipStream_t s);
+int tn_p8_launch_ws(const TnLaunch& l, const memhip_tn_problem_t& q, int accumulate, float* ws, hipStream_t s);
+int tn_p8_launch_group(const TnLaunch& l, const memhip_tn_problem_t* pr, int accumulate, float* ws, hipStream_t s);
 }
 
-extern "C" size_t memhip_gemm_bf16_tn_workspace(int R, int N, int K) { return memhip::gemm_tn_p8_workspace(R, N, K); }
+namespace {
 
-extern "C" int memhip_gemm_bf16_tn_ws(const void* A, int64_t lda, const void* B, int64_t ldb, int R, int N, int K,
-                                      float* out, int64_t ldo, int accumulate, void* workspace,
-                                      size_t workspace_bytes, memhip_stream_t stream);
-
-extern "C" int memhip_gemm_bf16_tn(const void* A, int64_t lda, const void* B, int64_t ldb, int R, int N, int K,
-                                   float* out, int64_t ldo, int accumulate, memhip_stream_t stream) {
-  return memhip_gemm_bf16_tn_ws(A, lda, B, ldb, R, N, K, out, ldo, accumulate, nullptr, 0, stream);
+int tn_128_launch(const TnLaunch& l, const memhip_tn_problem_t& q, hipStream_t s) {
+  if (l.memset_first)
+    MEMHIP_HIP(hipMemset2DAsync(q.out, (size_t)q.ldo * sizeof(float), 0, (size_t)q.K * sizeof(float), (size_t)q.N, s));
+  static bool attr_done = false;
+  if (!attr_done) {
+    MEMHIP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn_kernel),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, 2 * kStageBytes));
+    attr_done = true;
+  }
+  hipLaunchKernelGGL(gemm_tn_kernel, dim3(l.grid), dim3(kThreads), 2 * kStageBytes, s, (const __bf16*)q.A, (long long)q.lda,
+                     (const __bf16*)q.B, (long long)q.ldb, q.R, q.N, q.K, q.out, (long long)q.ldo, l.p[0].splits,
+                     l.p[0].rows_per_split, l.use_atomics);
+  return check_launch("gemm_bf16_tn");
 }
+
+TnPlan plan_now(const memhip_tn_problem_t* pr, int count, int accumulate, const void* ws, size_t ws_bytes, int stream_cus) {
+  const TnWorkspace w = {ws != nullptr, ((uintptr_t)ws & 15) == 0, ws_bytes};
+  return tn_plan(pr, count, accumulate, w, stream_cus, TnOptions{opt(OPT_TN_P8), opt(OPT_TN_GROUP)});
+}
+
+// validated problems: plan, then launch what the plan names
+int run(const memhip_tn_problem_t* pr, int count, int accumulate, void* ws, size_t ws_bytes, hipStream_t s) {
+  const TnPlan plan = plan_now(pr, count, accumulate, ws, ws_bytes, usable_cus(s));
+  for (int i = 0; i < plan.count; ++i) {
+    const TnLaunch& l = plan.l[i];
+    const memhip_tn_problem_t& q = pr[l.p[0].problem];
+    int rc = MEMHIP_OK;
+    switch (l.kind) {
+      case MEMHIP_TN_128: rc = tn_128_launch(l, q, s); break;
+      case MEMHIP_TN_P8_ATOMIC: rc = tn_p8_launch_atomic(l, q, s); break;
+      case MEMHIP_TN_P8_WS: rc = tn_p8_launch_ws(l, q, accumulate, (float*)ws, s); break;
+      case MEMHIP_TN_P8_GROUP: rc = tn_p8_launch_group(l, pr, accumulate, (float*)ws, s); break;
+    }
+    if (rc != MEMHIP_OK) return rc;
+  }
+  return MEMHIP_OK;
+}
+
+int validate_group(const memhip_tn_problem_t* problems, int count) {
+  MEMHIP_REQUIRE(problems && count >= 1 && count <= kTnGroupMax, "gemm_tn_group: 1..4 problems, got %d", count);
+  for (int i = 0; i < count; ++i) {
+    const memhip_tn_problem_t& q = problems[i];
+    MEMHIP_REQUIRE(q.R >= 0 && q.N > 0 && q.K > 0, "gemm_tn_group[%d]: bad shape R=%d N=%d K=%d", i, q.R, q.N, q.K);
+    MEMHIP_REQUIRE(q.R == 0 || (q.A && q.B && q.out), "gemm_tn_group[%d]: null pointer", i);
+    MEMHIP_REQUIRE(q.N % 8 == 0 && q.K % 8 == 0 && q.lda % 8 == 0 && q.ldb % 8 == 0 && ((uintptr_t)q.A & 15) == 0 &&
+                       ((uintptr_t)q.B & 15) == 0, "gemm_tn_group[%d]: operands must be 16-byte aligned, N/K/ld %% 8 == 0", i);
+  }
+  return MEMHIP_OK;
+}
+
+}  // namespace
+
+extern "C" size_t memhip_gemm_bf16_tn_workspace(int R, int N, int K) { return tn_workspace_bytes(R, N, K, max_cus()); }
 
 extern "C" int memhip_gemm_bf16_tn_ws(const void* A, int64_t lda, const void* B, int64_t ldb, int R, int N, int K,
                                       float* out, int64_t ldo, int accumulate, void* workspace,
@@ -222,69 +265,36 @@ extern "C" int memhip_gemm_bf16_tn_ws(const void* A, int64_t lda, const void* B,
   MEMHIP_REQUIRE(A && B && out, "gemm_tn: null pointer");
   MEMHIP_REQUIRE(N % 8 == 0 && K % 8 == 0 && lda % 8 == 0 && ldb % 8 == 0 && ((uintptr_t)A & 15) == 0 &&
                      ((uintptr_t)B & 15) == 0, "gemm_tn: operands must be 16-byte aligned, N/K/ld %% 8 == 0");
-  hipStream_t s = as_stream(stream);
-  const bool p8_on = opt(OPT_TN_P8) != 0;
-  if (p8_on) {
-    const int rc = gemm_tn_p8_dispatch(A, lda, B, ldb, R, N, K, out, ldo, accumulate, (float*)workspace,
-                                       workspace_bytes, s);
-    if (rc != MEMHIP_EUNSUPPORTED) return rc;
-  }
-  const int tiles = cdiv(N, BM) * cdiv(K, BN);
-  const int stages = cdiv(R, BR);
-  int splits = cdiv(768, tiles);                       // ~3 workgroups per CU
-  if (splits > stages / 4) splits = stages / 4;        // keep >= 4 stages (256 rows) per split
-  if (splits < 1) splits = 1;
-  const int rows_per_split = cdiv(stages, splits) * BR;
-  splits = cdiv(R, rows_per_split);
-  const int use_atomics = (splits > 1 || accumulate) ? 1 : 0;
-  if (splits > 1 && !accumulate)
-    MEMHIP_HIP(hipMemset2DAsync(out, (size_t)ldo * sizeof(float), 0, (size_t)K * sizeof(float), (size_t)N, s));
-  static bool attr_done = false;
-  if (!attr_done) {
-    MEMHIP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn_kernel),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, 2 * kStageBytes));
-    attr_done = true;
-  }
-  hipLaunchKernelGGL(gemm_tn_kernel, dim3(tiles * splits), dim3(kThreads), 2 * kStageBytes, s, (const __bf16*)A,
-                     (long long)lda, (const __bf16*)B, (long long)ldb, R, N, K, out, (long long)ldo, splits,
-                     rows_per_split, use_atomics);
-  return check_launch("gemm_bf16_tn");
+  const memhip_tn_problem_t q = {A, lda, B, ldb, out, ldo, R, N, K, 0};
+  return run(&q, 1, accumulate, workspace, workspace_bytes, as_stream(stream));
+}
+
+extern "C" int memhip_gemm_bf16_tn(const void* A, int64_t lda, const void* B, int64_t ldb, int R, int N, int K,
+                                   float* out, int64_t ldo, int accumulate, memhip_stream_t stream) {
+  return memhip_gemm_bf16_tn_ws(A, lda, B, ldb, R, N, K, out, ldo, accumulate, nullptr, 0, stream);
 }
 
 extern "C" size_t memhip_gemm_bf16_tn_group_workspace(const memhip_tn_problem_t* problems, int count) {
-  if (!problems || count <= 0) return 0;
-  size_t need = memhip::gemm_tn_p8_group_workspace(problems, count);
-  for (int i = 0; i < count; ++i) {                        // ... and enough for the one-by-one path
-    const size_t one = memhip::gemm_tn_p8_workspace(problems[i].R, problems[i].N, problems[i].K);
-    need = one > need ? one : need;
-  }
-  return need;
+  return memhip_gemm_bf16_tn_plan_workspace(problems, count, max_cus());
 }
 
 extern "C" int memhip_gemm_bf16_tn_group(const memhip_tn_problem_t* problems, int count, int accumulate, void* workspace,
                                          size_t workspace_bytes, memhip_stream_t stream) {
-  MEMHIP_REQUIRE(problems && count >= 1 && count <= 4, "gemm_tn_group: 1..4 problems, got %d", count);
-  bool all = true;
-  for (int i = 0; i < count; ++i) {
-    const memhip_tn_problem_t& q = problems[i];
-    MEMHIP_REQUIRE(q.R >= 0 && q.N > 0 && q.K > 0, "gemm_tn_group[%d]: bad shape R=%d N=%d K=%d", i, q.R, q.N, q.K);
-    MEMHIP_REQUIRE(q.R == 0 || (q.A && q.B && q.out), "gemm_tn_group[%d]: null pointer", i);
-    MEMHIP_REQUIRE(q.N % 8 == 0 && q.K % 8 == 0 && q.lda % 8 == 0 && q.ldb % 8 == 0 && ((uintptr_t)q.A & 15) == 0 &&
-                       ((uintptr_t)q.B & 15) == 0, "gemm_tn_group[%d]: operands must be 16-byte aligned, N/K/ld %% 8 == 0", i);
-    all = all && q.R > 0;
-  }
-  hipStream_t s = as_stream(stream);
-  if (all && count > 1 && opt(OPT_TN_P8) != 0 && opt(OPT_TN_GROUP) != 0) {
-    const int rc = gemm_tn_p8_group_dispatch(problems, count, accumulate, (float*)workspace, workspace_bytes, s);
-    if (rc != MEMHIP_EUNSUPPORTED) return rc;
-  }
-  for (int i = 0; i < count; ++i) {
-    const memhip_tn_problem_t& q = problems[i];
-    const int rc = memhip_gemm_bf16_tn_ws(q.A, q.lda, q.B, q.ldb, q.R, q.N, q.K, q.out, q.ldo, accumulate, workspace,
-                                          workspace_bytes, stream);
-    if (rc != MEMHIP_OK) return rc;
-  }
+  if (const int rc = validate_group(problems, count)) return rc;
+  return run(problems, count, accumulate, workspace, workspace_bytes, as_stream(stream));
+}
+
+extern "C" int memhip_gemm_bf16_tn_plan(const memhip_tn_problem_t* problems, int count, int accumulate, const void* workspace,
+                                        size_t workspace_bytes, int stream_cus, memhip_tn_plan_t* out_plan) {
+  MEMHIP_REQUIRE(out_plan, "gemm_tn plan: bad arguments");
+  if (const int rc = validate_group(problems, count)) return rc;
+  *out_plan = plan_now(problems, count, accumulate, workspace, workspace_bytes, stream_cus >= 0 ? stream_cus : usable_cus());
   return MEMHIP_OK;
+}
+
+extern "C" size_t memhip_gemm_bf16_tn_plan_workspace(const memhip_tn_problem_t* problems, int count, int device_cus) {
+  if (!problems || count <= 0) return 0;
+  return tn_group_workspace_bytes(problems, count, device_cus);
 }
 
 namespace {

@@ -16,6 +16,7 @@
 // both are staged through the idle ring.
 #include <atomic>
 #include "common.h"
+#include "gemm_tn_plan.hpp"
 
 #define P8_PRIO_MODE 0   // 0: s_setprio 1 around every MFMA block; 1: none; 2: none + waves 4-7 at priority 1 for the whole kernel
                          // dgrad kernels of the other stream, no difference: 38.28 vs 38.35 ms.  gemm_p8.hip: no difference either way)
@@ -25,7 +26,7 @@ namespace {
 
 using namespace memhip;
 
-constexpr int BM = 256, BN = 256, BR = 64;
+constexpr int BM = kTnP8Tile, BN = kTnP8Tile, BR = kTnStageRows;
 constexpr int kThreads = 512;
 constexpr int kHalf = BR * 128 * 2;     // 16 KiB: 64 tokens x 128 columns
 constexpr int kBuf = 4 * kHalf;         // A0 A1 B0 B1
@@ -309,11 +310,10 @@ __global__ __launch_bounds__(kThreads) void gemm_tn_p8_kernel(const __bf16* __re
 
 // ---- GROUPED launch (round 5): the weight gradients of up to four Linear layers whose operands are ready at the same time
 // (fc2 + fc1, proj + qkv of a block) as ONE grid with ONE common split count.  Alone, a 768 x 768 gradient has 9 tiles and
-// needs 28 row slices to fill 256 CUs (28 slabs of 2.4 MB for a 2.4 MB result, 1 800 rows of main loop per workgroup against
-// the same 256 KB write-out); beside the 27 tiles of the qkv gradient both run with 7 slices -- the shape of the fc1 launch.
+// is planned with 27 row slices on 256 CUs (27 slabs of 2.4 MB for a 2.4 MB result, 1 920 rows of main loop per workgroup
+// against the same 256 KB write-out); beside the 27 tiles of the qkv gradient both run with 7 slices -- the shape of the fc1 launch.
 // Workgroup ids are laid out product after product, (slice, tile) inside a product, so an XCD still works on consecutive
 // (slice, tile) ids of one product.
-constexpr int kTnGroupMax = 4;
 struct TnGroupProblem {
   const __bf16* A;
   const __bf16* B;
@@ -391,151 +391,52 @@ extern "C" int memhip_debug_tnp8_stamps(unsigned long long* host_out) {
 
 namespace memhip {
 
-static void tn_p8_plan(int R, int N, int K, int num_cu, int& tiles, int& splits, int& rows_per_split) {
-  tiles = (N / BM) * (K / BN);
-  const int pairs = cdiv(R, 2 * BR);                       // the token rows advance in pairs of K-tiles
-  splits = num_cu / tiles;
-  if (splits < 1) splits = 1;
-  if (splits > pairs / 2) splits = pairs / 2 > 0 ? pairs / 2 : 1;        // >= 256 rows per split
-  rows_per_split = cdiv(pairs, splits) * 2 * BR;
-  splits = cdiv(R, rows_per_split);
-}
-static int tn_p8_num_cu(hipStream_t s = nullptr) { return usable_cus(s); }
+// The launchers of the three p8 forms: each runs what its TnLaunch (gemm_tn_plan.cpp) says and decides nothing.
 
-// bytes of workspace with which the partial tiles go through plain stores + a reduction pass
-// (sized for EVERY CU: a launch stream without a reservation plans the most splits, whatever another stream reserved)
-size_t gemm_tn_p8_workspace(int R, int N, int K) {
-  if (N % BM != 0 || K % BN != 0 || R < 2048) return 0;
-  const int num_cu = max_cus();
-  if (!num_cu) return 0;
-  size_t need = 0;
-  for (int cu = num_cu; cu >= 8; cu -= 8) {                   // the split count is not monotone in the CU count: take the maximum
-    int tiles, splits, rps;
-    tn_p8_plan(R, N, K, cu, tiles, splits, rps);
-    const size_t b = splits > 1 ? (size_t)splits * N * K * sizeof(float) : 0;
-    need = b > need ? b : need;
-  }
-  return need;
+// the 128 KiB ring is above the default dynamic-LDS limit: raised once per kernel, in front of its first launch
+static int want_ring(std::atomic<bool>& done, const void* kernel, const char* what) {
+  if (done) return MEMHIP_OK;
+  const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kRing);
+  if (e != hipSuccess) return fail(MEMHIP_ELAUNCH, "%s: set smem attr: %s", what, hipGetErrorString(e));
+  done = true;
+  return MEMHIP_OK;
 }
 
-// MEMHIP_EUNSUPPORTED when the shape does not fit (caller falls back to the other TN kernels).
-int gemm_tn_p8_dispatch(const void* A, long long lda, const void* B, long long ldb, int R, int N, int K, float* out,
-                        long long ldo, int accumulate, float* ws, size_t ws_bytes, hipStream_t s) {
-  if (N % BM != 0 || K % BN != 0 || R < 2048) return MEMHIP_EUNSUPPORTED;
-  const int num_cu = tn_p8_num_cu(s);
-  if (!num_cu) return MEMHIP_EUNSUPPORTED;
-  int tiles, splits, rows_per_split;
-  tn_p8_plan(R, N, K, num_cu, tiles, splits, rows_per_split);
-  static std::atomic<bool> attr_done{false};
-  if (!attr_done) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn_p8_kernel<false>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, kRing);
-    if (e == hipSuccess)
-      e = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn_p8_kernel<true>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, kRing);
-    if (e != hipSuccess) return fail(MEMHIP_ELAUNCH, "gemm_tn_p8: set smem attr: %s", hipGetErrorString(e));
-    attr_done = true;
-  }
-  const size_t need = (size_t)splits * N * K * sizeof(float);
-  // (the reduction pass reads and writes `out` as float4: the pointer itself must be 16-byte aligned, not only ldo -- a caller's
-  // 4-byte-aligned gradient view takes the atomic path below)
-  if (ws && splits > 1 && ws_bytes >= need && ((uintptr_t)ws & 15) == 0 && ldo % 4 == 0 && ((uintptr_t)out & 15) == 0) {
-    hipLaunchKernelGGL(gemm_tn_p8_kernel<true>, dim3(tiles * splits), dim3(kThreads), kRing, s, (const __bf16*)A, lda,
-                       (const __bf16*)B, ldb, R, N, K, ws, (long long)K, rows_per_split);
-    const long long quads = (long long)N * K / 4;
-    hipLaunchKernelGGL(tn_reduce_kernel, dim3((unsigned)((quads + 255) / 256)), dim3(256), 0, s, ws, splits,
-                       (long long)N * K, N, K, out, ldo, accumulate);
-    return check_launch("gemm_bf16_tn(p8, workspace)");
-  }
-  if (!accumulate) {
-    hipError_t e = hipMemset2DAsync(out, (size_t)ldo * sizeof(float), 0, (size_t)K * sizeof(float), (size_t)N, s);
+int tn_p8_launch_atomic(const TnLaunch& l, const memhip_tn_problem_t& q, hipStream_t s) {
+  static std::atomic<bool> ring{false};
+  if (const int rc = want_ring(ring, reinterpret_cast<const void*>(gemm_tn_p8_kernel<false>), "gemm_tn_p8")) return rc;
+  if (l.memset_first) {
+    const hipError_t e = hipMemset2DAsync(q.out, (size_t)q.ldo * sizeof(float), 0, (size_t)q.K * sizeof(float), (size_t)q.N, s);
     if (e != hipSuccess) return fail(MEMHIP_ELAUNCH, "gemm_tn_p8: memset: %s", hipGetErrorString(e));
   }
-  hipLaunchKernelGGL(gemm_tn_p8_kernel<false>, dim3(tiles * splits), dim3(kThreads), kRing, s, (const __bf16*)A, lda,
-                     (const __bf16*)B, ldb, R, N, K, out, ldo, rows_per_split);
+  hipLaunchKernelGGL(gemm_tn_p8_kernel<false>, dim3(l.grid), dim3(kThreads), kRing, s, (const __bf16*)q.A, (long long)q.lda,
+                     (const __bf16*)q.B, (long long)q.ldb, q.R, q.N, q.K, q.out, (long long)q.ldo, l.p[0].rows_per_split);
   return check_launch("gemm_bf16_tn(p8)");
 }
 
-// ---- grouped launch: plan.  One split count for the whole group: the smallest number of rounds (grids of num_cu workgroups)
-// that keeps >= 80 % of the CUs busy, else the best of four.  (fc2 + fc1 of ViT-B, 72 tiles: ONE round of 216 workgroups with 3 row
-// slices each -- 55 MB of slabs -- instead of two rounds with 7: in the step 34.35-34.39 ms against 34.59-34.83, and against
-// 34.41-34.53 with fc2 / fc1 as single launches; the CUs such a round leaves idle take workgroups of the other stream.)
-static bool tn_group_plan(const memhip_tn_problem_t* pr, int count, int num_cu, TnGroup& g, int& total_wgs, int& total_quads,
-                          size_t& ws_floats) {
-  if (count < 2 || count > kTnGroupMax || !num_cu) return false;
-  int tiles_total = 0;
-  for (int i = 0; i < count; ++i) {
-    if (pr[i].N % BM != 0 || pr[i].K % BN != 0 || pr[i].R < 2048 || pr[i].ldo % 4 != 0 || ((uintptr_t)pr[i].out & 15) != 0) return false;
-    tiles_total += (pr[i].N / BM) * (pr[i].K / BN);
-  }
-  int best_s = 0;
-  double best_eff = 0.0;
-  for (int r = 1; r <= 4; ++r) {
-    const int sp = (r * num_cu) / tiles_total;
-    if (sp < 2) continue;
-    const double eff = (double)tiles_total * sp / ((double)r * num_cu);
-    if (eff > best_eff + 1e-9) { best_eff = eff; best_s = sp; }
-    if (eff >= 0.80) break;
-  }
-  if (best_s < 2) return false;
-  total_wgs = 0; total_quads = 0; ws_floats = 0;
-  g.count = count;
-  for (int i = 0; i < count; ++i) {
-    TnGroupProblem& q = g.p[i];
-    const int tiles = (pr[i].N / BM) * (pr[i].K / BN);
-    const int pairs = cdiv(pr[i].R, 2 * BR);
-    int sp = best_s;
-    if (sp > pairs / 2) sp = pairs / 2 > 0 ? pairs / 2 : 1;
-    q.rows_per_split = cdiv(pairs, sp) * 2 * BR;
-    q.splits = cdiv(pr[i].R, q.rows_per_split);
-    q.A = (const __bf16*)pr[i].A; q.B = (const __bf16*)pr[i].B;
-    q.lda = pr[i].lda; q.ldb = pr[i].ldb; q.ldo = pr[i].ldo;
-    q.R = pr[i].R; q.N = pr[i].N; q.K = pr[i].K;
-    q.out = pr[i].out;
-    q.ws = nullptr;
-    q.wg_begin = total_wgs;
-    q.quad_begin = total_quads;
-    total_wgs += tiles * q.splits;
-    total_quads += (int)(((long long)pr[i].N * pr[i].K / 4 + 255) / 256 * 256);      // whole blocks per product
-    ws_floats += (size_t)q.splits * pr[i].N * pr[i].K;
-  }
-  return true;
+int tn_p8_launch_ws(const TnLaunch& l, const memhip_tn_problem_t& q, int accumulate, float* ws, hipStream_t s) {
+  static std::atomic<bool> ring{false};
+  if (const int rc = want_ring(ring, reinterpret_cast<const void*>(gemm_tn_p8_kernel<true>), "gemm_tn_p8")) return rc;
+  hipLaunchKernelGGL(gemm_tn_p8_kernel<true>, dim3(l.grid), dim3(kThreads), kRing, s, (const __bf16*)q.A, (long long)q.lda,
+                     (const __bf16*)q.B, (long long)q.ldb, q.R, q.N, q.K, ws, (long long)q.K, l.p[0].rows_per_split);
+  hipLaunchKernelGGL(tn_reduce_kernel, dim3(l.reduce_grid), dim3(256), 0, s, ws, l.p[0].splits, (long long)q.N * q.K, q.N, q.K,
+                     q.out, (long long)q.ldo, accumulate);
+  return check_launch("gemm_bf16_tn(p8, workspace)");
 }
 
-size_t gemm_tn_p8_group_workspace(const memhip_tn_problem_t* pr, int count) {
-  const int num_cu = max_cus();
-  size_t need = 0;
-  for (int cu = num_cu; cu >= 8; cu -= 8) {
-    TnGroup g;
-    int wgs, quads;
-    size_t fl;
-    if (tn_group_plan(pr, count, cu, g, wgs, quads, fl) && fl * sizeof(float) > need) need = fl * sizeof(float);
-  }
-  return need;
-}
-
-// MEMHIP_EUNSUPPORTED: the caller runs the products one by one.
-int gemm_tn_p8_group_dispatch(const memhip_tn_problem_t* pr, int count, int accumulate, float* ws, size_t ws_bytes, hipStream_t s) {
+int tn_p8_launch_group(const TnLaunch& l, const memhip_tn_problem_t* pr, int accumulate, float* ws, hipStream_t s) {
+  static std::atomic<bool> ring{false};
+  if (const int rc = want_ring(ring, reinterpret_cast<const void*>(gemm_tn_p8_group_kernel), "gemm_tn_p8(group)")) return rc;
   TnGroup g;
-  int wgs, quads;
-  size_t fl;
-  if (!ws || ((uintptr_t)ws & 15) != 0 || !tn_group_plan(pr, count, tn_p8_num_cu(s), g, wgs, quads, fl) ||
-      fl * sizeof(float) > ws_bytes)
-    return MEMHIP_EUNSUPPORTED;
-  static std::atomic<bool> attr_done{false};
-  if (!attr_done) {
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn_p8_group_kernel),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, kRing);
-    if (e != hipSuccess) return fail(MEMHIP_ELAUNCH, "gemm_tn_p8(group): set smem attr: %s", hipGetErrorString(e));
-    attr_done = true;
+  g.count = l.count;
+  for (int i = 0; i < l.count; ++i) {
+    const TnPart& p = l.p[i];
+    const memhip_tn_problem_t& q = pr[p.problem];
+    g.p[i] = TnGroupProblem{(const __bf16*)q.A, (const __bf16*)q.B, ws + p.ws_offset, q.out, (long long)q.lda, (long long)q.ldb,
+                            (long long)q.ldo, q.R, q.N, q.K, p.rows_per_split, p.splits, p.wg_begin, p.quad_begin};
   }
-  float* w = ws;
-  for (int i = 0; i < count; ++i) {
-    g.p[i].ws = w;
-    w += (size_t)g.p[i].splits * g.p[i].N * g.p[i].K;
-  }
-  hipLaunchKernelGGL(gemm_tn_p8_group_kernel, dim3(wgs), dim3(kThreads), kRing, s, g);
-  hipLaunchKernelGGL(tn_reduce_group_kernel, dim3((unsigned)(quads / 256)), dim3(256), 0, s, g, accumulate);
+  hipLaunchKernelGGL(gemm_tn_p8_group_kernel, dim3(l.grid), dim3(kThreads), kRing, s, g);
+  hipLaunchKernelGGL(tn_reduce_group_kernel, dim3(l.reduce_grid), dim3(256), 0, s, g, accumulate);
   return check_launch("gemm_bf16_tn_group(p8)");
 }
 

@@ -72,6 +72,18 @@ def _timer_event():
     return GEMM_EVENT_POOL.pop() if GEMM_EVENT_POOL else torch.cuda.Event(enable_timing=True)
 
 
+def _timed(code, flops, fn):
+    """Run fn() between two HIP events on the launch stream when the per-launch timer is armed (bench.py)."""
+    if GEMM_TIMER is None:
+        fn()
+        return
+    e0, e1 = _timer_event(), _timer_event()
+    e0.record()
+    fn()
+    e1.record()
+    GEMM_TIMER.append((e0, e1, flops, code))
+
+
 def gemm_args(A, B, M, N, K, epi, out0=None, out1=None, bias=None, vec1=None, resid=None, aux=None,
               rowmask=None, keep_prob=1.0, colscale=1.0, colscale_n=0, rows_per_sample=1, accumulate=False, colsum=None,
               lda=None, ldb=None, ldo0=None, ldo1=None, ldr=None, ldaux=None, sample_map=None, colsum_copies=0, dropout=None):
@@ -104,14 +116,7 @@ def gemm_nt(A, B, M, N, K, epi, *args, **kw):
     colsum_copies > 1: `colsum` is a zeroed [copies, N] workspace, folded into the bias gradient by colsum_fold.
     dropout: a Dropout (epilogue EPI_RESIDUAL_DROP only)."""
     a = gemm_args(A, B, M, N, K, epi, *args, **kw)
-    if GEMM_TIMER is None:
-        check(lib.memhip_gemm_bf16_nt(C.byref(a), stream_ptr()), "gemm_bf16_nt")
-    else:
-        e0, e1 = _timer_event(), _timer_event()
-        e0.record()
-        check(lib.memhip_gemm_bf16_nt(C.byref(a), stream_ptr()), "gemm_bf16_nt")
-        e1.record()
-        GEMM_TIMER.append((e0, e1, 2.0 * M * N * K, epi))
+    _timed(epi, 2.0 * M * N * K, lambda: check(lib.memhip_gemm_bf16_nt(C.byref(a), stream_ptr()), "gemm_bf16_nt"))
 
 
 NT_128, NT_G256, NT_P8_256, NT_P8_128, NT_P8_PAIR = range(5)
@@ -325,18 +330,6 @@ def relpos_gather(table, index_i32, T, TP, heads, bias_pad, biasT_pad=None):
                                    stream_ptr()), "relpos_gather")
 
 
-def _timed(code, flops, fn):
-    """Run fn() between two HIP events on the launch stream when the per-launch timer is armed (bench.py)."""
-    if GEMM_TIMER is None:
-        fn()
-        return
-    e0, e1 = _timer_event(), _timer_event()
-    e0.record()
-    fn()
-    e1.record()
-    GEMM_TIMER.append((e0, e1, flops, code))
-
-
 def attn_fwd(qkv, B, T, D, heads, table, window, out, lse):
     _timed(200, 4.0 * B * T * T * D, lambda: check(
         lib.memhip_attn_fwd(ptr(qkv), qkv.stride(0), B, T, D, heads, ptr(table), window[0], window[1], ptr(out),
@@ -515,20 +508,18 @@ def gemm_tn_workspace(R, N, K):
     return v
 
 
+def _ws_arg(workspace):
+    """(pointer, bytes) of an optional uint8 scratch tensor"""
+    return (None, 0) if workspace is None else (ptr(workspace), workspace.numel() * workspace.element_size())
+
+
 def gemm_tn(A, B, R, N, K, out, accumulate=True, workspace=None):
     """out[N,K] (+)= A[R,N]^T @ B[R,K]  (weight gradient; A = dY, B = X, token-major bf16).  `workspace`:
     optional uint8 scratch tensor of >= gemm_tn_workspace(R,N,K) bytes (plain-store partial tiles)."""
-    ws, wsb = (ptr(workspace), workspace.numel() * workspace.element_size()) if workspace is not None else (None, 0)
-    if GEMM_TIMER is None:
-        check(lib.memhip_gemm_bf16_tn_ws(ptr(A), A.stride(0), ptr(B), B.stride(0), R, N, K, ptr(out), out.stride(0),
-                                         int(accumulate), ws, wsb, stream_ptr()), "gemm_bf16_tn")
-    else:
-        e0, e1 = _timer_event(), _timer_event()
-        e0.record()
-        check(lib.memhip_gemm_bf16_tn_ws(ptr(A), A.stride(0), ptr(B), B.stride(0), R, N, K, ptr(out), out.stride(0),
-                                         int(accumulate), ws, wsb, stream_ptr()), "gemm_bf16_tn")
-        e1.record()
-        GEMM_TIMER.append((e0, e1, 2.0 * R * N * K, 100))
+    ws, wsb = _ws_arg(workspace)
+    _timed(100, 2.0 * R * N * K, lambda: check(
+        lib.memhip_gemm_bf16_tn_ws(ptr(A), A.stride(0), ptr(B), B.stride(0), R, N, K, ptr(out), out.stride(0),
+                                   int(accumulate), ws, wsb, stream_ptr()), "gemm_bf16_tn"))
 
 
 class TnProblem(C.Structure):
@@ -545,31 +536,72 @@ def _tn_problems(problems):
     return arr
 
 
+def _tn_shapes(shapes):
+    """TnProblem array of the shapes [(R, N, K), ...] with dense leading dimensions and no pointers (workspace queries)"""
+    arr = (TnProblem * len(shapes))()
+    for q, (R, N, K) in zip(arr, shapes):
+        q.R, q.N, q.K, q.lda, q.ldb, q.ldo = R, N, K, N, K, K
+    return arr
+
+
 def gemm_tn_group_workspace(shapes):
     """bytes of scratch for gemm_tn_group over products of the shapes [(R, N, K), ...]"""
     key = tuple(shapes)
     if key in _TN_WS_CACHE:
         return _TN_WS_CACHE[key]
-    arr = (TnProblem * len(shapes))()
-    for q, (R, N, K) in zip(arr, shapes):
-        q.R, q.N, q.K, q.lda, q.ldb, q.ldo = R, N, K, N, K, K
-    v = _TN_WS_CACHE[key] = int(lib.memhip_gemm_bf16_tn_group_workspace(arr, len(shapes)))
+    v = _TN_WS_CACHE[key] = int(lib.memhip_gemm_bf16_tn_group_workspace(_tn_shapes(shapes), len(shapes)))
     return v
 
 
 def gemm_tn_group(problems, accumulate=True, workspace=None):
     """The weight gradients [(A = dY, B = X, R, N, K, out f32 [N, K]), ...] of up to four layers as ONE launch
     (memhip_gemm_bf16_tn_group); each product has the contract of gemm_tn."""
-    ws, wsb = (ptr(workspace), workspace.numel() * workspace.element_size()) if workspace is not None else (None, 0)
+    ws, wsb = _ws_arg(workspace)
     arr = _tn_problems(problems)
-    if GEMM_TIMER is None:
-        check(lib.memhip_gemm_bf16_tn_group(arr, len(problems), int(accumulate), ws, wsb, stream_ptr()), "gemm_bf16_tn_group")
-    else:
-        e0, e1 = _timer_event(), _timer_event()
-        e0.record()
-        check(lib.memhip_gemm_bf16_tn_group(arr, len(problems), int(accumulate), ws, wsb, stream_ptr()), "gemm_bf16_tn_group")
-        e1.record()
-        GEMM_TIMER.append((e0, e1, sum(2.0 * R * N * K for _, _, R, N, K, _ in problems), 100 + len(problems)))   # 102..104: a group
+    _timed(100 + len(problems), sum(2.0 * R * N * K for _, _, R, N, K, _ in problems), lambda: check(   # 102..104: a group
+        lib.memhip_gemm_bf16_tn_group(arr, len(problems), int(accumulate), ws, wsb, stream_ptr()), "gemm_bf16_tn_group"))
+
+
+TN_128, TN_P8_ATOMIC, TN_P8_WS, TN_P8_GROUP = range(4)
+
+
+class TnPart(C.Structure):
+    """== memhip_tn_part_t."""
+    _fields_ = [(n, i32) for n in ("problem", "tiles", "splits", "rows_per_split", "wg_begin", "quad_begin")] + [("ws_offset", i64)]
+
+
+class TnLaunch(C.Structure):
+    """== memhip_tn_launch_t."""
+    _fields_ = [(n, i32) for n in ("kind", "count", "grid", "reduce_grid", "memset_first", "use_atomics")] + \
+               [("ws_bytes", i64), ("p", TnPart * 4)]
+
+
+class TnPlan(C.Structure):
+    """== memhip_tn_plan_t."""
+    _fields_ = [("count", i32), ("reserved0", i32), ("l", TnLaunch * 4)]
+
+
+declare({"memhip_gemm_bf16_tn_plan": (i32, [vp, i32, i32, vp, sz, i32, C.POINTER(TnPlan)]),
+         "memhip_gemm_bf16_tn_plan_workspace": (sz, [vp, i32, i32])})
+
+
+def gemm_tn_plan(problems, accumulate=True, workspace=None, stream_cus=None):
+    """The launches gemm_tn_group (one problem: gemm_tn) makes under the current options, as a list of TnLaunch (kind TN_*,
+    grid, reduce_grid, memset_first, use_atomics, ws_bytes, and per product p[i]: problem, tiles, splits, rows_per_split,
+    wg_begin, quad_begin, ws_offset).  problems: as for gemm_tn_group, or a TnProblem array; workspace: a tensor, None or
+    (address, bytes).  Nothing is launched; with stream_cus no device is needed (default: the default stream's CUs)."""
+    arr = problems if isinstance(problems, C.Array) else _tn_problems(problems)
+    ws, wsb = workspace if isinstance(workspace, tuple) else _ws_arg(workspace)
+    plan = TnPlan()
+    check(lib.memhip_gemm_bf16_tn_plan(arr, len(arr), int(accumulate), ws, wsb, -1 if stream_cus is None else stream_cus,
+                                       C.byref(plan)), "gemm_bf16_tn_plan")
+    return [plan.l[i] for i in range(plan.count)]
+
+
+def gemm_tn_plan_workspace(problems, device_cus):
+    """gemm_tn_group_workspace as it answers on a device of device_cus CUs, for a TnProblem array (one product with ldo = K:
+    gemm_tn_workspace).  No device is needed."""
+    return int(lib.memhip_gemm_bf16_tn_plan_workspace(problems, len(problems), device_cus))
 
 
 def colsum_fold(ws, copies, N, out):

@@ -776,12 +776,15 @@ class ViTEngine(FlatParams):
             c["streams"][i][b0 * T:b1 * T].copy_(xout[b0 * T:b1 * T])
 
     # ------------------------------------------------------------------ backward
+    def _tn_ws_at_least(self, need):
+        """The partial-tile workspace of the weight-gradient GEMMs holds `need` bytes (it grows to the largest product once)."""
+        if need > self._tn_ws.numel():
+            self._tn_ws = torch.empty(need, dtype=torch.uint8, device=self.dev)
+
     def _wgrad(self, dY, X, R, n_out, n_in, gname, bias_grads=()):
         """grad[gname] [n_out, n_in] += dY[R, n_out]^T @ X[R, n_in]; bias_grads = ((grad_view, c0, c1), ...)
         column sums of dY[:, c0:c1] (the Linear bias gradients)."""
-        need = ops.gemm_tn_workspace(R, n_out, n_in)
-        if need > self._tn_ws.numel():                      # grows to the largest product once
-            self._tn_ws = torch.empty(need, dtype=torch.uint8, device=self.dev)
+        self._tn_ws_at_least(ops.gemm_tn_workspace(R, n_out, n_in))
         # (the weight matrices are WRITTEN by their one weight-gradient product per backward: they are not part of the
         # zero fill in front of backward, see _zero_small_grads; gradient accumulation adds instead)
         ops.gemm_tn(dY, X, R, n_out, n_in, self.G(gname).view(n_out, n_in), accumulate=self.accumulate_grads,
@@ -810,12 +813,10 @@ class ViTEngine(FlatParams):
     def _wgrad_group(self, items):
         """items = [(dY, X, R, n_out, n_in, gname), ...]: the weight gradients of layers whose operands are ready at the
         same time as ONE launch (ops.gemm_tn_group): the 768 x 768 proj gradient rides with the 7 row slices of the qkv
-        gradient instead of the 28 it needs alone to fill the chip (proj + qkv: 241 -> 212 us per block); fc2 + fc1 run as
+        gradient instead of the 27 it is planned with alone (proj + qkv: 241 -> 212 us per block); fc2 + fc1 run as
         ONE round of 216 workgroups with 3 row slices each instead of two launches with 7 (as two rounds of 504 they were
         no faster than two launches).  ViT-B step: 34.8 (single launches) -> 34.3 (proj + qkv) -> 33.9 ms (both pairs)."""
-        need = ops.gemm_tn_group_workspace([(R, n_out, n_in) for _, _, R, n_out, n_in, _ in items])
-        if need > self._tn_ws.numel():
-            self._tn_ws = torch.empty(need, dtype=torch.uint8, device=self.dev)
+        self._tn_ws_at_least(ops.gemm_tn_group_workspace([(R, n_out, n_in) for _, _, R, n_out, n_in, _ in items]))
         ops.gemm_tn_group([(dY, X, R, n_out, n_in, self.G(gname).view(n_out, n_in)) for dY, X, R, n_out, n_in, gname in items],
                           accumulate=self.accumulate_grads, workspace=self._tn_ws)
 
@@ -840,12 +841,11 @@ class ViTEngine(FlatParams):
             # the wgrad workspace is sized once so that it is never reallocated while the side stream uses it
             D, Hd = self.D, self.hidden
             M = self.B * self.T
-            need = max(ops.gemm_tn_group_workspace([(M, D, D), (M, 3 * D, D)]), ops.gemm_tn_group_workspace([(M, D, Hd), (M, Hd, D)]),
-                       ops.gemm_tn_workspace(M, 3 * D, D), ops.gemm_tn_workspace(M, Hd, D), ops.gemm_tn_workspace(M, D, Hd),
-                       ops.gemm_tn_workspace(M, D, D), ops.gemm_tn_workspace(self.Mm_cap or M, max(self.V, 1), D),
-                       ops.gemm_tn_workspace(self.B * self.L, D, self.Kpe))
-            if need > self._tn_ws.numel():
-                self._tn_ws = torch.empty(need, dtype=torch.uint8, device=self.dev)
+            self._tn_ws_at_least(max(
+                ops.gemm_tn_group_workspace([(M, D, D), (M, 3 * D, D)]), ops.gemm_tn_group_workspace([(M, D, Hd), (M, Hd, D)]),
+                ops.gemm_tn_workspace(M, 3 * D, D), ops.gemm_tn_workspace(M, Hd, D), ops.gemm_tn_workspace(M, D, Hd),
+                ops.gemm_tn_workspace(M, D, D), ops.gemm_tn_workspace(self.Mm_cap or M, max(self.V, 1), D),
+                ops.gemm_tn_workspace(self.B * self.L, D, self.Kpe)))
 
     def _on_side(self, fn):
         """Run fn() (weight-gradient work that only READS what the main stream has produced so far) on the side stream."""

@@ -136,12 +136,40 @@ def test_vitb_shapes_throughput_sanity():
         assert torch.isfinite(out.float()).all()
 
 
+# the parametrised shapes of test_gemm_tn_weight_gradient that the 256 x 256 kernel takes (whole tiles, >= 2048 rows); the
+# others run on the 128 x 128 kernel
+_TN_P8_SHAPES = {(50432 // 8, 2304, 768), (5000, 8192, 768), (2048, 256, 256), (50432, 768, 768), (4099, 3072, 768),
+                 (3000, 768, 3072), (2500, 512, 256)}
+
+
+def _check_tn_single_plan(ops, R, N, K):
+    """The plan (nothing is launched) names the kernel form each call of the test below reaches on this device."""
+    A, B = torch.empty((R, N), dtype=torch.bfloat16, device="cuda"), torch.empty((R, K), dtype=torch.bfloat16, device="cuda")
+    out = torch.empty((N, K), device="cuda")
+    ws = torch.empty(max(ops.gemm_tn_workspace(R, N, K), 16), dtype=torch.uint8, device="cuda")
+    for accumulate in (False, True):
+        (bare,) = ops.gemm_tn_plan([(A, B, R, N, K, out)], accumulate, None)
+        (with_ws,) = ops.gemm_tn_plan([(A, B, R, N, K, out)], accumulate, ws)
+        if (R, N, K) in _TN_P8_SHAPES:
+            assert bare.kind == ops.TN_P8_ATOMIC and bare.use_atomics and bare.memset_first == (not accumulate)
+            assert with_ws.kind == (ops.TN_P8_WS if with_ws.p[0].splits > 1 else ops.TN_P8_ATOMIC)
+            if with_ws.kind == ops.TN_P8_WS:         # the query sized the workspace for the slices this device plans
+                assert 0 < with_ws.ws_bytes <= ws.numel() and with_ws.reduce_grid > 0 and not with_ws.use_atomics
+        else:
+            assert bare.kind == with_ws.kind == ops.TN_128 and with_ws.ws_bytes == 0
+            assert bare.grid == -(-N // 128) * -(-K // 128) * bare.p[0].splits
+    if (R, N, K) == (70, 768, 512):                  # one slice: plain stores, nothing to clear
+        (l,) = ops.gemm_tn_plan([(A, B, R, N, K, out)], False, None)
+        assert (l.p[0].splits, l.memset_first, l.use_atomics) == (1, 0, 0)
+
+
 @pytest.mark.parametrize("R,N,K", [(256, 128, 128), (394, 768, 768), (50432 // 8, 2304, 768), (1000, 512, 3072),
                                    (333, 128, 512), (70, 768, 512), (5000, 8192, 768), (2048, 256, 256),
                                    (50432, 768, 768), (4099, 3072, 768), (3000, 768, 3072), (2500, 512, 256)])
 def test_gemm_tn_weight_gradient(R, N, K):
     """out[N,K] += A[R,N]^T @ B[R,K] with the transposing LDS read + split-K atomics."""
     from mem_amd import ops
+    _check_tn_single_plan(ops, R, N, K)
     # exact-integer check first (layout / k-permutation / swizzle mistakes are hard failures)
     g = torch.Generator(device="cuda").manual_seed(R)
     Ai = torch.randint(-2, 3, (R, N), generator=g, device="cuda").float()
@@ -174,13 +202,49 @@ def test_gemm_tn_weight_gradient(R, N, K):
     torch.testing.assert_close(cs, A.float().sum(0), rtol=1e-4, atol=1e-2)
 
 
-@pytest.mark.parametrize("shapes", [
-    [(50432, 768, 768), (50432, 2304, 768)],                       # proj + qkv of a ViT-B block: one grid, 7 row slices each
-    [(9001, 256, 512), (5000, 512, 256), (3000, 256, 256)],        # different row counts, ragged
-    [(4099, 768, 768), (4099, 768, 3072), (4099, 3072, 768), (4099, 2304, 768)],
-    [(3000, 768, 768), (300, 768, 768)],                           # second product outside the tile kernel: one by one
-    [(2500, 512, 256)],                                            # a group of one
-])
+# (shapes, the kinds of launch gemm_tn_group plans for them with the workspace its query asks for)
+_TN_GROUPS = [
+    ([(50432, 768, 768), (50432, 2304, 768)], ["group"]),          # proj + qkv of a ViT-B block: one grid, 7 row slices each
+    ([(9001, 256, 512), (5000, 512, 256), (3000, 256, 256)], ["group"]),        # different row counts, ragged
+    ([(4099, 768, 768), (4099, 768, 3072), (4099, 3072, 768), (4099, 2304, 768)], ["group"]),
+    ([(3000, 768, 768), (300, 768, 768)], ["p8_ws", "128"]),       # second product outside the tile kernel: one by one
+    ([(2500, 512, 256)], ["p8_ws"]),                               # a group of one
+    # the smallest group: 8 and 9 slices of 256 rows under a common count of 85 (the >= 256 rows clamp, per product), and
+    # the second product's workgroups, reduction quads and slabs start behind the first one's
+    ([(2048, 256, 256), (2304, 256, 512)], ["group"]),
+]
+
+
+def _check_tn_group_plan(ops, shapes, probs, ws):
+    kinds = {ops.TN_128: "128", ops.TN_P8_ATOMIC: "p8_atomic", ops.TN_P8_WS: "p8_ws", ops.TN_P8_GROUP: "group"}
+    want = dict((tuple(s), k) for s, k in _TN_GROUPS)[tuple(shapes)]
+    plan = ops.gemm_tn_plan(probs, False, ws)
+    assert [kinds[l.kind] for l in plan] == want, [kinds[l.kind] for l in plan]
+    assert all(l.ws_bytes <= ws.numel() for l in plan)
+    if want == ["group"]:
+        (l,) = plan
+        assert l.count == len(shapes) and not l.memset_first and not l.use_atomics
+        wgs = quads = floats = 0
+        for p, (R, N, K) in zip(l.p, shapes):
+            assert (p.wg_begin, p.quad_begin, p.ws_offset) == (wgs, quads, floats)
+            assert p.splits >= 2 and p.rows_per_split >= 256 and p.rows_per_split * (p.splits - 1) < R <= p.rows_per_split * p.splits
+            wgs, quads, floats = wgs + p.tiles * p.splits, quads + N * K // 4, floats + p.splits * N * K
+        assert (l.grid, l.reduce_grid, l.ws_bytes) == (wgs, quads // 256, floats * 4)
+    # without a workspace: product by product, no workspace form
+    bare = ops.gemm_tn_plan(probs, False, None)
+    assert [l.p[0].problem for l in bare] == list(range(len(shapes))) and all(l.ws_bytes == 0 and l.count == 1 for l in bare)
+    # what the comments above say, on the 256 CUs they were written for
+    at256 = ops.gemm_tn_plan(probs, False, ws, stream_cus=256)
+    if shapes[0] == (50432, 768, 768):
+        assert [(p.splits, p.rows_per_split) for p in at256[0].p[:2]] == [(7, 7296)] * 2 and at256[0].grid == 63 + 189
+    if shapes[0] == (2048, 256, 256):
+        assert [(p.tiles, p.splits, p.rows_per_split, p.wg_begin, p.quad_begin, p.ws_offset) for p in at256[0].p[:2]] == \
+            [(1, 8, 256, 0, 0, 0), (2, 9, 256, 8, 256 * 256 // 4, 8 * 256 * 256)]
+    if shapes[0] == (3000, 768, 768):
+        assert at256[1].kind == ops.TN_128 and at256[1].p[0].problem == 1
+
+
+@pytest.mark.parametrize("shapes", [s for s, _ in _TN_GROUPS])
 def test_gemm_tn_group_equals_single_calls(shapes):
     """memhip_gemm_bf16_tn_group: every product of the group has the single call's contract (exact on integer data, equal to
     the single call to fp32 rounding -- the row slices differ --, accumulate adds, same bits every run), whether the group
@@ -202,6 +266,7 @@ def test_gemm_tn_group_equals_single_calls(shapes):
     for (A, B), (R, N, K), o in zip(ops_in, shapes, single):
         ops.gemm_tn(A, B, R, N, K, o, accumulate=False, workspace=ws)
     probs = [(A, B, R, N, K, o) for (A, B), (R, N, K), o in zip(ops_in, shapes, outs)]
+    _check_tn_group_plan(ops, shapes, probs, ws)
     ops.gemm_tn_group(probs, accumulate=False, workspace=ws)
     first = [o.clone() for o in outs]
     for o, s1 in zip(outs, single):

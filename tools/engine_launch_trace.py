@@ -40,6 +40,8 @@ def fmt(v):
         return "{" + " ".join(f"{n}={getattr(v, n)!r}" for n, _ in v._fields_) + "}"
     if isinstance(v, (list, tuple)):
         return "[" + ", ".join(fmt(e) for e in v) + "]"
+    if isinstance(v, dict):                                       # the **kw of gemm_nt
+        return "{" + ", ".join(f"{k}={fmt(e)}" for k, e in v.items()) + "}"
     if isinstance(v, VE.ViTEngine) or callable(v) or type(v).__name__.startswith("MaeEngine"):
         return "."                                                # self of an engine call; the closure given to _on_side
     return repr(v)
