@@ -6,7 +6,15 @@ bf16 needs no loss scaling (``loss_scaler`` is utils.NativeScalerWithGradNormCou
 grouped AdamW); the deepspeed branch (``loss_scaler is None``) and the wandb image logging are not carried;
 ``update_freq`` > 1 accumulates the micro-batch gradients in the flat gradient buffer (``engine.accumulate_grads``;
 ``optimizer.zero_grad()`` clears it after the update); ``model_ema`` is updated through its own ``update(model)`` if
-one is passed."""
+one is passed.
+
+Data parallel (the reference steps under DDP, engine_for_finetuning.py:113-130): ``model._reducer`` (set by
+``parallel.attach_reducer(..., step_exchange=True)``; None on one rank, where nothing below changes) is the engine's gradient
+hook.  Per micro-step the loop tells it whether this one ends in an update -- buckets are exchanged there only, on the
+accumulated buffer -- and passes it to the scaler, whose ``finish()`` hands over what the engine did not (a frozen trunk: the
+head bucket) and joins.  A non-finite loss ends EVERY rank in the same iteration (MAX of the flag over the ranks, before that
+iteration's backward); the reducer is released on every exit path; ``ModelEma.update`` stays rank-local (identical
+parameters give identical averages)."""
 import math
 import sys
 from typing import Iterable, Optional
@@ -14,6 +22,7 @@ from typing import Iterable, Optional
 import torch
 
 from . import utils
+from .parallel import any_rank
 
 
 def accuracy(output, target, topk=(1,)):
@@ -60,10 +69,30 @@ def train_one_epoch(args, model: torch.nn.Module, criterion: torch.nn.Module, da
     for name in ("lr", "min_lr"):
         meters.add_meter(name, utils.SmoothedValue(window_size=1, fmt="{value:.6f}"))
     eng = getattr(model, "engine", None)
+    reducer = getattr(model, "_reducer", None)
+    if reducer is not None and hasattr(reducer, "set_frozen") and hasattr(model, "_trunk_frozen"):
+        reducer.set_frozen(model._trunk_frozen())
     if eng is not None:
         # update_freq > 1 (engine_for_finetuning.py:78,117-124): micro-batch gradients ADD into the flat buffer; the
         # optimizer.zero_grad() below is what clears it
         eng.accumulate_grads = update_freq > 1
+    try:
+        _train_steps(model, criterion, data_loader, optimizer, device, epoch, loss_scaler, max_norm, model_ema, mixup_fn,
+                     log_writer, first_it, lr_schedule_values, wd_schedule_values, num_training_steps_per_epoch, update_freq,
+                     meters, reducer)
+    finally:
+        if reducer is not None and hasattr(reducer, "release"):
+            reducer.release()                       # no pending handle or CU reservation outlives the epoch, whatever ended it
+        if eng is not None:
+            eng.accumulate_grads = False
+    meters.synchronize_between_processes()
+    print("Averaged stats:", meters)
+    return {k: meter.global_avg for k, meter in meters.meters.items()}
+
+
+def _train_steps(model, criterion, data_loader, optimizer, device, epoch, loss_scaler, max_norm, model_ema, mixup_fn, log_writer,
+                 first_it, lr_schedule_values, wd_schedule_values, num_training_steps_per_epoch, update_freq, meters, reducer):
+    from .engine_for_pretraining import _BAD_SAMPLES, check_bad_samples
     optimizer.zero_grad()
     for data_iter_step, (samples, targets) in enumerate(meters.log_every(data_loader, 10, "Epoch: [{}]".format(epoch))):
         step = data_iter_step // update_freq
@@ -75,19 +104,33 @@ def train_one_epoch(args, model: torch.nn.Module, criterion: torch.nn.Module, da
             samples, targets = mixup_fn(samples, targets)
         loss, output = train_class_batch(model, samples, targets, criterion)
         loss_value = loss.item()
-        if not math.isfinite(loss_value):
+        # (N ranks: the MAX of the flag over the ranks, so that every rank leaves HERE, before this iteration's backward
+        # starts a collective the others would never enter)
+        if any_rank(reducer, not math.isfinite(loss_value), loss.device):
             print("Loss is {}, stopping training".format(loss_value))
             sys.exit(1)
         # bf16: no loss scaling -- backward, fused clip, (grouped) AdamW; returns the pre-clip gradient norm
         do_update = (data_iter_step + 1) % update_freq == 0
         loss = loss / update_freq
-        grad_norm = loss_scaler(loss, optimizer, clip_grad=max_norm, parameters=model.parameters(), create_graph=False,
-                                update_grad=do_update)
+        if reducer is None:
+            grad_norm = loss_scaler(loss, optimizer, clip_grad=max_norm, parameters=model.parameters(), create_graph=False,
+                                    update_grad=do_update)
+        else:
+            if hasattr(reducer, "begin_micro_step"):
+                reducer.begin_micro_step(do_update)          # accumulating micro-steps start no collective
+            # samples a batched transform chain flagged on this device (engine_for_pretraining._note_status): the flag is made
+            # global before it gates the update, and every rank raises below
+            bad = _BAD_SAMPLES.get(str(loss.device))
+            grad_norm = loss_scaler(loss, optimizer, clip_grad=max_norm, parameters=model.parameters(), create_graph=False,
+                                    update_grad=do_update, reducer=reducer, poison=bad)
+            if bad is not None and do_update:
+                check_bad_samples(loss.device)
         if do_update:
             optimizer.zero_grad()
             if model_ema is not None:
                 model_ema.update(model)
-        torch.cuda.synchronize()
+        if loss.is_cuda:
+            torch.cuda.synchronize()
         min_lr, max_lr, wd_now = _optimizer_stats(optimizer)
         stats = {"loss": loss_value,
                  "class_acc": (output.max(-1)[-1] == targets).float().mean() if mixup_fn is None else None,
@@ -99,11 +142,6 @@ def train_one_epoch(args, model: torch.nn.Module, criterion: torch.nn.Module, da
             for k, v in stats.items():
                 log_writer.update(head="loss" if k in ("loss", "class_acc") else "opt", **{k: v})
             log_writer.set_step()
-    if eng is not None:
-        eng.accumulate_grads = False
-    meters.synchronize_between_processes()
-    print("Averaged stats:", meters)
-    return {k: meter.global_avg for k, meter in meters.meters.items()}
 
 
 @torch.no_grad()

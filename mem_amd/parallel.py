@@ -22,7 +22,14 @@ Options (both off by default = the reference's fp32 DDP exchange):
     of displacing workgroups of a grid that covers the whole chip (whose stragglers then run a second round).  The
     reservation is dropped by ``finish()`` / ``release()``; the training loops call ``release()`` on every exit path.
     No measurement on more than one GPU exists yet: the entrypoint leaves it at 0.
+
+``attach_reducer`` is what both entrypoints call (broadcast, hook, stale bf16 shadows).  The finetuning loop has modes the
+pretraining loop has not -- gradient accumulation, a frozen trunk whose backward the engine never enters -- and gets the
+reducer behind a ``StepExchange``: the same object to the engine (``grad_hook``) and to the scaler (``finish`` /
+``sync_flag``), which decides per micro-step whether a bucket is exchanged and hands over what the engine did not.
 """
+import os
+
 import torch
 import torch.distributed as dist
 
@@ -110,3 +117,93 @@ class GradReducer:
                 view.div_(self.world)
         self.handles = []
         self._reserve(False)
+
+
+class StepExchange:
+    """The reducer as the finetuning loop drives it (engine_for_finetuning.train_one_epoch); reducer-shaped, so it is the
+    engine's ``grad_hook`` and the scaler's ``reducer=`` at once.
+
+    * Accumulation (``update_freq`` > 1): micro-batch gradients ADD into ``flat_g``; a bucket averaged on a non-final
+      micro-step and then added to would be wrong.  ``begin_micro_step(do_update)`` arms the hook for the micro-step that
+      ends in an update only; the buckets are exchanged there, on the accumulated buffer (DDP ``no_sync`` arithmetic: the mean
+      is linear, so it equals reducing every micro-step).
+    * Buckets the engine never hands over: with a frozen trunk ``backward_trunk`` is not entered and the head / fc_norm
+      gradients come from torch autograd through the parameter views.  ``finish()`` -- called by the scaler after
+      ``loss.backward()`` on update steps only -- first hands every EXPECTED bucket that was not handed in this step to the
+      reducer, in index order (the same set in the same order on every rank), then joins.  ``expected`` is every bucket,
+      or bucket 0 (the head) alone for a frozen trunk: nothing of the trunk's range of ``flat_g`` is read or written."""
+
+    def __init__(self, reducer, frozen=False):
+        self.reducer = reducer
+        self.armed = True
+        self.handed = []                          # bucket indices given to the reducer in this step, in order
+        self.last_exchanged = []                  # ... in the last finished step
+        self.set_frozen(frozen)
+
+    def set_frozen(self, frozen):
+        self.frozen = bool(frozen)
+        self.expected = [0] if self.frozen else list(range(len(self.reducer.buckets)))
+
+    @property
+    def bytes_per_step(self):
+        """Wire bytes of one update step: the expected buckets, in the reducer's element size."""
+        esz = 2 if self.reducer.bucket_dtype is not None else 4
+        return sum(self.reducer.buckets[k][2] - self.reducer.buckets[k][1] for k in self.expected) * esz
+
+    def begin_micro_step(self, do_update):
+        self.armed = bool(do_update)
+        self.handed = []
+
+    def __call__(self, bucket_index):
+        if not self.armed:
+            return                                # an accumulating micro-step: no collective is started
+        if bucket_index in self.handed:
+            raise RuntimeError(f"bucket {bucket_index} handed to the gradient exchange twice in one step")
+        self.handed.append(bucket_index)
+        self.reducer(bucket_index)
+
+    def hand_missing(self):
+        """Every expected bucket the engine has not handed in this step, once, in index order; returns them."""
+        missing = [k for k in self.expected if k not in self.handed]
+        for k in missing:
+            self(k)
+        return missing
+
+    def finish(self):
+        self.hand_missing()
+        self.reducer.finish()
+        self.last_exchanged, self.handed = self.handed, []
+
+    def sync_flag(self, flag):
+        return self.reducer.sync_flag(flag)
+
+    def release(self):
+        self.reducer.release()
+        self.handed, self.armed = [], True
+
+
+def any_rank(reducer, flag, device="cpu"):
+    """True on EVERY rank when ``flag`` is true on any (MAX over the ranks through ``reducer.sync_flag``): a loop that leaves
+    on a rank-local condition -- a non-finite loss -- would strand the other ranks in the next collective."""
+    if reducer is None:
+        return bool(flag)
+    t = torch.tensor([1 if flag else 0], dtype=torch.int32, device=device)
+    return bool(int(reducer.sync_flag(t).item()))
+
+
+def attach_reducer(model, eng, step_exchange=False):
+    """What an entrypoint does once the process group exists and before anything copies the weights (optimizer, EMA twin): the
+    reducer over the engine's flat buffers (its constructor broadcasts rank 0's ``flat_p``), as ``model._reducer`` and the
+    engine's ``grad_hook``; the bf16 shadows are stale after the broadcast.  ``step_exchange``: behind a StepExchange (the
+    finetuning loop).  reserve_cus > 0 leaves CUs to RCCL's channel kernels while buckets are in flight; no measurement on
+    more than one GPU exists yet, so the default is 0 -- MEMHIP_RESERVE_CUS=16 tries it."""
+    red = GradReducer(eng.flat_g, eng.buckets, flat_p=eng.flat_p,
+                      reserve_cus=int(os.environ.get("MEMHIP_RESERVE_CUS", "0")),
+                      streams=lambda: [torch.cuda.current_stream(), eng._side])
+    if step_exchange:
+        frozen = getattr(model, "_trunk_frozen", None)
+        red = StepExchange(red, frozen=bool(frozen()) if frozen is not None else False)
+    model._reducer = red
+    eng.grad_hook = red
+    eng.weights_dirty = True
+    return red

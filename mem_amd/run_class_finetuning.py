@@ -13,7 +13,13 @@ the trunk forward-only (no activation stash, no backward).  Flags of the referen
 when set away from the value that turns them off (``REFUSED``); nothing is silently ignored.  Three defaults therefore
 differ from the reference's, whose own defaults select torchvision-side features: ``--aa`` (None instead of
 rand-m9-mstd0.5-inc1), ``--reprob`` (0 instead of 0.25) and ``--num_workers`` (0: the event chain runs on the GPU in this
-process).  ``--no_model_ema`` is an addition (the reference's ``--model_ema`` can only stay on)."""
+process).  ``--no_model_ema`` is an addition (the reference's ``--model_ema`` can only stay on).
+
+Data parallel (``torchrun --nproc_per_node N -m mem_amd.run_class_finetuning ...``; the reference wraps the model in DDP,
+mem/run_class_finetuning.py:559-565): ``parallel.attach_reducer`` broadcasts rank 0's weights BEFORE the EMA twin and the
+optimizer are built and exchanges the gradient buckets from the engine's backward hook through a ``parallel.StepExchange``
+(accumulation: on the update micro-step only; frozen trunk: the head bucket only).  ``--dist_eval`` shards the validation
+set; only the main process writes checkpoints, ``log.txt`` and ``eval.txt``."""
 import argparse
 import datetime
 import json
@@ -26,7 +32,8 @@ import numpy as np
 import torch
 
 from . import utils
-from .run_mem_pretraining import _config_file_args
+from .parallel import attach_reducer
+from .run_mem_pretraining import _config_file_args, ops_mod
 
 # flag -> (value that turns it off, why it is refused)
 REFUSED = {
@@ -262,7 +269,15 @@ def main(args):
     data_loader_train = torch.utils.data.DataLoader(dataset_train, sampler=sampler_train, batch_size=args.batch_size, **loader_args)
     data_loader_val = None
     if dataset_val is not None:
-        data_loader_val = torch.utils.data.DataLoader(dataset_val, sampler=torch.utils.data.SequentialSampler(dataset_val),
+        if args.dist_eval:
+            if len(dataset_val) % num_tasks != 0:
+                print("Warning: Enabling distributed evaluation with an eval dataset not divisible by process number. "
+                      "This will slightly alter validation results as extra duplicate entries are added to achieve "
+                      "equal num of samples per-process.")
+            sampler_val = torch.utils.data.DistributedSampler(dataset_val, num_replicas=num_tasks, rank=rank, shuffle=False)
+        else:
+            sampler_val = torch.utils.data.SequentialSampler(dataset_val)      # every rank evaluates the whole set
+        data_loader_val = torch.utils.data.DataLoader(dataset_val, sampler=sampler_val,
                                                       batch_size=int(1.5 * args.batch_size), num_workers=args.num_workers,
                                                       pin_memory=args.pin_mem, drop_last=False)
     model = get_model(args)
@@ -278,6 +293,20 @@ def main(args):
             print(f"{'froze' if name in frozen else 'kept'} {name}")
         print("Linear probing: the backbone is frozen (%d tensors), the trunk runs forward-only" % len(frozen))
     model.to(device)
+    eng = model.engine                                   # packs parameters into the flat buffers
+    # the model's drop-path / dropout generator is seeded from the run seed + rank HERE (every rank its own stream; one state
+    # per rank travels with the checkpoints), and the numerics switches of the run are recorded (utils.save_model: "numerics")
+    model._dp_stream = utils.DropPathStream()
+    model._dp_stream.seed(args.seed + utils.get_rank())
+    args.numerics = {"precision": "bf16",
+                     "gelu_dg": int(getattr(eng, "epi_gelu", None) == getattr(ops_mod(), "EPI_BIAS_GELU_DG", -1)),
+                     "dp_skip": bool(getattr(eng, "dp_skip", False))}
+    print("numerics:", args.numerics)
+    if args.distributed:
+        # BEFORE the EMA twin and the optimizer: both then see the weights rank 0 broadcast.  The loop drives the exchange
+        # through model._reducer (engine_for_finetuning.train_one_epoch): update micro-steps only, frozen trunk = head bucket
+        exchange = attach_reducer(model, eng, step_exchange=True)
+        print("Gradient exchange: %d bucket(s), %d bytes per update step" % (len(exchange.expected), exchange.bytes_per_step))
     model_ema = None
     if args.model_ema:
         model_ema = utils.ModelEma(model, decay=args.model_ema_decay, device="", resume="")

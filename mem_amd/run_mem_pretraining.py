@@ -25,7 +25,7 @@ from .datasets import build_pretraining_dataset
 from .engine_for_pretraining import evaluate, train_one_epoch
 from .modeling_pretrain import create_model
 from .optim_factory import create_optimizer
-from .parallel import GradReducer
+from .parallel import attach_reducer
 from .utils import NativeScalerWithGradNormCount as NativeScaler
 
 
@@ -257,13 +257,7 @@ def main(args):
                      "dp_skip": bool(getattr(eng, "dp_skip", False))}
     print("numerics:", args.numerics)
     if args.distributed:
-        # (parallel.py: reserve_cus > 0 leaves CUs to RCCL's channel kernels while buckets are in flight; no measurement on
-        # more than one GPU exists yet, so the default is 0 -- MEMHIP_RESERVE_CUS=16 tries it)
-        model._reducer = GradReducer(eng.flat_g, eng.buckets, flat_p=eng.flat_p,
-                                     reserve_cus=int(os.environ.get("MEMHIP_RESERVE_CUS", "0")),
-                                     streams=lambda: [torch.cuda.current_stream(), eng._side])
-        eng.grad_hook = model._reducer
-        eng.weights_dirty = True
+        attach_reducer(model, eng)         # (parallel.py: rank 0's weights everywhere, one all-reduce per bucket from backward)
     optimizer = create_optimizer(args, model_without_ddp)
     loss_scaler = NativeScaler()
     print("Use step level LR & WD scheduler!")
