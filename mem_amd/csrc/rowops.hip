@@ -8,6 +8,8 @@
 #include "common.h"
 #include "dropout.hpp"
 
+#include <type_traits>
+
 namespace {
 
 using namespace memhip;
@@ -32,65 +34,162 @@ __device__ __forceinline__ float div_newton(float a, float b, float r) {
 
 constexpr int kMaxChunks = 8;   // float4 chunks per lane: D <= 64*4*8 = 2048
 
+// ---------------------------------------------------------------- what the four row kernels share
+// NCH = float4 chunks per lane (D <= 256 * NCH): the per-lane arrays are sized for THIS D -- sized for the maximum they
+// cost 198 VGPRs (2 waves per SIMD) and the kernel could not hide HBM latency.  FULL: D == 256 * NCH, every lane owns
+// every chunk and the chunk guards do not exist (768, 1024, ...); ragged widths keep the guarded form.
+template <bool FULL>
+__device__ __forceinline__ bool chunk_ok(int i, int nch) {
+  if constexpr (FULL) return true;
+  else return i < nch;
+}
+
+// threadIdx.x >> 6 is the same in all 64 lanes but hipcc cannot prove it: through readfirstlane the row index, the map
+// lookups and the row statistics below are SGPR arithmetic and scalar loads, off the vector-memory queue
+__device__ __forceinline__ int wave_id() { return __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); }
+
+// rows r, r + stride, ... of one wave with their sample r / rps and offset r % rps: one division when the walk starts,
+// then smp += q, off += rem with one carry (stride = q * rps + rem)
+struct RowWalk {
+  int r, smp, off, stride, q, rem, rps;
+  __device__ __forceinline__ RowWalk(int r0, int stride_, int rps_) : r(r0), stride(stride_), rps(rps_) {
+    smp = r0 / rps; off = r0 - smp * rps;
+    q = stride / rps; rem = stride - q * rps;
+  }
+  __device__ __forceinline__ void next() {
+    r += stride; smp += q; off += rem;
+    if (off >= rps) { off -= rps; ++smp; }
+  }
+};
+
+// The per-column vectors (LayerNorm gamma / beta, layer scale) are read by every row: a workgroup copies them ONCE to the
+// front of its dynamic LDS (the column-sum area `red`, which is only needed after the row loop) and the rows read them with
+// ds_read_b128 -- they count on lgkmcnt and never sit between a row's loads and its stores.  b == NULL: ones.
+__device__ __forceinline__ void stage_columns(float4* dst, const float* a, const float* b, int nch) {
+  for (int i = threadIdx.x; i < nch; i += 256) {
+    dst[i] = reinterpret_cast<const float4*>(a)[i];
+    dst[nch + i] = b ? reinterpret_cast<const float4*>(b)[i] : float4{1.f, 1.f, 1.f, 1.f};
+  }
+  __syncthreads();
+}
+
+// The lane's index into the staged vectors, made opaque once per row: hipcc otherwise hoists the (loop-invariant) LDS
+// reads out of the row loop and keeps the vectors in registers -- the 12 VGPRs per vector that LDS is there to save.
+__device__ __forceinline__ int opaque(int v) {
+  asm volatile("" : "+v"(v));
+  return v;
+}
+
+// Rounding points.  The file is built with hipcc's default contraction (a * b + c may or may not become one fma, and
+// which of two products is the fused one follows the shape of the surrounding code; __fmul_rn is a plain product there).
+// Where a row output depends on it the choice is therefore written out, as the form these kernels have always computed:
+// mul_rn is a product that is rounded (never fused into a following add), __fmaf_rn a fused one -- a later change of the
+// code around them does not move a rounding.
+__device__ __forceinline__ float mul_rn(float a, float b) {
+#pragma clang fp contract(off)
+  return a * b;
+}
+__device__ __forceinline__ float sub_rn(float a, float b) {
+#pragma clang fp contract(off)
+  return a - b;
+}
+__device__ __forceinline__ float ln_dx(float gg, float xh, float m1, float m2) { return __fmaf_rn(-xh, m2, sub_rn(gg, m1)); }   // (gg - m1) - xh * m2, one rounding
+__device__ __forceinline__ float sq2(float a, float b) { return __fmaf_rn(a, a, mul_rn(b, b)); }   // a * a + round(b * b)
+
 // ---------------------------------------------------------------- LayerNorm forward
-// one wave per output row; x fp32 (row via row_idx), y bf16, mean/rstd saved for backward
+// one wave per output row; x fp32 (row via row_idx), y bf16, mean/rstd saved for backward.  One memory phase: the
+// workgroup's share of gamma / beta is requested right behind the row itself and parked in LDS while the two reductions run.
+template <int NCH, bool FULL>
 __global__ __launch_bounds__(256) void ln_fwd_kernel(const float* __restrict__ x, long long ldx,
                                                      const int* __restrict__ row_idx, int R, int D,
                                                      const float* __restrict__ gamma,
                                                      const float* __restrict__ beta, float eps,
                                                      __bf16* __restrict__ y, long long ldy,
                                                      float* __restrict__ mean, float* __restrict__ rstd) {
+  extern __shared__ float red[];   // gamma [D], beta [D]
   const int lane = threadIdx.x & 63;
-  const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (r >= R) return;
+  const int r0 = blockIdx.x * 4 + wave_id();
+  const bool act = r0 < R;                       // wave-uniform; an idle wave of the last workgroup redoes row R - 1 and stores nothing
+  const int r = act ? r0 : R - 1;
   const long long src = row_idx ? row_idx[r] : r;
   const float4* xr = reinterpret_cast<const float4*>(x + src * ldx);
   const int nch = D >> 2;
-  float4 v[kMaxChunks];
+  float4 v[NCH];
+#pragma unroll
+  for (int c = 0; c < NCH; ++c) {
+    const int i = lane + c * 64;
+    if (chunk_ok<FULL>(i, nch)) v[c] = xr[i];
+  }
+  constexpr int NST = (64 * NCH + 255) / 256;      // float4 pieces of gamma, and of beta, per thread
+  float4 sg[NST], sb[NST];
+#pragma unroll
+  for (int k = 0; k < NST; ++k) {           // unconditional (index clamped): under a lane mask hipcc waits for a load at once
+    const int i = min((int)threadIdx.x + k * 256, nch - 1);
+    sg[k] = reinterpret_cast<const float4*>(gamma)[i];
+    sb[k] = reinterpret_cast<const float4*>(beta)[i];
+  }
+  __builtin_amdgcn_sched_barrier(0);          // (hipcc otherwise sinks these loads behind the first reduction)
   float s = 0.f;
 #pragma unroll
-  for (int c = 0; c < kMaxChunks; ++c) {
-    const int i = lane + c * 64;
-    if (i < nch) { v[c] = xr[i]; s += (v[c].x + v[c].y) + (v[c].z + v[c].w); }
-  }
+  for (int c = 0; c < NCH; ++c)
+    if (chunk_ok<FULL>(lane + c * 64, nch)) s += (v[c].x + v[c].y) + (v[c].z + v[c].w);
   const float mu = wsum(s) / (float)D;
+  float4* lgb = reinterpret_cast<float4*>(red);
+#pragma unroll
+  for (int k = 0; k < NST; ++k) {           // (threads past the end write the last piece once more: the same value)
+    const int i = min((int)threadIdx.x + k * 256, nch - 1);
+    lgb[i] = sg[k];
+    lgb[nch + i] = sb[k];
+  }
   float q = 0.f;
 #pragma unroll
-  for (int c = 0; c < kMaxChunks; ++c) {
-    const int i = lane + c * 64;
-    if (i < nch) {
+  for (int c = 0; c < NCH; ++c) {
+    if (chunk_ok<FULL>(lane + c * 64, nch)) {
       const float a = v[c].x - mu, b = v[c].y - mu, cc = v[c].z - mu, d = v[c].w - mu;
-      q += (a * a + b * b) + (cc * cc + d * d);
+      q += sq2(a, b) + sq2(cc, d);
     }
   }
   const float var = wsum(q) / (float)D;          // biased, as nn.LayerNorm
   const float rs = 1.0f / sqrtf(var + eps);
+  __syncthreads();
+  if (!act) return;
   if (lane == 0) { mean[r] = mu; rstd[r] = rs; }
-  const float4* g4 = reinterpret_cast<const float4*>(gamma);
-  const float4* b4 = reinterpret_cast<const float4*>(beta);
   bf16x4* yr = reinterpret_cast<bf16x4*>(y + (long long)r * ldy);
 #pragma unroll
-  for (int c = 0; c < kMaxChunks; ++c) {
+  for (int c = 0; c < NCH; ++c) {
     const int i = lane + c * 64;
-    if (i < nch) {
-      const float4 g = g4[i], b = b4[i];
+    if (chunk_ok<FULL>(i, nch)) {
+      const float4 g = lgb[i], b = lgb[nch + i];
       bf16x4 o;
-      o[0] = (__bf16)((v[c].x - mu) * rs * g.x + b.x);
-      o[1] = (__bf16)((v[c].y - mu) * rs * g.y + b.y);
-      o[2] = (__bf16)((v[c].z - mu) * rs * g.z + b.z);
-      o[3] = (__bf16)((v[c].w - mu) * rs * g.w + b.w);
+      o[0] = (__bf16)__fmaf_rn(mul_rn(v[c].x - mu, rs), g.x, b.x);
+      o[1] = (__bf16)__fmaf_rn(mul_rn(v[c].y - mu, rs), g.y, b.y);
+      o[2] = (__bf16)__fmaf_rn(mul_rn(v[c].z - mu, rs), g.z, b.z);
+      o[3] = (__bf16)__fmaf_rn(mul_rn(v[c].w - mu, rs), g.w, b.w);
       yr[i] = o;
     }
   }
 }
 
 // ---------------------------------------------------------------- LayerNorm backward
-// workgroup = 4 waves x kRowsPerWave rows; dx per row (wave reductions), dgamma/dbeta per lane
-// column accumulated in registers over the workgroup's rows, then LDS -> one atomic per column.
+// workgroup = 4 waves; dx per row (wave reductions), dgamma/dbeta per lane column accumulated in registers over the
+// workgroup's rows, then LDS -> one atomic per column.
+//
+// The row loop of the three backward kernels is a three-deep software pipeline, all of it wave-uniform control flow:
+//   row k + 2: its bookkeeping (row_idx / sample maps) is fetched with scalar loads,
+//   row k + 1: its row loads are issued (addresses known since the iteration before) together with the scalar loads of
+//              its statistics,
+//   row k    : is reduced and stored; behind its stores the row of dres that row k + 1 adds to is requested (it is only
+//              needed behind k + 1's reductions, and asked for this late it needs no second set of registers).
+// vmcnt counts loads and stores in issue order, so a wait can leave the younger operations in flight only if their number
+// is the same on every path that reaches it.  In the row loop every load and store is therefore UNCONDITIONAL:
+//  - the loop only walks rows that take full part (the bookkeeping skips the others: scalar work, no vector memory),
+//  - the wave's last row, which has no successor to request, requests itself again (one row per wave from the caches).
+// The waits are then counted (vmcnt(n) with the next row's loads and this row's stores behind them), the next row's
+// loads stay in flight across the reductions and the stores, and a store is never waited for.  The loop is entered with
+// an empty queue (vm_drain), so that the counts that hold on its back-edge hold at its head.
+__device__ __forceinline__ void vm_drain() { __builtin_amdgcn_s_waitcnt(0x0F70); }   // s_waitcnt vmcnt(0) alone
 
-// NCH = float4 chunks per lane (D <= 256 * NCH): the per-lane arrays are sized for THIS D -- sized for the
-// maximum they cost 198 VGPRs (2 waves per SIMD) and the kernel could not hide HBM latency.
-template <int NCH>
+template <int NCH, bool FULL, bool ACC>
 __global__ __launch_bounds__(256) void ln_bwd_kernel(const __bf16* __restrict__ dy, long long lddy,
                                                      const float* __restrict__ x, long long ldx,
                                                      const int* __restrict__ row_idx, int R, int D,
@@ -98,68 +197,122 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const __bf16* __restrict__ 
                                                      const float* __restrict__ mean,
                                                      const float* __restrict__ rstd,
                                                      float* __restrict__ dres, long long lddres,
-                                                     int accumulate, float* __restrict__ dgamma,
-                                                     float* __restrict__ dbeta) {
-  extern __shared__ float red[];   // [4][2][D]
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+                                                     float* __restrict__ dgamma, float* __restrict__ dbeta) {
+  extern __shared__ float red[];   // [4][2][D]; during the row loop its front holds gamma [D]
+  const int lane = threadIdx.x & 63, wave = wave_id();
   const int nch = D >> 2;
-  const float4* g4 = reinterpret_cast<const float4*>(gamma);
-  float4 ag[NCH], ab[NCH], gm[NCH];
+  float4 ag[NCH], ab[NCH];
 #pragma unroll
   for (int c = 0; c < NCH; ++c) {
     ag[c] = float4{0, 0, 0, 0};
     ab[c] = float4{0, 0, 0, 0};
-    gm[c] = (lane + c * 64 < nch) ? g4[lane + c * 64] : float4{0, 0, 0, 0};
   }
   // rows are dealt to (workgroup, wave) round-robin: the column accumulators persist over ALL of a
   // workgroup's rows, so the number of same-address atomics is gridDim.x per column, not R/32
-  for (int r = blockIdx.x * 4 + wave; r < R; r += gridDim.x * 4) {
-    const long long src = row_idx ? row_idx[r] : r;
+  const int rstride = gridDim.x * 4;
+  float4 xn[NCH], prev[NCH];
+  bf16x4 dn[NCH];
+  auto issue = [&](int r, long long src, int lane) {
     const float4* xr = reinterpret_cast<const float4*>(x + src * ldx);
     const bf16x4* dyr = reinterpret_cast<const bf16x4*>(dy + (long long)r * lddy);
-    const float mu = mean[r], rs = rstd[r];
-    float4 xh[NCH], gg[NCH], prev[NCH];
-    float4* o = reinterpret_cast<float4*>(dres + src * lddres);
-    if (accumulate) {                       // issued with the row, not after the reductions
-#pragma unroll
-      for (int c = 0; c < NCH; ++c)
-        if (lane + c * 64 < nch) prev[c] = o[lane + c * 64];
-    }
-    float s1 = 0.f, s2 = 0.f;
 #pragma unroll
     for (int c = 0; c < NCH; ++c) {
       const int i = lane + c * 64;
-      if (i < nch) {
-        const float4 xv = xr[i];
-        const bf16x4 d4 = dyr[i];
-        const float4 g = gm[c];
+      if (chunk_ok<FULL>(i, nch)) {
+        xn[c] = xr[i];
+        dn[c] = dyr[i];
+      }
+    }
+  };
+  auto issue_prev = [&](long long src, int lane) {
+    const float4* o = reinterpret_cast<const float4*>(dres + src * lddres);
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) {
+      const int i = lane + c * 64;
+      if (chunk_ok<FULL>(i, nch)) prev[c] = o[i];
+    }
+  };
+  int r = blockIdx.x * 4 + wave;
+  long long src = 0;
+  float mu = 0.f, rs = 0.f;
+  if (r < R) {                     // the first row is on its way while gamma is staged
+    src = row_idx ? row_idx[r] : r;
+    issue(r, src, lane);
+    if constexpr (ACC) issue_prev(src, lane);
+    mu = mean[r]; rs = rstd[r];
+  }
+  float4* lg = reinterpret_cast<float4*>(red);
+  for (int i = threadIdx.x; i < nch; i += 256) lg[i] = reinterpret_cast<const float4*>(gamma)[i];
+  __syncthreads();
+  int r1 = r + rstride;
+  long long src1 = 0;
+  if (r1 < R) src1 = row_idx ? row_idx[r1] : r1;
+  int r2 = r1 + rstride;
+  vm_drain();
+  while (r < R) {
+    float4 xh[NCH], gg[NCH];
+    float s1 = 0.f, s2 = 0.f;
+    const int ol = opaque(lane);                     // (also keeps hipcc from hoisting a 64-bit lane pointer per stream)
+    const float4* lgl = lg + ol;
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) {
+      const int i = lane + c * 64;
+      if (chunk_ok<FULL>(i, nch)) {
+        const float4 xv = xn[c];
+        const bf16x4 d4 = dn[c];
+        const float4 g = lgl[c * 64];
         const float d0 = (float)d4[0], d1 = (float)d4[1], d2 = (float)d4[2], d3 = (float)d4[3];
-        xh[c] = float4{(xv.x - mu) * rs, (xv.y - mu) * rs, (xv.z - mu) * rs, (xv.w - mu) * rs};
-        gg[c] = float4{d0 * g.x, d1 * g.y, d2 * g.z, d3 * g.w};
+        xh[c] = float4{mul_rn(xv.x - mu, rs), mul_rn(xv.y - mu, rs), mul_rn(xv.z - mu, rs), mul_rn(xv.w - mu, rs)};
+        gg[c] = float4{mul_rn(d0, g.x), mul_rn(d1, g.y), mul_rn(d2, g.z), mul_rn(d3, g.w)};
         s1 += (gg[c].x + gg[c].y) + (gg[c].z + gg[c].w);
-        s2 += (gg[c].x * xh[c].x + gg[c].y * xh[c].y) + (gg[c].z * xh[c].z + gg[c].w * xh[c].w);
+        s2 += (mul_rn(gg[c].x, xh[c].x) + mul_rn(gg[c].y, xh[c].y)) + (mul_rn(gg[c].z, xh[c].z) + mul_rn(gg[c].w, xh[c].w));
         ag[c].x += d0 * xh[c].x; ag[c].y += d1 * xh[c].y; ag[c].z += d2 * xh[c].z; ag[c].w += d3 * xh[c].w;
         ab[c].x += d0; ab[c].y += d1; ab[c].z += d2; ab[c].w += d3;
       }
     }
+    float mu1 = 0.f, rs1 = 0.f;
+    long long src2 = 0;
+    const bool next = r1 < R;
+    const int rl = next ? r1 : r;                    // the last row requests itself again
+    const long long srcl = next ? src1 : src;
+    issue(rl, srcl, ol);
+    if (next) {
+      mu1 = mean[r1]; rs1 = rstd[r1];
+      if (r2 < R) src2 = row_idx ? row_idx[r2] : r2;
+    }
     const float m1 = wsum(s1) / (float)D, m2 = wsum(s2) / (float)D;
+    float4* o = reinterpret_cast<float4*>(dres + src * lddres);
 #pragma unroll
     for (int c = 0; c < NCH; ++c) {
-      const int i = lane + c * 64;
-      if (i < nch) {
-        float4 d{rs * (gg[c].x - m1 - xh[c].x * m2), rs * (gg[c].y - m1 - xh[c].y * m2),
-                 rs * (gg[c].z - m1 - xh[c].z * m2), rs * (gg[c].w - m1 - xh[c].w * m2)};
-        if (accumulate) { const float4 p = prev[c]; d.x += p.x; d.y += p.y; d.z += p.z; d.w += p.w; }
+      const int i = ol + c * 64;
+      if (chunk_ok<FULL>(i, nch)) {
+        const float4 t{ln_dx(gg[c].x, xh[c].x, m1, m2), ln_dx(gg[c].y, xh[c].y, m1, m2),
+                       ln_dx(gg[c].z, xh[c].z, m1, m2), ln_dx(gg[c].w, xh[c].w, m1, m2)};
+        float4 d;
+        if constexpr (ACC) {
+          const float4 p = prev[c];
+          d = float4{__fmaf_rn(rs, t.x, p.x), __fmaf_rn(rs, t.y, p.y), __fmaf_rn(rs, t.z, p.z), __fmaf_rn(rs, t.w, p.w)};
+        } else {
+          d = float4{mul_rn(rs, t.x), mul_rn(rs, t.y), mul_rn(rs, t.z), mul_rn(rs, t.w)};
+        }
         o[i] = d;
       }
     }
+    if constexpr (ACC) {
+      __builtin_amdgcn_sched_barrier(0);             // no load between the row's stores
+      issue_prev(srcl, ol);
+    }
+    r = r1; src = src1; mu = mu1; rs = rs1;
+    r1 = r2; src1 = src2;
+    r2 += rstride;
   }
+  __syncthreads();                 // every wave is done with gamma: `red` becomes the column-sum area
   float4* rg = reinterpret_cast<float4*>(red + (size_t)wave * 2 * D);
   float4* rb = reinterpret_cast<float4*>(red + (size_t)wave * 2 * D + D);
 #pragma unroll
   for (int c = 0; c < NCH; ++c) {
     const int i = lane + c * 64;
-    if (i < nch) { rg[i] = ag[c]; rb[i] = ab[c]; }
+    if (chunk_ok<FULL>(i, nch)) { rg[i] = ag[c]; rb[i] = ab[c]; }
   }
   __syncthreads();
   for (int n = threadIdx.x; n < D; n += 256) {
@@ -181,7 +334,7 @@ constexpr int kBrMaxChunks = 8;   // float4 chunks per lane: D <= 2048
 
 // Drop = {DropParams} (memhip_branch_bwd_drop): the branch had element-wise dropout, dt -> dt * keep * scale; empty: no
 // dropout (the kernel arguments and code of that form are those without the parameter)
-template <int NCH, class... Drop>
+template <int NCH, bool FULL, bool HAS_Y, class... Drop>
 __global__ __launch_bounds__(256) void branch_bwd_kernel(const float* __restrict__ dx, long long lddx,
                                                          const __bf16* __restrict__ y, long long ldy,
                                                          const float* __restrict__ gamma,
@@ -192,92 +345,119 @@ __global__ __launch_bounds__(256) void branch_bwd_kernel(const float* __restrict
                                                          Drop... drop) {
   // out_map (work-skipping stochastic depth): sample -> index of the sample among the KEPT ones, or -1.  The rows of a
   // dropped sample are neither read nor written; kept rows land at their compact position and are scaled by 1 / keep.
-  extern __shared__ float red[];   // [4][2][D]
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  extern __shared__ float red[];   // [4][2][D]; during the row loop its front holds gamma [D] (ones without one)
+  const int lane = threadIdx.x & 63, wave = wave_id();
   const int nch = D >> 2;
-  float4 g[NCH], ag[NCH], ab[NCH];
+  float4 ag[NCH], ab[NCH];
   const float rk = __frcp_rn(keep);
 #pragma unroll
   for (int c = 0; c < NCH; ++c) {
-    const int i = lane + c * 64;
-    g[c] = (gamma && i < nch) ? reinterpret_cast<const float4*>(gamma)[i] : float4{1.f, 1.f, 1.f, 1.f};
     ag[c] = float4{0, 0, 0, 0};
     ab[c] = float4{0, 0, 0, 0};
   }
-  // two rows per iteration: both rows' loads are in flight before either is consumed
-  const int stride = gridDim.x * 4;
-  for (int m0 = blockIdx.x * 4 + wave; m0 < M; m0 += 2 * stride) {
-    float4 dv[2][NCH];
-    bf16x4 yv[2][NCH];
-    float kk[2];
-    long long mo[2];                                       // output row (-1: nothing to do for this row)
+  // the pipeline of ln_bwd_kernel: maps two rows ahead, row loads one row ahead
+  float4 dn[NCH];
+  bf16x4 yn[HAS_Y ? NCH : 1];
+  auto issue = [&](int m, int lane) {
+    const float4* dr = reinterpret_cast<const float4*>(dx + (long long)m * lddx);
 #pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      const int m = m0 + u * stride;
-      const int mc = m < M ? m : M - 1;
-      const float4* dr = reinterpret_cast<const float4*>(dx + (long long)mc * lddx);
-      kk[u] = rowmask ? rowmask[mc / rps] : 1.f;
-      mo[u] = m < M ? m : -1;
-      if (out_map && m < M) {
-        const int smp = mc / rps, co = out_map[smp];
-        mo[u] = co < 0 ? -1 : (long long)co * rps + (mc - smp * rps);
-      }
-      if (mo[u] < 0) continue;
-#pragma unroll
-      for (int c = 0; c < NCH; ++c) {
-        const int i = lane + c * 64;
-        if (i < nch) {
-          dv[u][c] = dr[i];
-          if (y) yv[u][c] = reinterpret_cast<const bf16x4*>(y + (long long)mc * ldy)[i];
-        }
+    for (int c = 0; c < NCH; ++c) {
+      const int i = lane + c * 64;
+      if (chunk_ok<FULL>(i, nch)) {
+        dn[c] = dr[i];
+        if constexpr (HAS_Y) yn[c] = reinterpret_cast<const bf16x4*>(y + (long long)m * ldy)[i];
       }
     }
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      if (mo[u] < 0) continue;
-      bf16x4* orow = reinterpret_cast<bf16x4*>(dyo + mo[u] * lddy);
-      const float k = kk[u];
-#pragma unroll
-      for (int c = 0; c < NCH; ++c) {
-        const int i = lane + c * 64;
-        if (i < nch) {
-          float4 d = dv[u][c];
-          if (rowmask || out_map) {            // (dx * mask) / keep: reciprocal + one Newton step = the IEEE quotient
-            d.x = div_newton(d.x * k, keep, rk); d.y = div_newton(d.y * k, keep, rk);
-            d.z = div_newton(d.z * k, keep, rk); d.w = div_newton(d.w * k, keep, rk);
-          }
-          if constexpr (sizeof...(Drop) > 0) {   // the lane's 4 columns 4i.. are one half of the 8-column group i / 2
-            const DropParams dp = (drop, ...);
-            const unsigned kb = dropout_keep8(dp, (unsigned)(dp.row0 + m0 + u * stride), (unsigned)(i >> 1)) >> ((i & 1) * 4);
-            d.x = __fmul_rn(d.x, dropout_mul(dp, kb, 0)); d.y = __fmul_rn(d.y, dropout_mul(dp, kb, 1));
-            d.z = __fmul_rn(d.z, dropout_mul(dp, kb, 2)); d.w = __fmul_rn(d.w, dropout_mul(dp, kb, 3));
-          }
-          if (y) {
-            const bf16x4 yy = yv[u][c];
-            ag[c].x += d.x * (float)yy[0]; ag[c].y += d.y * (float)yy[1];
-            ag[c].z += d.z * (float)yy[2]; ag[c].w += d.w * (float)yy[3];
-          }
-          bf16x4 o;
-          o[0] = (__bf16)(d.x * g[c].x); o[1] = (__bf16)(d.y * g[c].y);
-          o[2] = (__bf16)(d.z * g[c].z); o[3] = (__bf16)(d.w * g[c].w);
-          orow[i] = o;
-          ab[c].x += (float)o[0]; ab[c].y += (float)o[1]; ab[c].z += (float)o[2]; ab[c].w += (float)o[3];
-        }
-      }
+  };
+  RowWalk w(blockIdx.x * 4 + wave, gridDim.x * 4, rps);
+  // the wave's next row that has an output row (rows of dropped samples have nothing to do); leaves w behind it
+  auto find = [&](int& m, int& mo, int& smp) {
+    for (;;) {
+      m = w.r; smp = w.smp; mo = -1;
+      if (m >= M) return;
+      mo = w.r;
+      if (out_map) { const int co = out_map[w.smp]; mo = co < 0 ? -1 : co * w.rps + w.off; }
+      w.next();
+      if (mo >= 0) return;
     }
+  };
+  int m, mo, smp;
+  float k = 1.f;
+  find(m, mo, smp);
+  if (m < M) {                     // the first row is on its way while gamma is staged
+    issue(m, lane);
+    if (rowmask) k = rowmask[smp];
   }
+  float4* lg = reinterpret_cast<float4*>(red);
+  for (int i = threadIdx.x; i < nch; i += 256)
+    lg[i] = gamma ? reinterpret_cast<const float4*>(gamma)[i] : float4{1.f, 1.f, 1.f, 1.f};
+  __syncthreads();
+  int m1, mo1, smp1;
+  find(m1, mo1, smp1);
+  vm_drain();
+  while (m < M) {
+    const int ol = opaque(lane);                     // (also keeps hipcc from hoisting a 64-bit lane pointer per stream)
+    float4 dv[NCH];
+    bf16x4 yv[HAS_Y ? NCH : 1];
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) {
+      if (chunk_ok<FULL>(lane + c * 64, nch)) {
+        dv[c] = dn[c];
+        if constexpr (HAS_Y) yv[c] = yn[c];
+      }
+    }
+    float k1 = 1.f;
+    const bool next = m1 < M;
+    issue(next ? m1 : m, ol);                  // the last row requests itself again
+    if (next && rowmask) k1 = rowmask[smp1];
+    int m2, mo2, smp2;
+    find(m2, mo2, smp2);
+    bf16x4* orow = reinterpret_cast<bf16x4*>(dyo + (long long)mo * lddy);
+    const float4* lgl = lg + ol;
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) {
+      const int i = ol + c * 64;
+      if (chunk_ok<FULL>(i, nch)) {
+        float4 d = dv[c];
+        if (rowmask || out_map) {            // (dx * mask) / keep: reciprocal + one Newton step = the IEEE quotient
+          d.x = div_newton(d.x * k, keep, rk); d.y = div_newton(d.y * k, keep, rk);
+          d.z = div_newton(d.z * k, keep, rk); d.w = div_newton(d.w * k, keep, rk);
+        }
+        if constexpr (sizeof...(Drop) > 0) {   // the lane's 4 columns 4i.. are one half of the 8-column group i / 2
+          const DropParams dp = (drop, ...);
+          const unsigned kb = dropout_keep8(dp, (unsigned)(dp.row0 + m), (unsigned)(i >> 1)) >> ((i & 1) * 4);
+          d.x = __fmul_rn(d.x, dropout_mul(dp, kb, 0)); d.y = __fmul_rn(d.y, dropout_mul(dp, kb, 1));
+          d.z = __fmul_rn(d.z, dropout_mul(dp, kb, 2)); d.w = __fmul_rn(d.w, dropout_mul(dp, kb, 3));
+        }
+        if constexpr (HAS_Y) {
+          const bf16x4 yy = yv[c];
+          ag[c].x += d.x * (float)yy[0]; ag[c].y += d.y * (float)yy[1];
+          ag[c].z += d.z * (float)yy[2]; ag[c].w += d.w * (float)yy[3];
+        }
+        const float4 g = lgl[c * 64];
+        bf16x4 o;
+        o[0] = (__bf16)(d.x * g.x); o[1] = (__bf16)(d.y * g.y);
+        o[2] = (__bf16)(d.z * g.z); o[3] = (__bf16)(d.w * g.w);
+        orow[i] = o;
+        ab[c].x += (float)o[0]; ab[c].y += (float)o[1]; ab[c].z += (float)o[2]; ab[c].w += (float)o[3];
+      }
+    }
+    m = m1; mo = mo1; k = k1;
+    m1 = m2; mo1 = mo2; smp1 = smp2;
+  }
+  __syncthreads();                 // every wave is done with gamma: `red` becomes the column-sum area
   float4* rg = reinterpret_cast<float4*>(red + (size_t)wave * 2 * D);
   float4* rb = reinterpret_cast<float4*>(red + (size_t)wave * 2 * D + D);
 #pragma unroll
   for (int c = 0; c < NCH; ++c) {
     const int i = lane + c * 64;
-    if (i < nch) { rg[i] = ag[c]; rb[i] = ab[c]; }
+    if (chunk_ok<FULL>(i, nch)) { rg[i] = ag[c]; rb[i] = ab[c]; }
   }
   __syncthreads();
   for (int n = threadIdx.x; n < D; n += 256) {
     float a = 0.f, b = 0.f;
 #pragma unroll
-    for (int w = 0; w < 4; ++w) { a += red[(size_t)w * 2 * D + n]; b += red[(size_t)w * 2 * D + D + n]; }
+    for (int w2 = 0; w2 < 4; ++w2) { a += red[(size_t)w2 * 2 * D + n]; b += red[(size_t)w2 * 2 * D + D + n]; }
     if (dgamma) atomicAdd(dgamma + n, a);
     if (dbias) atomicAdd(dbias + n, b);
   }
@@ -290,7 +470,7 @@ __global__ __launch_bounds__(256) void branch_bwd_kernel(const float* __restrict
 //   dx[r] += LN'(dy[r]) ;  dt = dx[r] * mask[r / rps] / keep ;  dyb[r] = bf16(dt * gb) ;
 //   dgamma_ln += sum dy*xhat ; dbeta_ln += sum dy ; dgb += sum dt*y ; dbias_b += sum dyb
 // Drop = {DropParams} (memhip_layernorm_bwd_branch_drop): the produced branch gradient carries the branch's dropout mask
-template <int NCH, bool HAS_Y, class... Drop>
+template <int NCH, bool FULL, bool HAS_Y, class... Drop>
 __global__ __launch_bounds__(256) void ln_bwd_branch_kernel(const __bf16* __restrict__ dy, long long lddy,
                                                             const float* __restrict__ x, long long ldx, int R, int D,
                                                             const float* __restrict__ gamma,
@@ -307,12 +487,10 @@ __global__ __launch_bounds__(256) void ln_bwd_branch_kernel(const __bf16* __rest
   // among the samples the LayerNorm'ed branch KEPT (dy, mean, rstd hold those samples only), -1: that branch skipped the
   // sample, its rows get no LayerNorm gradient.  out_map: the same for the branch whose output gradient is produced
   // (dyo holds the kept samples only, scaled by 1 / keep), -1: no output row.  NULL = identity.
-  extern __shared__ float red[];   // [4][4][D]
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  extern __shared__ float red[];   // [4][4][D]; during the row loop its front holds gamma [D] and gb [D] (ones without one)
+  const int lane = threadIdx.x & 63, wave = wave_id();
   const int nch = D >> 2;
-  float4 ag[NCH], ab[NCH], bg[HAS_Y ? NCH : 1], bb[NCH];      // the gamma vectors are re-read per row (L1): 24 VGPRs
-  const float4* g4 = reinterpret_cast<const float4*>(gamma);
-  const float4* gb4 = reinterpret_cast<const float4*>(gb);
+  float4 ag[NCH], ab[NCH], bg[HAS_Y ? NCH : 1], bb[NCH];      // the gamma vectors are re-read per row (LDS): 24 VGPRs
   const float rk = __frcp_rn(keep);
 #pragma unroll
   for (int c = 0; c < NCH; ++c) {
@@ -320,81 +498,94 @@ __global__ __launch_bounds__(256) void ln_bwd_branch_kernel(const __bf16* __rest
     if (HAS_Y) bg[c] = float4{0, 0, 0, 0};
   }
   // software prefetch: the raw loads of the wave's NEXT row are issued before the current row is reduced
-  const int rstride = gridDim.x * 4;
-  float4 xn[NCH], pn[NCH];
+  float4 xn[NCH], prev[NCH];
   bf16x4 dn[NCH], yn[HAS_Y ? NCH : 1];
-  long long rin_n = 0, rout_n = 0;                 // compact rows of the row whose loads are in flight (-1: not taking part)
-  auto load_row = [&](int r) {
-    rin_n = r; rout_n = r;
-    if (in_map || out_map) {
-      const int smp = r / rps, off = r - smp * rps;
-      if (in_map) { const int ci = in_map[smp]; rin_n = ci < 0 ? -1 : (long long)ci * rps + off; }
-      if (out_map) { const int co = out_map[smp]; rout_n = co < 0 ? -1 : (long long)co * rps + off; }
-    }
-    if (rin_n < 0 && rout_n < 0) return;
+  auto issue_x = [&](int r, int rin, int lane) {           // rin: the row's compact row in dy
     const float4* xr = reinterpret_cast<const float4*>(x + (long long)r * ldx);
-    const bf16x4* dyr = reinterpret_cast<const bf16x4*>(dy + (rin_n < 0 ? 0 : rin_n) * lddy);
+    const bf16x4* dyr = reinterpret_cast<const bf16x4*>(dy + (long long)rin * lddy);
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) {
+      const int i = lane + c * 64;
+      if (chunk_ok<FULL>(i, nch)) {
+        xn[c] = xr[i];
+        dn[c] = dyr[i];
+      }
+    }
+  };
+  auto issue_y = [&](int r, int lane) {
+    if constexpr (HAS_Y) {
+#pragma unroll
+      for (int c = 0; c < NCH; ++c) {
+        const int i = lane + c * 64;
+        if (chunk_ok<FULL>(i, nch)) yn[c] = reinterpret_cast<const bf16x4*>(yb + (long long)r * ldyb)[i];
+      }
+    }
+  };
+  auto issue_prev = [&](int r, int lane) {
     const float4* o = reinterpret_cast<const float4*>(dres + (long long)r * lddres);
 #pragma unroll
     for (int c = 0; c < NCH; ++c) {
       const int i = lane + c * 64;
-      if (i < nch) {
-        pn[c] = o[i];
-        if (rin_n >= 0) {
-          xn[c] = xr[i];
-          dn[c] = dyr[i];
+      if (chunk_ok<FULL>(i, nch)) prev[c] = o[i];
+    }
+  };
+  const int row0 = blockIdx.x * 4 + wave, rstride = gridDim.x * 4;
+  auto resolve = [&](const RowWalk& t, int& rin, int& rout) {      // compact rows (-1: not taking part)
+    rin = rout = t.r;
+    if (in_map) { const int ci = in_map[t.smp]; rin = ci < 0 ? -1 : ci * t.rps + t.off; }
+    if (out_map) { const int co = out_map[t.smp]; rout = co < 0 ? -1 : co * t.rps + t.off; }
+  };
+  int r, rin, rout;
+  float mu = 0.f, rs = 0.f, km = 1.f;
+  float4 xh[NCH], gg[NCH];
+  bf16x4 yv[HAS_Y ? NCH : 1];
+  float s1, s2;
+  float4 *lg = reinterpret_cast<float4*>(red), *lgb = lg + nch;
+  // the two halves of a row's step, on the state above
+  // ol: the lane, opaque once per row (also keeps hipcc from hoisting a 64-bit lane pointer per stream)
+  auto reduce_row = [&](bool has_in, int ol) {
+    s1 = s2 = 0.f;
+    const float4* lgl = lg + ol;
+    if (has_in) {
+#pragma unroll
+      for (int c = 0; c < NCH; ++c) {
+        if (chunk_ok<FULL>(lane + c * 64, nch)) {
+          if constexpr (HAS_Y) yv[c] = yn[c];
+          const float4 xv = xn[c];
+          const bf16x4 d4 = dn[c];
+          const float d0 = (float)d4[0], d1 = (float)d4[1], d2 = (float)d4[2], d3 = (float)d4[3];
+          xh[c] = float4{mul_rn(xv.x - mu, rs), mul_rn(xv.y - mu, rs), mul_rn(xv.z - mu, rs), mul_rn(xv.w - mu, rs)};
+          const float4 gmc = lgl[c * 64];
+          gg[c] = float4{mul_rn(d0, gmc.x), mul_rn(d1, gmc.y), mul_rn(d2, gmc.z), mul_rn(d3, gmc.w)};
+          s1 += (gg[c].x + gg[c].y) + (gg[c].z + gg[c].w);
+          s2 += (mul_rn(gg[c].x, xh[c].x) + mul_rn(gg[c].y, xh[c].y)) + (mul_rn(gg[c].z, xh[c].z) + mul_rn(gg[c].w, xh[c].w));
+          ag[c].x += d0 * xh[c].x; ag[c].y += d1 * xh[c].y; ag[c].z += d2 * xh[c].z; ag[c].w += d3 * xh[c].w;
+          ab[c].x += d0; ab[c].y += d1; ab[c].z += d2; ab[c].w += d3;
         }
-        if constexpr (HAS_Y) yn[c] = reinterpret_cast<const bf16x4*>(yb + (long long)r * ldyb)[i];
+      }
+    } else {                                         // no LayerNorm gradient for this row (rs = 0 below: d = prev)
+#pragma unroll
+      for (int c = 0; c < NCH; ++c) {
+        if (chunk_ok<FULL>(lane + c * 64, nch)) {
+          if constexpr (HAS_Y) yv[c] = yn[c];
+          xh[c] = gg[c] = float4{0.f, 0.f, 0.f, 0.f};
+        }
       }
     }
   };
-  int r = blockIdx.x * 4 + wave;
-  if (r < R) load_row(r);
-  for (; r < R; r += rstride) {
-    const long long rin = rin_n, rout = rout_n;
-    if (rin < 0 && rout < 0) {                     // dropped by both branches: the row of dres stays as it is
-      if (r + rstride < R) load_row(r + rstride);
-      continue;
-    }
-    float4* o = reinterpret_cast<float4*>(dres + (long long)r * lddres);
-    const float mu = rin >= 0 ? mean[rin] : 0.f, rs = rin >= 0 ? rstd[rin] : 0.f;
-    const float km = rowmask ? rowmask[r / rps] : 1.f;
-    float4 xh[NCH], gg[NCH], prev[NCH];
-    bf16x4 yv[HAS_Y ? NCH : 1];
-    float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-      const int i = lane + c * 64;
-      if (i < nch) {
-        prev[c] = pn[c];
-        if constexpr (HAS_Y) yv[c] = yn[c];
-        if (rin < 0) {                             // no LayerNorm gradient for this row (rs = 0 below: d = prev)
-          xh[c] = gg[c] = float4{0.f, 0.f, 0.f, 0.f};
-          continue;
-        }
-        const float4 xv = xn[c];
-        const bf16x4 d4 = dn[c];
-        const float d0 = (float)d4[0], d1 = (float)d4[1], d2 = (float)d4[2], d3 = (float)d4[3];
-        xh[c] = float4{(xv.x - mu) * rs, (xv.y - mu) * rs, (xv.z - mu) * rs, (xv.w - mu) * rs};
-        const float4 gmc = g4[i];
-        gg[c] = float4{d0 * gmc.x, d1 * gmc.y, d2 * gmc.z, d3 * gmc.w};
-        s1 += (gg[c].x + gg[c].y) + (gg[c].z + gg[c].w);
-        s2 += (gg[c].x * xh[c].x + gg[c].y * xh[c].y) + (gg[c].z * xh[c].z + gg[c].w * xh[c].w);
-        ag[c].x += d0 * xh[c].x; ag[c].y += d1 * xh[c].y; ag[c].z += d2 * xh[c].z; ag[c].w += d3 * xh[c].w;
-        ab[c].x += d0; ab[c].y += d1; ab[c].z += d2; ab[c].w += d3;
-      }
-    }
-    if (r + rstride < R) load_row(r + rstride);
+  auto store_row = [&](bool has_in, bool has_out, int ol) {
     const float m1 = wsum(s1) / (float)D, m2 = wsum(s2) / (float)D;
-    bf16x4* orow = reinterpret_cast<bf16x4*>(dyo + (rout < 0 ? 0 : rout) * lddyo);
+    float4* o = reinterpret_cast<float4*>(dres + (long long)r * lddres);
+    bf16x4* orow = reinterpret_cast<bf16x4*>(dyo + (long long)(has_out ? rout : 0) * lddyo);
+    const float4* lgbl = lgb + ol;
 #pragma unroll
     for (int c = 0; c < NCH; ++c) {
-      const int i = lane + c * 64;
-      if (i < nch) {
-        float4 d{prev[c].x + rs * (gg[c].x - m1 - xh[c].x * m2), prev[c].y + rs * (gg[c].y - m1 - xh[c].y * m2),
-                 prev[c].z + rs * (gg[c].z - m1 - xh[c].z * m2), prev[c].w + rs * (gg[c].w - m1 - xh[c].w * m2)};
-        if (rin >= 0) o[i] = d;
-        if (rout < 0) continue;
+      const int i = ol + c * 64;
+      if (chunk_ok<FULL>(i, nch)) {
+        float4 d{__fmaf_rn(rs, ln_dx(gg[c].x, xh[c].x, m1, m2), prev[c].x), __fmaf_rn(rs, ln_dx(gg[c].y, xh[c].y, m1, m2), prev[c].y),
+                 __fmaf_rn(rs, ln_dx(gg[c].z, xh[c].z, m1, m2), prev[c].z), __fmaf_rn(rs, ln_dx(gg[c].w, xh[c].w, m1, m2), prev[c].w)};
+        if (has_in) o[i] = d;
+        if (!has_out) continue;
         if (rowmask || out_map) {
           d.x = div_newton(d.x * km, keep, rk); d.y = div_newton(d.y * km, keep, rk);
           d.z = div_newton(d.z * km, keep, rk); d.w = div_newton(d.w * km, keep, rk);
@@ -409,7 +600,7 @@ __global__ __launch_bounds__(256) void ln_bwd_branch_kernel(const __bf16* __rest
           bg[c].x += d.x * (float)yv[c][0]; bg[c].y += d.y * (float)yv[c][1];
           bg[c].z += d.z * (float)yv[c][2]; bg[c].w += d.w * (float)yv[c][3];
         }
-        const float4 gbc = gb ? gb4[i] : float4{1.f, 1.f, 1.f, 1.f};
+        const float4 gbc = lgbl[c * 64];
         bf16x4 q;
         q[0] = (__bf16)(d.x * gbc.x); q[1] = (__bf16)(d.y * gbc.y);
         q[2] = (__bf16)(d.z * gbc.z); q[3] = (__bf16)(d.w * gbc.w);
@@ -417,19 +608,80 @@ __global__ __launch_bounds__(256) void ln_bwd_branch_kernel(const __bf16* __rest
         bb[c].x += (float)q[0]; bb[c].y += (float)q[1]; bb[c].z += (float)q[2]; bb[c].w += (float)q[3];
       }
     }
+  };
+  // ---- pass 1: the rows that take part in both branches, pipelined
+  RowWalk w(row0, rstride, rps);
+  auto find = [&](int& fr, int& frin, int& frout, int& fsmp) {     // the wave's next such row; leaves w behind it
+    for (;;) {
+      fr = w.r; fsmp = w.smp; frin = frout = -1;
+      if (fr >= R) return;
+      resolve(w, frin, frout);
+      w.next();
+      if ((frin | frout) >= 0) return;
+    }
+  };
+  int smp;
+  find(r, rin, rout, smp);
+  if (r < R) {                     // the first row is on its way while gamma and gb are staged
+    issue_x(r, rin, lane); issue_y(r, lane); issue_prev(r, lane);
+    mu = mean[rin]; rs = rstd[rin];
+    if (rowmask) km = rowmask[smp];
   }
+  stage_columns(lg, gamma, gb, nch);
+  int r1, rin1, rout1, smp1;
+  find(r1, rin1, rout1, smp1);
+  vm_drain();
+  while (r < R) {
+    const int ol = opaque(lane);
+    reduce_row(true, ol);
+    float mu1 = 0.f, rs1 = 0.f, km1 = 1.f;
+    const bool next = r1 < R;
+    const int rl = next ? r1 : r, rinl = next ? rin1 : rin;       // the last row requests itself again
+    issue_x(rl, rinl, ol); issue_y(rl, ol);
+    if (next) {
+      mu1 = mean[rin1]; rs1 = rstd[rin1];
+      if (rowmask) km1 = rowmask[smp1];
+    }
+    int r2, rin2, rout2, smp2;
+    find(r2, rin2, rout2, smp2);
+    store_row(true, true, ol);
+    __builtin_amdgcn_sched_barrier(0);               // no load between the row's stores
+    issue_prev(rl, ol);
+    r = r1; rin = rin1; rout = rout1; mu = mu1; rs = rs1; km = km1;
+    r1 = r2; rin1 = rin2; rout1 = rout2; smp1 = smp2;
+  }
+  // ---- pass 2: the rows of samples that ONE of the two branches dropped (dropped by both: the row of dres stays as it
+  // is), one at a time behind run-time conditions, with the waits hipcc derives for them
+  if (in_map || out_map) {
+    for (RowWalk v(row0, rstride, rps); v.r < R; v.next()) {
+      resolve(v, rin, rout);
+      if ((rin >= 0) == (rout >= 0)) continue;
+      r = v.r;
+      const int ol = opaque(lane);
+      issue_prev(r, ol); issue_y(r, ol);
+      mu = rs = 0.f;
+      if (rin >= 0) {
+        issue_x(r, rin, ol);
+        mu = mean[rin]; rs = rstd[rin];
+      }
+      km = rowmask ? rowmask[v.smp] : 1.f;
+      reduce_row(rin >= 0, ol);
+      store_row(rin >= 0, rout >= 0, ol);
+    }
+  }
+  __syncthreads();                 // every wave is done with gamma / gb: `red` becomes the column-sum area
   float4* r0 = reinterpret_cast<float4*>(red + (size_t)wave * 4 * D);
 #pragma unroll
   for (int c = 0; c < NCH; ++c) {
     const int i = lane + c * 64;
-    if (i < nch) { r0[i] = ag[c]; r0[nch + i] = ab[c]; r0[2 * nch + i] = HAS_Y ? bg[HAS_Y ? c : 0] : float4{0, 0, 0, 0}; r0[3 * nch + i] = bb[c]; }
+    if (chunk_ok<FULL>(i, nch)) { r0[i] = ag[c]; r0[nch + i] = ab[c]; r0[2 * nch + i] = HAS_Y ? bg[HAS_Y ? c : 0] : float4{0, 0, 0, 0}; r0[3 * nch + i] = bb[c]; }
   }
   __syncthreads();
   for (int n = threadIdx.x; n < D; n += 256) {
     float a = 0.f, b = 0.f, c2 = 0.f, d2 = 0.f;
 #pragma unroll
-    for (int w = 0; w < 4; ++w) {
-      const float* rw = red + (size_t)w * 4 * D;
+    for (int w2 = 0; w2 < 4; ++w2) {
+      const float* rw = red + (size_t)w2 * 4 * D;
       a += rw[n]; b += rw[D + n]; c2 += rw[2 * D + n]; d2 += rw[3 * D + n];
     }
     atomicAdd(dgamma + n, a);
@@ -650,6 +902,31 @@ __global__ __launch_bounds__(256) void ce_reduce_kernel(const float* __restrict_
 
 }  // namespace
 
+// NCH and FULL of a width: the guard-free instantiation wherever every lane owns every chunk (D a multiple of 256)
+#define ROW_DISPATCH(D, L)                                                                               \
+  do {                                                                                                   \
+    const int nchl_ = cdiv((D) / 4, 64);                                                                 \
+    const bool full_ = (D) % 256 == 0;                                                                   \
+    if (nchl_ <= 1) { if (full_) L(1, true); else L(1, false); }                                         \
+    else if (nchl_ <= 2) { if (full_) L(2, true); else L(2, false); }                                    \
+    else if (nchl_ <= 3) { if (full_) L(3, true); else L(3, false); }                                    \
+    else if (nchl_ <= 4) { if (full_) L(4, true); else L(4, false); }                                    \
+    else if (nchl_ == 5 && full_) L(5, true);                                                            \
+    else if (nchl_ == 8 && full_) L(8, true);                                                            \
+    else L(8, false);                                                                                    \
+  } while (0)
+
+// the same for a kernel whose widths end at 1024
+#define ROW_DISPATCH4(D, L)                                                                              \
+  do {                                                                                                   \
+    const int nchl_ = cdiv((D) / 4, 64);                                                                 \
+    const bool full_ = (D) % 256 == 0;                                                                   \
+    if (nchl_ <= 1) { if (full_) L(1, true); else L(1, false); }                                         \
+    else if (nchl_ <= 2) { if (full_) L(2, true); else L(2, false); }                                    \
+    else if (nchl_ <= 3) { if (full_) L(3, true); else L(3, false); }                                    \
+    else { if (full_) L(4, true); else L(4, false); }                                                    \
+  } while (0)
+
 extern "C" int memhip_layernorm_fwd(const float* x, int64_t ldx, const int32_t* row_idx, int R, int D,
                                     const float* gamma, const float* beta, float eps, void* y,
                                     int64_t ldy, float* mean, float* rstd, memhip_stream_t stream) {
@@ -657,8 +934,11 @@ extern "C" int memhip_layernorm_fwd(const float* x, int64_t ldx, const int32_t* 
   if (R == 0) return MEMHIP_OK;
   MEMHIP_REQUIRE(x && gamma && beta && y && mean && rstd, "layernorm_fwd: null pointer");
   MEMHIP_REQUIRE(ldx % 4 == 0 && ldy % 4 == 0, "layernorm_fwd: ld must be a multiple of 4");
-  hipLaunchKernelGGL(ln_fwd_kernel, dim3(cdiv(R, 4)), dim3(256), 0, as_stream(stream), x, (long long)ldx,
-                     row_idx, R, D, gamma, beta, eps, (__bf16*)y, (long long)ldy, mean, rstd);
+#define LNF_LAUNCH(N, F)                                                                                 \
+  hipLaunchKernelGGL((ln_fwd_kernel<N, F>), dim3(cdiv(R, 4)), dim3(256), (size_t)2 * D * sizeof(float), as_stream(stream), \
+                     x, (long long)ldx, row_idx, R, D, gamma, beta, eps, (__bf16*)y, (long long)ldy, mean, rstd)
+  ROW_DISPATCH(D, LNF_LAUNCH);
+#undef LNF_LAUNCH
   return check_launch("layernorm_fwd");
 }
 
@@ -673,17 +953,15 @@ extern "C" int memhip_layernorm_bwd(const void* dy, int64_t lddy, const float* x
   int grid = cdiv(R, 4);
   const int cap = opt(OPT_LN_BWD_GRID) * 4 / 3;      // (4/3 of the fused kernel's grid: this one needs half the LDS per workgroup)
   if (grid > cap) grid = cap;
-#define LNB_LAUNCH(N)                                                                                    \
-  hipLaunchKernelGGL(ln_bwd_kernel<N>, dim3(grid), dim3(256), (size_t)8 * D * sizeof(float), as_stream(stream), \
+#define LNB_LAUNCH(N, F)                                                                                 \
+  if (accumulate) LNB_LAUNCH2(N, F, true); else LNB_LAUNCH2(N, F, false)
+#define LNB_LAUNCH2(N, F, A)                                                                             \
+  hipLaunchKernelGGL((ln_bwd_kernel<N, F, A>), dim3(grid), dim3(256), (size_t)8 * D * sizeof(float), as_stream(stream), \
                      (const __bf16*)dy, (long long)lddy, x, (long long)ldx, row_idx, R, D, gamma, mean, rstd, dres, \
-                     (long long)lddres, accumulate, dgamma, dbeta)
-  const int nchl = cdiv(D / 4, 64);
-  if (nchl <= 1) LNB_LAUNCH(1);
-  else if (nchl <= 2) LNB_LAUNCH(2);
-  else if (nchl <= 3) LNB_LAUNCH(3);
-  else if (nchl <= 4) LNB_LAUNCH(4);
-  else LNB_LAUNCH(8);
+                     (long long)lddres, dgamma, dbeta)
+  ROW_DISPATCH(D, LNB_LAUNCH);
 #undef LNB_LAUNCH
+#undef LNB_LAUNCH2
   return check_launch("layernorm_bwd");
 }
 
@@ -702,25 +980,23 @@ static int branch_bwd_impl(const float* dx, int64_t lddx, const void* y, int64_t
   MEMHIP_REQUIRE(D <= 64 * 4 * kBrMaxChunks, "branch_bwd: D=%d too large", D);
   int grid = cdiv(M, 4);
   if (grid > 1024) grid = 1024;
-#define BRB_LAUNCH(N)                                                                                    \
-  if (drop) BRB_LAUNCH_D(N); else                                                                        \
-  hipLaunchKernelGGL(branch_bwd_kernel<N>, dim3(grid), dim3(256), (size_t)8 * D * sizeof(float), as_stream(stream), \
+#define BRB_LAUNCH(N, F)                                                                                 \
+  if (y) BRB_LAUNCH_Y(N, F, true); else BRB_LAUNCH_Y(N, F, false)
+#define BRB_LAUNCH_Y(N, F, Y)                                                                            \
+  if (drop) BRB_LAUNCH_D(N, F, Y); else                                                                  \
+  hipLaunchKernelGGL((branch_bwd_kernel<N, F, Y>), dim3(grid), dim3(256), (size_t)8 * D * sizeof(float), as_stream(stream), \
                      dx, (long long)lddx, (const __bf16*)y, (long long)ldy, gamma, rowmask, keep_prob,    \
                      rows_per_sample > 0 ? rows_per_sample : 1, M, D, (__bf16*)dy, (long long)lddy, dgamma, dbias, \
                      (const int*)out_map)
-#define BRB_LAUNCH_D(N)                                                                                  \
-  hipLaunchKernelGGL((branch_bwd_kernel<N, DropParams>), dim3(grid), dim3(256), (size_t)8 * D * sizeof(float),  \
+#define BRB_LAUNCH_D(N, F, Y)                                                                            \
+  hipLaunchKernelGGL((branch_bwd_kernel<N, F, Y, DropParams>), dim3(grid), dim3(256), (size_t)8 * D * sizeof(float),  \
                      as_stream(stream), dx, (long long)lddx, (const __bf16*)y, (long long)ldy, gamma, rowmask, keep_prob, \
                      rows_per_sample > 0 ? rows_per_sample : 1, M, D, (__bf16*)dy, (long long)lddy, dgamma, dbias, \
                      (const int*)out_map, drop_params(*drop))
-  const int nchl = cdiv(D / 4, 64);
-  if (nchl <= 1) BRB_LAUNCH(1);
-  else if (nchl <= 2) BRB_LAUNCH(2);
-  else if (nchl <= 3) BRB_LAUNCH(3);
-  else if (nchl <= 4) BRB_LAUNCH(4);
-  else BRB_LAUNCH(8);
+  ROW_DISPATCH(D, BRB_LAUNCH);
 #undef BRB_LAUNCH
 #undef BRB_LAUNCH_D
+#undef BRB_LAUNCH_Y
   return check_launch("branch_bwd");
 }
 
@@ -809,28 +1085,24 @@ static int ln_bwd_branch_impl(const void* dy, int64_t lddy, const float* x, int6
   if (D > 768 && cap > 512) cap = 512;                 // D = 1024: 64 KiB of LDS and 212 VGPRs per workgroup, two per CU (tools/ln_bwd_probe.py:
                                                        // 76 864 rows 301 -> 262 us, 19 216 rows 69 -> 64 us)
   if (grid > cap) grid = cap;
-#define LBB_LAUNCH(N)                                                                                    \
-  if (drop) { if (y_branch) LBB_LAUNCH2D(N, true); else LBB_LAUNCH2D(N, false); }                       \
-  else if (y_branch) LBB_LAUNCH2(N, true); else LBB_LAUNCH2(N, false)
-#define LBB_LAUNCH2(N, Y)                                                                                \
-  hipLaunchKernelGGL((ln_bwd_branch_kernel<N, Y>), dim3(grid), dim3(256), (size_t)16 * D * sizeof(float), \
+#define LBB_LAUNCH(N, F)                                                                                 \
+  if (drop) { if (y_branch) LBB_LAUNCH2D(N, F, true); else LBB_LAUNCH2D(N, F, false); }                 \
+  else if (y_branch) LBB_LAUNCH2(N, F, true); else LBB_LAUNCH2(N, F, false)
+#define LBB_LAUNCH2(N, F, Y)                                                                              \
+  hipLaunchKernelGGL((ln_bwd_branch_kernel<N, F, Y>), dim3(grid), dim3(256), (size_t)16 * D * sizeof(float), \
                      as_stream(stream), (const __bf16*)dy, (long long)lddy, x, (long long)ldx, R, D, gamma, mean, \
                      rstd, dres, (long long)lddres, dgamma, dbeta, (const __bf16*)y_branch, (long long)ldyb, \
                      gamma_branch, rowmask, keep_prob, rows_per_sample > 0 ? rows_per_sample : 1,         \
                      (__bf16*)dy_branch, (long long)lddyb, dgamma_branch, dbias_branch, (const int*)in_map, \
                      (const int*)out_map)
-#define LBB_LAUNCH2D(N, Y)                                                                               \
-  hipLaunchKernelGGL((ln_bwd_branch_kernel<N, Y, DropParams>), dim3(grid), dim3(256), (size_t)16 * D * sizeof(float), \
+#define LBB_LAUNCH2D(N, F, Y)                                                                            \
+  hipLaunchKernelGGL((ln_bwd_branch_kernel<N, F, Y, DropParams>), dim3(grid), dim3(256), (size_t)16 * D * sizeof(float), \
                      as_stream(stream), (const __bf16*)dy, (long long)lddy, x, (long long)ldx, R, D, gamma, mean, \
                      rstd, dres, (long long)lddres, dgamma, dbeta, (const __bf16*)y_branch, (long long)ldyb, \
                      gamma_branch, rowmask, keep_prob, rows_per_sample > 0 ? rows_per_sample : 1,         \
                      (__bf16*)dy_branch, (long long)lddyb, dgamma_branch, dbias_branch, (const int*)in_map, \
                      (const int*)out_map, drop_params(*drop))
-  const int nchl = cdiv(D / 4, 64);
-  if (nchl <= 1) LBB_LAUNCH(1);
-  else if (nchl <= 2) LBB_LAUNCH(2);
-  else if (nchl <= 3) LBB_LAUNCH(3);
-  else LBB_LAUNCH(4);
+  ROW_DISPATCH4(D, LBB_LAUNCH);
 #undef LBB_LAUNCH
 #undef LBB_LAUNCH2
 #undef LBB_LAUNCH2D
