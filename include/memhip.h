@@ -35,9 +35,11 @@
 extern "C" {
 #endif
 
-#define MEMHIP_ABI_VERSION 7   /* 7: the finetuning recipe (memhip_mixup, memhip_mix_targets, memhip_ce_soft, memhip_ema_update), and -- additive, no
+#define MEMHIP_ABI_VERSION 8   /* 8: one entry point per backward family, optional features as struct fields (memhip_branch_bwd, memhip_layernorm_bwd_branch,
+                                  memhip_attn_bwd take an args struct; memhip_gemm_bf16_tn takes the workspace; the *_map / *_drop / *_out / *_ws symbols are gone);
+                                  7: the finetuning recipe (memhip_mixup, memhip_mix_targets, memhip_ce_soft, memhip_ema_update), and -- additive, no
                                   existing signature changed, so the number stays -- memhip_pool_tokens / memhip_pool_tokens_bwd, memhip_gemm_bf16_nt_plan, memhip_tokens_to_maps / memhip_maps_to_tokens_add, memhip_conv_plan, memhip_gemm_bf16_tn_plan / memhip_gemm_bf16_tn_plan_workspace; 6: element-wise dropout (memhip_dropout_t, epilogue RESIDUAL_DROP, memhip_gemm_args_t.dropout, the
-                                  *_drop row kernels); 5 (round 6): memhip_build_flags, memhip_attn_bwd_ws / _out_ws / _workspace; 4 (round 5): epilogues 6 / 7 carry the stored GELU derivative as FP16 (since round 4), certified-tokenizer entry points */
+                                  dropout in the row kernels); 5 (round 6): memhip_build_flags, the attention backward's workspace, memhip_attn_bwd_workspace; 4 (round 5): epilogues 6 / 7 carry the stored GELU derivative as FP16 (since round 4), certified-tokenizer entry points */
 
 #define MEMHIP_OK 0
 #define MEMHIP_EINVAL (-1)   /* bad argument (shape / alignment / null) */
@@ -387,26 +389,22 @@ int memhip_gemm_bf16_nt_plan(const memhip_gemm_args_t* args, int stream_cus, int
  * bf16 with the reduction over ROWS): the dY^T @ X that autograd computes for every Linear /
  * Conv2d weight on the path.  No transposed copies: fragments are read with the transposing LDS
  * read; split-K over the rows with fp32 atomics.  accumulate=1: add into `out` (pre-zeroed by
- * the caller); accumulate=0: overwrite. */
-int memhip_gemm_bf16_tn(const void* A, int64_t lda, const void* B, int64_t ldb, int R, int N, int K,
-                        float* out, int64_t ldo, int accumulate, memhip_stream_t stream);
-/* Same product with a caller-owned scratch buffer of memhip_gemm_bf16_tn_workspace(R,N,K) bytes (0 = the
- * shape has no use for one): the per-slice partial tiles are then written with plain stores and summed
- * by a reduction pass instead of fp32 atomics (64 MB of atomics per ViT-B weight gradient otherwise).
- * workspace NULL / too small: identical to memhip_gemm_bf16_tn.  The sum order is fixed, so the result
- * is run-to-run deterministic. */
+ * the caller); accumulate=0: overwrite.
+ * workspace: caller-owned scratch of memhip_gemm_bf16_tn_workspace(R,N,K) bytes (0 = the shape has no use for one): the per-slice
+ * partial tiles are then written with plain stores and summed by a reduction pass in a fixed order (run-to-run deterministic)
+ * instead of fp32 atomics (64 MB of atomics per ViT-B weight gradient otherwise).  NULL / too small: the atomic form. */
 size_t memhip_gemm_bf16_tn_workspace(int R, int N, int K);
-int memhip_gemm_bf16_tn_ws(const void* A, int64_t lda, const void* B, int64_t ldb, int R, int N, int K,
-                           float* out, int64_t ldo, int accumulate, void* workspace, size_t workspace_bytes,
-                           memhip_stream_t stream);
+int memhip_gemm_bf16_tn(const void* A, int64_t lda, const void* B, int64_t ldb, int R, int N, int K,
+                        float* out, int64_t ldo, int accumulate, void* workspace, size_t workspace_bytes,
+                        memhip_stream_t stream);
 /* The weight gradients of up to 4 Linear layers whose operands are ready at the same time (fc2 + fc1, proj + qkv of a
  * Block: mem/modeling_finetune.py:160-189 backward) as ONE launch: the products share one grid and one common count of row
  * slices, so a small product (768 x 768: 9 tiles) runs with the 7 row slices of its neighbour instead of the 27 it plans
- * alone to fill the chip, and the group has one reduction pass.  Each product has the contract of memhip_gemm_bf16_tn_ws
+ * alone to fill the chip, and the group has one reduction pass.  Each product has the contract of memhip_gemm_bf16_tn
  * (fixed sum order: run-to-run deterministic; the order differs from the single call's, so the two agree to fp32 rounding,
  * not bitwise).  workspace: memhip_gemm_bf16_tn_group_workspace(problems, count) bytes (also >= what each product needs
  * alone).  Whether a group runs as one grid is decided by tn_plan (mem_amd/csrc/gemm_tn_plan.cpp; memhip_gemm_bf16_tn_plan
- * shows the decision); a group that does not is computed product by product, each exactly as memhip_gemm_bf16_tn_ws would
+ * shows the decision); a group that does not is computed product by product, each exactly as memhip_gemm_bf16_tn would
  * -- same results contract. */
 typedef struct memhip_tn_problem {
   const void* A; int64_t lda;       /* dY  bf16 [R, N] */
@@ -419,7 +417,7 @@ size_t memhip_gemm_bf16_tn_group_workspace(const memhip_tn_problem_t* problems, 
 int memhip_gemm_bf16_tn_group(const memhip_tn_problem_t* problems, int count, int accumulate, void* workspace,
                               size_t workspace_bytes, memhip_stream_t stream);
 
-/* The dispatch of memhip_gemm_bf16_tn / _tn_ws / _tn_group as data (additive to ABI 7): the ordered launches with their row
+/* The dispatch of memhip_gemm_bf16_tn / _tn_group as data (additive to ABI 7): the ordered launches with their row
  * slices, grids and workspace layout.  memhip_gemm_bf16_tn_plan validates `problems` like memhip_gemm_bf16_tn_group (a single
  * call is a group of one) and plans with the current option values for a stream of stream_cus usable CUs (>= 0: no device
  * is needed; < 0: what the default stream has on the current device).  Nothing is launched; of the pointers only the address
@@ -496,56 +494,49 @@ int memhip_layerscale_grad(const void* W_bf16, int64_t ldw, const float* dW, int
                            const float* dbias, const float* gamma, int N, int K, float* dgamma,
                            memhip_stream_t stream);
 
-/* memhip_layernorm_bwd (accumulating, no row gather) fused with the memhip_branch_bwd that follows it in a
- * block's backward: the updated dres row is consumed in registers (one pass over the fp32 gradient stream
- * less).  Arguments = those of the two calls; D <= 1024. */
-int memhip_layernorm_bwd_branch(const void* dy_bf16, int64_t lddy, const float* x, int64_t ldx, int R, int D,
-                                const float* gamma, const float* mean, const float* rstd, float* dres,
-                                int64_t lddres, float* dgamma, float* dbeta, const void* y_branch_bf16, int64_t ldyb,
-                                const float* gamma_branch, const float* rowmask, float keep_prob,
-                                int rows_per_sample, void* dy_branch_bf16, int64_t lddyb, float* dgamma_branch,
-                                float* dbias_branch, memhip_stream_t stream);
-
-/* Backward of `x = x + drop_path(gamma * y)` (mem/modeling_finetune.py:187-188):
- * dy bf16 = bf16(dt * gamma), dgamma += sum_m dt*y, dbias += sum_m dy with
- * dt = dx * rowmask[m / rows_per_sample] / keep_prob.  gamma/rowmask/dgamma/dbias may be NULL; y may be NULL
- * when dgamma is (see memhip_layerscale_grad). */
-int memhip_branch_bwd(const float* dx, int64_t lddx, const void* y_bf16, int64_t ldy, const float* gamma,
-                      const float* rowmask, float keep_prob, int rows_per_sample, int M, int D,
-                      void* dy_bf16, int64_t lddy, float* dgamma, float* dbias, memhip_stream_t stream);
-/* Stochastic depth as WORK SKIPPING (timm drop_path, mem/modeling_finetune.py:42-53,187-188: a dropped sample's branch
- * contributes nothing, so nothing of it is computed).  Sample maps, i32 [samples]: sample -> its index among the samples the
- * branch KEPT this step, or -1.  memhip_branch_bwd_map: out_map places the kept samples' rows of dy compactly (row
- * out_map[s] * rows_per_sample + t) scaled by 1 / keep_prob; dropped samples are neither read nor written.
- * memhip_layernorm_bwd_branch_map: in_map says which samples the LayerNorm'ed branch kept (dy / mean / rstd hold those
- * samples only; the others get no LayerNorm gradient), out_map the same for the branch whose output gradient is produced.
- * M / R count the rows of the residual stream (all samples).  rowmask and y must be NULL; NULL maps = identity. */
-int memhip_branch_bwd_map(const float* dx, int64_t lddx, const void* y_bf16, int64_t ldy, const float* gamma,
-                          const float* rowmask, float keep_prob, int rows_per_sample, int M, int D,
-                          void* dy_bf16, int64_t lddy, float* dgamma, float* dbias, const int32_t* out_map,
-                          memhip_stream_t stream);
-int memhip_layernorm_bwd_branch_map(const void* dy_bf16, int64_t lddy, const float* x, int64_t ldx, int R, int D,
-                                    const float* gamma, const float* mean, const float* rstd, float* dres,
-                                    int64_t lddres, float* dgamma, float* dbeta, const void* y_branch_bf16, int64_t ldyb,
-                                    const float* gamma_branch, const float* rowmask, float keep_prob,
-                                    int rows_per_sample, void* dy_branch_bf16, int64_t lddyb, float* dgamma_branch,
-                                    float* dbias_branch, const int32_t* in_map, const int32_t* out_map,
-                                    memhip_stream_t stream);
-/* The two _map calls for a branch with element-wise dropout (epilogue RESIDUAL_DROP in the forward): the branch gradient
- * becomes dy = bf16(dt * keep * scale * gamma) (dt after drop path as above; dt * keep * scale rounded once in fp32, then
- * * gamma), dbias += sum dy, and dgamma (when y is given) += sum dt * keep * scale * y.  The mask of the branch's site is
- * regenerated (memhip_dropout_t, row = residual-stream row + row0); `dropout` must not be NULL. */
-int memhip_branch_bwd_drop(const float* dx, int64_t lddx, const void* y_bf16, int64_t ldy, const float* gamma,
-                           const float* rowmask, float keep_prob, int rows_per_sample, int M, int D,
-                           void* dy_bf16, int64_t lddy, float* dgamma, float* dbias, const int32_t* out_map,
-                           const memhip_dropout_t* dropout, memhip_stream_t stream);
-int memhip_layernorm_bwd_branch_drop(const void* dy_bf16, int64_t lddy, const float* x, int64_t ldx, int R, int D,
-                                     const float* gamma, const float* mean, const float* rstd, float* dres,
-                                     int64_t lddres, float* dgamma, float* dbeta, const void* y_branch_bf16, int64_t ldyb,
-                                     const float* gamma_branch, const float* rowmask, float keep_prob,
-                                     int rows_per_sample, void* dy_branch_bf16, int64_t lddyb, float* dgamma_branch,
-                                     float* dbias_branch, const int32_t* in_map, const int32_t* out_map,
-                                     const memhip_dropout_t* dropout, memhip_stream_t stream);
+/* Backward of `x = x + drop_path(gamma * y)` (mem/modeling_finetune.py:187-188), the residual branch whose OUTPUT gradient is
+ * produced: dy = bf16(dt * gamma), dgamma += sum_m dt*y, dbias += sum_m dy with dt = dx * rowmask[m / rows_per_sample] / keep_prob.
+ * Host structs, read at the call; an optional feature is a field whose NULL / 0 value means "off". */
+typedef struct memhip_branch {
+  const void* y; int64_t ldy;   /* bf16 [rows, D] branch output, NULL when dgamma is (see memhip_layerscale_grad) */
+  const float* gamma;           /* layer scale [D], NULL = none */
+  const float* rowmask;         /* stochastic depth as a keep mask per sample (0/1), NULL = off */
+  float keep_prob;              /* 1 - drop_prob */
+  int32_t rows_per_sample;
+  void* dy; int64_t lddy;       /* bf16 out */
+  float* dgamma; float* dbias;  /* f32 [D], ACCUMULATED; NULL = not wanted */
+  const int32_t* out_map;       /* stochastic depth as WORK SKIPPING (timm drop_path, mem/modeling_finetune.py:42-53,187-188: nothing of a
+                                   dropped sample's branch is computed): i32 [samples], sample -> its index among the samples the branch
+                                   KEPT this step, or -1.  The kept samples' rows of dy are placed compactly (row out_map[s] *
+                                   rows_per_sample + t) scaled by 1 / keep_prob; dropped samples are neither read nor written.  rowmask
+                                   and y must be NULL.  NULL = identity */
+  const memhip_dropout_t* dropout;  /* the branch had element-wise dropout (epilogue RESIDUAL_DROP in the forward): dy = bf16(dt * keep *
+                                   scale * gamma) (dt after drop path; dt * keep * scale rounded once in fp32, then * gamma), dbias += sum dy,
+                                   dgamma += sum dt * keep * scale * y.  The mask of the branch's site is regenerated (memhip_dropout_t, row =
+                                   residual-stream row + row0); D % 8 == 0.  NULL = no dropout */
+} memhip_branch_t;
+typedef struct memhip_branch_bwd_args {
+  const float* dx; int64_t lddx;   /* f32 [M, D], the gradient of the residual stream */
+  int32_t M, D;                    /* M counts the rows of the residual stream (all samples) */
+  memhip_branch_t branch;
+} memhip_branch_bwd_args_t;
+int memhip_branch_bwd(const memhip_branch_bwd_args_t* args, memhip_stream_t stream);
+/* memhip_layernorm_bwd (accumulating, no row gather) fused with the memhip_branch_bwd that follows it in a block's backward:
+ * the updated dres row is consumed in registers (one pass over the fp32 gradient stream less).  The LayerNorm fields are
+ * memhip_layernorm_bwd's, `branch` is memhip_branch_bwd's with dx = dres; D <= 1024; R counts residual-stream rows. */
+typedef struct memhip_ln_bwd_branch_args {
+  const void* dy; int64_t lddy;    /* bf16 */
+  const float* x; int64_t ldx;
+  int32_t R, D;
+  const float* gamma; const float* mean; const float* rstd;
+  float* dres; int64_t lddres;
+  float* dgamma; float* dbeta;
+  const int32_t* in_map;           /* work skipping, as branch.out_map: which samples the LayerNorm'ed branch kept (dy / mean / rstd hold
+                                      those samples only; the others get no LayerNorm gradient).  With either map branch.rowmask and
+                                      branch.y must be NULL.  NULL = identity */
+  memhip_branch_t branch;
+} memhip_ln_bwd_branch_args_t;
+int memhip_layernorm_bwd_branch(const memhip_ln_bwd_branch_args_t* args, memhip_stream_t stream);
 
 /* Backward of the token assembly (mem/modeling_pretrain.py:101-108): dcls += dx[cls rows],
  * dmask_token += sum dx*w, dy bf16 [B*L, D] = bf16(dx*(1-w)); mask u8 [B*L]. */
@@ -586,43 +577,40 @@ int memhip_attn_fwd(const void* qkv, int64_t ldqkv, int B, int T, int D, int hea
                     int window_h, int window_w, void* out, int64_t ldo, float* lse, memhip_stream_t stream);
 int memhip_attn_delta(const void* dout, const void* out, int64_t ldo, int64_t rows, int heads, float* delta,
                       memhip_stream_t stream);
-int memhip_attn_bwd(const void* qkv, int64_t ldqkv, const void* dout, int64_t ldo, const float* lse,
-                    float* delta, const float* table, int window_h, int window_w, int B, int T, int D,
-                    int heads, float scale, void* dqkv, int64_t lddqkv, float* dtable, float* dq_bias,
-                    float* dv_bias, memhip_stream_t stream);
-/* The same backward given the forward OUTPUT `out` (bf16 [B*T, D], leading dimension ldout) instead of a filled `delta`:
- * rowsum(dout * out) is computed by the library -- inside the fused 14 x 14 kernel when that kernel applies (no separate
- * pass over dout and out: 25 us per ViT-B layer at B = 256), otherwise by memhip_attn_delta into `delta` (then
- * ldout == ldo is required).  `delta` is still the [(2*B*T + 4) * heads] workspace.  (Attention.forward backward,
- * mem/modeling_finetune.py:137-154.) */
-int memhip_attn_bwd_out(const void* qkv, int64_t ldqkv, const void* dout, int64_t ldo, const void* out, int64_t ldout,
-                        const float* lse, float* delta, const float* table, int window_h, int window_w, int B, int T,
-                        int D, int heads, float scale, void* dqkv, int64_t lddqkv, float* dtable, float* dq_bias,
-                        float* dv_bias, memhip_stream_t stream);
-/* The same two calls with a caller-owned WORKSPACE (round 6).  For the long windows the slot-layout kernels take (40 or 20 tokens
- * wide, more than 256 tokens: BASELINE configs[4]) the backward then runs in its dS-storing form: the dK / dV kernel writes
- * dS (bf16) to the workspace and owns the table gradient, the dQ kernel is a streaming product over it -- the score tile is
- * computed once instead of twice.  memhip_attn_bwd_workspace returns the bytes that form wants (0: this shape has no such
- * form); ws == NULL, too few bytes or any other shape = exactly memhip_attn_bwd / memhip_attn_bwd_out.  The workspace is
- * scratch: nothing is kept in it between calls.  Same outputs and rounding points either way (the table gradient is summed
- * in another order: fixed-point buckets per workgroup, then float atomics).  (Attention.forward backward,
- * mem/modeling_finetune.py:137-154, RelativePositionBias :213-247.) */
+/* Attention.forward backward (mem/modeling_finetune.py:137-154, RelativePositionBias :213-247).  Host struct, read at the call. */
+typedef struct memhip_attn_bwd_args {
+  const void* qkv; int64_t ldqkv;
+  const void* dout; int64_t ldo;
+  const void* out; int64_t ldout;  /* the forward OUTPUT (bf16 [B*T, D]): rowsum(dout * out) is computed by the library -- inside the fused
+                                      14 x 14 kernel when that kernel applies (no separate pass over dout and out: 25 us per ViT-B layer at
+                                      B = 256), otherwise by memhip_attn_delta into `delta` (then ldout == ldo is required).  NULL = the
+                                      caller filled `delta` with memhip_attn_delta */
+  const float* lse;
+  float* delta;                    /* always the [(2*B*T + 4) * heads] workspace described above */
+  const float* table;
+  int32_t window_h, window_w, B, T, D, heads;
+  float scale;
+  int32_t reserved0;
+  void* dqkv; int64_t lddqkv;
+  float* dtable; float* dq_bias; float* dv_bias;
+  void* ws; int64_t ws_bytes;      /* caller-owned scratch (round 6).  For the long windows the slot-layout kernels take (40 or 20 tokens wide,
+                                      more than 256 tokens: BASELINE configs[4]) the backward then runs in its dS-storing form: the dK / dV
+                                      kernel writes dS (bf16) to the workspace and owns the table gradient, the dQ kernel is a streaming
+                                      product over it -- the score tile is computed once instead of twice.  memhip_attn_bwd_workspace returns
+                                      the bytes that form wants (0: this shape has no such form); NULL, misaligned, too small or any other
+                                      shape = the recomputing form.  Nothing is kept in it between calls.  Same outputs and rounding points
+                                      either way (the table gradient is summed in another order: fixed-point buckets per workgroup, then
+                                      float atomics) */
+} memhip_attn_bwd_args_t;
+int memhip_attn_bwd(const memhip_attn_bwd_args_t* args, memhip_stream_t stream);
 int64_t memhip_attn_bwd_workspace(int B, int T, int heads, int window_h, int window_w);
-int memhip_attn_bwd_ws(const void* qkv, int64_t ldqkv, const void* dout, int64_t ldo, const float* lse,
-                       float* delta, const float* table, int window_h, int window_w, int B, int T, int D,
-                       int heads, float scale, void* dqkv, int64_t lddqkv, float* dtable, float* dq_bias,
-                       float* dv_bias, void* ws, int64_t ws_bytes, memhip_stream_t stream);
-int memhip_attn_bwd_out_ws(const void* qkv, int64_t ldqkv, const void* dout, int64_t ldo, const void* out, int64_t ldout,
-                           const float* lse, float* delta, const float* table, int window_h, int window_w, int B, int T,
-                           int D, int heads, float scale, void* dqkv, int64_t lddqkv, float* dtable, float* dq_bias,
-                           float* dv_bias, void* ws, int64_t ws_bytes, memhip_stream_t stream);
 
-/* The dispatch of memhip_attn_fwd / memhip_attn_bwd* as data (additive to ABI 7): the kernel family, its template arguments,
+/* The dispatch of memhip_attn_fwd / memhip_attn_bwd as data (additive to ABI 7): the kernel family, its template arguments,
  * the samples-per-workgroup numbers the kernels take and the ordered launches, auxiliary ones included.
  * memhip_attn_plan_fwd / _bwd validate the shape like the calls themselves and plan with the current option values for a
  * stream with stream_cus usable CUs; they launch nothing and need no device.  has_dtable / has_dv_bias: the call gives
- * dtable / dv_bias; has_out: the call gives the forward output (memhip_attn_bwd_out*); ws / ws_bytes: the workspace of the
- * *_ws calls (checked for NULL and alignment, never read).  A shape no family takes: MEMHIP_EUNSUPPORTED, as from the call. */
+ * dtable / dv_bias; has_out: the call gives the forward output; ws / ws_bytes: the call's workspace
+ * (checked for NULL and alignment, never read).  A shape no family takes: MEMHIP_EUNSUPPORTED, as from the call. */
 #define MEMHIP_ATTN_16 1        /* attn16.hip: the 14 x 14 window, fused backward */
 #define MEMHIP_ATTN_SMALL 2     /* attn.hip: up to 256 tokens held on chip */
 #define MEMHIP_ATTN_WIN 3       /* attn_win.hip: slot layout, windows 40 / 20 wide; backward recomputes the scores */

@@ -680,33 +680,6 @@ AttnBwdFlags bwd_flags(bool dtable, bool dv_bias, bool out, const void* ws, int6
   return AttnBwdFlags{dtable, dv_bias, out, ws && ((uintptr_t)ws & 15) == 0, ws_bytes};
 }
 
-// The four backward entry points are this one call: validate -> plan -> launch.  from_out: a memhip_attn_bwd_out* call -- `out`
-// is required, and rowsum(dout * out) is computed by the library (inside the fused 14 x 14 kernel when it applies, otherwise
-// by attn_delta_kernel into `delta`); ws / ws_bytes: the caller-owned workspace of the *_ws calls.
-int attn_bwd(bool from_out, const void* qkv, int64_t ldqkv, const void* dout, int64_t ldo, const void* out, int64_t ldout,
-             const float* lse, float* delta, const float* table, int window_h, int window_w, int B, int T, int D, int heads,
-             float scale, void* dqkv, int64_t lddqkv, float* dtable, float* dq_bias, float* dv_bias, void* ws, int64_t ws_bytes,
-             memhip_stream_t stream) {
-  if (const int rc = validate_shape(false, B, T, D, heads, window_h, window_w)) return rc;
-  if (B == 0) return MEMHIP_OK;
-  MEMHIP_REQUIRE(qkv && dout && (out || !from_out) && lse && delta && table && dqkv, "attn_bwd: null pointer");
-  MEMHIP_REQUIRE(ldqkv % 8 == 0 && ldo % 8 == 0 && ldout % 8 == 0 && lddqkv % 8 == 0, "attn_bwd: ld must be a multiple of 8");
-  hipStream_t s = as_stream(stream);
-  AttnArgs a = {};
-  a.qkv = qkv; a.ldqkv = ldqkv; a.table = table; a.out = const_cast<void*>(out); a.ldout = ldout;
-  a.lse = const_cast<float*>(lse); a.dout = dout; a.ldo = ldo; a.delta = delta;
-  a.stats = delta + 2LL * B * T * heads;
-  a.scale = scale; a.dqkv = dqkv; a.lddqkv = lddqkv; a.dtable = dtable; a.dq_bias = dq_bias; a.dv_bias = dv_bias; a.ws = ws;
-  a.B = B; a.T = T; a.D = D; a.heads = heads; a.window_h = window_h; a.window_w = window_w;
-  const AttnPlan p = attn_plan_bwd(AttnShape{B, T, heads, window_h, window_w}, bwd_flags(dtable, dv_bias, out, ws, ws_bytes),
-                                   usable_cus(s), options_now());
-  // attn_delta_kernel reads dout and out with one leading dimension
-  MEMHIP_REQUIRE(!out || p.family == MEMHIP_ATTN_16 || ldo == ldout,
-                 "attn_bwd: dout and out must share a leading dimension on this path");
-  if (!p.count) return unsupported(p, false, T, window_h, window_w);
-  return run(a, p, false, s);
-}
-
 }  // namespace
 
 extern "C" int memhip_attn_tokens_padded(int T) { return ((T + 31) / 32) * 32; }
@@ -759,36 +732,30 @@ extern "C" int memhip_attn_delta(const void* dout, const void* out, int64_t ldo,
   return check_launch("attn_delta");
 }
 
-extern "C" int memhip_attn_bwd(const void* qkv, int64_t ldqkv, const void* dout, int64_t ldo, const float* lse,
-                               float* delta, const float* table, int window_h, int window_w, int B,
-                               int T, int D, int heads, float scale, void* dqkv, int64_t lddqkv, float* dtable,
-                               float* dq_bias, float* dv_bias, memhip_stream_t stream) {
-  return attn_bwd(false, qkv, ldqkv, dout, ldo, nullptr, 0, lse, delta, table, window_h, window_w, B, T, D, heads, scale, dqkv,
-                  lddqkv, dtable, dq_bias, dv_bias, nullptr, 0, stream);
-}
-
-extern "C" int memhip_attn_bwd_ws(const void* qkv, int64_t ldqkv, const void* dout, int64_t ldo, const float* lse,
-                                  float* delta, const float* table, int window_h, int window_w, int B,
-                                  int T, int D, int heads, float scale, void* dqkv, int64_t lddqkv, float* dtable,
-                                  float* dq_bias, float* dv_bias, void* ws, int64_t ws_bytes, memhip_stream_t stream) {
-  return attn_bwd(false, qkv, ldqkv, dout, ldo, nullptr, 0, lse, delta, table, window_h, window_w, B, T, D, heads, scale, dqkv,
-                  lddqkv, dtable, dq_bias, dv_bias, ws, ws_bytes, stream);
-}
-
-extern "C" int memhip_attn_bwd_out(const void* qkv, int64_t ldqkv, const void* dout, int64_t ldo, const void* out, int64_t ldout,
-                                   const float* lse, float* delta, const float* table, int window_h, int window_w, int B,
-                                   int T, int D, int heads, float scale, void* dqkv, int64_t lddqkv, float* dtable,
-                                   float* dq_bias, float* dv_bias, memhip_stream_t stream) {
-  return attn_bwd(true, qkv, ldqkv, dout, ldo, out, ldout, lse, delta, table, window_h, window_w, B, T, D, heads, scale, dqkv,
-                  lddqkv, dtable, dq_bias, dv_bias, nullptr, 0, stream);
-}
-
-extern "C" int memhip_attn_bwd_out_ws(const void* qkv, int64_t ldqkv, const void* dout, int64_t ldo, const void* out, int64_t ldout,
-                                      const float* lse, float* delta, const float* table, int window_h, int window_w, int B,
-                                      int T, int D, int heads, float scale, void* dqkv, int64_t lddqkv, float* dtable,
-                                      float* dq_bias, float* dv_bias, void* ws, int64_t ws_bytes, memhip_stream_t stream) {
-  return attn_bwd(true, qkv, ldqkv, dout, ldo, out, ldout, lse, delta, table, window_h, window_w, B, T, D, heads, scale, dqkv,
-                  lddqkv, dtable, dq_bias, dv_bias, ws, ws_bytes, stream);
+// validate -> plan -> launch.  With `out`, rowsum(dout * out) is computed by the library (inside the fused 14 x 14 kernel when it
+// applies, otherwise by attn_delta_kernel into `delta`)
+extern "C" int memhip_attn_bwd(const memhip_attn_bwd_args_t* args, memhip_stream_t stream) {
+  MEMHIP_REQUIRE(args, "attn_bwd: null args");
+  const memhip_attn_bwd_args_t& g = *args;
+  if (const int rc = validate_shape(false, g.B, g.T, g.D, g.heads, g.window_h, g.window_w)) return rc;
+  if (g.B == 0) return MEMHIP_OK;
+  MEMHIP_REQUIRE(g.qkv && g.dout && g.lse && g.delta && g.table && g.dqkv, "attn_bwd: null pointer");
+  MEMHIP_REQUIRE(g.ldqkv % 8 == 0 && g.ldo % 8 == 0 && g.ldout % 8 == 0 && g.lddqkv % 8 == 0, "attn_bwd: ld must be a multiple of 8");
+  hipStream_t s = as_stream(stream);
+  AttnArgs a = {};
+  a.qkv = g.qkv; a.ldqkv = g.ldqkv; a.table = g.table; a.out = const_cast<void*>(g.out); a.ldout = g.ldout;
+  a.lse = const_cast<float*>(g.lse); a.dout = g.dout; a.ldo = g.ldo; a.delta = g.delta;
+  a.stats = g.delta + 2LL * g.B * g.T * g.heads;
+  a.scale = g.scale; a.dqkv = g.dqkv; a.lddqkv = g.lddqkv; a.dtable = g.dtable; a.dq_bias = g.dq_bias; a.dv_bias = g.dv_bias;
+  a.ws = g.ws;
+  a.B = g.B; a.T = g.T; a.D = g.D; a.heads = g.heads; a.window_h = g.window_h; a.window_w = g.window_w;
+  const AttnPlan p = attn_plan_bwd(AttnShape{g.B, g.T, g.heads, g.window_h, g.window_w},
+                                   bwd_flags(g.dtable, g.dv_bias, g.out, g.ws, g.ws_bytes), usable_cus(s), options_now());
+  // attn_delta_kernel reads dout and out with one leading dimension
+  MEMHIP_REQUIRE(!g.out || p.family == MEMHIP_ATTN_16 || g.ldo == g.ldout,
+                 "attn_bwd: dout and out must share a leading dimension on this path");
+  if (!p.count) return unsupported(p, false, g.T, g.window_h, g.window_w);
+  return run(a, p, false, s);
 }
 
 extern "C" int64_t memhip_attn_bwd_workspace(int B, int T, int heads, int window_h, int window_w) {

@@ -189,10 +189,6 @@ __device__ __forceinline__ float lds_f32_at(const float* base, int byte_off) {
 }
 
 // ---- host side: the launchers obey the plan (attn_plan.hpp) and test nothing themselves.
-// a runtime boolean as a template argument: f(std::true_type{}) or f(std::false_type{})
-template <typename F>
-int dispatch_bool(bool b, F&& f) { return b ? f(std::true_type{}) : f(std::false_type{}); }
-
 template <typename K>
 int set_lds_attr(K kernel, bool* done) {
   if (!*done) {

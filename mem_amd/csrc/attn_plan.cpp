@@ -1,4 +1,4 @@
-// The dispatch policy of memhip_attn_fwd / memhip_attn_bwd* (DESIGN.md section 4 summarises it; these functions are the truth).
+// The dispatch policy of memhip_attn_fwd / memhip_attn_bwd (DESIGN.md section 4 summarises it; these functions are the truth).
 // Every shape test, option test and LDS-budget comparison of the attention entry points is here, once; the launchers obey.
 #include "attn_plan.hpp"
 

@@ -1,4 +1,4 @@
-// Which kernels take a memhip_attn_fwd / memhip_attn_bwd* call, with which template arguments, grids and LDS sizes:
+// Which kernels take a memhip_attn_fwd / memhip_attn_bwd call, with which template arguments, grids and LDS sizes:
 // attn_plan_fwd / attn_plan_bwd (attn_plan.cpp) are the one place that decides, once per call, from the shape, the flags of
 // the call, the stream's CU count and a snapshot of the options.  Host arithmetic only: memhip_attn_plan_fwd / _bwd return
 // the same plan without a device (tests/test_attn_plan_cpu.py checks the DESIGN.md table through them).

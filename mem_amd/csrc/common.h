@@ -4,6 +4,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstdint>
+#include <type_traits>
 #include "../../include/memhip.h"
 
 namespace memhip {
@@ -38,6 +39,10 @@ int max_cus();     // all CUs, reservations ignored (workspace sizing)
 inline hipStream_t as_stream(memhip_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
 
 inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
+
+// a runtime boolean as a template argument: f(std::true_type{}) or f(std::false_type{})
+template <typename F>
+int dispatch_bool(bool b, F&& f) { return b ? f(std::true_type{}) : f(std::false_type{}); }
 
 }  // namespace memhip
 

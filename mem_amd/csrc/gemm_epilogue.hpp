@@ -41,9 +41,6 @@ int dispatch_epilogue(int epi, F&& f) {
     default: return fail(MEMHIP_EINVAL, "gemm: unknown epilogue %d", epi);
   }
 }
-// (for the template flags of a launch: f(std::true_type) / f(std::false_type))
-template <class F>
-int dispatch_bool(bool b, F&& f) { return b ? f(std::true_type{}) : f(std::false_type{}); }
 
 // residual-stream row of the dropout mask from the row the residual epilogue resolved (relative to resid / aux: with a
 // sample map the caller's rows, without it the rows of this launch's range, which starts m_base rows in)

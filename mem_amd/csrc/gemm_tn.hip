@@ -257,9 +257,9 @@ int validate_group(const memhip_tn_problem_t* problems, int count) {
 
 extern "C" size_t memhip_gemm_bf16_tn_workspace(int R, int N, int K) { return tn_workspace_bytes(R, N, K, max_cus()); }
 
-extern "C" int memhip_gemm_bf16_tn_ws(const void* A, int64_t lda, const void* B, int64_t ldb, int R, int N, int K,
-                                      float* out, int64_t ldo, int accumulate, void* workspace,
-                                      size_t workspace_bytes, memhip_stream_t stream) {
+extern "C" int memhip_gemm_bf16_tn(const void* A, int64_t lda, const void* B, int64_t ldb, int R, int N, int K,
+                                   float* out, int64_t ldo, int accumulate, void* workspace,
+                                   size_t workspace_bytes, memhip_stream_t stream) {
   MEMHIP_REQUIRE(R >= 0 && N > 0 && K > 0, "gemm_tn: bad shape R=%d N=%d K=%d", R, N, K);
   if (R == 0) return MEMHIP_OK;
   MEMHIP_REQUIRE(A && B && out, "gemm_tn: null pointer");
@@ -267,11 +267,6 @@ extern "C" int memhip_gemm_bf16_tn_ws(const void* A, int64_t lda, const void* B,
                      ((uintptr_t)B & 15) == 0, "gemm_tn: operands must be 16-byte aligned, N/K/ld %% 8 == 0");
   const memhip_tn_problem_t q = {A, lda, B, ldb, out, ldo, R, N, K, 0};
   return run(&q, 1, accumulate, workspace, workspace_bytes, as_stream(stream));
-}
-
-extern "C" int memhip_gemm_bf16_tn(const void* A, int64_t lda, const void* B, int64_t ldb, int R, int N, int K,
-                                   float* out, int64_t ldo, int accumulate, memhip_stream_t stream) {
-  return memhip_gemm_bf16_tn_ws(A, lda, B, ldb, R, N, K, out, ldo, accumulate, nullptr, 0, stream);
 }
 
 extern "C" size_t memhip_gemm_bf16_tn_group_workspace(const memhip_tn_problem_t* problems, int count) {

@@ -13,7 +13,7 @@ bool reducible(const memhip_tn_problem_t& q) { return q.ldo % 4 == 0 && aligned1
 int p8_tiles(const memhip_tn_problem_t& q) { return (q.N / kTnP8Tile) * (q.K / kTnP8Tile); }
 size_t slab_floats(const memhip_tn_problem_t& q, int splits) { return (size_t)splits * q.N * q.K; }
 
-// Product i on its own (R > 0), as memhip_gemm_bf16_tn_ws runs it.
+// Product i on its own (R > 0), as memhip_gemm_bf16_tn runs it.
 TnLaunch single(const memhip_tn_problem_t& q, int i, int accumulate, const TnWorkspace& ws, int cus, const TnOptions& o) {
   TnLaunch l = {};
   TnPart& p = l.p[0];

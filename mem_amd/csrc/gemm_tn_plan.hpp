@@ -1,5 +1,5 @@
 // Which kernel form, how many row slices and which part of the workspace every product of a weight-gradient call gets:
-// tn_plan (gemm_tn_plan.cpp) is the one place that decides, once per call, for memhip_gemm_bf16_tn / _tn_ws / _tn_group
+// tn_plan (gemm_tn_plan.cpp) is the one place that decides, once per call, for memhip_gemm_bf16_tn / _tn_group
 // and for the two workspace queries.  Host arithmetic only: memhip_gemm_bf16_tn_plan returns the same plan without a
 // device (tests/test_tn_plan_cpu.py pins it to the launchers it replaced).
 #pragma once

@@ -332,7 +332,7 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const __bf16* __restrict__ 
 // column sums cost gridDim.x atomics per column (same-address atomics are the slow part)
 constexpr int kBrMaxChunks = 8;   // float4 chunks per lane: D <= 2048
 
-// Drop = {DropParams} (memhip_branch_bwd_drop): the branch had element-wise dropout, dt -> dt * keep * scale; empty: no
+// Drop = {DropParams} (memhip_branch_t.dropout): the branch had element-wise dropout, dt -> dt * keep * scale; empty: no
 // dropout (the kernel arguments and code of that form are those without the parameter)
 template <int NCH, bool FULL, bool HAS_Y, class... Drop>
 __global__ __launch_bounds__(256) void branch_bwd_kernel(const float* __restrict__ dx, long long lddx,
@@ -469,7 +469,7 @@ __global__ __launch_bounds__(256) void branch_bwd_kernel(const float* __restrict
 // dx is produced, stored and consumed in registers -- one pass over the fp32 gradient stream less.
 //   dx[r] += LN'(dy[r]) ;  dt = dx[r] * mask[r / rps] / keep ;  dyb[r] = bf16(dt * gb) ;
 //   dgamma_ln += sum dy*xhat ; dbeta_ln += sum dy ; dgb += sum dt*y ; dbias_b += sum dyb
-// Drop = {DropParams} (memhip_layernorm_bwd_branch_drop): the produced branch gradient carries the branch's dropout mask
+// Drop = {DropParams} (memhip_branch_t.dropout): the produced branch gradient carries the branch's dropout mask
 template <int NCH, bool FULL, bool HAS_Y, class... Drop>
 __global__ __launch_bounds__(256) void ln_bwd_branch_kernel(const __bf16* __restrict__ dy, long long lddy,
                                                             const float* __restrict__ x, long long ldx, int R, int D,
@@ -902,30 +902,24 @@ __global__ __launch_bounds__(256) void ce_reduce_kernel(const float* __restrict_
 
 }  // namespace
 
-// NCH and FULL of a width: the guard-free instantiation wherever every lane owns every chunk (D a multiple of 256)
-#define ROW_DISPATCH(D, L)                                                                               \
-  do {                                                                                                   \
-    const int nchl_ = cdiv((D) / 4, 64);                                                                 \
-    const bool full_ = (D) % 256 == 0;                                                                   \
-    if (nchl_ <= 1) { if (full_) L(1, true); else L(1, false); }                                         \
-    else if (nchl_ <= 2) { if (full_) L(2, true); else L(2, false); }                                    \
-    else if (nchl_ <= 3) { if (full_) L(3, true); else L(3, false); }                                    \
-    else if (nchl_ <= 4) { if (full_) L(4, true); else L(4, false); }                                    \
-    else if (nchl_ == 5 && full_) L(5, true);                                                            \
-    else if (nchl_ == 8 && full_) L(8, true);                                                            \
-    else L(8, false);                                                                                    \
-  } while (0)
-
-// the same for a kernel whose widths end at 1024
-#define ROW_DISPATCH4(D, L)                                                                              \
-  do {                                                                                                   \
-    const int nchl_ = cdiv((D) / 4, 64);                                                                 \
-    const bool full_ = (D) % 256 == 0;                                                                   \
-    if (nchl_ <= 1) { if (full_) L(1, true); else L(1, false); }                                         \
-    else if (nchl_ <= 2) { if (full_) L(2, true); else L(2, false); }                                    \
-    else if (nchl_ <= 3) { if (full_) L(3, true); else L(3, false); }                                    \
-    else { if (full_) L(4, true); else L(4, false); }                                                    \
-  } while (0)
+// NCH and FULL of a width as template arguments: f(std::integral_constant<int, NCH>{}, std::bool_constant<FULL>{}), the guard-free
+// instantiation wherever every lane owns every chunk (D a multiple of 256).  MAXN = 4: a kernel whose widths end at 1024;
+// 8: beyond 1024 only 1280 and 2048 have a form of their own, every other width takes the guarded <8>
+template <int MAXN, class F>
+void dispatch_width(int D, F&& f) {
+  const int nch = cdiv(D / 4, 64);
+  const bool full = D % 256 == 0;
+  const auto either = [&](auto N) { if (full) f(N, std::true_type{}); else f(N, std::false_type{}); };
+  if (nch <= 1) either(std::integral_constant<int, 1>{});
+  else if (nch <= 2) either(std::integral_constant<int, 2>{});
+  else if (nch <= 3) either(std::integral_constant<int, 3>{});
+  else if (MAXN == 4 || nch <= 4) either(std::integral_constant<int, 4>{});
+  else if constexpr (MAXN == 8) {
+    if (nch == 5 && full) f(std::integral_constant<int, 5>{}, std::true_type{});
+    else if (nch == 8 && full) f(std::integral_constant<int, 8>{}, std::true_type{});
+    else f(std::integral_constant<int, 8>{}, std::false_type{});
+  }
+}
 
 extern "C" int memhip_layernorm_fwd(const float* x, int64_t ldx, const int32_t* row_idx, int R, int D,
                                     const float* gamma, const float* beta, float eps, void* y,
@@ -934,11 +928,10 @@ extern "C" int memhip_layernorm_fwd(const float* x, int64_t ldx, const int32_t* 
   if (R == 0) return MEMHIP_OK;
   MEMHIP_REQUIRE(x && gamma && beta && y && mean && rstd, "layernorm_fwd: null pointer");
   MEMHIP_REQUIRE(ldx % 4 == 0 && ldy % 4 == 0, "layernorm_fwd: ld must be a multiple of 4");
-#define LNF_LAUNCH(N, F)                                                                                 \
-  hipLaunchKernelGGL((ln_fwd_kernel<N, F>), dim3(cdiv(R, 4)), dim3(256), (size_t)2 * D * sizeof(float), as_stream(stream), \
-                     x, (long long)ldx, row_idx, R, D, gamma, beta, eps, (__bf16*)y, (long long)ldy, mean, rstd)
-  ROW_DISPATCH(D, LNF_LAUNCH);
-#undef LNF_LAUNCH
+  dispatch_width<kMaxChunks>(D, [&](auto N, auto F) {
+    hipLaunchKernelGGL((ln_fwd_kernel<decltype(N)::value, decltype(F)::value>), dim3(cdiv(R, 4)), dim3(256), (size_t)2 * D * sizeof(float), as_stream(stream),
+                       x, (long long)ldx, row_idx, R, D, gamma, beta, eps, (__bf16*)y, (long long)ldy, mean, rstd);
+  });
   return check_launch("layernorm_fwd");
 }
 
@@ -953,77 +946,49 @@ extern "C" int memhip_layernorm_bwd(const void* dy, int64_t lddy, const float* x
   int grid = cdiv(R, 4);
   const int cap = opt(OPT_LN_BWD_GRID) * 4 / 3;      // (4/3 of the fused kernel's grid: this one needs half the LDS per workgroup)
   if (grid > cap) grid = cap;
-#define LNB_LAUNCH(N, F)                                                                                 \
-  if (accumulate) LNB_LAUNCH2(N, F, true); else LNB_LAUNCH2(N, F, false)
-#define LNB_LAUNCH2(N, F, A)                                                                             \
-  hipLaunchKernelGGL((ln_bwd_kernel<N, F, A>), dim3(grid), dim3(256), (size_t)8 * D * sizeof(float), as_stream(stream), \
-                     (const __bf16*)dy, (long long)lddy, x, (long long)ldx, row_idx, R, D, gamma, mean, rstd, dres, \
-                     (long long)lddres, dgamma, dbeta)
-  ROW_DISPATCH(D, LNB_LAUNCH);
-#undef LNB_LAUNCH
-#undef LNB_LAUNCH2
+  dispatch_width<kMaxChunks>(D, [&](auto N, auto F) {
+    dispatch_bool(accumulate, [&](auto A) {
+      hipLaunchKernelGGL((ln_bwd_kernel<decltype(N)::value, decltype(F)::value, decltype(A)::value>), dim3(grid), dim3(256), (size_t)8 * D * sizeof(float), as_stream(stream),
+                         (const __bf16*)dy, (long long)lddy, x, (long long)ldx, row_idx, R, D, gamma, mean, rstd, dres,
+                         (long long)lddres, dgamma, dbeta);
+      return 0;
+    });
+  });
   return check_launch("layernorm_bwd");
 }
 
-static int branch_bwd_impl(const float* dx, int64_t lddx, const void* y, int64_t ldy,
-                           const float* gamma, const float* rowmask, float keep_prob,
-                           int rows_per_sample, int M, int D, void* dy, int64_t lddy,
-                           float* dgamma, float* dbias, const int32_t* out_map, const memhip_dropout_t* drop,
-                           memhip_stream_t stream) {
+// the one launch text of branch_bwd_kernel; drop = drop_params(*dropout) or nothing
+template <int NCH, bool FULL, bool HAS_Y, class... Drop>
+static void branch_bwd_launch(const memhip_branch_bwd_args_t& a, int grid, memhip_stream_t stream, Drop... drop) {
+  const memhip_branch_t& b = a.branch;
+  hipLaunchKernelGGL((branch_bwd_kernel<NCH, FULL, HAS_Y, Drop...>), dim3(grid), dim3(256), (size_t)8 * a.D * sizeof(float),
+                     as_stream(stream), a.dx, (long long)a.lddx, (const __bf16*)b.y, (long long)b.ldy, b.gamma, b.rowmask,
+                     b.keep_prob, b.rows_per_sample > 0 ? b.rows_per_sample : 1, a.M, a.D, (__bf16*)b.dy, (long long)b.lddy,
+                     b.dgamma, b.dbias, (const int*)b.out_map, drop...);
+}
+
+extern "C" int memhip_branch_bwd(const memhip_branch_bwd_args_t* args, memhip_stream_t stream) {
+  MEMHIP_REQUIRE(args, "branch_bwd: null args");
+  const memhip_branch_t& b = args->branch;
+  const int M = args->M, D = args->D;
   MEMHIP_REQUIRE(M >= 0 && D > 0 && D % 4 == 0, "branch_bwd: bad M=%d D=%d", M, D);
-  MEMHIP_REQUIRE(!drop || D % 8 == 0, "branch_bwd_drop: D=%d must be a multiple of 8", D);
-  MEMHIP_REQUIRE(!out_map || (!rowmask && !y && rows_per_sample > 0), "branch_bwd: out_map excludes rowmask / y");
+  MEMHIP_REQUIRE(!b.dropout || D % 8 == 0, "branch_bwd_drop: D=%d must be a multiple of 8", D);
+  MEMHIP_REQUIRE(!b.out_map || (!b.rowmask && !b.y && b.rows_per_sample > 0), "branch_bwd: out_map excludes rowmask / y");
   if (M == 0) return MEMHIP_OK;
-  MEMHIP_REQUIRE(dx && dy, "branch_bwd: null pointer");
-  MEMHIP_REQUIRE(y || !dgamma, "branch_bwd: dgamma needs y (or use memhip_layerscale_grad)");
-  MEMHIP_REQUIRE(lddx % 4 == 0 && ldy % 4 == 0 && lddy % 4 == 0, "branch_bwd: ld must be a multiple of 4");
+  MEMHIP_REQUIRE(args->dx && b.dy, "branch_bwd: null pointer");
+  MEMHIP_REQUIRE(b.y || !b.dgamma, "branch_bwd: dgamma needs y (or use memhip_layerscale_grad)");
+  MEMHIP_REQUIRE(args->lddx % 4 == 0 && b.ldy % 4 == 0 && b.lddy % 4 == 0, "branch_bwd: ld must be a multiple of 4");
   MEMHIP_REQUIRE(D <= 64 * 4 * kBrMaxChunks, "branch_bwd: D=%d too large", D);
   int grid = cdiv(M, 4);
   if (grid > 1024) grid = 1024;
-#define BRB_LAUNCH(N, F)                                                                                 \
-  if (y) BRB_LAUNCH_Y(N, F, true); else BRB_LAUNCH_Y(N, F, false)
-#define BRB_LAUNCH_Y(N, F, Y)                                                                            \
-  if (drop) BRB_LAUNCH_D(N, F, Y); else                                                                  \
-  hipLaunchKernelGGL((branch_bwd_kernel<N, F, Y>), dim3(grid), dim3(256), (size_t)8 * D * sizeof(float), as_stream(stream), \
-                     dx, (long long)lddx, (const __bf16*)y, (long long)ldy, gamma, rowmask, keep_prob,    \
-                     rows_per_sample > 0 ? rows_per_sample : 1, M, D, (__bf16*)dy, (long long)lddy, dgamma, dbias, \
-                     (const int*)out_map)
-#define BRB_LAUNCH_D(N, F, Y)                                                                            \
-  hipLaunchKernelGGL((branch_bwd_kernel<N, F, Y, DropParams>), dim3(grid), dim3(256), (size_t)8 * D * sizeof(float),  \
-                     as_stream(stream), dx, (long long)lddx, (const __bf16*)y, (long long)ldy, gamma, rowmask, keep_prob, \
-                     rows_per_sample > 0 ? rows_per_sample : 1, M, D, (__bf16*)dy, (long long)lddy, dgamma, dbias, \
-                     (const int*)out_map, drop_params(*drop))
-  ROW_DISPATCH(D, BRB_LAUNCH);
-#undef BRB_LAUNCH
-#undef BRB_LAUNCH_D
-#undef BRB_LAUNCH_Y
+  dispatch_width<kBrMaxChunks>(D, [&](auto N, auto F) {
+    dispatch_bool(b.y, [&](auto Y) {
+      if (b.dropout) branch_bwd_launch<decltype(N)::value, decltype(F)::value, decltype(Y)::value>(*args, grid, stream, drop_params(*b.dropout));
+      else branch_bwd_launch<decltype(N)::value, decltype(F)::value, decltype(Y)::value>(*args, grid, stream);
+      return 0;
+    });
+  });
   return check_launch("branch_bwd");
-}
-
-extern "C" int memhip_branch_bwd_map(const float* dx, int64_t lddx, const void* y, int64_t ldy,
-                                     const float* gamma, const float* rowmask, float keep_prob,
-                                     int rows_per_sample, int M, int D, void* dy, int64_t lddy,
-                                     float* dgamma, float* dbias, const int32_t* out_map, memhip_stream_t stream) {
-  return branch_bwd_impl(dx, lddx, y, ldy, gamma, rowmask, keep_prob, rows_per_sample, M, D, dy, lddy, dgamma, dbias, out_map,
-                         nullptr, stream);
-}
-
-extern "C" int memhip_branch_bwd_drop(const float* dx, int64_t lddx, const void* y, int64_t ldy,
-                                      const float* gamma, const float* rowmask, float keep_prob,
-                                      int rows_per_sample, int M, int D, void* dy, int64_t lddy,
-                                      float* dgamma, float* dbias, const int32_t* out_map, const memhip_dropout_t* dropout,
-                                      memhip_stream_t stream) {
-  MEMHIP_REQUIRE(dropout, "branch_bwd_drop: null dropout");
-  return branch_bwd_impl(dx, lddx, y, ldy, gamma, rowmask, keep_prob, rows_per_sample, M, D, dy, lddy, dgamma, dbias, out_map,
-                         dropout, stream);
-}
-
-extern "C" int memhip_branch_bwd(const float* dx, int64_t lddx, const void* y, int64_t ldy,
-                                 const float* gamma, const float* rowmask, float keep_prob,
-                                 int rows_per_sample, int M, int D, void* dy, int64_t lddy,
-                                 float* dgamma, float* dbias, memhip_stream_t stream) {
-  return memhip_branch_bwd_map(dx, lddx, y, ldy, gamma, rowmask, keep_prob, rows_per_sample, M, D, dy, lddy, dgamma, dbias,
-                               nullptr, stream);
 }
 
 extern "C" int memhip_embed_bwd(const float* dx, int64_t lddx, const uint8_t* mask, int B, int L, int D,
@@ -1059,22 +1024,31 @@ extern "C" int memhip_cross_entropy(void* logits, int64_t ld, const int64_t* lab
   return check_launch("cross_entropy");
 }
 
-static int ln_bwd_branch_impl(const void* dy, int64_t lddy, const float* x, int64_t ldx, int R, int D,
-                              const float* gamma, const float* mean, const float* rstd, float* dres,
-                              int64_t lddres, float* dgamma, float* dbeta, const void* y_branch,
-                              int64_t ldyb, const float* gamma_branch, const float* rowmask,
-                              float keep_prob, int rows_per_sample, void* dy_branch, int64_t lddyb,
-                              float* dgamma_branch, float* dbias_branch, const int32_t* in_map,
-                              const int32_t* out_map, const memhip_dropout_t* drop, memhip_stream_t stream) {
+// the one launch text of ln_bwd_branch_kernel; drop = drop_params(*dropout) or nothing
+template <int NCH, bool FULL, bool HAS_Y, class... Drop>
+static void ln_bwd_branch_launch(const memhip_ln_bwd_branch_args_t& a, int grid, memhip_stream_t stream, Drop... drop) {
+  const memhip_branch_t& b = a.branch;
+  hipLaunchKernelGGL((ln_bwd_branch_kernel<NCH, FULL, HAS_Y, Drop...>), dim3(grid), dim3(256), (size_t)16 * a.D * sizeof(float),
+                     as_stream(stream), (const __bf16*)a.dy, (long long)a.lddy, a.x, (long long)a.ldx, a.R, a.D, a.gamma, a.mean,
+                     a.rstd, a.dres, (long long)a.lddres, a.dgamma, a.dbeta, (const __bf16*)b.y, (long long)b.ldy, b.gamma,
+                     b.rowmask, b.keep_prob, b.rows_per_sample > 0 ? b.rows_per_sample : 1, (__bf16*)b.dy, (long long)b.lddy,
+                     b.dgamma, b.dbias, (const int*)a.in_map, (const int*)b.out_map, drop...);
+}
+
+extern "C" int memhip_layernorm_bwd_branch(const memhip_ln_bwd_branch_args_t* args, memhip_stream_t stream) {
+  MEMHIP_REQUIRE(args, "layernorm_bwd_branch: null args");
+  const memhip_ln_bwd_branch_args_t& a = *args;
+  const memhip_branch_t& b = a.branch;
+  const int R = a.R, D = a.D;
   MEMHIP_REQUIRE(R >= 0 && D > 0 && D % 4 == 0 && D <= 64 * 4 * 4, "layernorm_bwd_branch: D=%d unsupported (<= 1024)", D);
-  MEMHIP_REQUIRE(!drop || D % 8 == 0, "layernorm_bwd_branch_drop: D=%d must be a multiple of 8", D);
-  MEMHIP_REQUIRE(!(in_map || out_map) || (!rowmask && !y_branch && rows_per_sample > 0),
+  MEMHIP_REQUIRE(!b.dropout || D % 8 == 0, "layernorm_bwd_branch_drop: D=%d must be a multiple of 8", D);
+  MEMHIP_REQUIRE(!(a.in_map || b.out_map) || (!b.rowmask && !b.y && b.rows_per_sample > 0),
                  "layernorm_bwd_branch: sample maps exclude rowmask / y_branch");
   if (R == 0) return MEMHIP_OK;
-  MEMHIP_REQUIRE(dy && x && gamma && mean && rstd && dres && dgamma && dbeta && dy_branch,
+  MEMHIP_REQUIRE(a.dy && a.x && a.gamma && a.mean && a.rstd && a.dres && a.dgamma && a.dbeta && b.dy,
                  "layernorm_bwd_branch: null pointer");
-  MEMHIP_REQUIRE(y_branch || !dgamma_branch, "layernorm_bwd_branch: dgamma_branch needs y_branch");
-  MEMHIP_REQUIRE(ldx % 4 == 0 && lddy % 4 == 0 && lddres % 4 == 0 && ldyb % 4 == 0 && lddyb % 4 == 0,
+  MEMHIP_REQUIRE(b.y || !b.dgamma, "layernorm_bwd_branch: dgamma_branch needs y_branch");
+  MEMHIP_REQUIRE(a.ldx % 4 == 0 && a.lddy % 4 == 0 && a.lddres % 4 == 0 && b.ldy % 4 == 0 && b.lddy % 4 == 0,
                  "layernorm_bwd_branch: ld must be a multiple of 4");
   int grid = cdiv(R, 4);
   int cap = opt(OPT_LN_BWD_GRID);                      // 2048 (round 5).  768 = 3 resident workgroups per CU = one full round was the optimum of the
@@ -1085,65 +1059,19 @@ static int ln_bwd_branch_impl(const void* dy, int64_t lddy, const float* x, int6
   if (D > 768 && cap > 512) cap = 512;                 // D = 1024: 64 KiB of LDS and 212 VGPRs per workgroup, two per CU (tools/ln_bwd_probe.py:
                                                        // 76 864 rows 301 -> 262 us, 19 216 rows 69 -> 64 us)
   if (grid > cap) grid = cap;
-#define LBB_LAUNCH(N, F)                                                                                 \
-  if (drop) { if (y_branch) LBB_LAUNCH2D(N, F, true); else LBB_LAUNCH2D(N, F, false); }                 \
-  else if (y_branch) LBB_LAUNCH2(N, F, true); else LBB_LAUNCH2(N, F, false)
-#define LBB_LAUNCH2(N, F, Y)                                                                              \
-  hipLaunchKernelGGL((ln_bwd_branch_kernel<N, F, Y>), dim3(grid), dim3(256), (size_t)16 * D * sizeof(float), \
-                     as_stream(stream), (const __bf16*)dy, (long long)lddy, x, (long long)ldx, R, D, gamma, mean, \
-                     rstd, dres, (long long)lddres, dgamma, dbeta, (const __bf16*)y_branch, (long long)ldyb, \
-                     gamma_branch, rowmask, keep_prob, rows_per_sample > 0 ? rows_per_sample : 1,         \
-                     (__bf16*)dy_branch, (long long)lddyb, dgamma_branch, dbias_branch, (const int*)in_map, \
-                     (const int*)out_map)
-#define LBB_LAUNCH2D(N, F, Y)                                                                            \
-  hipLaunchKernelGGL((ln_bwd_branch_kernel<N, F, Y, DropParams>), dim3(grid), dim3(256), (size_t)16 * D * sizeof(float), \
-                     as_stream(stream), (const __bf16*)dy, (long long)lddy, x, (long long)ldx, R, D, gamma, mean, \
-                     rstd, dres, (long long)lddres, dgamma, dbeta, (const __bf16*)y_branch, (long long)ldyb, \
-                     gamma_branch, rowmask, keep_prob, rows_per_sample > 0 ? rows_per_sample : 1,         \
-                     (__bf16*)dy_branch, (long long)lddyb, dgamma_branch, dbias_branch, (const int*)in_map, \
-                     (const int*)out_map, drop_params(*drop))
-  ROW_DISPATCH4(D, LBB_LAUNCH);
-#undef LBB_LAUNCH
-#undef LBB_LAUNCH2
-#undef LBB_LAUNCH2D
+  dispatch_width<4>(D, [&](auto N, auto F) {     // (dropout outside HAS_Y: the order in which the instantiations have always been emitted)
+    if (b.dropout)
+      dispatch_bool(b.y, [&](auto Y) {
+        ln_bwd_branch_launch<decltype(N)::value, decltype(F)::value, decltype(Y)::value>(a, grid, stream, drop_params(*b.dropout));
+        return 0;
+      });
+    else
+      dispatch_bool(b.y, [&](auto Y) {
+        ln_bwd_branch_launch<decltype(N)::value, decltype(F)::value, decltype(Y)::value>(a, grid, stream);
+        return 0;
+      });
+  });
   return check_launch("layernorm_bwd_branch");
-}
-
-extern "C" int memhip_layernorm_bwd_branch_map(const void* dy, int64_t lddy, const float* x, int64_t ldx, int R, int D,
-                                               const float* gamma, const float* mean, const float* rstd, float* dres,
-                                               int64_t lddres, float* dgamma, float* dbeta, const void* y_branch,
-                                               int64_t ldyb, const float* gamma_branch, const float* rowmask,
-                                               float keep_prob, int rows_per_sample, void* dy_branch, int64_t lddyb,
-                                               float* dgamma_branch, float* dbias_branch, const int32_t* in_map,
-                                               const int32_t* out_map, memhip_stream_t stream) {
-  return ln_bwd_branch_impl(dy, lddy, x, ldx, R, D, gamma, mean, rstd, dres, lddres, dgamma, dbeta, y_branch, ldyb,
-                            gamma_branch, rowmask, keep_prob, rows_per_sample, dy_branch, lddyb, dgamma_branch, dbias_branch,
-                            in_map, out_map, nullptr, stream);
-}
-
-extern "C" int memhip_layernorm_bwd_branch_drop(const void* dy, int64_t lddy, const float* x, int64_t ldx, int R, int D,
-                                                const float* gamma, const float* mean, const float* rstd, float* dres,
-                                                int64_t lddres, float* dgamma, float* dbeta, const void* y_branch,
-                                                int64_t ldyb, const float* gamma_branch, const float* rowmask,
-                                                float keep_prob, int rows_per_sample, void* dy_branch, int64_t lddyb,
-                                                float* dgamma_branch, float* dbias_branch, const int32_t* in_map,
-                                                const int32_t* out_map, const memhip_dropout_t* dropout,
-                                                memhip_stream_t stream) {
-  MEMHIP_REQUIRE(dropout, "layernorm_bwd_branch_drop: null dropout");
-  return ln_bwd_branch_impl(dy, lddy, x, ldx, R, D, gamma, mean, rstd, dres, lddres, dgamma, dbeta, y_branch, ldyb,
-                            gamma_branch, rowmask, keep_prob, rows_per_sample, dy_branch, lddyb, dgamma_branch, dbias_branch,
-                            in_map, out_map, dropout, stream);
-}
-
-extern "C" int memhip_layernorm_bwd_branch(const void* dy, int64_t lddy, const float* x, int64_t ldx, int R, int D,
-                                           const float* gamma, const float* mean, const float* rstd, float* dres,
-                                           int64_t lddres, float* dgamma, float* dbeta, const void* y_branch,
-                                           int64_t ldyb, const float* gamma_branch, const float* rowmask,
-                                           float keep_prob, int rows_per_sample, void* dy_branch, int64_t lddyb,
-                                           float* dgamma_branch, float* dbias_branch, memhip_stream_t stream) {
-  return memhip_layernorm_bwd_branch_map(dy, lddy, x, ldx, R, D, gamma, mean, rstd, dres, lddres, dgamma, dbeta, y_branch,
-                                         ldyb, gamma_branch, rowmask, keep_prob, rows_per_sample, dy_branch, lddyb,
-                                         dgamma_branch, dbias_branch, nullptr, nullptr, stream);
 }
 
 extern "C" int memhip_layerscale_grad(const void* W_bf16, int64_t ldw, const float* dW, int64_t lddw, const float* bias,

@@ -7,7 +7,7 @@ import ctypes as C
 
 import torch
 
-from ._lib import check, declare, f32, i32, i64, lib, ptr, stream_ptr, sz, vp
+from ._lib import check, declare, f32, f64, i32, i64, lib, ptr, stream_ptr, sz, vp
 
 EPI_BIAS_BF16, EPI_BIAS_GELU, EPI_RESIDUAL, EPI_DGELU, EPI_F32, EPI_PATCH_EMBED, EPI_BIAS_GELU_DG, EPI_MUL_AUX = range(8)
 EPI_RESIDUAL_DROP = 8
@@ -42,6 +42,31 @@ class GemmArgs(C.Structure):
                 ("dropout", vp)]
 
 
+class Branch(C.Structure):
+    """== memhip_branch_t: the residual branch whose output gradient a row call produces."""
+    _fields_ = [("y", vp), ("ldy", i64), ("gamma", vp), ("rowmask", vp), ("keep_prob", f32), ("rows_per_sample", i32),
+                ("dy", vp), ("lddy", i64), ("dgamma", vp), ("dbias", vp), ("out_map", vp), ("dropout", vp)]
+
+
+class BranchBwdArgs(C.Structure):
+    """== memhip_branch_bwd_args_t."""
+    _fields_ = [("dx", vp), ("lddx", i64), ("M", i32), ("D", i32), ("branch", Branch)]
+
+
+class LnBwdBranchArgs(C.Structure):
+    """== memhip_ln_bwd_branch_args_t."""
+    _fields_ = [("dy", vp), ("lddy", i64), ("x", vp), ("ldx", i64), ("R", i32), ("D", i32), ("gamma", vp), ("mean", vp),
+                ("rstd", vp), ("dres", vp), ("lddres", i64), ("dgamma", vp), ("dbeta", vp), ("in_map", vp), ("branch", Branch)]
+
+
+class AttnBwdArgs(C.Structure):
+    """== memhip_attn_bwd_args_t."""
+    _fields_ = [("qkv", vp), ("ldqkv", i64), ("dout", vp), ("ldo", i64), ("out", vp), ("ldout", i64), ("lse", vp), ("delta", vp),
+                ("table", vp), ("window_h", i32), ("window_w", i32), ("B", i32), ("T", i32), ("D", i32), ("heads", i32),
+                ("scale", f32), ("reserved0", i32), ("dqkv", vp), ("lddqkv", i64), ("dtable", vp), ("dq_bias", vp),
+                ("dv_bias", vp), ("ws", vp), ("ws_bytes", i64)]
+
+
 class NtLaunch(C.Structure):
     """== memhip_nt_launch_t."""
     _fields_ = [(n, i32) for n in ("kind", "row0", "rows", "tail_rows", "guard", "copy", "grid", "tail_grid")]
@@ -53,6 +78,9 @@ class NtPlan(C.Structure):
 
 
 declare({"memhip_gemm_bf16_nt": (i32, [C.POINTER(GemmArgs), vp]),
+         "memhip_branch_bwd": (i32, [C.POINTER(BranchBwdArgs), vp]),
+         "memhip_layernorm_bwd_branch": (i32, [C.POINTER(LnBwdBranchArgs), vp]),
+         "memhip_attn_bwd": (i32, [C.POINTER(AttnBwdArgs), vp]),
          "memhip_gemm_bf16_nt_plan": (i32, [C.POINTER(GemmArgs), i32, i32, C.POINTER(NtPlan)])})
 
 
@@ -135,29 +163,17 @@ def gemm_nt_plan(a, stream_cus=None, device_cus=None):
     return [plan.l[i] for i in range(plan.count)]
 
 
-f64 = C.c_double
 declare({
     "memhip_layernorm_fwd": (i32, [vp, i64, vp, i32, i32, vp, vp, f32, vp, i64, vp, vp, vp]),
     "memhip_layernorm_bwd": (i32, [vp, i64, vp, i64, vp, i32, i32, vp, vp, vp, vp, i64, i32, vp, vp, vp]),
-    "memhip_layernorm_bwd_branch": (i32, [vp, i64, vp, i64, i32, i32, vp, vp, vp, vp, i64, vp, vp, vp, i64, vp, vp, f32,
-                                          i32, vp, i64, vp, vp, vp]),
     "memhip_layerscale_grad": (i32, [vp, i64, vp, i64, vp, vp, vp, i32, i32, vp, vp]),
-    "memhip_branch_bwd": (i32, [vp, i64, vp, i64, vp, vp, f32, i32, i32, i32, vp, i64, vp, vp, vp]),
-    "memhip_branch_bwd_map": (i32, [vp, i64, vp, i64, vp, vp, f32, i32, i32, i32, vp, i64, vp, vp, vp, vp]),
-    "memhip_layernorm_bwd_branch_map": (i32, [vp, i64, vp, i64, i32, i32, vp, vp, vp, vp, i64, vp, vp, vp, i64, vp, vp, f32,
-                                              i32, vp, i64, vp, vp, vp, vp, vp]),
     "memhip_embed_bwd": (i32, [vp, i64, vp, i32, i32, i32, vp, i64, vp, vp, vp]),
     "memhip_cross_entropy": (i32, [vp, i64, vp, i32, i32, f32, vp, vp, i32, vp, vp]),
     "memhip_attn_tokens_padded": (i32, [i32]),
     "memhip_relpos_gather": (i32, [vp, vp, i32, i32, i32, vp, vp, vp]),
     "memhip_attn_fwd": (i32, [vp, i64, i32, i32, i32, i32, vp, i32, i32, vp, i64, vp, vp]),
     "memhip_attn_delta": (i32, [vp, vp, i64, i64, i32, vp, vp]),
-    "memhip_attn_bwd": (i32, [vp, i64, vp, i64, vp, vp, vp, i32, i32, i32, i32, i32, i32, f32, vp, i64, vp, vp, vp, vp]),
-    "memhip_attn_bwd_out": (i32, [vp, i64, vp, i64, vp, i64, vp, vp, vp, i32, i32, i32, i32, i32, i32, f32, vp, i64, vp, vp, vp, vp]),
     "memhip_attn_bwd_workspace": (i64, [i32, i32, i32, i32, i32]),
-    "memhip_attn_bwd_ws": (i32, [vp, i64, vp, i64, vp, vp, vp, i32, i32, i32, i32, i32, i32, f32, vp, i64, vp, vp, vp, vp, i64, vp]),
-    "memhip_attn_bwd_out_ws": (i32, [vp, i64, vp, i64, vp, i64, vp, vp, vp, i32, i32, i32, i32, i32, i32, f32, vp, i64, vp, vp, vp,
-                                      vp, i64, vp]),
     "memhip_cast_f32_bf16": (i32, [vp, vp, i64, vp]),
     "memhip_copy_samples_f32": (i32, [vp, vp, vp, i32, i64, vp]),
     "memhip_zero": (i32, [vp, i64, vp]),
@@ -184,9 +200,6 @@ declare({
     "memhip_adamw": (i32, [vp, vp, vp, vp, i64, vp, f64, f64, f64, f64, f64, i32, vp, f64, vp]),
     "memhip_transpose_cast_batched": (i32, [vp, vp, i32, i32, vp]),
     "memhip_adamw_groups": (i32, [vp, vp, vp, vp, i64, vp, vp, i32, f64, f64, f64, i32, vp, f64, vp]),
-    "memhip_branch_bwd_drop": (i32, [vp, i64, vp, i64, vp, vp, f32, i32, i32, i32, vp, i64, vp, vp, vp, C.POINTER(Dropout), vp]),
-    "memhip_layernorm_bwd_branch_drop": (i32, [vp, i64, vp, i64, i32, i32, vp, vp, vp, vp, i64, vp, vp, vp, i64, vp, vp, f32,
-                                               i32, vp, i64, vp, vp, vp, vp, C.POINTER(Dropout), vp]),
     "memhip_dropout_mask": (i32, [C.POINTER(Dropout), i32, i32, i32, vp, vp]),
     "memhip_dropout_rows_f32": (i32, [C.POINTER(Dropout), vp, i64, i32, i32, vp]),
 })
@@ -213,23 +226,22 @@ def layernorm_bwd(dy, x, gamma, mean, rstd, dres, dgamma, dbeta, R, D, accumulat
                                    ptr(dgamma), ptr(dbeta), stream_ptr()), "layernorm_bwd")
 
 
+def _branch(y, gamma, rowmask, keep_prob, rows_per_sample, dy, dgamma, dbias, out_map, dropout):
+    """The Branch of the two row wrappers.  `dropout` (a Dropout) is referenced, not copied: the library reads it on the host
+    inside the call, and the wrapper's frame holds it until then."""
+    return Branch(_p(y), y.stride(0) if y is not None else 0, _p(gamma), _p(rowmask), keep_prob, rows_per_sample, _p(dy),
+                  dy.stride(0), _p(dgamma), _p(dbias), _p(out_map), None if dropout is None else C.addressof(dropout))
+
+
 def layernorm_bwd_branch(dy, x, gamma, mean, rstd, dres, dgamma, dbeta, R, D, y_b, gamma_b, dy_b, dgamma_b, dbias_b,
                          rowmask=None, keep_prob=1.0, rows_per_sample=1, in_map=None, out_map=None, dropout=None):
     """layernorm_bwd(accumulate=True) + the branch_bwd that reads the updated dres, in one pass.  in_map / out_map (i32
     [samples], -1 = dropped): work-skipping stochastic depth, dy / mean / rstd and dy_b then hold kept samples only.
-    dropout: the Dropout of the branch whose gradient dy_b is (memhip_layernorm_bwd_branch_drop)."""
-    if dropout is not None:
-        check(lib.memhip_layernorm_bwd_branch_drop(
-            ptr(dy), dy.stride(0), ptr(x), x.stride(0), R, D, ptr(gamma), ptr(mean), ptr(rstd), ptr(dres), dres.stride(0),
-            ptr(dgamma), ptr(dbeta), ptr(y_b), y_b.stride(0) if y_b is not None else 0, ptr(gamma_b), ptr(rowmask), keep_prob,
-            rows_per_sample, ptr(dy_b), dy_b.stride(0), ptr(dgamma_b), ptr(dbias_b), ptr(in_map), ptr(out_map), C.byref(dropout),
-            stream_ptr()), "layernorm_bwd_branch_drop")
-        return
-    check(lib.memhip_layernorm_bwd_branch_map(ptr(dy), dy.stride(0), ptr(x), x.stride(0), R, D, ptr(gamma), ptr(mean),
-                                              ptr(rstd), ptr(dres), dres.stride(0), ptr(dgamma), ptr(dbeta), ptr(y_b),
-                                              y_b.stride(0) if y_b is not None else 0, ptr(gamma_b), ptr(rowmask), keep_prob,
-                                              rows_per_sample, ptr(dy_b), dy_b.stride(0), ptr(dgamma_b), ptr(dbias_b),
-                                              ptr(in_map), ptr(out_map), stream_ptr()), "layernorm_bwd_branch")
+    dropout: the Dropout of the branch whose gradient dy_b is."""
+    a = LnBwdBranchArgs(_p(dy), dy.stride(0), _p(x), x.stride(0), R, D, _p(gamma), _p(mean), _p(rstd), _p(dres), dres.stride(0),
+                        _p(dgamma), _p(dbeta), _p(in_map),
+                        _branch(y_b, gamma_b, rowmask, keep_prob, rows_per_sample, dy_b, dgamma_b, dbias_b, out_map, dropout))
+    check(lib.memhip_layernorm_bwd_branch(C.byref(a), stream_ptr()), "layernorm_bwd_branch")
 
 
 def layerscale_grad(W16, dW, bias, dbias, gamma, N, K, dgamma):
@@ -239,14 +251,9 @@ def layerscale_grad(W16, dW, bias, dbias, gamma, N, K, dgamma):
 
 
 def branch_bwd(dx, y, gamma, dy, dgamma, dbias, M, D, rowmask=None, keep_prob=1.0, rows_per_sample=1, out_map=None, dropout=None):
-    if dropout is not None:
-        check(lib.memhip_branch_bwd_drop(ptr(dx), dx.stride(0), ptr(y), y.stride(0) if y is not None else 0, ptr(gamma),
-                                         ptr(rowmask), keep_prob, rows_per_sample, M, D, ptr(dy), dy.stride(0), ptr(dgamma),
-                                         ptr(dbias), ptr(out_map), C.byref(dropout), stream_ptr()), "branch_bwd_drop")
-        return
-    check(lib.memhip_branch_bwd_map(ptr(dx), dx.stride(0), ptr(y), y.stride(0) if y is not None else 0, ptr(gamma), ptr(rowmask),
-                                    keep_prob, rows_per_sample, M, D, ptr(dy), dy.stride(0), ptr(dgamma), ptr(dbias),
-                                    ptr(out_map), stream_ptr()), "branch_bwd")
+    a = BranchBwdArgs(_p(dx), dx.stride(0), M, D,
+                      _branch(y, gamma, rowmask, keep_prob, rows_per_sample, dy, dgamma, dbias, out_map, dropout))
+    check(lib.memhip_branch_bwd(C.byref(a), stream_ptr()), "branch_bwd")
 
 
 def gemv_acc(W, N, K, x, y, x_acc=None, zero=None):
@@ -396,17 +403,10 @@ def attn_bwd(qkv, dout, lse, delta, table, window, B, T, D, heads, scale, dqkv, 
     """out = the forward output: rowsum(dout * out) is computed by the library (inside the fused 14 x 14 kernel when it
     applies); without it `delta` must have been filled by attn_delta.  ws = a uint8 scratch tensor of at least
     attn_bwd_workspace(...) bytes: the long-window backward then stores dS instead of computing it twice."""
-    wsp, wsn = (ptr(ws), ws.numel() * ws.element_size()) if ws is not None else (None, 0)
-    if out is not None:
-        _timed(201, 10.0 * B * T * T * D, lambda: check(
-            lib.memhip_attn_bwd_out_ws(ptr(qkv), qkv.stride(0), ptr(dout), dout.stride(0), ptr(out), out.stride(0), ptr(lse),
-                                       ptr(delta), ptr(table), window[0], window[1], B, T, D, heads, scale, ptr(dqkv),
-                                       dqkv.stride(0), ptr(dtable), ptr(dq_bias), ptr(dv_bias), wsp, wsn, stream_ptr()), "attn_bwd_out"))
-        return
-    _timed(201, 10.0 * B * T * T * D, lambda: check(
-        lib.memhip_attn_bwd_ws(ptr(qkv), qkv.stride(0), ptr(dout), dout.stride(0), ptr(lse), ptr(delta), ptr(table),
-                               window[0], window[1], B, T, D, heads, scale, ptr(dqkv), dqkv.stride(0), ptr(dtable),
-                               ptr(dq_bias), ptr(dv_bias), wsp, wsn, stream_ptr()), "attn_bwd"))
+    a = AttnBwdArgs(_p(qkv), qkv.stride(0), _p(dout), dout.stride(0), _p(out), out.stride(0) if out is not None else 0, _p(lse),
+                    _p(delta), _p(table), window[0], window[1], B, T, D, heads, scale, 0, _p(dqkv), dqkv.stride(0), _p(dtable),
+                    _p(dq_bias), _p(dv_bias), _p(ws), ws.numel() * ws.element_size() if ws is not None else 0)
+    _timed(201, 10.0 * B * T * T * D, lambda: check(lib.memhip_attn_bwd(C.byref(a), stream_ptr()), "attn_bwd"))
 
 
 def residual_rows(x, rows_i32, y, gamma, rowkeep, keep_prob, R, D, out):
@@ -484,8 +484,7 @@ def adamw_groups(p, g, m, v, n, group_of_chunk, group_table, n_groups, beta1, be
 
 
 declare({
-    "memhip_gemm_bf16_tn": (i32, [vp, i64, vp, i64, i32, i32, i32, vp, i64, i32, vp]),
-    "memhip_gemm_bf16_tn_ws": (i32, [vp, i64, vp, i64, i32, i32, i32, vp, i64, i32, vp, sz, vp]),
+    "memhip_gemm_bf16_tn": (i32, [vp, i64, vp, i64, i32, i32, i32, vp, i64, i32, vp, sz, vp]),
     "memhip_gemm_bf16_tn_workspace": (sz, [i32, i32, i32]),
     "memhip_gemm_bf16_tn_group_workspace": (sz, [vp, i32]),
     "memhip_gemm_bf16_tn_group": (i32, [vp, i32, i32, vp, sz, vp]),
@@ -518,8 +517,8 @@ def gemm_tn(A, B, R, N, K, out, accumulate=True, workspace=None):
     optional uint8 scratch tensor of >= gemm_tn_workspace(R,N,K) bytes (plain-store partial tiles)."""
     ws, wsb = _ws_arg(workspace)
     _timed(100, 2.0 * R * N * K, lambda: check(
-        lib.memhip_gemm_bf16_tn_ws(ptr(A), A.stride(0), ptr(B), B.stride(0), R, N, K, ptr(out), out.stride(0),
-                                   int(accumulate), ws, wsb, stream_ptr()), "gemm_bf16_tn"))
+        lib.memhip_gemm_bf16_tn(ptr(A), A.stride(0), ptr(B), B.stride(0), R, N, K, ptr(out), out.stride(0),
+                                int(accumulate), ws, wsb, stream_ptr()), "gemm_bf16_tn"))
 
 
 class TnProblem(C.Structure):

@@ -197,7 +197,7 @@ def parent_bwd(B, T, H, Wh, Ww, cus, o16, owin, dtable, dv_bias, out, ws, ws_byt
         nwg = nwg16(B, H, cus)
         return A16, dict(nwg=nwg, fd=int(out), **vbdt), [("attn16_bwd_kernel", (nwg * H, 1, 1), 7 * 64, LDS_BWD16)]
     L = []
-    if out:                                                                    # memhip_attn_bwd_out_ws: memhip_attn_delta first
+    if out:                                                                    # memhip_attn_bwd with `out`: memhip_attn_delta first
         L.append(("attn_delta_kernel", ((B * T * H + 31) // 32, 1, 1), 256, 0))
     nkb = (T + 31) // 32
     TP = nkb * 32

@@ -165,7 +165,7 @@ def test_attention_fwd_bwd(B, T, H, win):
 @pytest.mark.parametrize("B,T,H,win", [(2, 321, 2, (16, 20)), (3, 261, 3, (13, 20)), (4, 281, 3, (7, 40)), (9, 1041, 4, (26, 40)),
                                        (9, 921, 4, (23, 40)), (3, 1201, 2, (30, 40)), (40, 1201, 16, (30, 40))])
 def test_attention_bwd_ds_storing_form(B, T, H, win):
-    """The dS-storing backward of the long-window kernels (memhip_attn_bwd_ws: the dK / dV kernel stores dS and owns the table
+    """The dS-storing backward of the long-window kernels (memhip_attn_bwd with a workspace: the dK / dV kernel stores dS and owns the table
     gradient, the dQ kernel is a streaming product over it) against the same oracle as the recomputing form; B = 40 x 16 heads:
     workgroups persistent over several samples, more than 16 samples per workgroup split."""
     from mem_amd import ops
@@ -287,7 +287,7 @@ def test_attn16_equals_general_kernels():
 @pytest.mark.parametrize("B,T,H,win,with_table", [(29, 197, 3, (14, 14), True), (14, 197, 12, (14, 14), False), (1, 197, 2, (14, 14), True),
                                                  (5, 25, 2, (4, 6), True), (2, 321, 2, (16, 20), True)])
 def test_attention_backward_from_the_forward_output(B, T, H, win, with_table):
-    """memhip_attn_bwd_out: rowsum(dO * O) computed by the library (inside the fused 14 x 14 backward; a delta pass in front
+    """memhip_attn_bwd with the forward output: rowsum(dO * O) computed by the library (inside the fused 14 x 14 backward; a delta pass in front
     of the general / streaming kernels) == memhip_attn_delta + memhip_attn_bwd on the same inputs (Attention.forward backward,
     mem/modeling_finetune.py:137-154).  B = 1 / 14 / 29: one, uneven and several samples per workgroup (first-sample path,
     the next-sample loads of the last sample)."""

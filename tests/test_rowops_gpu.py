@@ -435,7 +435,7 @@ BRB_CASES = [(768, 255, 197), (1024, 63, 1201), (260, 2, 197), (768, 3, 5)]    #
 @pytest.mark.parametrize("D,B,rps", BRB_CASES)
 @pytest.mark.parametrize("exact", [True, False])
 def test_branch_bwd(D, B, rps, exact):
-    """memhip_branch_bwd_map: rowmask with y and gamma, y = None, gamma = None, out_map (mixed, all kept, all dropped).
+    """memhip_branch_bwd: rowmask with y and gamma, y = None, gamma = None, out_map (mixed, all kept, all dropped).
     M = B * rps is odd: the last iteration of the two-rows-per-iteration loop has one row."""
     from mem_amd import ops
     g = _gen(400 + D + B)

@@ -1,4 +1,4 @@
-"""-m "not gpu": the dispatch of the weight-gradient GEMMs (memhip_gemm_bf16_tn / _tn_ws / _tn_group), checked through the
+"""-m "not gpu": the dispatch of the weight-gradient GEMMs (memhip_gemm_bf16_tn / _tn_group), checked through the
 plan query memhip_gemm_bf16_tn_plan against a transcription of the launchers the plan replaced (group dispatch -> single
 dispatch -> the 128 x 128 kernel's inline arithmetic), and the two workspace queries against a transcription of theirs.
 The query validates and plans like the calls and launches nothing: pointers are placeholders of which only the address
@@ -79,7 +79,7 @@ def old_group_plan(pr, num_cu):
 
 
 def old_single(i, q, accumulate, ws, ws_bytes, num_cu, p8_on):
-    """memhip_gemm_bf16_tn_ws behind its validation (R > 0)"""
+    """memhip_gemm_bf16_tn behind its validation (R > 0)"""
     R, N, K, out, ldo = q
     if p8_on and N % 256 == 0 and K % 256 == 0 and R >= 2048 and num_cu:           # gemm_tn_p8_dispatch
         tiles, splits, rows = old_p8_plan(R, N, K, num_cu)
