@@ -36,7 +36,7 @@ extern "C" {
 #endif
 
 #define MEMHIP_ABI_VERSION 8   /* 8: one entry point per backward family, optional features as struct fields (memhip_branch_bwd, memhip_layernorm_bwd_branch,
-                                  memhip_attn_bwd take an args struct; memhip_gemm_bf16_tn takes the workspace; the *_map / *_drop / *_out / *_ws symbols are gone);
+                                  memhip_attn_bwd take an args struct; memhip_gemm_bf16_tn takes the workspace; the *_map / *_drop / *_out / *_ws symbols are gone; additive since: the memhip_neck_* entry points of the feature-pyramid necks);
                                   7: the finetuning recipe (memhip_mixup, memhip_mix_targets, memhip_ce_soft, memhip_ema_update), and -- additive, no
                                   existing signature changed, so the number stays -- memhip_pool_tokens / memhip_pool_tokens_bwd, memhip_gemm_bf16_nt_plan, memhip_tokens_to_maps / memhip_maps_to_tokens_add, memhip_conv_plan, memhip_gemm_bf16_tn_plan / memhip_gemm_bf16_tn_plan_workspace; 6: element-wise dropout (memhip_dropout_t, epilogue RESIDUAL_DROP, memhip_gemm_args_t.dropout, the
                                   dropout in the row kernels); 5 (round 6): memhip_build_flags, the attention backward's workspace, memhip_attn_bwd_workspace; 4 (round 5): epilogues 6 / 7 carry the stored GELU derivative as FP16 (since round 4), certified-tokenizer entry points */
@@ -932,6 +932,51 @@ int memhip_tokens_to_maps(const float* x, int64_t ldx, int b0, int b1, int T, in
  * exactly one fp32 add per element, no atomics (every dx element has one writer: the result is deterministic); cls rows,
  * columns >= D and other samples are untouched.  Same shape rules (dx 16-byte aligned, lddx % 4 == 0). */
 int memhip_maps_to_tokens_add(const float* dmap, int b0, int b1, int T, int D, float* dx, int64_t lddx, memhip_stream_t stream);
+
+/* ------------------------------------------------------------------------
+ * Feature-pyramid necks of the segmentation backbone (necks.hip; additive to ABI 8)
+ * replaces fpn1 = ConvTranspose2d(2,2) -> SyncBatchNorm -> GELU -> ConvTranspose2d(2,2) and fpn2 = ConvTranspose2d(2,2)
+ *          (and their autograd backward) around the bf16 GEMMs              mem/semantic_segmentation/backbone/mem.py:331-346
+ * ------------------------------------------------------------------------
+ * A ConvTranspose2d with kernel = stride = 2 is Y = X W: pixel rows X [R, D] (row = (b, y, x)), the weight [D, D, 2, 2] read
+ * as the [D, 4D] matrix it is in memory (column 4 co + q, q = 2i + j).  Y [R, 4D] is INTERLEAVED: row r holds the four
+ * output pixels (2y + i, 2x + j) of input pixel r per channel; as plain rows the same values are Z [4R, D],
+ * Z[4r + q, co] = Y[r, 4 co + q].  A second level nests: row 16 r0 + 4 qa + qb is pixel (4y + 2ia + ib, 4x + 2ja + jb).
+ * All bf16 buffers are dense and 16-byte aligned, D % 64 == 0; every kernel is pure streaming through a 64 x 64 LDS tile,
+ * 16-byte lane accesses (8 on the fp32 side of level 1), ragged last tiles neither read nor written; no atomics.
+ *
+ * memhip_neck_maps_to_rows: map f32 [B, D, 2^level Hp, 2^level Wp] -> bf16 (round to nearest even),
+ *   level 0: plain rows [B Hp Wp, D]; level 1 / 2: interleaved [B Hp Wp 4^(level-1), 4D] in the nested order above (the
+ *   gradient of an upsampled map as the A operand of the dgrad / wgrad products).  map: 4- / 8- / 16-byte aligned at level
+ *   0 / 1 / 2 (level 0 moves 16 bytes per lane when Hp Wp % 4 == 0 and map is 16-byte aligned, single floats otherwise).
+ * memhip_neck_rows_to_maps: the inverse, bf16 -> f32 (exact). */
+int memhip_neck_maps_to_rows(const float* map, int B, int D, int Hp, int Wp, int level, void* rows_bf16, memhip_stream_t stream);
+int memhip_neck_rows_to_maps(const void* rows_bf16, int B, int D, int Hp, int Wp, int level, float* map, memhip_stream_t stream);
+/* Column sums in two stages: at most MEMHIP_NECK_GROUPS partials per channel, stored to `workspace`
+ * (memhip_neck_sums_workspace(D) bytes) and added by a finish kernel in fixed order (bit-reproducible).
+ * memhip_neck_colstats: y bf16 [R, 4D] interleaved, shift f32 [D] -> out f32 [3, D] = count (4R), sum (x - shift),
+ *   sum (x - shift)^2 per channel: with shift near the channel mean (the convolution's bias) the variance
+ *   sum2 / n - (sum / n)^2 keeps its digits under a common offset.  The longest chain of fp32 additions behind one output is
+ *   4 ceil(R / (8 G)) + 8 + G with G = min(ceil(R / 8), MEMHIP_NECK_GROUPS). */
+#define MEMHIP_NECK_GROUPS 128
+size_t memhip_neck_sums_workspace(int D);
+int memhip_neck_colstats(const void* y_bf16, int64_t R, int D, const float* shift, float* workspace, size_t workspace_bytes,
+                         float* out, memhip_stream_t stream);
+/* z bf16 [4R, D] = bf16(gelu(gamma (y - mean) rstd + beta)) (fp32 chain, exact-erf GELU, one rounding), y bf16 [R, 4D]
+ * interleaved; mean / rstd are the batch statistics in train() and the running ones in eval(). */
+int memhip_neck_bn_gelu_fwd(const void* y_bf16, int64_t R, int D, const float* mean, const float* rstd, const float* gamma,
+                            const float* beta, void* z_bf16, memhip_stream_t stream);
+/* Backward of the above from da bf16 [4R, D] (gradient w.r.t. z) and the stored y: with xhat = (y - mean) rstd,
+ * u = gamma xhat + beta, g = da gelu'(u):
+ *   _sums:  out f32 [2, D] = sum g (= dbeta), sum g xhat (= dgamma) per channel
+ *   _apply: dy bf16 [R, 4D] interleaved = gamma rstd (g - sums[0] inv_n - xhat sums[1] inv_n); inv_n = 1 / (elements per
+ *           channel over all ranks), sums = the (all-reduced) output of _sums. */
+int memhip_neck_bn_gelu_bwd_sums(const void* da_bf16, const void* y_bf16, int64_t R, int D, const float* mean, const float* rstd,
+                                 const float* gamma, const float* beta, float* workspace, size_t workspace_bytes, float* out,
+                                 memhip_stream_t stream);
+int memhip_neck_bn_gelu_bwd_apply(const void* da_bf16, const void* y_bf16, int64_t R, int D, const float* mean, const float* rstd,
+                                  const float* gamma, const float* beta, const float* sums, float inv_n, void* dy_bf16,
+                                  memhip_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -907,3 +907,103 @@ def maps_to_tokens_add(dmap, dx, B, T, b0=0, b1=None):
     assert 0 <= b0 < b1 <= B, (b0, b1, B)
     check(lib.memhip_maps_to_tokens_add(ptr(dmap), b0, b1, T, D, ptr(dx), dx.stride(0), stream_ptr()), "maps_to_tokens_add")
     return dx
+
+
+# ---------------------------------------------------------------- feature-pyramid necks (csrc/necks.hip)
+declare({
+    "memhip_neck_maps_to_rows": (i32, [vp, i32, i32, i32, i32, i32, vp, vp]),
+    "memhip_neck_rows_to_maps": (i32, [vp, i32, i32, i32, i32, i32, vp, vp]),
+    "memhip_neck_sums_workspace": (sz, [i32]),
+    "memhip_neck_colstats": (i32, [vp, i64, i32, vp, vp, sz, vp, vp]),
+    "memhip_neck_bn_gelu_fwd": (i32, [vp, i64, i32, vp, vp, vp, vp, vp, vp]),
+    "memhip_neck_bn_gelu_bwd_sums": (i32, [vp, vp, i64, i32, vp, vp, vp, vp, vp, sz, vp, vp]),
+    "memhip_neck_bn_gelu_bwd_apply": (i32, [vp, vp, i64, i32, vp, vp, vp, vp, vp, f32, vp, vp]),
+})
+NECK_GROUPS = 128        # == MEMHIP_NECK_GROUPS: the most partials per channel of the two-stage column sums
+
+
+def _neck_rows_shape(B, D, Hp, Wp, level):
+    R0 = B * Hp * Wp
+    return (R0, D) if level == 0 else (R0 * 4 ** (level - 1), 4 * D)
+
+
+def neck_maps_to_rows(x, level, out=None):
+    """x f32 [B, D, 2^level Hp, 2^level Wp] contiguous -> bf16 rows: [B Hp Wp, D] (level 0) or the interleaved
+    [B Hp Wp 4^(level-1), 4D] of a map upsampled `level` times (include/memhip.h: the nested row / column order)."""
+    assert x.dtype == torch.float32 and x.dim() == 4 and x.is_contiguous() and level in (0, 1, 2)
+    B, D = x.shape[:2]
+    Hp, Wp = x.shape[2] >> level, x.shape[3] >> level
+    assert (Hp << level, Wp << level) == tuple(x.shape[2:]), (tuple(x.shape), level)
+    shape = _neck_rows_shape(B, D, Hp, Wp, level)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.bfloat16, device=x.device)
+    assert out.dtype == torch.bfloat16 and out.is_contiguous() and tuple(out.shape) == shape
+    check(lib.memhip_neck_maps_to_rows(ptr(x), B, D, Hp, Wp, level, ptr(out), stream_ptr()), "neck_maps_to_rows")
+    return out
+
+
+def neck_rows_to_maps(rows, B, D, Hp, Wp, level, out=None):
+    """The inverse of neck_maps_to_rows: bf16 rows -> f32 [B, D, 2^level Hp, 2^level Wp]."""
+    assert rows.dtype == torch.bfloat16 and rows.is_contiguous() and tuple(rows.shape) == _neck_rows_shape(B, D, Hp, Wp, level)
+    shape = (B, D, Hp << level, Wp << level)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=rows.device)
+    assert out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == shape
+    check(lib.memhip_neck_rows_to_maps(ptr(rows), B, D, Hp, Wp, level, ptr(out), stream_ptr()), "neck_rows_to_maps")
+    return out
+
+
+def neck_sums_workspace(D, device):
+    return torch.empty(int(lib.memhip_neck_sums_workspace(D)) // 4, dtype=torch.float32, device=device)
+
+
+def neck_colstats(y, shift, ws, out=None):
+    """y bf16 [R, 4D] interleaved, shift f32 [D] -> out f32 [3, D]: count, sum (x - shift), sum (x - shift)^2 per channel."""
+    R, D = y.shape[0], y.shape[1] // 4
+    assert y.dtype == torch.bfloat16 and y.is_contiguous() and shift.dtype == torch.float32 and shift.numel() == D
+    if out is None:
+        out = torch.empty((3, D), dtype=torch.float32, device=y.device)
+    assert out.dtype == torch.float32 and out.is_contiguous() and out.numel() == 3 * D
+    check(lib.memhip_neck_colstats(ptr(y), R, D, ptr(shift), ptr(ws), ws.numel() * 4, ptr(out), stream_ptr()), "neck_colstats")
+    return out
+
+
+def neck_bn_gelu_fwd(y, mean, rstd, gamma, beta, out=None):
+    """y bf16 [R, 4D] interleaved -> bf16 [4R, D] = gelu(gamma (y - mean) rstd + beta), de-interleaved."""
+    R, D = y.shape[0], y.shape[1] // 4
+    assert y.dtype == torch.bfloat16 and y.is_contiguous()
+    assert all(v.dtype == torch.float32 and v.numel() == D and v.is_contiguous() for v in (mean, rstd, gamma, beta))
+    if out is None:
+        out = torch.empty((4 * R, D), dtype=torch.bfloat16, device=y.device)
+    assert out.dtype == torch.bfloat16 and out.is_contiguous() and tuple(out.shape) == (4 * R, D)
+    check(lib.memhip_neck_bn_gelu_fwd(ptr(y), R, D, ptr(mean), ptr(rstd), ptr(gamma), ptr(beta), ptr(out), stream_ptr()),
+          "neck_bn_gelu_fwd")
+    return out
+
+
+def neck_bn_gelu_bwd_sums(da, y, mean, rstd, gamma, beta, ws, out=None):
+    """out f32 [2, D] = per channel sum g, sum g xhat with g = da gelu'(gamma xhat + beta) (da bf16 [4R, D], y bf16 [R, 4D])."""
+    R, D = y.shape[0], y.shape[1] // 4
+    assert y.dtype == torch.bfloat16 and y.is_contiguous() and da.dtype == torch.bfloat16 and da.is_contiguous()
+    assert tuple(da.shape) == (4 * R, D)
+    assert all(v.dtype == torch.float32 and v.numel() == D and v.is_contiguous() for v in (mean, rstd, gamma, beta))
+    if out is None:
+        out = torch.empty((2, D), dtype=torch.float32, device=y.device)
+    assert out.dtype == torch.float32 and out.is_contiguous() and out.numel() == 2 * D
+    check(lib.memhip_neck_bn_gelu_bwd_sums(ptr(da), ptr(y), R, D, ptr(mean), ptr(rstd), ptr(gamma), ptr(beta), ptr(ws),
+                                           ws.numel() * 4, ptr(out), stream_ptr()), "neck_bn_gelu_bwd_sums")
+    return out
+
+
+def neck_bn_gelu_bwd_apply(da, y, mean, rstd, gamma, beta, sums, inv_n, out=None):
+    """dy bf16 [R, 4D] interleaved = gamma rstd (g - sums[0] inv_n - xhat sums[1] inv_n)."""
+    R, D = y.shape[0], y.shape[1] // 4
+    assert y.dtype == torch.bfloat16 and y.is_contiguous() and da.dtype == torch.bfloat16 and da.is_contiguous()
+    assert tuple(da.shape) == (4 * R, D) and sums.dtype == torch.float32 and sums.is_contiguous() and sums.numel() == 2 * D
+    assert all(v.dtype == torch.float32 and v.numel() == D and v.is_contiguous() for v in (mean, rstd, gamma, beta))
+    if out is None:
+        out = torch.empty((R, 4 * D), dtype=torch.bfloat16, device=y.device)
+    assert out.dtype == torch.bfloat16 and out.is_contiguous() and tuple(out.shape) == (R, 4 * D)
+    check(lib.memhip_neck_bn_gelu_bwd_apply(ptr(da), ptr(y), R, D, ptr(mean), ptr(rstd), ptr(gamma), ptr(beta), ptr(sums),
+                                            float(inv_n), ptr(out), stream_ptr()), "neck_bn_gelu_bwd_apply")
+    return out

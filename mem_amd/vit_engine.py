@@ -163,6 +163,7 @@ class ViTEngine(FlatParams):
         self.B_stash = 0                 # batch size the backward-only buffers are allocated for (_alloc_stash)
         self.step_masks = None
         self.weights_dirty = True
+        self.w16_version = 0             # counts the refreshes of the bf16 shadows (necks.FusedNecks re-makes its transposed copies)
         self._zero_plans = {}
         self.grad_hook = None            # called as grad_hook(bucket_index) when a bucket's grads are final
         self.hook_on_side = True         # the hook runs on the weight-gradient stream: no per-layer join (_bucket_ready)
@@ -406,6 +407,7 @@ class ViTEngine(FlatParams):
             self._build_transpose_descs()
         ops.transpose_cast_batched(self._tdesc, self._tprefix, self._tn, self._ttiles)
         self.weights_dirty = False
+        self.w16_version += 1
 
     def _build_transpose_descs(self):
         """Descriptors of the [in,out]-major bf16 weight copies (one batched launch per step, memhip_transpose_cast_batched)."""
@@ -1181,6 +1183,7 @@ class ViTEngine(FlatParams):
         elif not self.weights_dirty:
             assert end <= self.head_end, "partial weight update: the head bucket only (no transposed copies to refresh)"
             ops.cast_f32_bf16(self.flat_p[:end], self.flat_w16[:end], end)
+            self.w16_version += 1
 
     def adamw_step(self, m, v, lr, wd, step, betas=(0.9, 0.95), eps=1e-8, max_norm=0.0):
         if not (self.overlap_optimizer and self.head_kind == "mlm" and not self.fwd_two_streams):
@@ -1217,6 +1220,7 @@ class ViTEngine(FlatParams):
         self._opt_ev = self._opt_events
         self._opt_done = self._opt_events["__done__"]
         self.weights_dirty = False
+        self.w16_version += 1
 
     def _wait_params(self, bucket):
         """The launch stream waits until the pipelined optimizer has updated (and cast) the parameters of `bucket`."""
