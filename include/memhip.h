@@ -35,7 +35,9 @@
 extern "C" {
 #endif
 
-#define MEMHIP_ABI_VERSION 8   /* 8: one entry point per backward family, optional features as struct fields (memhip_branch_bwd, memhip_layernorm_bwd_branch,
+#define MEMHIP_ABI_VERSION 9   /* 9: the tokenizer takes one args struct: memhip_conv2d_nhwc and memhip_conv_plan read the same memhip_conv_args_t; one
+                                  memhip_nchw_to_padded_nhwc4 and one memhip_argmax_rows with a mode argument; the per-mode symbols (_bf16 / _f32 / _f32_dyn / _f32_ex / _f16x2) are gone;
+                                  8: one entry point per backward family, optional features as struct fields (memhip_branch_bwd, memhip_layernorm_bwd_branch,
                                   memhip_attn_bwd take an args struct; memhip_gemm_bf16_tn takes the workspace; the *_map / *_drop / *_out / *_ws symbols are gone; additive since: the memhip_neck_* entry points of the feature-pyramid necks);
                                   7: the finetuning recipe (memhip_mixup, memhip_mix_targets, memhip_ce_soft, memhip_ema_update), and -- additive, no
                                   existing signature changed, so the number stays -- memhip_pool_tokens / memhip_pool_tokens_bwd, memhip_gemm_bf16_nt_plan, memhip_tokens_to_maps / memhip_maps_to_tokens_add, memhip_conv_plan, memhip_gemm_bf16_tn_plan / memhip_gemm_bf16_tn_plan_workspace; 6: element-wise dropout (memhip_dropout_t, epilogue RESIDUAL_DROP, memhip_gemm_args_t.dropout, the
@@ -706,81 +708,85 @@ int memhip_mae_loss(const float* pred, const float* img, const float* mask, int 
  *          encoder stack / ResBlock                   eventvae/vae/vae_model.py:29-42,86-101
  * called every pretraining step at                   mem/engine_for_pretraining.py:144
  * ------------------------------------------------------------------------
- * Activations are bf16 NHWC with a one-pixel zero border: [B, H+2, W+2, C] (the caller zeroes the
- * buffers once; the kernels only write interiors).  conv2d: out = [relu](conv(in, weight) + bias) [+ add];
- * weight bf16 [C_out, k*k*C_in] packed (ky, kx, c)-major; shapes 4x4/s2/p1, 3x3/s1/p1, 1x1/s1/p0;
- * C_in = 4 (first layer: 3 channels + 1 zero, 4x4 only) or a multiple of 64; out_padded = 0 writes a
- * dense [B*Ho*Wo, C_out] matrix (the token logits).  `add` has the layout of `out` (ResBlock residual).
- * Precision: bf16 operands, fp32 accumulate (the reference runs this stage in fp32 / TF32). */
-int memhip_conv2d_nhwc_bf16(const void* in, const void* weight, const float* bias, const void* add, void* out,
-                            int B, int H, int W, int Cin, int Cout, int ksize, int stride, int pad, int relu,
-                            int out_padded, memhip_stream_t stream);
-/* x f32 NCHW [B, C<=4, H, W] -> bf16 [B, H+2, W+2, 4] interior; mean/std f32 [C] or both NULL (DiscreteVAE.norm) */
-int memhip_nchw_to_padded_nhwc4(const float* x, int B, int C, int H, int W, const float* mean, const float* stdv,
-                                void* out, memhip_stream_t stream);
-/* ids i64 [M] = argmax over the N columns of logits bf16 [M, ld] (first maximum) */
-int memhip_argmax_rows_bf16(const void* logits, int64_t ld, int M, int N, int64_t* ids, memhip_stream_t stream);
-
-/* The same three entry points in fp32 -- the EXACT-label mode (default): the reference computes the tokenizer in fp32
+ * Three modes (MEMHIP_CONV_*), one set of entry points.  conv2d: out = [relu](conv(in, weight) + bias) [+ add] on NHWC
+ * activations with a one-pixel zero border, [B, H+2, W+2, C] (the caller zeroes the buffers once; the kernels only write
+ * interiors); weight [C_out, k*k*C_in] packed (ky, kx, c)-major; `add` has the layout of `out` (ResBlock residual).
+ *
+ * MEMHIP_CONV_BF16: activations and weights bf16, fp32 accumulate (the reference runs this stage in fp32 / TF32).  Shapes
+ * 4x4/s2/p1, 3x3/s1/p1, 1x1/s1/p0; C_in = 4 (first layer: 3 channels + 1 zero, 4x4 only) or a multiple of 64; C_out a
+ * multiple of 8.
+ *
+ * MEMHIP_CONV_F32 -- the EXACT-label mode (default): the reference computes the tokenizer in fp32
  * (mem/engine_for_pretraining.py:140-145 is outside the autocast block at :147) and its output is an integer, so the
  * labels are produced with fp32 operands and fp32 accumulation (v_mfma_f32_16x16x4_f32, an fmaf chain over k).
- * Activations fp32 NHWC with the one-pixel zero border, weight fp32 [C_out, k*k*C_in] (ky, kx, c)-major; any kernel
- * size 1..4, stride >= 1, pad 0/1; C_in, C_out multiples of 4, k*k*C_in a multiple of 32.
- * argmax_rows_f32: ids = first maximum of each row; top2_gap (f32 [M], may be NULL) = best - runner-up logit. */
-int memhip_conv2d_nhwc_f32(const float* in, const float* weight, const float* bias, const float* add, float* out,
-                           int B, int H, int W, int Cin, int Cout, int ksize, int stride, int pad, int relu,
-                           int out_padded, memhip_stream_t stream);
-int memhip_nchw_to_padded_nhwc4_f32(const float* x, int B, int C, int H, int W, const float* mean, const float* stdv,
-                                    float* out, memhip_stream_t stream);
-int memhip_argmax_rows_f32(const float* logits, int64_t ld, int M, int N, int64_t* ids, float* top2_gap,
-                           memhip_stream_t stream);
+ * Activations and weights fp32; any kernel size 1..4, stride >= 1, pad 0/1; C_in, C_out multiples of 4, k*k*C_in a
+ * multiple of 32.
+ *
+ * MEMHIP_CONV_F16X2 -- "fp16 x 2" (opt-in, `--tokenizer_impl hip_fp16x2`): every fp32 value travels as two fp16 planes
+ * hi = fp16(v), lo = fp16((v - hi) * 2048); a product is three fp16 MFMAs (hi*hi + (hi*lo + lo*hi) / 2048, exact products,
+ * fp32 accumulation).  Logits within 1.4e-5 of the fp32 module at a spread of 1.77 (between the exact fp32 mode and the bf16
+ * mode), ~2x faster than fp32.  Tensors: base pointer of the hi plane + plane stride to the lo plane; weights
+ * [2][C_out, k*k*C_in]; shapes as MEMHIP_CONV_BF16.
+ *
+ * A field that the mode does not have must be 0 / NULL (MEMHIP_EINVAL otherwise); B == 0 is MEMHIP_OK, nothing is read. */
+enum { MEMHIP_CONV_BF16, MEMHIP_CONV_F32, MEMHIP_CONV_F16X2 };
+typedef struct memhip_conv_args {
+  int32_t mode;               /* MEMHIP_CONV_* */
+  int32_t reserved0;
+  const void* in;             /* [B, H+2, W+2, Cin] */
+  int64_t in_plane;           /* the four *_plane: MEMHIP_CONV_F16X2 only, elements from the hi plane to the lo plane */
+  const void* weight;         /* [Cout, ksize*ksize*Cin] */
+  int64_t w_plane;
+  const float* bias;          /* f32 [Cout], or NULL */
+  const void* add;            /* residual, laid out like `out`, or NULL */
+  int64_t add_plane;
+  void* out;                  /* [B, Ho+2, Wo+2, Cout] interior, or see out_padded / out_f32 */
+  int64_t out_plane;
+  int32_t B, H, W, Cin, Cout, ksize, stride, pad;
+  int32_t relu;
+  int32_t out_padded;         /* 0: `out` is a dense [B*Ho*Wo, Cout] matrix (the token logits) */
+  int32_t out_f32;            /* MEMHIP_CONV_F16X2 only: `out` is the dense fp32 logit matrix (out_padded = 0, out_plane unused) */
+  int32_t reserved1;
+  const int32_t* n_active;    /* MEMHIP_CONV_F32 only; NULL = static batch.  Device int32: only the first *n_active samples
+                                 of the capacity B are live (the grid covers the capacity; tiles behind the live rows return at once) */
+} memhip_conv_args_t;
+int memhip_conv2d_nhwc(const memhip_conv_args_t* args, memhip_stream_t stream);
+/* x f32 NCHW [B, C<=4, H, W] -> the interior of `out` [B, H+2, W+2, 4] in the activation format of `mode` (out_plane:
+ * MEMHIP_CONV_F16X2 only, else 0); mean/std f32 [C] or both NULL (DiscreteVAE.norm) */
+int memhip_nchw_to_padded_nhwc4(const float* x, int B, int C, int H, int W, const float* mean, const float* stdv, void* out,
+                                int64_t out_plane, int mode, memhip_stream_t stream);
+/* ids i64 [M] = argmax over the N columns of logits [M, ld] (first maximum; a NaN is the greatest).  mode = the logits' type:
+ * MEMHIP_CONV_BF16 (N, ld multiples of 8; top2_gap, row_rms, n_samples NULL) or MEMHIP_CONV_F32 (multiples of 4; the
+ * fp16x2 mode's logits are fp32 too).  fp32, each may be NULL: top2_gap f32 [M] = best - runner-up logit, row_rms f32 [M] =
+ * sqrt(mean_n logit^2); with n_samples (device int32) only the first *n_samples x rows_per_sample rows exist. */
+int memhip_argmax_rows(const void* logits, int mode, int64_t ld, int M, int N, int64_t* ids, float* top2_gap, float* row_rms,
+                       const int32_t* n_samples, int rows_per_sample, memhip_stream_t stream);
 
 /* Certified split-precision tokenizer (round 5; replaces the same reference lines: eventvae/vae/vae_model.py:153-158, called
- * at mem/engine_for_pretraining.py:139-145 in fp32).  The fp16x2 convolutions below produce the logits; a label is ACCEPTED
+ * at mem/engine_for_pretraining.py:139-145 in fp32).  The fp16x2 convolutions produce the logits; a label is ACCEPTED
  * only where its top-2 gap exceeds kappa x the row's rms (kappa = twice a stated bound on the fp16x2 logit deviation relative
  * to the row rms: then the fp32 argmax is the same index); every sample that holds a token below the margin is recomputed
- * on the fp32 path above and its labels are replaced.  Everything is decided on the device (no host synchronisation):
- *   argmax_rows_f32_ex   argmax_rows_f32 + row_rms (f32 [M], may be NULL) = sqrt(mean_n logit^2); with n_samples (device
- *                        int32, may be NULL) only the first *n_samples x rows_per_sample rows exist
+ * on the fp32 path (memhip_conv_args_t.n_active, memhip_argmax_rows' n_samples) and its labels are replaced.  Everything is
+ * decided on the device (no host synchronisation):
  *   tok_flag_samples     list (int32 [B]) = indices of the samples with a token whose gap is not > kappa x rms (ascending),
  *                        count[0] = their number; stats (int64 [2], may be NULL): += flagged samples, += 1 call
- *   tok_gather_images_f32  nchw_to_padded_nhwc4_f32 of the samples list[offset + j], j < n_round[0] = clamp(count - offset, 0, R)
+ *   tok_gather_images_f32  the fp32 nchw_to_padded_nhwc4 of the samples list[offset + j], j < n_round[0] = clamp(count - offset, 0, R)
  *                        into slots 0.. of `out` (n_round is written: the dynamic batch of the round)
- *   conv2d_nhwc_f32_dyn  conv2d_nhwc_f32 on a buffer with capacity B of which only the first *n_active samples are live
- *                        (the grid covers the capacity; tiles behind the live rows return at once)
  *   tok_scatter_ids      ids_out[list[offset + j] * tokens_per_sample + t] = ids_in[j * tokens_per_sample + t], j < *n_round */
-int memhip_argmax_rows_f32_ex(const float* logits, int64_t ld, int M, int N, int64_t* ids, float* top2_gap, float* row_rms,
-                              const int32_t* n_samples, int rows_per_sample, memhip_stream_t stream);
 int memhip_tok_flag_samples(const float* top2_gap, const float* row_rms, int B, int tokens_per_sample, float kappa,
                             int32_t* list, int32_t* count, int64_t* stats, memhip_stream_t stream);
 int memhip_tok_gather_images_f32(const float* x, int C, int H, int W, const float* mean, const float* stdv,
                                  const int32_t* list, const int32_t* count, int offset, int R, float* out, int32_t* n_round,
                                  memhip_stream_t stream);
-int memhip_conv2d_nhwc_f32_dyn(const float* in, const float* weight, const float* bias, const float* add, float* out,
-                               int B, int H, int W, int Cin, int Cout, int ksize, int stride, int pad, int relu,
-                               int out_padded, const int32_t* n_active, memhip_stream_t stream);
 int memhip_tok_scatter_ids(const int64_t* ids_in, const int32_t* list, const int32_t* n_round, int offset, int R,
                            int tokens_per_sample, int64_t* ids_out, memhip_stream_t stream);
 
-/* "fp16 x 2" mode (opt-in, `--tokenizer_impl hip_fp16x2`): every fp32 value travels as two fp16 planes hi = fp16(v),
- * lo = fp16((v - hi) * 2048); a product is three fp16 MFMAs (hi*hi + (hi*lo + lo*hi) / 2048, exact products, fp32
- * accumulation).  Logits within 1.4e-5 of the fp32 module at a spread of 1.77 (between the exact fp32 mode and the bf16
- * mode), ~2x faster than fp32.  Tensors: base pointer of the hi plane + plane stride in elements to the lo plane; weights
- * [2][C_out, k*k*C_in]; shapes as memhip_conv2d_nhwc_bf16; out_f32 = 1 writes the dense fp32 logit matrix. */
-int memhip_conv2d_nhwc_f16x2(const void* in, int64_t in_plane, const void* weight, int64_t w_plane, const float* bias,
-                             const void* add, int64_t add_plane, void* out, int64_t out_plane, int B, int H, int W, int Cin,
-                             int Cout, int ksize, int stride, int pad, int relu, int out_padded, int out_f32,
-                             memhip_stream_t stream);
-int memhip_nchw_to_padded_nhwc4_f16x2(const float* x, int B, int C, int H, int W, const float* mean, const float* stdv,
-                                      void* out, int64_t out_plane, memhip_stream_t stream);
-
-/* The dispatch of the four conv2d entry points above as data (additive to ABI 7): the layer's geometry and the ordered
- * launches.  memhip_conv_plan validates the shape like the call of that mode (same messages, same return codes) and plans
- * with the current value of the "conv_waves" option for a device of device_cus CUs (< 0: the current device's); it launches
- * nothing and needs no device when device_cus is given.  has_add: the call gives `add`; out_f32: MEMHIP_CONV_F16X2 only;
- * dynamic: MEMHIP_CONV_F32 only, the plan of memhip_conv2d_nhwc_f32_dyn -- two launches, of which the one whose
- * [dyn_lo, dyn_hi) holds *n_active works. */
-enum { MEMHIP_CONV_BF16, MEMHIP_CONV_F32, MEMHIP_CONV_F16X2 };
+/* The dispatch of memhip_conv2d_nhwc as data: the layer's geometry and the ordered launches.  memhip_conv_plan takes the
+ * struct of the call and validates it like the call (same messages, same return codes), except that in / weight / out may be
+ * NULL: no pointer is dereferenced, `add` and `n_active` only say whether the call has a residual / a dynamic batch (two
+ * launches, of which the one whose [dyn_lo, dyn_hi) holds *n_active works).  It plans with the current value of the
+ * "conv_waves" option for a device of device_cus CUs (< 0: the current device's); it launches nothing and needs no device
+ * when device_cus is given. */
 enum { MEMHIP_CONV_K_BF16,          /* conv_gemm_kernel */
        MEMHIP_CONV_K_F32,           /* conv_gemm_f32_kernel: 128-row tiles */
        MEMHIP_CONV_K_F32_M32,       /* conv_gemm_f32_m32_kernel: 32-row tiles, dynamic batch only */
@@ -802,8 +808,7 @@ typedef struct memhip_conv_plan {
   int32_t count;
   memhip_conv_launch_t l[2];
 } memhip_conv_plan_t;
-int memhip_conv_plan(int mode, int B, int H, int W, int Cin, int Cout, int ksize, int stride, int pad, int has_add,
-                     int out_f32, int out_padded, int dynamic, int device_cus, memhip_conv_plan_t* out);
+int memhip_conv_plan(const memhip_conv_args_t* args, int device_cus, memhip_conv_plan_t* out);
 
 /* ------------------------------------------------------------------------
  * Layout / dtype movers

@@ -237,40 +237,30 @@ __global__ __launch_bounds__(256) void argmax_rows_kernel(const __bf16* __restri
 
 static_assert(BM == kConvTileM && BN == kConvTileN && BK == kConvBK16 && 2 * kStageBytes == kConvLdsBf16, "conv_plan.hpp: tile, LDS bytes");
 
-// validate -> plan -> launch (conv_plan.cpp holds the rules)
-extern "C" int memhip_conv2d_nhwc_bf16(const void* in, const void* weight, const float* bias, const void* add,
-                                       void* out, int B, int H, int W, int Cin, int Cout, int ksize, int stride,
-                                       int pad, int relu, int out_padded, memhip_stream_t stream) {
-  const ConvFlags f = {add != nullptr, false, out_padded != 0, false};
-  ConvGeom g;
-  if (int rc = conv_validate(MEMHIP_CONV_BF16, B, H, W, Cin, Cout, ksize, stride, pad, f, in && weight && out, &g)) return rc;
-  const ConvPlan plan = conv_plan(MEMHIP_CONV_BF16, g, f, ConvOptions{0}, 0);
-  if (!plan.count) return MEMHIP_OK;
+namespace memhip {
+
+int conv_bf16_launch(const memhip_conv_args_t& a, const ConvGeom& g, const ConvPlan& plan, memhip_stream_t stream) {
   ConvArgs p;
-  p.in = (const __bf16*)in; p.w = (const __bf16*)weight; p.bias = bias; p.add = (const __bf16*)add; p.out = (__bf16*)out;
+  p.in = (const __bf16*)a.in; p.w = (const __bf16*)a.weight; p.bias = a.bias; p.add = (const __bf16*)a.add; p.out = (__bf16*)a.out;
   fill_geom(p, g);
-  p.kh = ksize; p.out_padded = out_padded; p.relu = relu; p.cin4 = Cin == 4 ? 1 : 0;
+  p.kh = a.ksize; p.out_padded = a.out_padded; p.relu = a.relu; p.cin4 = a.Cin == 4 ? 1 : 0;
   if (int rc = conv_launch<conv_gemm_kernel>(plan.l[0], as_stream(stream), p)) return rc;
   return check_launch("conv2d_nhwc_bf16");
 }
 
-extern "C" int memhip_nchw_to_padded_nhwc4(const float* x, int B, int C, int H, int W, const float* mean,
-                                           const float* stdv, void* out, memhip_stream_t stream) {
-  MEMHIP_REQUIRE(B >= 0 && C >= 1 && C <= 4 && H > 0 && W > 0, "nchw_to_padded_nhwc4: bad shape");
-  if (B == 0) return MEMHIP_OK;
-  MEMHIP_REQUIRE(x && out && (!mean == !stdv), "nchw_to_padded_nhwc4: null pointer");
+int to_nhwc4_bf16_launch(const float* x, int B, int C, int H, int W, const float* mean, const float* stdv, void* out, int64_t,
+                         memhip_stream_t stream) {
   const long long n = (long long)B * H * W;
   hipLaunchKernelGGL(nchw_to_padded_nhwc4_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, as_stream(stream),
                      x, B, C, H, W, mean, stdv, (__bf16*)out);
   return check_launch("nchw_to_padded_nhwc4");
 }
 
-extern "C" int memhip_argmax_rows_bf16(const void* logits, int64_t ld, int M, int N, int64_t* ids,
-                                       memhip_stream_t stream) {
-  MEMHIP_REQUIRE(M >= 0 && N > 0 && N % 8 == 0 && ld % 8 == 0, "argmax_rows: N and ld must be multiples of 8");
-  if (M == 0) return MEMHIP_OK;
-  MEMHIP_REQUIRE(logits && ids, "argmax_rows: null pointer");
+int argmax_rows_bf16_launch(const void* logits, int64_t ld, int M, int N, int64_t* ids, float*, float*, const int32_t*, int,
+                            memhip_stream_t stream) {
   hipLaunchKernelGGL(argmax_rows_kernel, dim3((M + 3) / 4), dim3(256), 0, as_stream(stream), (const __bf16*)logits,
                      (long long)ld, M, N, (long long*)ids);
   return check_launch("argmax_rows_bf16");
 }
+
+}  // namespace memhip

@@ -594,21 +594,15 @@ static_assert(BM == kConvTileM && BN == kConvTileN && WBM == kConvWideM && WBN =
 static_assert(2 * kStageBytes == kConvLdsF16x2 && 3 * kWStage == kConvLdsF16x2Wide &&
                   2 * kTileBytes + 2 * 2 * kTileBytes + 8 * 16 * 72 * 4 == kConvLdsF16x2First, "conv_plan.hpp: LDS bytes");
 
-// validate -> plan -> launch (conv_plan.cpp holds the rules: which layer gets the first-layer kernel, the wide tile, <4> or <8>)
-extern "C" int memhip_conv2d_nhwc_f16x2(const void* in, int64_t in_plane, const void* weight, int64_t w_plane, const float* bias,
-                                        const void* add, int64_t add_plane, void* out, int64_t out_plane, int B, int H, int W,
-                                        int Cin, int Cout, int ksize, int stride, int pad, int relu, int out_padded,
-                                        int out_f32, memhip_stream_t stream) {
-  const ConvFlags f = {add != nullptr, out_f32 != 0, out_padded != 0, false};
-  ConvGeom g;
-  if (int rc = conv_validate(MEMHIP_CONV_F16X2, B, H, W, Cin, Cout, ksize, stride, pad, f, in && weight && out, &g)) return rc;
-  const ConvPlan plan = conv_plan(MEMHIP_CONV_F16X2, g, f, ConvOptions{opt(OPT_CONV_WAVES)}, max_cus());
-  if (!plan.count) return MEMHIP_OK;
+namespace memhip {
+
+// the plan names the kernel (conv_plan.cpp: which layer gets the first-layer kernel, the wide tile, <4> or <8>)
+int conv_f16x2_launch(const memhip_conv_args_t& a, const ConvGeom& g, const ConvPlan& plan, memhip_stream_t stream) {
   ConvArgsH p;
-  p.in = (const _Float16*)in; p.in_plane = in_plane; p.w = (const _Float16*)weight; p.w_plane = w_plane; p.bias = bias;
-  p.add = (const _Float16*)add; p.add_plane = add_plane; p.out = out; p.out_plane = out_plane;
+  p.in = (const _Float16*)a.in; p.in_plane = a.in_plane; p.w = (const _Float16*)a.weight; p.w_plane = a.w_plane; p.bias = a.bias;
+  p.add = (const _Float16*)a.add; p.add_plane = a.add_plane; p.out = a.out; p.out_plane = a.out_plane;
   fill_geom(p, g);
-  p.kh = ksize; p.out_padded = out_padded; p.relu = relu; p.cin4 = Cin == 4 ? 1 : 0; p.out_f32 = out_f32;
+  p.kh = a.ksize; p.out_padded = a.out_padded; p.relu = a.relu; p.cin4 = a.Cin == 4 ? 1 : 0; p.out_f32 = a.out_f32;
   const ConvLaunch& l = plan.l[0];
   const hipStream_t s = as_stream(stream);
   int rc = MEMHIP_EINVAL;
@@ -622,13 +616,12 @@ extern "C" int memhip_conv2d_nhwc_f16x2(const void* in, int64_t in_plane, const 
   return check_launch(l.kernel == MEMHIP_CONV_K_F16X2_FIRST ? "conv2d_nhwc_f16x2(first)" : "conv2d_nhwc_f16x2");
 }
 
-extern "C" int memhip_nchw_to_padded_nhwc4_f16x2(const float* x, int B, int C, int H, int W, const float* mean,
-                                                 const float* stdv, void* out, int64_t out_plane, memhip_stream_t stream) {
-  MEMHIP_REQUIRE(B >= 0 && C >= 1 && C <= 4 && H > 0 && W > 0, "nchw_to_padded_nhwc4_f16x2: bad shape");
-  if (B == 0) return MEMHIP_OK;
-  MEMHIP_REQUIRE(x && out && (!mean == !stdv), "nchw_to_padded_nhwc4_f16x2: null pointer");
+int to_nhwc4_f16x2_launch(const float* x, int B, int C, int H, int W, const float* mean, const float* stdv, void* out,
+                          int64_t out_plane, memhip_stream_t stream) {
   const long long n = (long long)B * H * W;
   hipLaunchKernelGGL(nchw_to_padded_nhwc4_f16x2_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, as_stream(stream),
                      x, B, C, H, W, mean, stdv, (_Float16*)out, (long long)out_plane);
   return check_launch("nchw_to_padded_nhwc4_f16x2");
 }
+
+}  // namespace memhip

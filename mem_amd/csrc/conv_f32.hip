@@ -493,20 +493,14 @@ static_assert(BM == kConvTileM && BN == kConvTileN && SBM == kConvF32SmallM && B
 static_assert(2 * kStageFloats * sizeof(float) == kConvLdsF32 && 2 * (SBM * PITCH + kTileFloats) * sizeof(float) == kConvLdsF32M32,
               "conv_plan.hpp: LDS bytes");
 
-// validate -> plan -> launch (conv_plan.cpp holds the rules).  Dynamic batch (n_active): the plan names both tile forms, each
-// with the range of live-sample counts it works for.
-static int conv2d_nhwc_f32_impl(const float* in, const float* weight, const float* bias, const float* add, float* out,
-                                int B, int H, int W, int Cin, int Cout, int ksize, int stride, int pad, int relu,
-                                int out_padded, const int* n_active, memhip_stream_t stream) {
-  const ConvFlags f = {add != nullptr, false, out_padded != 0, n_active != nullptr};
-  ConvGeom g;
-  if (int rc = conv_validate(MEMHIP_CONV_F32, B, H, W, Cin, Cout, ksize, stride, pad, f, in && weight && out, &g)) return rc;
-  const ConvPlan plan = conv_plan(MEMHIP_CONV_F32, g, f, ConvOptions{0}, 0);
-  if (!plan.count) return MEMHIP_OK;
+namespace memhip {
+
+// Dynamic batch (n_active): the plan names both tile forms, each with the range of live-sample counts it works for.
+int conv_f32_launch(const memhip_conv_args_t& a, const ConvGeom& g, const ConvPlan& plan, memhip_stream_t stream) {
   ConvArgsF32 p;
-  p.in = in; p.w = weight; p.bias = bias; p.add = add; p.out = out;
+  p.in = (const float*)a.in; p.w = (const float*)a.weight; p.bias = a.bias; p.add = (const float*)a.add; p.out = (float*)a.out;
   fill_geom(p, g);
-  p.out_padded = out_padded; p.relu = relu; p.n_active = n_active;
+  p.out_padded = a.out_padded; p.relu = a.relu; p.n_active = a.n_active;
   for (int i = 0; i < plan.count; ++i) {
     const ConvLaunch& l = plan.l[i];
     p.dyn_lo = l.dyn_lo; p.dyn_hi = l.dyn_hi;
@@ -514,55 +508,27 @@ static int conv2d_nhwc_f32_impl(const float* in, const float* weight, const floa
                                                      : conv_launch<conv_gemm_f32_kernel>(l, as_stream(stream), p);
     if (rc) return rc;
   }
-  return check_launch(n_active ? "conv2d_nhwc_f32(dyn)" : "conv2d_nhwc_f32");
+  return check_launch(a.n_active ? "conv2d_nhwc_f32(dyn)" : "conv2d_nhwc_f32");
 }
 
-extern "C" int memhip_conv2d_nhwc_f32(const float* in, const float* weight, const float* bias, const float* add, float* out,
-                                      int B, int H, int W, int Cin, int Cout, int ksize, int stride, int pad, int relu,
-                                      int out_padded, memhip_stream_t stream) {
-  return conv2d_nhwc_f32_impl(in, weight, bias, add, out, B, H, W, Cin, Cout, ksize, stride, pad, relu, out_padded, nullptr, stream);
-}
-
-extern "C" int memhip_conv2d_nhwc_f32_dyn(const float* in, const float* weight, const float* bias, const float* add, float* out,
-                                          int B, int H, int W, int Cin, int Cout, int ksize, int stride, int pad, int relu,
-                                          int out_padded, const int32_t* n_active, memhip_stream_t stream) {
-  MEMHIP_REQUIRE(n_active, "conv2d_f32_dyn: null n_active");
-  return conv2d_nhwc_f32_impl(in, weight, bias, add, out, B, H, W, Cin, Cout, ksize, stride, pad, relu, out_padded, n_active, stream);
-}
-
-extern "C" int memhip_nchw_to_padded_nhwc4_f32(const float* x, int B, int C, int H, int W, const float* mean,
-                                               const float* stdv, float* out, memhip_stream_t stream) {
-  MEMHIP_REQUIRE(B >= 0 && C >= 1 && C <= 4 && H > 0 && W > 0, "nchw_to_padded_nhwc4_f32: bad shape");
-  if (B == 0) return MEMHIP_OK;
-  MEMHIP_REQUIRE(x && out && (!mean == !stdv), "nchw_to_padded_nhwc4_f32: null pointer");
+int to_nhwc4_f32_launch(const float* x, int B, int C, int H, int W, const float* mean, const float* stdv, void* out, int64_t,
+                        memhip_stream_t stream) {
   const long long n = (long long)B * H * W;
   hipLaunchKernelGGL(nchw_to_padded_nhwc4_f32_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, as_stream(stream),
-                     x, B, C, H, W, mean, stdv, out);
+                     x, B, C, H, W, mean, stdv, (float*)out);
   return check_launch("nchw_to_padded_nhwc4_f32");
 }
 
-extern "C" int memhip_argmax_rows_f32(const float* logits, int64_t ld, int M, int N, int64_t* ids, float* top2_gap,
-                                      memhip_stream_t stream) {
-  MEMHIP_REQUIRE(M >= 0 && N > 0 && N % 4 == 0 && ld % 4 == 0, "argmax_rows_f32: N and ld must be multiples of 4");
-  if (M == 0) return MEMHIP_OK;
-  MEMHIP_REQUIRE(logits && ids, "argmax_rows_f32: null pointer");
-  hipLaunchKernelGGL(argmax_rows_f32_kernel, dim3((M + 3) / 4), dim3(256), 0, as_stream(stream), logits, (long long)ld, M, N,
-                     (long long*)ids, top2_gap, (float*)nullptr, (const int*)nullptr, 0);
+// with n_samples the grid is persistent: at most 2048 workgroups walk the live rows
+int argmax_rows_f32_launch(const void* logits, int64_t ld, int M, int N, int64_t* ids, float* top2_gap, float* row_rms,
+                           const int32_t* n_samples, int rows_per_sample, memhip_stream_t stream) {
+  const int blocks = (M + 3) / 4;
+  hipLaunchKernelGGL(argmax_rows_f32_kernel, dim3(n_samples && blocks > 2048 ? 2048 : blocks), dim3(256), 0, as_stream(stream),
+                     (const float*)logits, (long long)ld, M, N, (long long*)ids, top2_gap, row_rms, (const int*)n_samples, rows_per_sample);
   return check_launch("argmax_rows_f32");
 }
 
-extern "C" int memhip_argmax_rows_f32_ex(const float* logits, int64_t ld, int M, int N, int64_t* ids, float* top2_gap,
-                                         float* row_rms, const int32_t* n_samples, int rows_per_sample,
-                                         memhip_stream_t stream) {
-  MEMHIP_REQUIRE(M >= 0 && N > 0 && N % 4 == 0 && ld % 4 == 0, "argmax_rows_f32_ex: N and ld must be multiples of 4");
-  MEMHIP_REQUIRE(!n_samples || rows_per_sample > 0, "argmax_rows_f32_ex: rows_per_sample");
-  if (M == 0) return MEMHIP_OK;
-  MEMHIP_REQUIRE(logits && ids, "argmax_rows_f32_ex: null pointer");
-  const int blocks = (M + 3) / 4;
-  hipLaunchKernelGGL(argmax_rows_f32_kernel, dim3(n_samples && blocks > 2048 ? 2048 : blocks), dim3(256), 0, as_stream(stream),
-                     logits, (long long)ld, M, N, (long long*)ids, top2_gap, row_rms, (const int*)n_samples, rows_per_sample);
-  return check_launch("argmax_rows_f32_ex");
-}
+}  // namespace memhip
 
 extern "C" int memhip_tok_flag_samples(const float* top2_gap, const float* row_rms, int B, int tokens_per_sample, float kappa,
                                        int32_t* list, int32_t* count, int64_t* stats, memhip_stream_t stream) {

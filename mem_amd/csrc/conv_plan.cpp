@@ -1,6 +1,6 @@
-// The dispatch policy of the tokenizer convolutions (memhip_conv2d_nhwc_bf16 / _f32 / _f32_dyn / _f16x2): what a call must
-// look like (conv_validate) and which kernels it gets (conv_plan).  Every shape test, option test and grid formula of the
-// three launchers is here, once; the launchers obey.
+// The dispatch policy of the tokenizer convolutions (memhip_conv2d_nhwc, one memhip_conv_args_t for the three modes): what a
+// call must look like (conv_validate) and which kernels it gets (conv_plan).  Every shape test, option test and grid formula
+// of the three launchers is here, once; the launchers obey.
 #include "conv_plan.hpp"
 #include "common.h"
 
@@ -17,31 +17,30 @@ void push(ConvPlan& a, int kernel, int grid, int block, int lds, int dyn_lo = 0,
 //                (16-byte stores of 16-bit values); f16x2 alone: the fp32 output is the dense logit matrix.
 //   f32:         any kernel size 1..4, stride >= 1, pad 0 / 1; C_in % 4 and C_out % 4 (16-byte chunks of floats); the only
 //                mode that can be asked for an empty output, and checks for it; K % 32.
-int validate16(const char* name, bool f16x2, int B, int H, int W, int Cin, int Cout, int ksize, int stride, int pad,
-               const ConvFlags& f, bool ptrs_ok, ConvGeom* g) {
-  MEMHIP_REQUIRE(B >= 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0, "%s: bad shape", name);
-  if (B == 0) return MEMHIP_OK;
+int validate16(const char* name, bool f16x2, const memhip_conv_args_t& a, const ConvFlags& f, bool ptrs_ok, ConvGeom* g) {
+  MEMHIP_REQUIRE(a.B >= 0 && a.H > 0 && a.W > 0 && a.Cin > 0 && a.Cout > 0, "%s: bad shape", name);
+  if (a.B == 0) return MEMHIP_OK;
   MEMHIP_REQUIRE(ptrs_ok, "%s: null pointer", name);
-  MEMHIP_REQUIRE((ksize == 4 && stride == 2 && pad == 1) || (ksize == 3 && stride == 1 && pad == 1) ||
-                     (ksize == 1 && stride == 1 && pad == 0),
+  MEMHIP_REQUIRE((a.ksize == 4 && a.stride == 2 && a.pad == 1) || (a.ksize == 3 && a.stride == 1 && a.pad == 1) ||
+                     (a.ksize == 1 && a.stride == 1 && a.pad == 0),
                  "%s: only the encoder's shapes (4x4/s2/p1, 3x3/s1/p1, 1x1) are provided", name);
-  MEMHIP_REQUIRE(Cin == 4 ? (ksize == 4) : (Cin % 64 == 0), "%s: C_in must be 4 (first layer, 4x4) or a multiple of 64", name);
-  MEMHIP_REQUIRE(Cout % 8 == 0, "%s: C_out must be a multiple of 8", name);
+  MEMHIP_REQUIRE(a.Cin == 4 ? (a.ksize == 4) : (a.Cin % 64 == 0), "%s: C_in must be 4 (first layer, 4x4) or a multiple of 64", name);
+  MEMHIP_REQUIRE(a.Cout % 8 == 0, "%s: C_out must be a multiple of 8", name);
   if (f16x2) MEMHIP_REQUIRE(!(f.out_f32 && f.out_padded), "%s: the fp32 output is the dense token-logit matrix", name);
-  *g = conv_geom(B, H, W, Cin, Cout, ksize, stride, pad);
+  *g = conv_geom(a);
   MEMHIP_REQUIRE(g->K % kConvBK16 == 0, "%s: K = %d must be a multiple of 64", name, g->K);
   MEMHIP_REQUIRE(g->M < (1LL << 31), "%s: too many output pixels", name);
   return MEMHIP_OK;
 }
 
-int validate_f32(int B, int H, int W, int Cin, int Cout, int ksize, int stride, int pad, bool ptrs_ok, ConvGeom* g) {
-  MEMHIP_REQUIRE(B >= 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0, "conv2d_f32: bad shape");
-  if (B == 0) return MEMHIP_OK;
+int validate_f32(const memhip_conv_args_t& a, bool ptrs_ok, ConvGeom* g) {
+  MEMHIP_REQUIRE(a.B >= 0 && a.H > 0 && a.W > 0 && a.Cin > 0 && a.Cout > 0, "conv2d_f32: bad shape");
+  if (a.B == 0) return MEMHIP_OK;
   MEMHIP_REQUIRE(ptrs_ok, "conv2d_f32: null pointer");
-  MEMHIP_REQUIRE(ksize >= 1 && ksize <= 4 && stride >= 1 && pad >= 0 && pad <= 1,
+  MEMHIP_REQUIRE(a.ksize >= 1 && a.ksize <= 4 && a.stride >= 1 && a.pad >= 0 && a.pad <= 1,
                  "conv2d_f32: kernel size 1..4, padding 0 or 1 (one-pixel border layout)");
-  MEMHIP_REQUIRE(Cin % 4 == 0 && Cout % 4 == 0, "conv2d_f32: C_in and C_out must be multiples of 4");
-  *g = conv_geom(B, H, W, Cin, Cout, ksize, stride, pad);
+  MEMHIP_REQUIRE(a.Cin % 4 == 0 && a.Cout % 4 == 0, "conv2d_f32: C_in and C_out must be multiples of 4");
+  *g = conv_geom(a);
   MEMHIP_REQUIRE(g->Ho > 0 && g->Wo > 0, "conv2d_f32: empty output");
   MEMHIP_REQUIRE(g->K % kConvBK32 == 0, "conv2d_f32: K = %d must be a multiple of %d", g->K, kConvBK32);
   MEMHIP_REQUIRE(g->M < (1LL << 31), "conv2d_f32: too many output pixels");
@@ -50,12 +49,21 @@ int validate_f32(int B, int H, int W, int Cin, int Cout, int ksize, int stride, 
 
 }  // namespace
 
-int conv_validate(int mode, int B, int H, int W, int Cin, int Cout, int ksize, int stride, int pad, const ConvFlags& f,
-                  bool ptrs_ok, ConvGeom* g) {
+int conv_validate(const memhip_conv_args_t* a, bool query, ConvFlags* f, ConvGeom* g) {
+  *f = ConvFlags{};
   *g = ConvGeom{};
-  if (mode == MEMHIP_CONV_F32) return validate_f32(B, H, W, Cin, Cout, ksize, stride, pad, ptrs_ok, g);
+  MEMHIP_REQUIRE(a, "conv2d: null args");
+  const int mode = a->mode;
+  MEMHIP_REQUIRE(mode == MEMHIP_CONV_BF16 || mode == MEMHIP_CONV_F32 || mode == MEMHIP_CONV_F16X2, "conv2d: unknown mode %d", mode);
+  MEMHIP_REQUIRE(!a->n_active || mode == MEMHIP_CONV_F32, "conv2d: only the fp32 mode has a dynamic batch (n_active)");
+  MEMHIP_REQUIRE(!a->out_f32 || mode == MEMHIP_CONV_F16X2, "conv2d: out_f32 is a flag of the fp16x2 mode");
+  MEMHIP_REQUIRE(mode == MEMHIP_CONV_F16X2 || !(a->in_plane || a->w_plane || a->add_plane || a->out_plane),
+                 "conv2d: plane strides are fields of the fp16x2 mode");
+  *f = ConvFlags{a->add != nullptr, a->out_f32 != 0, a->out_padded != 0, a->n_active != nullptr};
+  const bool ptrs_ok = query || (a->in && a->weight && a->out);
+  if (mode == MEMHIP_CONV_F32) return validate_f32(*a, ptrs_ok, g);
   const bool f16x2 = mode == MEMHIP_CONV_F16X2;
-  return validate16(f16x2 ? "conv2d_f16x2" : "conv2d", f16x2, B, H, W, Cin, Cout, ksize, stride, pad, f, ptrs_ok, g);
+  return validate16(f16x2 ? "conv2d_f16x2" : "conv2d", f16x2, *a, *f, ptrs_ok, g);
 }
 
 ConvPlan conv_plan(int mode, const ConvGeom& g, const ConvFlags& f, const ConvOptions& o, int device_cus) {
@@ -115,16 +123,12 @@ ConvPlan conv_plan(int mode, const ConvGeom& g, const ConvFlags& f, const ConvOp
 
 }  // namespace memhip
 
-extern "C" int memhip_conv_plan(int mode, int B, int H, int W, int Cin, int Cout, int ksize, int stride, int pad, int has_add,
-                                int out_f32, int out_padded, int dynamic, int device_cus, memhip_conv_plan_t* out) {
+extern "C" int memhip_conv_plan(const memhip_conv_args_t* args, int device_cus, memhip_conv_plan_t* out) {
   using namespace memhip;
   MEMHIP_REQUIRE(out, "conv_plan: null pointer");
-  MEMHIP_REQUIRE(mode == MEMHIP_CONV_BF16 || mode == MEMHIP_CONV_F32 || mode == MEMHIP_CONV_F16X2, "conv_plan: unknown mode %d", mode);
-  MEMHIP_REQUIRE(!dynamic || mode == MEMHIP_CONV_F32, "conv_plan: only the fp32 mode has a dynamic batch");
-  MEMHIP_REQUIRE(!out_f32 || mode == MEMHIP_CONV_F16X2, "conv_plan: out_f32 is a flag of the fp16x2 mode");
-  const ConvFlags f = {has_add != 0, out_f32 != 0, out_padded != 0, dynamic != 0};
+  ConvFlags f;
   ConvGeom g;
-  if (int rc = conv_validate(mode, B, H, W, Cin, Cout, ksize, stride, pad, f, true, &g)) return rc;
-  *out = conv_plan(mode, g, f, ConvOptions{opt(OPT_CONV_WAVES)}, device_cus >= 0 ? device_cus : max_cus());
+  if (int rc = conv_validate(args, true, &f, &g)) return rc;
+  *out = conv_plan(args->mode, g, f, ConvOptions{opt(OPT_CONV_WAVES)}, device_cus >= 0 ? device_cus : max_cus());
   return MEMHIP_OK;
 }

@@ -1,8 +1,8 @@
-// Which kernels take a memhip_conv2d_nhwc_bf16 / _f32 / _f32_dyn / _f16x2 call, with which grids, workgroup sizes and LDS
-// bytes: conv_geom is the one place that derives a layer's geometry, conv_validate the one place that accepts or rejects a
-// call, conv_plan (conv_plan.cpp) the one place that decides the dispatch -- once per call, from the geometry, the flags of
-// the call, the device's CU count and a snapshot of the options.  Host arithmetic only: memhip_conv_plan returns the same
-// plan without a device (tests/test_conv_plan_cpu.py checks it against the cascades it replaced).
+// Which kernels take a memhip_conv2d_nhwc call, with which grids, workgroup sizes and LDS bytes: conv_geom is the one place
+// that derives a layer's geometry, conv_validate the one place that reads a memhip_conv_args_t and accepts or rejects it,
+// conv_plan (conv_plan.cpp) the one place that decides the dispatch -- once per call, from the geometry, the flags of the
+// call, the device's CU count and a snapshot of the options.  Host arithmetic only: memhip_conv_plan takes the struct of the
+// call and returns the same plan without a device (tests/test_conv_plan_cpu.py checks it against the cascades it replaced).
 #pragma once
 #include <cstdint>
 #include "../../include/memhip.h"
@@ -25,14 +25,14 @@ struct ConvGeom {
   int Hp, Wp, Ho, Wo, K, off;
   int64_t M;
 };
-inline ConvGeom conv_geom(int B, int H, int W, int Cin, int Cout, int ksize, int stride, int pad) {
+inline ConvGeom conv_geom(const memhip_conv_args_t& a) {
   ConvGeom g;
-  g.B = B; g.Cin = Cin; g.Cout = Cout; g.ksize = ksize; g.stride = stride;
-  g.Hp = H + 2; g.Wp = W + 2;
-  g.Ho = (H + 2 * pad - ksize) / stride + 1; g.Wo = (W + 2 * pad - ksize) / stride + 1;
-  g.K = ksize * ksize * Cin;
-  g.off = 1 - pad;
-  g.M = (int64_t)B * g.Ho * g.Wo;
+  g.B = a.B; g.Cin = a.Cin; g.Cout = a.Cout; g.ksize = a.ksize; g.stride = a.stride;
+  g.Hp = a.H + 2; g.Wp = a.W + 2;
+  g.Ho = (a.H + 2 * a.pad - a.ksize) / a.stride + 1; g.Wo = (a.W + 2 * a.pad - a.ksize) / a.stride + 1;
+  g.K = a.ksize * a.ksize * a.Cin;
+  g.off = 1 - a.pad;
+  g.M = (int64_t)a.B * g.Ho * g.Wo;
   return g;
 }
 
@@ -46,12 +46,24 @@ struct ConvOptions { int conv_waves; };
 typedef memhip_conv_launch_t ConvLaunch;
 typedef memhip_conv_plan_t ConvPlan;
 
-// Accepts or rejects a call like the parent launchers did, per mode and word for word; *g is filled on MEMHIP_OK (g->M == 0
-// for an empty batch: nothing to launch).  ptrs_ok: in, weight and out are non-null (the plan query has no pointers: true).
-int conv_validate(int mode, int B, int H, int W, int Cin, int Cout, int ksize, int stride, int pad, const ConvFlags& f,
-                  bool ptrs_ok, ConvGeom* g);
+// The one reader of the struct, for the call and for the plan query: accepts or rejects it like the parent launchers did, per
+// mode and word for word, and rejects a field the mode does not have; *f and *g are filled on MEMHIP_OK (g->M == 0 for an
+// empty batch: nothing to launch).  query: in, weight and out may be null (the query dereferences nothing).
+int conv_validate(const memhip_conv_args_t* a, bool query, ConvFlags* f, ConvGeom* g);
 
 // device_cus: max_cus().  mode MEMHIP_CONV_*; a geometry conv_validate accepted.
 ConvPlan conv_plan(int mode, const ConvGeom& g, const ConvFlags& f, const ConvOptions& o, int device_cus);
+
+// The launchers, one of each per mode in MEMHIP_CONV_* order (conv.hip, conv_f32.hip, conv_f16x2.hip); their arguments are
+// validated by the entry points (conv_entry.cpp), so a mode ignores what it does not have.  conv: fill the kernel arguments
+// from the struct and its geometry and launch what the plan names (plan.count >= 1); to_nhwc4: the input conversion; argmax_rows.
+typedef int ConvLaunchFn(const memhip_conv_args_t& a, const ConvGeom& g, const ConvPlan& plan, memhip_stream_t stream);
+typedef int ToNhwc4LaunchFn(const float* x, int B, int C, int H, int W, const float* mean, const float* stdv, void* out,
+                            int64_t out_plane, memhip_stream_t stream);
+typedef int ArgmaxLaunchFn(const void* logits, int64_t ld, int M, int N, int64_t* ids, float* top2_gap, float* row_rms,
+                           const int32_t* n_samples, int rows_per_sample, memhip_stream_t stream);
+ConvLaunchFn conv_bf16_launch, conv_f32_launch, conv_f16x2_launch;
+ToNhwc4LaunchFn to_nhwc4_bf16_launch, to_nhwc4_f32_launch, to_nhwc4_f16x2_launch;
+ArgmaxLaunchFn argmax_rows_bf16_launch, argmax_rows_f32_launch;
 
 }  // namespace memhip

@@ -184,16 +184,10 @@ declare({
     "memhip_im2col_bf16": (i32, [vp, i32, i32, i32, i32, i32, i32, vp, vp]),
     "memhip_fill_cls": (i32, [vp, i64, i32, i32, i32, vp, vp]),
     "memhip_gemv_bf16_acc": (i32, [vp, i64, i32, i32, vp, vp, vp, vp, vp]),
-    "memhip_conv2d_nhwc_bf16": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
-    "memhip_nchw_to_padded_nhwc4": (i32, [vp, i32, i32, i32, i32, vp, vp, vp, vp]),
-    "memhip_argmax_rows_bf16": (i32, [vp, i64, i32, i32, vp, vp]),
-    "memhip_conv2d_nhwc_f32": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
-    "memhip_nchw_to_padded_nhwc4_f32": (i32, [vp, i32, i32, i32, i32, vp, vp, vp, vp]),
-    "memhip_argmax_rows_f32": (i32, [vp, i64, i32, i32, vp, vp, vp]),
-    "memhip_argmax_rows_f32_ex": (i32, [vp, i64, i32, i32, vp, vp, vp, vp, i32, vp]),
+    "memhip_nchw_to_padded_nhwc4": (i32, [vp, i32, i32, i32, i32, vp, vp, vp, i64, i32, vp]),
+    "memhip_argmax_rows": (i32, [vp, i32, i64, i32, i32, vp, vp, vp, vp, i32, vp]),
     "memhip_tok_flag_samples": (i32, [vp, vp, i32, i32, f32, vp, vp, vp, vp]),
     "memhip_tok_gather_images_f32": (i32, [vp, i32, i32, i32, vp, vp, vp, vp, i32, i32, vp, vp, vp]),
-    "memhip_conv2d_nhwc_f32_dyn": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp]),
     "memhip_tok_scatter_ids": (i32, [vp, vp, vp, i32, i32, i32, vp, vp]),
     "memhip_grad_norm_workspace": (sz, []),
     "memhip_grad_norm": (i32, [vp, i64, vp, vp, sz, vp]),
@@ -262,44 +256,56 @@ def gemv_acc(W, N, K, x, y, x_acc=None, zero=None):
           "gemv_bf16_acc")
 
 
+CONV_MODES = ("bf16", "fp32", "fp16x2")                  # MEMHIP_CONV_*; the precisions of HipTokenizer
+_CONV_MODE = {torch.bfloat16: 0, torch.float32: 1, torch.float16: 2}     # index of CONV_MODES by the dtype of the activations
+_F16X2 = 2
+
+
+class ConvArgs(C.Structure):
+    """== memhip_conv_args_t."""
+    _fields_ = [("mode", i32), ("reserved0", i32), ("in", vp), ("in_plane", i64), ("weight", vp), ("w_plane", i64),
+                ("bias", vp), ("add", vp), ("add_plane", i64), ("out", vp), ("out_plane", i64)] + \
+               [(n, i32) for n in ("B", "H", "W", "Cin", "Cout", "ksize", "stride", "pad", "relu", "out_padded", "out_f32",
+                                   "reserved1")] + [("n_active", vp)]
+
+
+declare({"memhip_conv2d_nhwc": (i32, [C.POINTER(ConvArgs), vp])})
+
+
+def conv_args(mode, B, H, W, Cin, Cout, ksize, stride, pad, x=None, weight=None, bias=None, out=None, relu=False, add=None,
+              out_padded=True, out_f32=False, n_active=None, planes=(0, 0, 0, 0)):
+    """The memhip_conv_args_t of conv2d_nhwc / conv_plan: mode is an index of CONV_MODES, the tensors are addresses or None,
+    planes = (in, weight, add, out) plane strides (fp16x2)."""
+    return ConvArgs(mode, 0, x, planes[0], weight, planes[1], bias, add, planes[2], out, planes[3], B, H, W, Cin, Cout, ksize,
+                    stride, pad, int(relu), int(out_padded), int(out_f32), 0, n_active)
+
+
 def conv2d_nhwc(x_pad, weight, bias, out, B, H, W, Cin, Cout, ksize, stride, pad, relu=False, add=None, out_padded=True,
                 n_active=None):
-    """x_pad [B,H+2,W+2,Cin] -> out [B,Ho+2,Wo+2,Cout] interior (or dense [B*Ho*Wo,Cout]); bf16 or fp32 by x_pad.dtype.
+    """x_pad [B,H+2,W+2,Cin] -> out [B,Ho+2,Wo+2,Cout] interior (or dense [B*Ho*Wo,Cout]); bf16, fp32 or fp16x2 by x_pad.dtype.
+    fp16x2: x_pad, weight, add, out are fp16 [2 (hi / lo plane), ...], or out is the dense fp32 logit matrix.
     n_active (fp32 only): device int32 [1], the number of live samples of the capacity B."""
-    if x_pad.dtype == torch.float32:
-        assert weight.dtype == torch.float32 and out.dtype == torch.float32 and (add is None or add.dtype == torch.float32)
-        if n_active is not None:
-            check(lib.memhip_conv2d_nhwc_f32_dyn(ptr(x_pad), ptr(weight), ptr(bias), ptr(add), ptr(out), B, H, W, Cin, Cout,
-                                                 ksize, stride, pad, int(relu), int(out_padded), ptr(n_active), stream_ptr()),
-                  "conv2d_nhwc_f32_dyn")
-            return
-        check(lib.memhip_conv2d_nhwc_f32(ptr(x_pad), ptr(weight), ptr(bias), ptr(add), ptr(out), B, H, W, Cin, Cout, ksize,
-                                         stride, pad, int(relu), int(out_padded), stream_ptr()), "conv2d_nhwc_f32")
-        return
-    check(lib.memhip_conv2d_nhwc_bf16(ptr(x_pad), ptr(weight), ptr(bias), ptr(add), ptr(out), B, H, W, Cin, Cout, ksize,
-                                      stride, pad, int(relu), int(out_padded), stream_ptr()), "conv2d_nhwc_bf16")
+    mode = _CONV_MODE[x_pad.dtype]
+    out_f32 = mode == _F16X2 and out.dtype == torch.float32
+    assert weight.dtype == x_pad.dtype and (out_f32 or out.dtype == x_pad.dtype) and (add is None or add.dtype == x_pad.dtype)
+    planes = (0, 0, 0, 0) if mode != _F16X2 else (x_pad.stride(0), weight.stride(0), 0 if add is None else add.stride(0),
+                                             0 if out_f32 else out.stride(0))
+    a = conv_args(mode, B, H, W, Cin, Cout, ksize, stride, pad, _p(x_pad), _p(weight), _p(bias), _p(out), relu, _p(add),
+                  out_padded and not out_f32, out_f32, _p(n_active), planes)
+    check(lib.memhip_conv2d_nhwc(C.byref(a), stream_ptr()), "conv2d_nhwc")
 
 
 def nchw_to_padded_nhwc4(x, out, mean=None, std=None):
+    """x f32 [B, C<=4, H, W] -> the interior of out [B, H+2, W+2, 4] (fp16: [2, B, ...]), the mode by out.dtype."""
     B, Cc, H, W = x.shape
-    if out.dtype == torch.float32:
-        check(lib.memhip_nchw_to_padded_nhwc4_f32(ptr(x), B, Cc, H, W, ptr(mean), ptr(std), ptr(out), stream_ptr()),
-              "nchw_to_padded_nhwc4_f32")
-        return
-    check(lib.memhip_nchw_to_padded_nhwc4(ptr(x), B, Cc, H, W, ptr(mean), ptr(std), ptr(out), stream_ptr()),
-          "nchw_to_padded_nhwc4")
+    mode = _CONV_MODE[out.dtype]
+    check(lib.memhip_nchw_to_padded_nhwc4(ptr(x), B, Cc, H, W, ptr(mean), ptr(std), ptr(out), out.stride(0) if mode == _F16X2 else 0,
+                                          mode, stream_ptr()), "nchw_to_padded_nhwc4")
 
 
 def argmax_rows(logits, M, N, ids, gap=None, rms=None, n_samples=None, rows_per_sample=0):
-    if logits.dtype == torch.float32:
-        if rms is not None or n_samples is not None:
-            check(lib.memhip_argmax_rows_f32_ex(ptr(logits), logits.stride(0), M, N, ptr(ids), ptr(gap), ptr(rms), ptr(n_samples),
-                                                rows_per_sample, stream_ptr()), "argmax_rows_f32_ex")
-            return
-        check(lib.memhip_argmax_rows_f32(ptr(logits), logits.stride(0), M, N, ptr(ids), ptr(gap), stream_ptr()),
-              "argmax_rows_f32")
-        return
-    check(lib.memhip_argmax_rows_bf16(ptr(logits), logits.stride(0), M, N, ptr(ids), stream_ptr()), "argmax_rows_bf16")
+    check(lib.memhip_argmax_rows(ptr(logits), _CONV_MODE[logits.dtype], logits.stride(0), M, N, ptr(ids), ptr(gap), ptr(rms),
+                                 ptr(n_samples), rows_per_sample, stream_ptr()), "argmax_rows")
 
 
 def tok_flag_samples(gap, rms, B, hw, kappa, lst, count, stats=None):
@@ -729,32 +735,7 @@ def mae_loss(pred, img, mask, B, Cc, H, W, patch, only_masked, row_loss, dpred, 
                               ptr(scratch2), stream_ptr()), "mae_loss")
 
 
-# ---------------------------------------------------------------- fp16 x 2 tokenizer mode (csrc/conv_f16x2.hip)
-declare({
-    "memhip_conv2d_nhwc_f16x2": (i32, [vp, i64, vp, i64, vp, vp, i64, vp, i64, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32,
-                                       i32, vp]),
-    "memhip_nchw_to_padded_nhwc4_f16x2": (i32, [vp, i32, i32, i32, i32, vp, vp, vp, i64, vp]),
-})
-
-
-def conv2d_nhwc_f16x2(x2, w2, bias, out, B, H, W, Cin, Cout, ksize, stride, pad, relu=False, add2=None, out_padded=True):
-    """x2 fp16 [2,B,H+2,W+2,Cin] (hi / lo planes), w2 fp16 [2,Cout,K] -> out fp16 [2,B,Ho+2,Wo+2,Cout] interior, or a dense
-    fp32 [B*Ho*Wo, Cout] matrix when `out` is float32."""
-    out_f32 = out.dtype == torch.float32
-    check(lib.memhip_conv2d_nhwc_f16x2(ptr(x2), x2.stride(0), ptr(w2), w2.stride(0), ptr(bias), ptr(add2),
-                                       add2.stride(0) if add2 is not None else 0, ptr(out), 0 if out_f32 else out.stride(0),
-                                       B, H, W, Cin, Cout, ksize, stride, pad, int(relu), int(out_padded and not out_f32),
-                                       int(out_f32), stream_ptr()), "conv2d_nhwc_f16x2")
-
-
-def nchw_to_padded_nhwc4_f16x2(x, out2, mean=None, std=None):
-    B, Cc, H, W = x.shape
-    check(lib.memhip_nchw_to_padded_nhwc4_f16x2(ptr(x), B, Cc, H, W, ptr(mean), ptr(std), ptr(out2), out2.stride(0), stream_ptr()),
-          "nchw_to_padded_nhwc4_f16x2")
-
-
 # ---------------------------------------------------------------- the dispatch of the tokenizer convolutions (csrc/conv_plan.cpp)
-CONV_MODES = ("bf16", "fp32", "fp16x2")                  # MEMHIP_CONV_*; the precisions of HipTokenizer
 # kernel names of ConvLaunch.kernel (MEMHIP_CONV_K_*), as they appear in a kernel trace
 CONV_KERNELS = ("conv_gemm_kernel", "conv_gemm_f32_kernel", "conv_gemm_f32_m32_kernel", "conv_gemm_f16x2_kernel<4>",
                 "conv_gemm_f16x2_kernel<8>", "conv_gemm_f16x2_wide_kernel", "conv_gemm_f16x2_first_kernel")
@@ -779,18 +760,20 @@ class ConvPlan(C.Structure):
         return [(l.name, l.grid, l.block, l.lds, l.dyn_lo, l.dyn_hi) for l in self.l[:self.count]]
 
 
-declare({"memhip_conv_plan": (i32, [i32] * 14 + [C.POINTER(ConvPlan)])})
+declare({"memhip_conv_plan": (i32, [C.POINTER(ConvArgs), i32, C.POINTER(ConvPlan)])})
 
 
 def conv_plan(mode, B, H, W, Cin, Cout, ksize, stride, pad, add=False, out_f32=False, out_padded=True, dynamic=False,
               device_cus=None):
-    """The ConvPlan of conv2d_nhwc (mode "bf16" / "fp32"; dynamic: with n_active) or conv2d_nhwc_f16x2 (mode "fp16x2") for this
-    layer under the current `conv_waves` option: geometry and `.launches`.  Validates like the call (fp16x2: out_f32 goes with out_padded=False, the dense logit matrix).  Nothing is launched; no
-    device is needed when device_cus is given (default: the library asks the current device)."""
+    """The ConvPlan of conv2d_nhwc (mode "bf16" / "fp32" / "fp16x2"; dynamic: with n_active) for this layer under the current
+    `conv_waves` option: geometry and `.launches`.  The query takes the struct of the call (conv_args; a dummy address stands
+    for `add` / `n_active`, nothing is dereferenced) and validates like the call (fp16x2: out_f32 goes with out_padded=False,
+    the dense logit matrix).  Nothing is launched; no device is needed when device_cus is given (default: the library asks
+    the current device)."""
+    a = conv_args(CONV_MODES.index(mode), B, H, W, Cin, Cout, ksize, stride, pad, add=16 if add else None,
+                  out_padded=out_padded, out_f32=out_f32, n_active=16 if dynamic else None)
     plan = ConvPlan()
-    check(lib.memhip_conv_plan(CONV_MODES.index(mode), B, H, W, Cin, Cout, ksize, stride, pad, int(add), int(out_f32),
-                               int(out_padded), int(dynamic), -1 if device_cus is None else device_cus,
-                               C.byref(plan)), "conv_plan")
+    check(lib.memhip_conv_plan(C.byref(a), -1 if device_cus is None else device_cus, C.byref(plan)), "conv_plan")
     return plan
 
 

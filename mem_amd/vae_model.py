@@ -135,12 +135,6 @@ class HipTokenizer:
         self._exact = None
         self.dt = {"fp32": torch.float32, "bf16": torch.bfloat16, "fp16x2": torch.float16}[precision]
         self.planes = 2 if precision == "fp16x2" else 1
-        # the convolution and the input conversion of this precision, chosen once; the two conv callables spell the residual
-        # keyword differently (ops.conv2d_nhwc: add, ops.conv2d_nhwc_f16x2: add2)
-        if self.planes == 2:
-            self._conv, self._add_kw, self._to_nhwc = ops.conv2d_nhwc_f16x2, "add2", ops.nchw_to_padded_nhwc4_f16x2
-        else:
-            self._conv, self._add_kw, self._to_nhwc = ops.conv2d_nhwc, "add", ops.nchw_to_padded_nhwc4
         dev = next(vae.parameters()).device
         assert dev.type == "cuda", "HipTokenizer needs the model on the GPU"
         self.dev, self.H, self.W = dev, vae.input_H, vae.input_W
@@ -252,7 +246,7 @@ class HipTokenizer:
         """The encoder from self.x0 to self.logits on `n` samples (the batch, or the capacity of a dynamic-batch call); kw goes
         to every convolution (n_active).  Owns the ResBlock buffer rotation: t1, t2 = the first pool buffers that are not
         the block's input.  Returns the output size (h, w)."""
-        conv = self._conv
+        conv = self.ops.conv2d_nhwc
         cur, h, w = self.x0, self.H, self.W
         for kind, L in self.layers:
             if kind == "conv":
@@ -267,8 +261,7 @@ class HipTokenizer:
                 t2 = next(t for t in pool if t is not cur and t is not t1)
                 conv(cur, c1.w, c1.b, t1, n, h, w, c1.cin, c1.cout, c1.k, c1.stride, c1.pad, relu=True, **kw)
                 conv(t1, c2.w, c2.b, t2, n, h, w, c2.cin, c2.cout, c2.k, c2.stride, c2.pad, relu=True, **kw)
-                conv(t2, c3.w, c3.b, t1, n, h, w, c3.cin, c3.cout, c3.k, c3.stride, c3.pad, relu=False,
-                     **{self._add_kw: cur}, **kw)                                                     # net(x) + x
+                conv(t2, c3.w, c3.b, t1, n, h, w, c3.cin, c3.cout, c3.k, c3.stride, c3.pad, relu=False, add=cur, **kw)   # net(x) + x
                 cur = t1
             else:
                 conv(cur, L.w, L.b, self.logits, n, h, w, L.cin, L.cout, L.k, L.stride, L.pad, relu=False, out_padded=False, **kw)
@@ -282,7 +275,7 @@ class HipTokenizer:
         images = images.contiguous()
         B = images.shape[0]
         self._alloc(B)
-        self._to_nhwc(images, self.x0, *(self.norm or (None, None)))
+        ops.nchw_to_padded_nhwc4(images, self.x0, *(self.norm or (None, None)))
         h, w = self._walk(B)
         M, hw = B * h * w, h * w
         if not self.certify:

@@ -5,8 +5,10 @@ Layout: a few lines of C, compiled against the header with the host compiler, pr
 field list comes from the header, so a mirror must name its fields as C does, in C's order.  A struct without a mirror, or a
 mirror without a struct, fails.
 
-Validation: memhip_branch_bwd, memhip_layernorm_bwd_branch and memhip_attn_bwd check their arguments before any launch, so
-every rule is exercised here through ctypes with dummy addresses -- nothing is dereferenced and no case reaches a launch."""
+Validation: memhip_branch_bwd, memhip_layernorm_bwd_branch, memhip_attn_bwd and memhip_conv2d_nhwc check their arguments before
+any launch, so every rule is exercised here through ctypes with dummy addresses -- nothing is dereferenced and no case reaches
+a launch.  memhip_conv_plan takes the struct of the convolution call: every call that is rejected is rejected by the query with
+the same code and the same message."""
 import ctypes as C
 import os
 import re
@@ -27,7 +29,7 @@ def _mirrors():
             "memhip_tn_problem_t": ops.TnProblem, "memhip_tn_part_t": ops.TnPart, "memhip_tn_launch_t": ops.TnLaunch,
             "memhip_tn_plan_t": ops.TnPlan,
             "memhip_attn_launch_t": ops.AttnLaunch, "memhip_attn_plan_t": ops.AttnPlan,
-            "memhip_conv_launch_t": ops.ConvLaunch, "memhip_conv_plan_t": ops.ConvPlan,
+            "memhip_conv_launch_t": ops.ConvLaunch, "memhip_conv_plan_t": ops.ConvPlan, "memhip_conv_args_t": ops.ConvArgs,
             "memhip_branch_t": ops.Branch, "memhip_branch_bwd_args_t": ops.BranchBwdArgs,
             "memhip_ln_bwd_branch_args_t": ops.LnBwdBranchArgs, "memhip_attn_bwd_args_t": ops.AttnBwdArgs}
 
@@ -88,7 +90,7 @@ def c_layout(tmp_path_factory):
 
 def test_every_header_struct_has_its_mirror():
     structs, mirrors = set(_header_structs()), set(_mirrors())
-    assert len(structs) >= 17
+    assert len(structs) >= 18
     assert structs - mirrors - set(UNMIRRORED) == set(), "structs of the header without a ctypes mirror"
     assert mirrors - structs == set(), "ctypes mirrors of structs the header does not have"
     assert set(UNMIRRORED) <= structs - mirrors, "UNMIRRORED lists a struct that is gone or has a mirror"
@@ -193,3 +195,63 @@ def test_attn_bwd_validation():
         _rejected(fn, args(**{field: None}), "attn_bwd: null pointer")
     for field in ("ldqkv", "ldo", "ldout", "lddqkv"):
         _rejected(fn, args(**{field: 772}), "attn_bwd: ld must be a multiple of 8")
+
+
+def test_conv2d_nhwc_validation_and_the_plan_query_agree():
+    """Every rejection rule of the three modes, the rejections of a field the mode does not have, the empty batch and
+    args == NULL -- and for each rejected struct memhip_conv_plan answers with the same code and the same message."""
+    from mem_amd import _lib, ops
+    fn = "memhip_conv2d_nhwc"
+    BF16, F32, F16X2 = range(3)
+
+    def args(mode, B=2, H=14, W=14, Cin=64, Cout=64, k=3, s=1, p=1, **kw):
+        a = ops.conv_args(mode, B, H, W, Cin, Cout, k, s, p, x=P, weight=P, out=P)
+        for key, v in kw.items():
+            setattr(a, key, v)
+        return a
+
+    def rejected(a, message):
+        """by the call and by the query alike"""
+        rc, err = _call(fn, a)
+        assert rc == -1 and message in err, (rc, err)
+        plan = ops.ConvPlan()
+        rc_q = _lib.lib.memhip_conv_plan(None if a is None else C.byref(a), 256, C.byref(plan))
+        assert (rc_q, _lib.lib.memhip_last_error().decode()) == (rc, err)
+
+    rejected(None, "conv2d: null args")
+    rejected(args(3), "conv2d: unknown mode 3")
+    rejected(args(-1), "conv2d: unknown mode -1")
+    # a field that the mode does not have
+    for mode in (BF16, F16X2):
+        rejected(args(mode, n_active=P), "conv2d: only the fp32 mode has a dynamic batch (n_active)")
+    for mode in (BF16, F32):
+        rejected(args(mode, out_f32=1, out_padded=0), "conv2d: out_f32 is a flag of the fp16x2 mode")
+        for plane in ("in_plane", "w_plane", "add_plane", "out_plane"):
+            rejected(args(mode, **{plane: 4096}), "conv2d: plane strides are fields of the fp16x2 mode")
+    # the two 16-bit modes, each under its own name
+    for mode, name in ((BF16, "conv2d"), (F16X2, "conv2d_f16x2")):
+        for bad in (dict(B=-1), dict(H=0), dict(W=-3), dict(Cin=0), dict(Cout=0)):
+            rejected(args(mode, **bad), name + ": bad shape")
+        for k, s, p in ((2, 2, 0), (4, 1, 1), (3, 1, 0), (1, 1, 1), (3, 2, 1), (5, 1, 1)):
+            rejected(args(mode, k=k, s=s, p=p), name + ": only the encoder's shapes (4x4/s2/p1, 3x3/s1/p1, 1x1) are provided")
+        rejected(args(mode, Cin=32), name + ": C_in must be 4 (first layer, 4x4) or a multiple of 64")
+        rejected(args(mode, Cin=4), name + ": C_in must be 4 (first layer, 4x4) or a multiple of 64")       # 3x3 on 4 channels
+        rejected(args(mode, Cout=36), name + ": C_out must be a multiple of 8")
+        rejected(args(mode, B=1 << 20, H=224, W=224, k=1, s=1, p=0), name + ": too many output pixels")
+    rejected(args(F16X2, out_f32=1, out_padded=1), "conv2d_f16x2: the fp32 output is the dense token-logit matrix")
+    # the fp32 mode
+    for bad in (dict(B=-1), dict(H=0), dict(W=-3), dict(Cin=0), dict(Cout=0)):
+        rejected(args(F32, **bad), "conv2d_f32: bad shape")
+    for k, s, p in ((0, 1, 1), (5, 1, 1), (3, 0, 1), (3, 1, -1), (3, 1, 2)):
+        rejected(args(F32, k=k, s=s, p=p), "conv2d_f32: kernel size 1..4, padding 0 or 1 (one-pixel border layout)")
+    rejected(args(F32, Cin=6), "conv2d_f32: C_in and C_out must be multiples of 4")
+    rejected(args(F32, Cout=10), "conv2d_f32: C_in and C_out must be multiples of 4")
+    rejected(args(F32, H=2, W=2, k=4, p=0), "conv2d_f32: empty output")
+    rejected(args(F32, Cin=4), "conv2d_f32: K = 36 must be a multiple of 32")
+    rejected(args(F32, B=1 << 20, H=224, W=224, k=1, s=1, p=0), "conv2d_f32: too many output pixels")
+    for mode, name in ((BF16, "conv2d"), (F32, "conv2d_f32"), (F16X2, "conv2d_f16x2")):
+        # the call alone needs in / weight / out; the query asks about a call it does not make
+        for field in ("in", "weight", "out"):
+            _rejected(fn, args(mode, **{field: None}), name + ": null pointer")
+        # an empty batch: nothing to do, nothing read
+        assert _call(fn, ops.conv_args(mode, 0, 14, 14, 64, 64, 3, 1, 1))[0] == 0

@@ -1,5 +1,6 @@
-"""-m "not gpu": the dispatch of the tokenizer convolutions (memhip_conv2d_nhwc_bf16 / _f32 / _f32_dyn / _f16x2), checked through
-the plan query memhip_conv_plan.  The query validates and plans like the calls themselves and launches nothing."""
+"""-m "not gpu": the dispatch of the tokenizer convolutions (memhip_conv2d_nhwc, one memhip_conv_args_t for the bf16 / fp32 /
+fp32 dynamic / fp16x2 calls), checked through the plan query memhip_conv_plan.  The query takes the struct of the call (ops.conv_plan
+builds it), validates and plans like the call itself and launches nothing."""
 from collections import Counter
 
 import numpy as np

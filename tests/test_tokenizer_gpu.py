@@ -279,11 +279,11 @@ def test_tokenizer_fp16x2_mode():
     x2 = planes(xp)
     w2 = planes(w.permute(0, 2, 3, 1).reshape(cout, -1).contiguous())
     dense = torch.zeros(Bn * h * h, cout, device="cuda")
-    ops.conv2d_nhwc_f16x2(x2, w2, b, dense, Bn, h, h, cin, cout, k, s, p, relu=False, out_padded=False)
+    ops.conv2d_nhwc(x2, w2, b, dense, Bn, h, h, cin, cout, k, s, p, relu=False, out_padded=False)
     err = (dense.view(Bn, h, h, cout).permute(0, 3, 1, 2).double() - ref).abs().max().item()
     assert err <= 3e-6 * float(ref.abs().max()), err
     out2 = torch.zeros(2, Bn, h + 2, h + 2, cout, dtype=torch.float16, device="cuda")
-    ops.conv2d_nhwc_f16x2(x2, w2, b, out2, Bn, h, h, cin, cout, k, s, p, relu=True)
+    ops.conv2d_nhwc(x2, w2, b, out2, Bn, h, h, cin, cout, k, s, p, relu=True)
     got = (out2[0].float() + out2[1].float() / 2048.0)[:, 1:-1, 1:-1].permute(0, 3, 1, 2).double()
     assert (got - torch.relu(ref)).abs().max().item() <= 3e-6 * float(ref.abs().max())
     assert out2[:, :, 0].abs().max() == 0 and out2[:, :, :, 0].abs().max() == 0
@@ -358,11 +358,11 @@ def test_fp16x2_wide_tile_equals_the_128_tile_bit_for_bit():
             plan = ops.conv_plan("fp16x2", Bn, h, h, cin, cout, k, s, p)
             assert [l[0] for l in plan.launches] == [{8: "conv_gemm_f16x2_kernel<8>", 32: "conv_gemm_f16x2_wide_kernel"}[w]]
             dense = torch.full((Bn * h * h, cout), 7.0, device="cuda")
-            ops.conv2d_nhwc_f16x2(x2, w2, b, dense, Bn, h, h, cin, cout, k, s, p, relu=False, out_padded=False)
+            ops.conv2d_nhwc(x2, w2, b, dense, Bn, h, h, cin, cout, k, s, p, relu=False, out_padded=False)
             o_relu = torch.zeros(2, Bn, h + 2, h + 2, cout, dtype=torch.float16, device="cuda")
-            ops.conv2d_nhwc_f16x2(x2, w2, b, o_relu, Bn, h, h, cin, cout, k, s, p, relu=True)
+            ops.conv2d_nhwc(x2, w2, b, o_relu, Bn, h, h, cin, cout, k, s, p, relu=True)
             o_add = torch.zeros(2, Bn, h + 2, h + 2, cout, dtype=torch.float16, device="cuda")
-            ops.conv2d_nhwc_f16x2(x2, w2, b, o_add, Bn, h, h, cin, cout, k, s, p, relu=False, add2=addp)
+            ops.conv2d_nhwc(x2, w2, b, o_add, Bn, h, h, cin, cout, k, s, p, relu=False, add=addp)
             outs[w] = (dense, o_relu, o_add)
         for a, c in zip(outs[8], outs[32]):
             assert torch.equal(a, c)
