@@ -35,7 +35,8 @@
 extern "C" {
 #endif
 
-#define MEMHIP_ABI_VERSION 9   /* 9: the tokenizer takes one args struct: memhip_conv2d_nhwc and memhip_conv_plan read the same memhip_conv_args_t; one
+#define MEMHIP_ABI_VERSION 10  /* 10: the rasterizer takes one args struct: memhip_rasterize and memhip_rasterize_plan read the same memhip_raster_args_t; the
+                                  memhip_rasterize_f64 / _aug_f64 / _var_f64 / _binned_f64 / _workspace / _binned_workspace symbols are gone; 9: the tokenizer takes one args struct: memhip_conv2d_nhwc and memhip_conv_plan read the same memhip_conv_args_t; one
                                   memhip_nchw_to_padded_nhwc4 and one memhip_argmax_rows with a mode argument; the per-mode symbols (_bf16 / _f32 / _f32_dyn / _f32_ex / _f16x2) are gone;
                                   8: one entry point per backward family, optional features as struct fields (memhip_branch_bwd, memhip_layernorm_bwd_branch,
                                   memhip_attn_bwd take an args struct; memhip_gemm_bf16_tn takes the workspace; the *_map / *_drop / *_out / *_ws symbols are gone; additive since: the memhip_neck_* entry points of the feature-pyramid necks);
@@ -68,7 +69,7 @@ const char* memhip_build_flags(void);
  * launch, 0: two launches), "tn_group" (1: memhip_gemm_bf16_tn_group runs its products as one grid, 0: one by one);
  * round 6: "conv_waves" (16: the fp16x2 tokenizer convolutions run 8 waves per workgroup and the phase-interleaved 256 x 128 tile
  * on every layer whose grid fills the chip twice; 32: that tile at every size; 8: 8 waves, 128 x 128 tiles only; 4: 4 waves, one per SIMD),
- * "raster_bands" (0: memhip_rasterize_binned_f64 chooses the bands per sample from the batch size; n > 0: n bands, raised to
+ * "raster_bands" (0: the binned rasterizer chooses the bands per sample from the batch size; n > 0: n bands, raised to
  * the fewest the canvas allows).
  * Unknown name: MEMHIP_EINVAL.  Results do not depend on any option (same contract, different kernel or timing). */
 int memhip_set_option(const char* name, int value);
@@ -91,16 +92,13 @@ int memhip_stream_reserve_cus(memhip_stream_t stream, int cus);
  *           same bytes viewed as (H, W, 3); the Python mirror transposes)
  * status    i32 [B]  out: number of events of sample b whose flat pixel index
  *           x + W*y fell outside [-H*W, H*W) (the reference raises IndexError)
- * workspace u32 [B, 3, H*W] (memhip_rasterize_workspace)
+ * workspace device scratch of memhip_raster_plan_t.ws_bytes bytes
  * Semantics: x,y truncated toward zero; only p == +1 / p == -1 count; counts
  * are exact mod 256; NumPy negative-index wrap kept; time surface (optional)
  * = (t - tmin) / (tmax - tmin) * 255 truncated to u8, last event in array
- * order wins.
+ * order wins.  The call is memhip_rasterize (memhip_raster_args_t), below the
+ * augmentation record it carries.
  */
-size_t memhip_rasterize_workspace(int B, int H, int W);
-int memhip_rasterize_f64(const double* ev, const int64_t* offsets, int B, int H, int W,
-                         int time_surface, uint8_t* out, int32_t* status,
-                         void* workspace, size_t workspace_bytes, memhip_stream_t stream);
 
 /* Event-level augmentations fused into the rasterizer's single read of the
  * events (no intermediate (N',4) arrays):
@@ -127,36 +125,80 @@ typedef struct memhip_event_aug {
 #define MEMHIP_AUG_INFER_FLIP_W 1
 #define MEMHIP_AUG_INFER_FILT_W 2
 #define MEMHIP_AUG_INFER_FILT_H 4
-int memhip_rasterize_aug_f64(const double* ev, const int64_t* offsets, const memhip_event_aug_t* aug,
-                             int B, int H, int W, int time_surface, uint8_t* out, int32_t* status,
-                             void* workspace, size_t workspace_bytes, memhip_stream_t stream);
 
-/* The same rasterizer for LONG streams (N-ImageNet scale, ~1 M events per sample;
- * BASELINE configs[3]) without time surface: two streaming passes (events ->
- * 2-byte pixel keys sorted by band of the canvas -> LDS counters per band)
- * instead of one global atomic per event.  Same semantics, outputs and status
- * as memhip_rasterize_aug_f64(time_surface = 0).
- * n_events  upper bound on offsets[B] - offsets[0] (sizes the key workspace; a
- *           sample that would exceed it gets status |= 1<<30 and a zero image)
- * status    written for every sample by the second pass (the caller zeroes nothing)
- * Canvas limit: H*W <= 64 * 40000 pixels (MEMHIP_EUNSUPPORTED beyond). */
-size_t memhip_rasterize_binned_workspace(int B, int H, int W, int64_t n_events);
-int memhip_rasterize_binned_f64(const double* ev, const int64_t* offsets, const memhip_event_aug_t* aug,
-                                int B, int H, int W, int64_t n_events, uint8_t* out, int32_t* status,
-                                void* workspace, size_t workspace_bytes, memhip_stream_t stream);
+/* The one rasterizer call (ABI 10): a host struct, read at the call.  Four kernel families compute the same image:
+ *   MEMHIP_RASTER_BINNED      two streaming passes (events -> 2-byte pixel keys sorted by band of the canvas -> LDS counters per
+ *                             band) instead of one global atomic per event: long streams (N-ImageNet scale, BASELINE
+ *                             configs[3]) and, measured, every smaller batch too.  No time surface; H*W <= 64 * 40000 pixels.
+ *                             A sample whose events would exceed n_events gets status |= 1 << 30 and a zero image; status is
+ *                             written for every sample by the second pass.
+ *   MEMHIP_RASTER_LDS         one pass, counters privatised in LDS per band of rows: small canvases without time surface.
+ *   MEMHIP_RASTER_GLOBAL      one global u32 atomic per event and a folding pass: any canvas, the time surface.
+ *   MEMHIP_RASTER_GLOBAL_VAR  the same with per-sample canvases (`dims`, written by memhip_aug_resolve stage 1).
+ * `form` says which may run: MEMHIP_RASTER_AUTO = binned where it applies (no time surface, no dims, canvas within the band
+ * limit), else as MEMHIP_RASTER_SINGLE = LDS where it applies ("raster_lds" option on, no time surface, no dims, at most 6
+ * bands of rows, `out` 4-byte aligned), else global; MEMHIP_RASTER_BINNED forces the two passes (MEMHIP_EINVAL with
+ * time_surface or dims, MEMHIP_EUNSUPPORTED beyond the band limit).  B == 0 is MEMHIP_OK, nothing is read. */
+enum { MEMHIP_RASTER_AUTO = 0, MEMHIP_RASTER_SINGLE = 1, MEMHIP_RASTER_BINNED = 2,        /* form (BINNED: also a family) */
+       MEMHIP_RASTER_LDS = 3, MEMHIP_RASTER_GLOBAL = 4, MEMHIP_RASTER_GLOBAL_VAR = 5 };   /* family */
+typedef struct memhip_raster_args {
+  const double* ev;                  /* 16-byte aligned */
+  const int64_t* offsets;
+  const memhip_event_aug_t* aug;     /* device array of B records, or NULL for none */
+  const int32_t* dims;               /* NULL: one H x W canvas for the batch.  Device i32 [B, 2]: sample b is rasterized on
+                                        dims[b] = (H_b, W_b) and stored densely ([3, H_b, W_b]) at the start of its slot of 3*H*W
+                                        bytes of `out` (rest of the slot zero); H, W are then the maxima */
+  int32_t B, H, W, time_surface;
+  int32_t form;                      /* MEMHIP_RASTER_AUTO / _SINGLE / _BINNED */
+  int32_t reserved0;
+  int64_t n_events;                  /* >= 0: upper bound on offsets[B] - offsets[0] (sizes the key workspace of the binned family) */
+  uint8_t* out;                      /* u8 [B, 3, H, W] */
+  int32_t* status;                   /* i32 [B] */
+  void* workspace;                   /* device, workspace_bytes >= memhip_raster_plan_t.ws_bytes */
+  size_t workspace_bytes;
+} memhip_raster_args_t;
+int memhip_rasterize(const memhip_raster_args_t* args, memhip_stream_t stream);
+
+/* The dispatch of memhip_rasterize as data.  memhip_rasterize_plan takes the struct of the call and validates it like the call
+ * (same messages, same return codes), except that every pointer may be NULL: only address bits are read (null and alignment; a
+ * NULL pointer counts as aligned, and workspace_bytes is compared only when `workspace` is given).  It plans with the current
+ * values of the "raster_lds" and "raster_bands" options for a device of device_cus CUs (< 0: the current device's); it
+ * launches nothing and needs no device when device_cus is given. */
+enum { MEMHIP_RASTER_K_COUNT,      /* raster_count: global atomics */
+       MEMHIP_RASTER_K_FINALIZE,   /* raster_finalize: u32 bins -> u8 planes, time surface */
+       MEMHIP_RASTER_K_LDS,        /* raster_lds_kernel */
+       MEMHIP_RASTER_K_BIN_KEYS,   /* raster_bin_keys: pass 1 */
+       MEMHIP_RASTER_K_BIN_ACCUM };/* raster_bin_accum: pass 2 */
+typedef struct memhip_raster_launch {
+  int32_t kernel;             /* MEMHIP_RASTER_K_* */
+  int32_t grid_x, grid_y;     /* workgroups (grid_y = B) */
+  int32_t block;              /* workgroup size */
+  int32_t lds;                /* dynamic LDS bytes */
+} memhip_raster_launch_t;
+typedef struct memhip_raster_plan {
+  int32_t family;             /* MEMHIP_RASTER_LDS / _GLOBAL / _GLOBAL_VAR / _BINNED; 0: B == 0, nothing to do */
+  int32_t rows_per_band, bands;   /* LDS: bands of whole rows */
+  int32_t band_px, nb;        /* binned: nb bands of band_px pixels (a multiple of 4), the last one shorter, none empty */
+  int32_t bx;                 /* binned: the grid_x of pass 1, which pass 2 receives as an argument */
+  uint64_t ws_bytes;          /* workspace the call needs */
+  uint64_t off_bins, off_tstat;             /* byte offsets of the workspace's parts: single-pass forms (u32 bins, u64 tstat) */
+  uint64_t off_keys, off_hdr, off_bad_slots;   /* binned (u16 keys, u32 chunk headers, i32 one slot per pass-1 workgroup) */
+                              /* every part starts at a 16-byte boundary but off_bad_slots, which is 4-byte aligned: it follows
+                                 the chunk headers of 129 words each directly (the layout and ws_bytes of the earlier ABIs are
+                                 kept), and its int32 slots are stored and loaded one at a time */
+  uint64_t clear_ws_bytes, clear_status_bytes, clear_out_bytes;   /* zeroed in front of the launches (0: not cleared) */
+  int32_t count;
+  memhip_raster_launch_t l[2];
+} memhip_raster_plan_t;
+int memhip_rasterize_plan(const memhip_raster_args_t* args, int device_cus, memhip_raster_plan_t* out);
 
 /* Data-dependent canvases without a host round trip (mem/datasets.py:516,537-540,572-575: "W = x.max() + 1"):
  *   memhip_events_extent(raw window) -> memhip_aug_resolve(stage 0) fills the inferred flip / filter sizes of aug[b];
  *   memhip_events_extent(with aug)   -> memhip_aug_resolve(stage 1) writes the canvas dims[b] = (H_b, W_b)
  *   (fixed_h / fixed_w > 0 override; empty samples or canvases beyond hmax x wmax: dims (0,0), status |= 1 << 29);
- *   memhip_rasterize_var_f64 rasterizes sample b on its own canvas, stored densely ([3, H_b, W_b]) at the start of
- *   its slot of 3 * Hmax * Wmax bytes of `out` (rest of the slot zero).  Semantics per sample = memhip_rasterize_aug_f64;
- *   workspace = memhip_rasterize_workspace(B, Hmax, Wmax). */
+ *   memhip_rasterize with memhip_raster_args_t.dims rasterizes sample b on its own canvas. */
 int memhip_aug_resolve(const double* extent, memhip_event_aug_t* aug, int B, int stage, int fixed_h, int fixed_w,
                        int hmax, int wmax, int32_t* dims, int32_t* status, memhip_stream_t stream);
-int memhip_rasterize_var_f64(const double* ev, const int64_t* offsets, const memhip_event_aug_t* aug,
-                             const int32_t* dims, int B, int Hmax, int Wmax, int time_surface, uint8_t* out,
-                             int32_t* status, void* workspace, size_t workspace_bytes, memhip_stream_t stream);
 
 /* Per-sample extent of the (augmented) events, for the reference's data-dependent
  * canvas "W = xs.max()+1" (mem/datasets.py:516,538-540,572-575).

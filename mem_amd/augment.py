@@ -21,11 +21,10 @@ import numpy as np
 import torch
 
 from . import transforms as T
-from ._lib import C, check, declare, i32, i64, lib, ptr, stream_ptr, sz, vp
+from ._lib import C, check, declare, i32, i64, lib, ptr, stream_ptr, vp
 
 declare({
     "memhip_aug_resolve": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp]),
-    "memhip_rasterize_var_f64": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, sz, vp]),
     "memhip_resample_to_f32": (i32, [vp, vp, i64, i32, i32, i32, vp, i32, i32, i32, vp, vp]),
     "memhip_to_uint8": (i32, [vp, i64, vp, vp]),
     "memhip_rand_augment_u8": (i32, [vp, vp, vp, i32, i32, i32, vp]),
@@ -288,7 +287,7 @@ class BatchAugPipeline:
         aug = up(aug_h)
         st = stream_ptr()
         stages = {}
-        from .datasets import events_extent, rasterize
+        from .datasets import events_extent, raster_args, raster_run, rasterize
         if contiguous:
             offs = torch.from_numpy(np.concatenate([win[:, 0], win[-1:, 1]])).to(dev, non_blocking=True)
             ev_w = ev
@@ -313,11 +312,9 @@ class BatchAugPipeline:
             dims = torch.empty((B, 2), dtype=torch.int32, device=dev)
             check(lib.memhip_aug_resolve(ptr(ext), ptr(aug), B, 1, 0, 0, Hm, Wm, ptr(dims), ptr(status), st), "aug_resolve")
             img = torch.empty((B, 3 * Hm * Wm), dtype=torch.uint8, device=dev)
-            wsb = lib.memhip_rasterize_workspace(B, Hm, Wm)
-            ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
             st2 = torch.empty(B, dtype=torch.int32, device=dev)
-            check(lib.memhip_rasterize_var_f64(ptr(ev_w), ptr(offs), ptr(aug), ptr(dims), B, Hm, Wm, int(cfg.time_surface),
-                                               ptr(img), ptr(st2), ptr(ws), wsb, st), "rasterize_var")
+            raster_run(raster_args(B, Hm, Wm, cfg.time_surface, n_events=int(ev_w.shape[0]), ev=ptr(ev_w), offsets=ptr(offs),
+                                   aug=ptr(aug), dims=ptr(dims), out=ptr(img), status=ptr(st2)), dev, st)
             H, W, slot = 0, 0, 3 * Hm * Wm
             stages["dims"] = dims
         stages["raster"] = img

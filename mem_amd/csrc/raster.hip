@@ -5,14 +5,13 @@
 // that resolve in the XCD L2 / memory side, and a second streaming pass folds the u32 bins to
 // the reference's wrap-around uint8 counts.  Algorithmic bytes: 32*N + 3*H*W per sample.
 #include "common.h"
+#include "raster_plan.hpp"
 
 static_assert(sizeof(memhip_event_aug_t) == 56, "memhip_event_aug_t ABI layout");
 
 
 namespace {
-
-constexpr int kThreads = 256;
-constexpr int kEvPerThread = 8;
+using namespace memhip::raster;     // thread counts, band and chunk sizes: raster_plan.hpp, shared with the plan
 
 // order-preserving map double -> u64 (so integer atomic max == fp max)
 __device__ __forceinline__ unsigned long long enc_f64(double v) {
@@ -105,7 +104,7 @@ __global__ __launch_bounds__(kThreads) void raster_count(
     int32_t* __restrict__ status, const int32_t* __restrict__ dims, long long slot_px) {
   const int b = blockIdx.y;
   const long long beg = offsets[b], end = offsets[b + 1];
-  if (dims) { H = dims[2 * b]; W = dims[2 * b + 1]; }       // per-sample canvas (memhip_rasterize_var_f64)
+  if (dims) { H = dims[2 * b]; W = dims[2 * b + 1]; }       // per-sample canvas (memhip_raster_args_t.dims)
   const long long HW = (long long)H * W;
   if (HW <= 0) return;
   unsigned int* pos = bins + (size_t)b * 3 * (dims ? slot_px : HW);
@@ -208,10 +207,6 @@ __global__ __launch_bounds__(kThreads) void raster_finalize(
 // of rows): its u32 counters for [pos, neg] x band live in LDS, it scans ALL events of the sample (the
 // re-reads of the other bands hit L2), and writes the wrapped uint8 counts straight to the output --
 // no workspace, no memset, no second pass.  Used when a sample needs <= kMaxBands bands.
-constexpr int kLdsThreads = 1024;
-constexpr int kBandPixels = 14336;            // 2 polarities x 14336 x 4 B = 112 KiB of LDS
-constexpr int kMaxBands = 6;
-
 __global__ __launch_bounds__(kLdsThreads) void raster_lds_kernel(
     const double* __restrict__ ev, const int64_t* __restrict__ offsets,
     const memhip_event_aug_t* __restrict__ augs, int H, int W, int rows_per_band,
@@ -292,19 +287,6 @@ __global__ __launch_bounds__(kLdsThreads) void raster_lds_kernel(
 // Counters: ONE u32 per pixel = [neg count : 16 | pos count : 16].  Only counts mod 256 are observable, so
 // 16 bits are enough provided the carry out of the low half is undone: the low half changes only by +1, so
 // exactly the add that sees 0xFFFF there carries, and that thread takes the carry back out of the high half.
-constexpr int kBinThreads = 512;
-constexpr int kBinEvPerThread = 8;
-constexpr int kBinChunk = kBinThreads * kBinEvPerThread;   // 4096 events
-constexpr int kBinParts = 2;                               // the next chunk is requested in this many parts (4: the same, 8: 5 % slower)
-constexpr int kBinMaxBands = 64;
-constexpr int kBinBandPixels = 40000;                      // pixels of a band: 16-bit key (0xFFFF is the pad key), 160 000 B of LDS counters in pass 2
-constexpr int kBinSegs = 2 * kBinMaxBands;                 // a chunk's keys are sorted by (band, polarity): two segments per band
-constexpr int kBinHdr = kBinSegs + 1;                      // segment boundaries of a chunk
-constexpr int kBinSlots = kBinChunk + 8 * kBinSegs;        // key slots of a chunk: events + padding of every segment to 8
-constexpr int kAccThreads = 1024;
-constexpr int kBinKeyGrid = 4096;                           // pass-1 workgroups in all (rounded up to whole samples)
-constexpr int kBinOverflow = 1 << 30;                      // status flag: n_events smaller than the offsets say
-
 // The wave's 64 rows of one step as TWO fully contiguous 1-KiB wave-instructions (lane l loads 16 bytes at 16 l: half a row):
 // an even lane 2e ends up with row e (its own (x, y) from the first KiB, (t, p) from its odd neighbour), an odd lane 2e + 1
 // with row 32 + e (its own (t, p) from the second KiB, (x, y) from its even neighbour) -- one DPP exchange inside the lane pair.
@@ -524,136 +506,66 @@ __global__ __launch_bounds__(kAccThreads) void raster_bin_accum(
   }
 }
 
-// bands of whole pixels (not rows): band_px pixels each, the last one shorter
-inline bool bin_geometry(int H, int W, int* band_px, int* nb, int want_nb = 0) {
-  const long long HW = (long long)H * W;
-  long long n = (HW + kBinBandPixels - 1) / kBinBandPixels;
-  if (want_nb > n && want_nb <= kBinMaxBands) n = want_nb;
-  if (n > kBinMaxBands) return false;
-  long long px = (HW + n - 1) / n;
-  px = (px + 3) & ~3ll;                     // 4-pixel aligned bands keep the u32 output stores
-  if (px > kBinBandPixels) { px = kBinBandPixels; n = (HW + px - 1) / px; if (n > kBinMaxBands) return false; }
-  *band_px = (int)px;
-  *nb = (int)n;
-  return true;
-}
-
-// Bands per sample for a batch of B samples.  Pass 2 runs one workgroup per (sample, band); a workgroup with > 80 KB of counters has a
-// CU to itself and takes ~0.22 us per 1000 pixels of its band (launch, clearing and writing its planes) + ~220 us per million events /
-// bands (its keys), so what the pass costs is set by how many ROUNDS of workgroups the chip needs.  480 x 640 needs eight bands of
-// 38 400 pixels: 32 samples are 256 workgroups = one round (36.9 us under rocprofv3; the ten 15-bit-key bands of the first half of
-// round 6 were 320 workgroups = two rounds, 44.3 us), 64 samples two rounds (72 us; twelve bands = three rounds of smaller workgroups:
-// 68 us -- the model calls them equal).  The candidates run from the fewest bands the LDS allows to twice that; more bands cost pass 1
-// padding and shorter segments, so a larger count has to promise 10 % and batches that fit one round keep the fewest bands.
-inline int choose_bands(int H, int W, int B, long long n_events) {
-  const int forced = memhip::opt(memhip::OPT_RASTER_BANDS);
-  if (forced > 0) return forced;
-  const long long HW = (long long)H * W;
-  const int nmin = (int)((HW + kBinBandPixels - 1) / kBinBandPixels);
-  int cus = memhip::max_cus();
-  if (cus <= 0) cus = 256;
-  if ((long long)B * nmin <= cus) return nmin;                                  // one round either way
-  int best = nmin;
-  double best_cost = 0.0;
-  for (int nbv = nmin; nbv <= 2 * nmin + 4 && nbv <= kBinMaxBands; ++nbv) {
-    const long long px = ((HW + nbv - 1) / nbv + 3) & ~3ll;
-    const int per_cu = (size_t)px * 4 * 2 + 1024 <= 160 * 1024 ? 2 : 1;       // 1024-thread workgroups: two per CU at most
-    const long long rounds = ((long long)B * nbv + (long long)cus * per_cu - 1) / ((long long)cus * per_cu);
-    const double cost = (double)rounds * (0.22e-3 * (double)px + 220.0e-6 * ((double)n_events / B) / nbv) * (per_cu == 2 ? 2.0 : 1.0);
-    if (nbv == nmin || cost < best_cost * 0.9) { best = nbv; best_cost = cost; }
-  }
-  return best;
-}
-
 }  // namespace
 
-extern "C" size_t memhip_rasterize_workspace(int B, int H, int W) {
-  size_t bins = (size_t)B * 3 * H * W * sizeof(unsigned int);
-  bins = (bins + 15) & ~(size_t)15;
-  return bins + (size_t)B * 2 * sizeof(unsigned long long);
-}
-
-extern "C" int memhip_rasterize_aug_f64(const double* ev, const int64_t* offsets,
-                                        const memhip_event_aug_t* aug, int B, int H, int W,
-                                        int time_surface, uint8_t* out, int32_t* status,
-                                        void* workspace, size_t workspace_bytes,
-                                        memhip_stream_t stream) {
-  MEMHIP_REQUIRE(B >= 0 && H > 0 && W > 0, "rasterize: bad shape B=%d H=%d W=%d", B, H, W);
-  if (B == 0) return MEMHIP_OK;
-  MEMHIP_REQUIRE(ev && offsets && out && status && workspace, "rasterize: null pointer");
-  MEMHIP_REQUIRE(((uintptr_t)ev & 15) == 0, "rasterize: ev must be 16-byte aligned");
-  const size_t need = memhip_rasterize_workspace(B, H, W);
-  if (workspace_bytes < need)
-    return memhip::fail(MEMHIP_EWORKSPACE, "rasterize: workspace %zu < %zu", workspace_bytes, need);
+// The one launcher: validate and plan through raster_plan (raster_plan.cpp), clear what the plan says, launch what it lists.
+extern "C" int memhip_rasterize(const memhip_raster_args_t* args, memhip_stream_t stream) {
+  memhip_raster_plan_t plan;
+  if (int rc = memhip::raster_plan(args, false, memhip::RasterOptions{memhip::opt(memhip::OPT_RASTER_LDS), memhip::opt(memhip::OPT_RASTER_BANDS)},
+                                   -1, &plan))
+    return rc;
+  if (plan.count == 0) return MEMHIP_OK;
+  const memhip_raster_args_t& a = *args;
   hipStream_t s = memhip::as_stream(stream);
-  {
-    // privatised-counter path (see raster_lds_kernel): small canvas, no time surface
-    int rpb = kBandPixels / W;
-    const int bands = rpb > 0 ? memhip::cdiv(H, rpb) : kMaxBands + 1;
-    const bool lds_on = memhip::opt(memhip::OPT_RASTER_LDS) != 0;
-    if (lds_on && !time_surface && bands <= kMaxBands && ((uintptr_t)out & 3) == 0) {
-      rpb = memhip::cdiv(H, bands);                        // even bands
-      MEMHIP_HIP(hipMemsetAsync(status, 0, (size_t)B * sizeof(int32_t), s));
-      static bool attr_done = false;
-      if (!attr_done) {
-        MEMHIP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(raster_lds_kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 2 * kBandPixels * 4));
-        attr_done = true;
-      }
-      hipLaunchKernelGGL(raster_lds_kernel, dim3(bands, B), dim3(kLdsThreads), (size_t)2 * rpb * W * 4, s, ev, offsets,
-                         aug, H, W, rpb, out, status);
-      return memhip::check_launch("rasterize(lds)");
+  // the dynamic LDS of the two kernels that need more than the default is allowed once, by the first call of their family
+  static bool lds_attr_done = false, accum_attr_done = false;
+  if (plan.family == MEMHIP_RASTER_LDS && !lds_attr_done) {
+    MEMHIP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(raster_lds_kernel),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, 2 * kBandPixels * 4));
+    lds_attr_done = true;
+  }
+  if (plan.family == MEMHIP_RASTER_BINNED && !accum_attr_done) {
+    MEMHIP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(raster_bin_accum),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, kBinBandPixels * 4));
+    accum_attr_done = true;
+  }
+  if (plan.clear_ws_bytes) MEMHIP_HIP(hipMemsetAsync(a.workspace, 0, plan.clear_ws_bytes, s));
+  if (plan.clear_status_bytes) MEMHIP_HIP(hipMemsetAsync(a.status, 0, plan.clear_status_bytes, s));
+  if (plan.clear_out_bytes) MEMHIP_HIP(hipMemsetAsync(a.out, 0, plan.clear_out_bytes, s));
+  char* const ws = (char*)a.workspace;
+  unsigned int* const bins = (unsigned int*)(ws + plan.off_bins);
+  unsigned long long* const tstat = (unsigned long long*)(ws + plan.off_tstat);
+  unsigned short* const keys = (unsigned short*)(ws + plan.off_keys);
+  unsigned int* const hdr = (unsigned int*)(ws + plan.off_hdr);
+  int32_t* const bad_slots = (int32_t*)(ws + plan.off_bad_slots);
+  const long long slot = (long long)a.H * a.W;             // pixels of a sample's slot (per-sample canvases)
+  for (int i = 0; i < plan.count; ++i) {
+    const memhip_raster_launch_t& l = plan.l[i];
+    const dim3 grid(l.grid_x, l.grid_y), block(l.block);
+    switch (l.kernel) {
+      case MEMHIP_RASTER_K_LDS:
+        hipLaunchKernelGGL(raster_lds_kernel, grid, block, (size_t)l.lds, s, a.ev, a.offsets, a.aug, a.H, a.W, plan.rows_per_band,
+                           a.out, a.status);
+        break;
+      case MEMHIP_RASTER_K_COUNT:
+        hipLaunchKernelGGL(raster_count, grid, block, 0, s, a.ev, a.offsets, a.aug, a.H, a.W, a.time_surface, bins, tstat,
+                           a.status, a.dims, a.dims ? slot : 0LL);
+        break;
+      case MEMHIP_RASTER_K_FINALIZE:
+        hipLaunchKernelGGL(raster_finalize, grid, block, 0, s, a.ev, a.offsets, a.aug, a.H, a.W, a.time_surface, bins, tstat,
+                           a.out, a.dims, a.dims ? slot : 0LL);
+        break;
+      case MEMHIP_RASTER_K_BIN_KEYS:
+        hipLaunchKernelGGL(raster_bin_keys, grid, block, 0, s, a.ev, a.offsets, a.aug, a.H, a.W, plan.band_px, plan.nb,
+                           (long long)a.n_events, keys, hdr, bad_slots, udiv_prepare((unsigned)plan.band_px));
+        break;
+      case MEMHIP_RASTER_K_BIN_ACCUM:
+        hipLaunchKernelGGL(raster_bin_accum, grid, block, (size_t)l.lds, s, a.offsets, a.H, a.W, plan.band_px,
+                           (long long)a.n_events, keys, hdr, a.out, bad_slots, plan.bx, a.status);
+        break;
     }
   }
-  size_t bins_bytes = ((size_t)B * 3 * H * W * sizeof(unsigned int) + 15) & ~(size_t)15;
-  unsigned int* bins = (unsigned int*)workspace;
-  unsigned long long* tstat = (unsigned long long*)((char*)workspace + bins_bytes);
-  MEMHIP_HIP(hipMemsetAsync(workspace, 0, need, s));
-  MEMHIP_HIP(hipMemsetAsync(status, 0, (size_t)B * sizeof(int32_t), s));
-  // enough blocks per sample to fill the chip at small B, grid-stride beyond
-  int bx = B >= 256 ? 8 : (B >= 32 ? 32 : 256);
-  dim3 g1(bx, B);
-  hipLaunchKernelGGL(raster_count, g1, dim3(kThreads), 0, s, ev, offsets, aug, H, W, time_surface,
-                     bins, tstat, status, (const int32_t*)nullptr, 0LL);
-  long long HW = (long long)H * W;
-  int fx = (int)((HW + kThreads - 1) / kThreads);
-  if (fx > 64) fx = 64;
-  dim3 g2(fx, B);
-  hipLaunchKernelGGL(raster_finalize, g2, dim3(kThreads), 0, s, ev, offsets, aug, H, W,
-                     time_surface, bins, tstat, out, (const int32_t*)nullptr, 0LL);
   return memhip::check_launch("rasterize");
-}
-
-// Per-sample canvases (the reference's data-dependent "W = xs.max() + 1", datasets.py:572-575): sample b is
-// rasterized on dims[b] = (H_b, W_b) and stored DENSELY ([3, H_b, W_b], pitch W_b) at the start of its slot of
-// 3 * Hmax * Wmax bytes.  Global-atomic form (any canvas, time surface supported).
-extern "C" int memhip_rasterize_var_f64(const double* ev, const int64_t* offsets, const memhip_event_aug_t* aug,
-                                        const int32_t* dims, int B, int Hmax, int Wmax, int time_surface, uint8_t* out,
-                                        int32_t* status, void* workspace, size_t workspace_bytes,
-                                        memhip_stream_t stream) {
-  MEMHIP_REQUIRE(B >= 0 && Hmax > 0 && Wmax > 0, "rasterize_var: bad shape B=%d Hmax=%d Wmax=%d", B, Hmax, Wmax);
-  if (B == 0) return MEMHIP_OK;
-  MEMHIP_REQUIRE(ev && offsets && dims && out && status && workspace, "rasterize_var: null pointer");
-  MEMHIP_REQUIRE(((uintptr_t)ev & 15) == 0, "rasterize_var: ev must be 16-byte aligned");
-  const size_t need = memhip_rasterize_workspace(B, Hmax, Wmax);
-  if (workspace_bytes < need)
-    return memhip::fail(MEMHIP_EWORKSPACE, "rasterize_var: workspace %zu < %zu", workspace_bytes, need);
-  hipStream_t s = memhip::as_stream(stream);
-  const long long slot = (long long)Hmax * Wmax;
-  size_t bins_bytes = ((size_t)B * 3 * slot * sizeof(unsigned int) + 15) & ~(size_t)15;
-  unsigned int* bins = (unsigned int*)workspace;
-  unsigned long long* tstat = (unsigned long long*)((char*)workspace + bins_bytes);
-  MEMHIP_HIP(hipMemsetAsync(workspace, 0, need, s));
-  MEMHIP_HIP(hipMemsetAsync(status, 0, (size_t)B * sizeof(int32_t), s));
-  MEMHIP_HIP(hipMemsetAsync(out, 0, (size_t)B * 3 * slot, s));
-  int bx = B >= 256 ? 8 : (B >= 32 ? 32 : 256);
-  hipLaunchKernelGGL(raster_count, dim3(bx, B), dim3(kThreads), 0, s, ev, offsets, aug, Hmax, Wmax, time_surface,
-                     bins, tstat, status, dims, slot);
-  int fx = (int)((slot + kThreads - 1) / kThreads);
-  if (fx > 64) fx = 64;
-  hipLaunchKernelGGL(raster_finalize, dim3(fx, B), dim3(kThreads), 0, s, ev, offsets, aug, Hmax, Wmax,
-                     time_surface, bins, tstat, out, dims, slot);
-  return memhip::check_launch("rasterize_var");
 }
 
 namespace {
@@ -702,14 +614,6 @@ extern "C" int memhip_aug_resolve(const double* extent, memhip_event_aug_t* aug,
   hipLaunchKernelGGL(aug_resolve_kernel, dim3((B + 255) / 256), dim3(256), 0, memhip::as_stream(stream), extent, aug, B, stage,
                      fixed_h, fixed_w, hmax, wmax, dims, status);
   return memhip::check_launch("aug_resolve");
-}
-
-extern "C" int memhip_rasterize_f64(const double* ev, const int64_t* offsets, int B, int H, int W,
-                                    int time_surface, uint8_t* out, int32_t* status,
-                                    void* workspace, size_t workspace_bytes,
-                                    memhip_stream_t stream) {
-  return memhip_rasterize_aug_f64(ev, offsets, nullptr, B, H, W, time_surface, out, status,
-                                  workspace, workspace_bytes, stream);
 }
 
 namespace {
@@ -769,54 +673,4 @@ extern "C" int memhip_events_extent(const double* ev, const int64_t* offsets,
                      reinterpret_cast<unsigned long long*>(extent));
   hipLaunchKernelGGL(extent_decode, dim3(nb), dim3(kThreads), 0, s, extent, B);
   return memhip::check_launch("events_extent");
-}
-
-extern "C" size_t memhip_rasterize_binned_workspace(int B, int H, int W, int64_t n_events) {
-  (void)H; (void)W;
-  if (B <= 0 || n_events < 0) return 0;
-  const size_t chunks = (size_t)n_events / kBinChunk + (size_t)B + 1;
-  const size_t keys = (chunks * kBinSlots * sizeof(unsigned short) + 15) & ~(size_t)15;
-  const size_t hdr = chunks * kBinHdr * sizeof(unsigned int);
-  return keys + hdr + ((size_t)kBinKeyGrid + (size_t)B) * sizeof(int32_t);     // + one slot per pass-1 workgroup
-}
-
-extern "C" int memhip_rasterize_binned_f64(const double* ev, const int64_t* offsets,
-                                           const memhip_event_aug_t* aug, int B, int H, int W,
-                                           int64_t n_events, uint8_t* out, int32_t* status,
-                                           void* workspace, size_t workspace_bytes, memhip_stream_t stream) {
-  MEMHIP_REQUIRE(B >= 0 && H > 0 && W > 0 && n_events >= 0, "rasterize_binned: bad shape B=%d H=%d W=%d", B, H, W);
-  if (B == 0) return MEMHIP_OK;
-  MEMHIP_REQUIRE(ev && offsets && out && status && workspace, "rasterize_binned: null pointer");
-  MEMHIP_REQUIRE(((uintptr_t)ev & 15) == 0 && ((uintptr_t)out & 3) == 0, "rasterize_binned: ev must be 16-byte, out 4-byte aligned");
-  int band_px = 0, nb = 0;
-  if (!bin_geometry(H, W, &band_px, &nb, choose_bands(H, W, B, n_events)))
-    return memhip::fail(MEMHIP_EUNSUPPORTED, "rasterize_binned: %dx%d canvas needs more than %d bands", H, W, kBinMaxBands);
-  const size_t need = memhip_rasterize_binned_workspace(B, H, W, n_events);
-  if (workspace_bytes < need)
-    return memhip::fail(MEMHIP_EWORKSPACE, "rasterize_binned: workspace %zu < %zu", workspace_bytes, need);
-  hipStream_t s = memhip::as_stream(stream);
-  unsigned short* keys = (unsigned short*)workspace;
-  const size_t keys_bytes = ((((size_t)n_events / kBinChunk + (size_t)B + 1) * kBinSlots * sizeof(unsigned short)) + 15) & ~(size_t)15;
-  unsigned int* hdr = (unsigned int*)((char*)workspace + keys_bytes);
-  const size_t chunk_slots = (size_t)n_events / kBinChunk + (size_t)B + 1;
-  int32_t* bad_slots = (int32_t*)((char*)hdr + chunk_slots * kBinHdr * sizeof(unsigned int));
-  static bool attr_done = false;
-  if (!attr_done) {
-    MEMHIP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(raster_bin_accum),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, kBinBandPixels * 4));
-    attr_done = true;
-  }
-  // chunks per sample are only known on the device: enough workgroups per sample to fill the chip at
-  // small B, grid-stride beyond
-  const long long avg_chunks = n_events / ((long long)B * kBinChunk) + 1;
-  // (4096 workgroups in all: 64 x 1 M events 462 -> 454 us against 2048, 470 with 1024; 32 x 1 M: 241 / 241 / 246 / 249 us
-  // with 4096 / 2048 / 1024 / 512)
-  long long bx = (kBinKeyGrid + B - 1) / B;                                    // (bx * B <= kBinKeyGrid + B slots)
-  if (bx > 4 * avg_chunks) bx = 4 * avg_chunks;
-  if (bx < 1) bx = 1;
-  hipLaunchKernelGGL(raster_bin_keys, dim3((unsigned)bx, B), dim3(kBinThreads), 0, s, ev, offsets, aug, H, W, band_px, nb,
-                     (long long)n_events, keys, hdr, bad_slots, udiv_prepare((unsigned)band_px));
-  hipLaunchKernelGGL(raster_bin_accum, dim3(nb, B), dim3(kAccThreads), (size_t)band_px * 4, s, offsets, H, W, band_px,
-                     (long long)n_events, keys, hdr, out, bad_slots, (int)bx, status);
-  return memhip::check_launch("rasterize_binned");
 }

@@ -19,22 +19,8 @@ import numpy as np
 import torch
 
 from . import transforms as T
-from ._lib import check, declare, i32, lib, ptr, require_gpu, stream_ptr, sz, vp
+from ._lib import check, declare, i32, i64, lib, ptr, require_gpu, stream_ptr, sz, vp
 from .masking_generator import MaskingGenerator, MaskingGeneratorRandomLocation
-
-declare({
-    "memhip_rasterize_workspace": (sz, [i32, i32, i32]),
-    "memhip_rasterize_f64": (i32, [vp, vp, i32, i32, i32, i32, vp, vp, vp, sz, vp]),
-    "memhip_rasterize_aug_f64": (i32, [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, sz, vp]),
-    "memhip_rasterize_binned_workspace": (sz, [i32, i32, i32, C.c_int64]),
-    "memhip_rasterize_binned_f64": (i32, [vp, vp, vp, i32, i32, i32, C.c_int64, vp, vp, vp, sz, vp]),
-    "memhip_events_extent": (i32, [vp, vp, vp, i32, vp, vp]),
-})
-
-# rasterize() uses the two-pass binned kernels (csrc/raster.hip) whenever there is no time surface and the canvas is
-# within their band limit; the time surface keeps the global-atomic form; binned=False forces the single-pass kernels
-_BINNED_MAX_PIXELS = 64 * 40000
-
 
 
 class EventAug(C.Structure):
@@ -62,32 +48,93 @@ def _new_aug_array(n):
     return a
 
 
+RASTER_AUTO, RASTER_SINGLE, RASTER_BINNED, RASTER_LDS, RASTER_GLOBAL, RASTER_GLOBAL_VAR = range(6)   # MEMHIP_RASTER_*
+RASTER_FAMILIES = {0: None, RASTER_BINNED: "binned", RASTER_LDS: "lds", RASTER_GLOBAL: "global", RASTER_GLOBAL_VAR: "global_var"}
+RASTER_KERNELS = ("raster_count", "raster_finalize", "raster_lds_kernel", "raster_bin_keys", "raster_bin_accum")
+
+
+class RasterArgs(C.Structure):
+    """== memhip_raster_args_t."""
+    _fields_ = [("ev", vp), ("offsets", vp), ("aug", vp), ("dims", vp)] + \
+               [(n, i32) for n in ("B", "H", "W", "time_surface", "form", "reserved0")] + \
+               [("n_events", i64), ("out", vp), ("status", vp), ("workspace", vp), ("workspace_bytes", sz)]
+
+
+class RasterLaunch(C.Structure):
+    """== memhip_raster_launch_t."""
+    _fields_ = [(n, i32) for n in ("kernel", "grid_x", "grid_y", "block", "lds")]
+
+    @property
+    def name(self):
+        return RASTER_KERNELS[self.kernel]
+
+
+class RasterPlan(C.Structure):
+    """== memhip_raster_plan_t."""
+    _fields_ = [(n, i32) for n in ("family", "rows_per_band", "bands", "band_px", "nb", "bx")] + \
+               [(n, C.c_uint64) for n in ("ws_bytes", "off_bins", "off_tstat", "off_keys", "off_hdr", "off_bad_slots",
+                                          "clear_ws_bytes", "clear_status_bytes", "clear_out_bytes")] + \
+               [("count", i32), ("l", RasterLaunch * 2)]
+
+    @property
+    def family_name(self):
+        return RASTER_FAMILIES[self.family]
+
+    @property
+    def launches(self):
+        """[(kernel name, grid_x, grid_y, workgroup size, dynamic LDS bytes)], in launch order."""
+        return [(l.name, l.grid_x, l.grid_y, l.block, l.lds) for l in self.l[:self.count]]
+
+
+declare({
+    "memhip_rasterize": (i32, [C.POINTER(RasterArgs), vp]),
+    "memhip_rasterize_plan": (i32, [C.POINTER(RasterArgs), i32, C.POINTER(RasterPlan)]),
+    "memhip_events_extent": (i32, [vp, vp, vp, i32, vp, vp]),
+})
+
+
+def raster_args(B, H, W, time_surface=False, form=RASTER_AUTO, n_events=0, ev=None, offsets=None, aug=None, dims=None,
+                out=None, status=None, workspace=None, workspace_bytes=0):
+    """The memhip_raster_args_t of memhip_rasterize / memhip_rasterize_plan; the tensors are addresses or None."""
+    return RasterArgs(ev, offsets, aug, dims, B, H, W, int(bool(time_surface)), form, 0, n_events, out, status, workspace,
+                      workspace_bytes)
+
+
+def raster_plan(args, device_cus=None):
+    """The RasterPlan of this call under the current `raster_lds` / `raster_bands` options: family, bands, workspace bytes
+    and layout, clears and `.launches`.  Validates like the call, except that pointers may be None; nothing is launched, and
+    no device is needed when device_cus is given (default: the library asks the current device)."""
+    plan = RasterPlan()
+    check(lib.memhip_rasterize_plan(C.byref(args), -1 if device_cus is None else device_cus, C.byref(plan)), "rasterize_plan")
+    return plan
+
+
+def raster_run(args, device, stream=None):
+    """memhip_rasterize with the workspace the plan of `args` asks for."""
+    # (the call plans again inside; the two cannot disagree on ws_bytes: it depends on B, H, W, n_events and on which of
+    # binned / single pass the struct selects, never on an option or the device's CU count)
+    args.workspace_bytes = raster_plan(args).ws_bytes
+    ws = torch.empty((args.workspace_bytes,), dtype=torch.uint8, device=device)
+    args.workspace = ptr(ws)
+    check(lib.memhip_rasterize(C.byref(args), stream_ptr() if stream is None else stream), "rasterize")
+
+
 def rasterize(ev, offsets, H, W, time_surface=False, aug=None, strict=True, binned=None, status_out=None):
     """ev f64 [n,4] (cuda), offsets i64 [B+1] (cuda), aug = uint8 cuda view of B aug records or
     None -> u8 [B,3,H,W] (cuda).  strict: raise IndexError like the reference when an event lands
     outside the canvas (costs one host sync); with strict=False pass a list as status_out to receive the
-    per-sample i32 count of such events (device tensor) and check it later.  binned: None = choose by size,
-    True/False = force the two-pass long-stream kernels / the single-pass kernels."""
+    per-sample i32 count of such events (device tensor) and check it later.  binned: None = the library chooses
+    (measured on MI355X: the two-pass kernels beat the single-pass LDS kernel at every size tried -- 256 x 30 000 events on
+    224 x 224: 69 us vs 145 us -- so they run wherever there is no time surface and the canvas is within their band limit),
+    True/False = force the two-pass long-stream kernels (no time surface) / the single-pass kernels."""
     require_gpu()
     B = offsets.numel() - 1
     out = torch.empty((B, 3, H, W), dtype=torch.uint8, device=ev.device)
     status = torch.empty((B,), dtype=torch.int32, device=ev.device)
-    n_rows = int(ev.shape[0])
-    if binned is None:
-        # measured on MI355X: the two-pass kernels beat the single-pass LDS kernel at every size tried (256 x 30 000
-        # events on 224 x 224: 69 us vs 145 us -- the single pass re-reads the events once per band of the canvas)
-        binned = not time_surface and B > 0 and H * W <= _BINNED_MAX_PIXELS
-    if binned:
-        # n_rows bounds offsets[B] - offsets[0] without a host sync
-        wsb = lib.memhip_rasterize_binned_workspace(B, H, W, n_rows)
-        ws = torch.empty((wsb,), dtype=torch.uint8, device=ev.device)
-        check(lib.memhip_rasterize_binned_f64(ptr(ev), ptr(offsets), ptr(aug), B, H, W, n_rows, ptr(out), ptr(status),
-                                              ptr(ws), wsb, stream_ptr()), "rasterize_binned")
-    else:
-        wsb = lib.memhip_rasterize_workspace(B, H, W)
-        ws = torch.empty((wsb,), dtype=torch.uint8, device=ev.device)
-        check(lib.memhip_rasterize_aug_f64(ptr(ev), ptr(offsets), ptr(aug), B, H, W, int(bool(time_surface)),
-                                           ptr(out), ptr(status), ptr(ws), wsb, stream_ptr()), "rasterize")
+    form = RASTER_AUTO if binned is None else RASTER_BINNED if binned else RASTER_SINGLE
+    # the rows of ev bound offsets[B] - offsets[0] without a host sync
+    raster_run(raster_args(B, H, W, time_surface, form, int(ev.shape[0]), ptr(ev), ptr(offsets), ptr(aug), None, ptr(out),
+                           ptr(status)), ev.device)
     if status_out is not None:
         status_out.append(status)
     if strict and int(status.sum().item()) != 0:

@@ -29,8 +29,8 @@ def test_version_and_arch():
 def test_error_reporting_without_gpu():
     """Argument validation happens before any launch: usable (and loud) on a CPU box."""
     from mem_amd import _lib
-    from mem_amd import datasets  # noqa: F401  (declares the signatures)
-    rc = _lib.lib.memhip_rasterize_f64(None, None, 1, 0, 0, 0, None, None, None, 0, None)
+    from mem_amd import datasets
+    rc = _lib.lib.memhip_rasterize(ctypes.byref(datasets.raster_args(1, 0, 0)), None)
     assert rc == -1
     assert b"bad shape" in _lib.lib.memhip_last_error()
 

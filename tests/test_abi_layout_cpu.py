@@ -5,10 +5,10 @@ Layout: a few lines of C, compiled against the header with the host compiler, pr
 field list comes from the header, so a mirror must name its fields as C does, in C's order.  A struct without a mirror, or a
 mirror without a struct, fails.
 
-Validation: memhip_branch_bwd, memhip_layernorm_bwd_branch, memhip_attn_bwd and memhip_conv2d_nhwc check their arguments before
-any launch, so every rule is exercised here through ctypes with dummy addresses -- nothing is dereferenced and no case reaches
-a launch.  memhip_conv_plan takes the struct of the convolution call: every call that is rejected is rejected by the query with
-the same code and the same message."""
+Validation: memhip_branch_bwd, memhip_layernorm_bwd_branch, memhip_attn_bwd, memhip_conv2d_nhwc and memhip_rasterize check their
+arguments before any launch, so every rule is exercised here through ctypes with dummy addresses -- nothing is dereferenced and
+no case reaches a launch.  memhip_conv_plan and memhip_rasterize_plan take the struct of their call: every call that is rejected
+is rejected by the query with the same code and the same message."""
 import ctypes as C
 import os
 import re
@@ -24,7 +24,8 @@ HEADER = os.path.join(ROOT, "include", "memhip.h")
 
 def _mirrors():
     from mem_amd import datasets, ops
-    return {"memhip_event_aug_t": datasets.EventAug, "memhip_dropout_t": ops.Dropout, "memhip_gemm_args_t": ops.GemmArgs,
+    return {"memhip_event_aug_t": datasets.EventAug, "memhip_raster_args_t": datasets.RasterArgs,
+            "memhip_raster_launch_t": datasets.RasterLaunch, "memhip_raster_plan_t": datasets.RasterPlan, "memhip_dropout_t": ops.Dropout, "memhip_gemm_args_t": ops.GemmArgs,
             "memhip_nt_launch_t": ops.NtLaunch, "memhip_nt_plan_t": ops.NtPlan,
             "memhip_tn_problem_t": ops.TnProblem, "memhip_tn_part_t": ops.TnPart, "memhip_tn_launch_t": ops.TnLaunch,
             "memhip_tn_plan_t": ops.TnPlan,
@@ -255,3 +256,51 @@ def test_conv2d_nhwc_validation_and_the_plan_query_agree():
             _rejected(fn, args(mode, **{field: None}), name + ": null pointer")
         # an empty batch: nothing to do, nothing read
         assert _call(fn, ops.conv_args(mode, 0, 14, 14, 64, 64, 3, 1, 1))[0] == 0
+
+
+def test_rasterize_validation_and_the_plan_query_agree():
+    """Every rejection rule of memhip_rasterize, the empty batch and args == NULL -- and for each rejected struct
+    memhip_rasterize_plan answers with the same code and the same message."""
+    from mem_amd import _lib, datasets as D
+    fn = "memhip_rasterize"
+
+    def args(B=2, H=224, W=224, ts=False, form=D.RASTER_AUTO, n_events=1000, **kw):
+        a = D.raster_args(B, H, W, ts, form, n_events, ev=P, offsets=P, out=P, status=P, workspace=P, workspace_bytes=1 << 40)
+        for key, v in kw.items():
+            setattr(a, key, v)
+        return a
+
+    def rejected(a, message, code=-1):
+        """by the call and by the query alike"""
+        rc, err = _call(fn, a)
+        assert rc == code and message in err, (rc, err)
+        plan = D.RasterPlan()
+        rc_q = _lib.lib.memhip_rasterize_plan(None if a is None else C.byref(a), 256, C.byref(plan))
+        assert (rc_q, _lib.lib.memhip_last_error().decode()) == (rc, err)
+
+    rejected(None, "rasterize: null args")
+    for bad in (dict(B=-1), dict(H=0), dict(W=-3)):
+        rejected(args(**bad), "rasterize: bad shape B=%d H=%d W=%d" % tuple(dict(dict(B=2, H=224, W=224), **bad).values()))
+    rejected(args(n_events=-1), "rasterize: n_events=-1 must not be negative")
+    for form in (-1, 3, D.RASTER_LDS):
+        rejected(args(form=form), "rasterize: unknown form %d" % form)
+    rejected(args(ts=True, form=D.RASTER_BINNED), "rasterize: the binned form has no time surface and no per-sample canvases")
+    rejected(args(dims=P, form=D.RASTER_BINNED), "rasterize: the binned form has no time surface and no per-sample canvases")
+    rejected(args(B=0, dims=P, form=D.RASTER_BINNED), "rasterize: the binned form has no time surface and no per-sample canvases")
+    for form in (D.RASTER_AUTO, D.RASTER_SINGLE, D.RASTER_BINNED):
+        rejected(args(form=form, ev=P + 8), "rasterize: ev must be 16-byte aligned")
+    # the two-pass kernels store 4 bytes at a time; AUTO chooses them for this canvas, the single-pass forms take any `out`
+    for form in (D.RASTER_AUTO, D.RASTER_BINNED):
+        rejected(args(form=form, out=P + 2), "rasterize: out must be 4-byte aligned for the binned form")
+    rejected(args(H=1601, W=1600, form=D.RASTER_BINNED), "rasterize: 1601x1600 canvas needs more than 64 bands", code=-4)
+    # workspace too small, per family: the query compares workspace_bytes whenever it is given a workspace
+    for kw in (dict(form=D.RASTER_BINNED), dict(form=D.RASTER_SINGLE), dict(form=D.RASTER_SINGLE, ts=True), dict(dims=P)):
+        need = D.raster_plan(args(workspace=None, **kw), 256).ws_bytes
+        assert need > 0
+        rejected(args(workspace_bytes=need - 1, **kw), "rasterize: workspace %d < %d" % (need - 1, need), code=-2)
+    # the call alone needs its pointers; the query asks about a call it does not make
+    for field in ("ev", "offsets", "out", "status", "workspace"):
+        _rejected(fn, args(**{field: None}), "rasterize: null pointer")
+        assert _lib.lib.memhip_rasterize_plan(C.byref(args(**{field: None})), 256, C.byref(D.RasterPlan())) == 0
+    # an empty batch: nothing to do, nothing read
+    assert _call(fn, D.raster_args(0, 224, 224))[0] == 0

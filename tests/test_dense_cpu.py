@@ -29,7 +29,7 @@ def test_dense_symbols_are_declared_exported_and_bound():
     lib = _lib()
     from mem_amd import ops
     header = open(os.path.join(ROOT, "include", "memhip.h")).read()
-    assert lib.memhip_abi_version() == 9                                        # (7 when these symbols came, additively; 8: the struct entry points; 9: the tokenizer's args struct)
+    assert lib.memhip_abi_version() == 10                                       # (7 when these symbols came, additively; 8: the struct entry points; 9: the tokenizer's args struct; 10: the rasterizer's)
     for name in ("memhip_tokens_to_maps", "memhip_maps_to_tokens_add"):
         assert f"int {name}(" in header, name
         assert hasattr(lib, name), name

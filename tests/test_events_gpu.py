@@ -1,5 +1,6 @@
 """-m gpu: HIP rasterizer / fused event augs / event_norm vs the oracle and the reference goldens
 (bit-exact: integer voxel bins; fp32 transforms with exact zeroing)."""
+import ctypes
 import json
 import os
 import random
@@ -57,6 +58,53 @@ def test_rasterizer_batched_ragged_vs_oracle():
                 continue                                  # 0/0 time surface: reference yields NaN casts
             want = E.event_arr_to_img(evs[b], H, W, ts).transpose(2, 0, 1)
             assert np.array_equal(got[b], want), (ts, b)
+
+
+def test_one_entry_every_family_and_form_vs_oracle():
+    """memhip_rasterize through datasets.rasterize, bit-equal to the oracle for every legal form x time surface, with the
+    kernel family the plan reports for each call asserted: binned under AUTO / BINNED, the LDS family under SINGLE on small
+    canvases, the global atomics under SINGLE on 480 x 640 and wherever there is a time surface (per-sample canvases, the fourth
+    family, run in test_augment_gpu.py::test_full_chain_vs_oracle).  Ragged batch around the 4096-event chunk; fractional and
+    negative-wrapping coordinates, p == 0, a pixel hit more than 255 times.  5 x 7 and 2 x 3 are canvases whose band count the
+    plan corrects (35 pixels in 64 forced bands: 9 bands of 4 pixels, none of them behind the canvas)."""
+    from mem_amd import _lib
+    from mem_amd import datasets as D
+    from oracle import events_np as E
+    rng = np.random.default_rng(23)
+    ns = [0, 1, 4095, 4096, 4097, 9000]
+    forms = {None: D.RASTER_AUTO, False: D.RASTER_SINGLE, True: D.RASTER_BINNED}
+    ran = set()
+    try:
+        for (H, W), single in (((5, 7), "lds"), ((2, 3), "lds"), ((224, 224), "lds"), ((480, 640), "global")):
+            evs = []
+            for n in ns:
+                evs.append(np.stack([rng.uniform(0, W, n), rng.uniform(0, H, n), np.sort(rng.integers(0, 300000, n)),
+                                     rng.integers(-1, 2, n)], 1).astype(np.float64).reshape(n, 4))       # p in {-1, 0, 1}
+            evs[5][:900, :2] = (0.61 * W, 0.61 * H); evs[5][:900, 3] = 1                               # > 255 hits on one pixel
+            evs[5][900:1300, :2] = (0.61 * W, 0.61 * H); evs[5][900:1300, 3] = -1
+            evs[4][:50, 1] = -1.0 - rng.integers(0, H - 1, 50)                                          # negative flat index: NumPy wrap
+            ev, off = _ev_dev(np.concatenate(evs)), _off(*ns)
+            # (a single timestamp is a 0 / 0 time surface: the reference yields NaN casts, that plane is not compared)
+            want = {ts: [E.event_arr_to_img(e, H, W, ts and np.ptp(e[:, 2]) > 0).transpose(2, 0, 1) if len(e)
+                         else np.zeros((3, H, W), np.uint8) for e in evs] for ts in (False, True)}
+            assert int(want[False][5][0].max()) > 0 and int(want[True][5][1].max()) > 0
+            for bands in ((0, 64) if H * W < 256 else (0,)):
+                _lib.set_option("raster_bands", bands)
+                for binned, ts in ((None, False), (None, True), (False, False), (False, True), (True, False)):
+                    plan = D.raster_plan(D.raster_args(len(ns), H, W, ts, forms[binned], int(ev.shape[0])))
+                    family = "global" if ts else single if binned is False else "binned"
+                    assert plan.family_name == family, (H, W, bands, binned, ts, plan.family_name)
+                    if family == "binned":
+                        assert (plan.nb - 1) * plan.band_px < H * W <= plan.nb * plan.band_px and (bands == 0 or plan.nb > 1)
+                    ran.add(family)
+                    got = D.rasterize(ev, off, H, W, ts, binned=binned).cpu().numpy()
+                    for b, n in enumerate(ns):
+                        if ts and n and np.ptp(evs[b][:, 2]) == 0:
+                            got[b][1] = 0
+                        assert np.array_equal(got[b], want[ts][b]), (H, W, bands, binned, ts, b)
+    finally:
+        _lib.set_option("raster_bands", 0)
+    assert ran == {"binned", "lds", "global"}
 
 
 def test_fused_augs_vs_oracle_chain():
@@ -330,11 +378,13 @@ def test_binned_rasterizer_key_workspace_too_small_is_flagged_per_sample():
     evs[0][:3, 1] = H + 5                                            # three events below the canvas: IndexError in the reference
     ev, off = _ev_dev(np.concatenate(evs)), _off(*ns)
     n_cap = 9000                                                     # sample 0 fits (5000), sample 1 ends at 12000, sample 2 at 12300
-    wsb = lib.memhip_rasterize_binned_workspace(3, H, W, n_cap)
-    ws = torch.empty((wsb,), dtype=torch.uint8, device="cuda")
     out = torch.full((3, 3, H, W), 7, dtype=torch.uint8, device="cuda")
     status = torch.full((3,), -1, dtype=torch.int32, device="cuda")
-    rc = lib.memhip_rasterize_binned_f64(ptr(ev), ptr(off), None, 3, H, W, n_cap, ptr(out), ptr(status), ptr(ws), wsb, stream_ptr())
+    a = D.raster_args(3, H, W, False, D.RASTER_BINNED, n_cap, ptr(ev), ptr(off), None, None, ptr(out), ptr(status))
+    a.workspace_bytes = D.raster_plan(a).ws_bytes
+    ws = torch.empty((a.workspace_bytes,), dtype=torch.uint8, device="cuda")
+    a.workspace = ptr(ws)
+    rc = lib.memhip_rasterize(ctypes.byref(a), stream_ptr())
     assert rc == 0
     st = status.cpu().tolist()
     assert st == [3, 1 << 30, 1 << 30], st

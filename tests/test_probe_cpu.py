@@ -22,7 +22,7 @@ def _bad(rc, lib, word):
 
 def test_pool_symbols_are_exported_and_the_abi_number_stays():
     lib = _lib()
-    assert lib.memhip_abi_version() == 9                                        # (7 when these symbols came, additively; 8: the struct entry points; 9: the tokenizer's args struct)
+    assert lib.memhip_abi_version() == 10                                       # (7 when these symbols came, additively; 8: the struct entry points; 9: the tokenizer's args struct; 10: the rasterizer's)
     for name in ("memhip_pool_tokens", "memhip_pool_tokens_bwd"):
         assert hasattr(lib, name), name
 

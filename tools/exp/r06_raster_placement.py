@@ -2,7 +2,7 @@
 lie?  One process, one events tensor; the key workspace and the output are placed at a sweep of byte offsets inside one big allocation."""
 import os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
-from mem_amd._lib import lib, ptr, stream_ptr
+from mem_amd._lib import check, lib, ptr, stream_ptr
 from mem_amd import datasets as D   # declares the entry points
 import ctypes as C
 B, n, H, W = 64, 1_000_000, 480, 640
@@ -12,7 +12,7 @@ t = torch.rand((B * n,), generator=g, device="cuda", dtype=torch.float64) * 3e5
 p = torch.randint(0, 2, (B * n,), generator=g, device="cuda") * 2 - 1
 big = torch.empty((3 << 30,), dtype=torch.uint8, device="cuda")            # events live INSIDE it too, at a chosen offset
 off = torch.arange(0, B + 1, device="cuda", dtype=torch.int64) * n
-wsb = lib.memhip_rasterize_binned_workspace(B, H, W, B * n)
+wsb = D.raster_plan(D.raster_args(B, H, W, False, D.RASTER_BINNED, B * n)).ws_bytes
 status = torch.empty((B,), dtype=torch.int32, device="cuda")
 base = big.data_ptr()
 def run(ev_off, ws_off, out_off, k=20):
@@ -20,7 +20,8 @@ def run(ev_off, ws_off, out_off, k=20):
     evt = big[ev_off: ev_off + B * n * 32].view(torch.float64).view(B * n, 4)
     evt.copy_(torch.stack([x.double(), y.double(), t, p.double()], 1))
     ws = C.c_void_p(base + ws_off); out = C.c_void_p(base + out_off)
-    f = lambda: lib.memhip_rasterize_binned_f64(ptr(evt), ptr(off), None, B, H, W, B * n, out, ptr(status), ws, wsb, stream_ptr())
+    args = D.raster_args(B, H, W, False, D.RASTER_BINNED, B * n, ptr(evt), ptr(off), None, None, out, ptr(status), ws, wsb)
+    f = lambda: check(lib.memhip_rasterize(C.byref(args), stream_ptr()), "rasterize")
     f(); f()
     a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     torch.cuda.synchronize(); a.record()
