@@ -36,7 +36,7 @@ extern "C" {
 #endif
 
 #define MEMHIP_ABI_VERSION 10  /* 10: the rasterizer takes one args struct: memhip_rasterize and memhip_rasterize_plan read the same memhip_raster_args_t; the
-                                  memhip_rasterize_f64 / _aug_f64 / _var_f64 / _binned_f64 / _workspace / _binned_workspace symbols are gone; 9: the tokenizer takes one args struct: memhip_conv2d_nhwc and memhip_conv_plan read the same memhip_conv_args_t; one
+                                  memhip_rasterize_f64 / _aug_f64 / _var_f64 / _binned_f64 / _workspace / _binned_workspace symbols are gone (additive since: memhip_convt2d_nhwc, memhip_convt_plan, memhip_kl_uniform_rows of the tokenizer's decoder); 9: the tokenizer takes one args struct: memhip_conv2d_nhwc and memhip_conv_plan read the same memhip_conv_args_t; one
                                   memhip_nchw_to_padded_nhwc4 and one memhip_argmax_rows with a mode argument; the per-mode symbols (_bf16 / _f32 / _f32_dyn / _f32_ex / _f16x2) are gone;
                                   8: one entry point per backward family, optional features as struct fields (memhip_branch_bwd, memhip_layernorm_bwd_branch,
                                   memhip_attn_bwd take an args struct; memhip_gemm_bf16_tn takes the workspace; the *_map / *_drop / *_out / *_ws symbols are gone; additive since: the memhip_neck_* entry points of the feature-pyramid necks);
@@ -835,7 +835,8 @@ enum { MEMHIP_CONV_K_BF16,          /* conv_gemm_kernel */
        MEMHIP_CONV_K_F16X2_W4,      /* conv_gemm_f16x2_kernel<4> */
        MEMHIP_CONV_K_F16X2_W8,      /* conv_gemm_f16x2_kernel<8> */
        MEMHIP_CONV_K_F16X2_WIDE,    /* conv_gemm_f16x2_wide_kernel: 256 x 128 tile */
-       MEMHIP_CONV_K_F16X2_FIRST }; /* conv_gemm_f16x2_first_kernel: C_in = 4, persistent */
+       MEMHIP_CONV_K_F16X2_FIRST,   /* conv_gemm_f16x2_first_kernel: C_in = 4, persistent */
+       MEMHIP_CONV_K_BF16_T };      /* convt_gemm_kernel: the decoder's transposed convolution (memhip_convt_plan only) */
 typedef struct memhip_conv_launch {
   int32_t kernel;             /* MEMHIP_CONV_K_* */
   int32_t grid;               /* workgroups */
@@ -851,6 +852,31 @@ typedef struct memhip_conv_plan {
   memhip_conv_launch_t l[2];
 } memhip_conv_plan_t;
 int memhip_conv_plan(const memhip_conv_args_t* args, int device_cus, memhip_conv_plan_t* out);
+
+/* ------------------------------------------------------------------------
+ * dVAE tokenizer, decoder side and evaluation (additive at ABI 10: plain arguments; at the next ABI bump these belong in an
+ * args struct like memhip_conv_args_t, one for the call and the plan query)
+ * replaces nn.ConvTranspose2d(4, stride 2, padding 1)  eventvae/vae/vae_model.py:92
+ *          DiscreteVAE.decode                           eventvae/vae/vae_model.py:160-171
+ *          the KL term of the dVAE loss / evaluate      eventvae/vae/vae_model.py:203-206 (evaluate: :216-266)
+ * ------------------------------------------------------------------------
+ * memhip_convt2d_nhwc: out = [relu](conv_transpose(in, W, stride 2, padding 1) + bias), bf16 operands, fp32 accumulation, on
+ * the tokenizer's activation format: in bf16 [B, H+2, W+2, Cin] with a zero border -> the INTERIOR of out bf16
+ * [B, 2H+2, 2W+2, Cout] (the border ring is never written; the caller zeroes the buffer once).  Four output phases (py, px),
+ * each a 2x2-tap stride-1 implicit GEMM (M = B*H*W, K = 4*Cin, N = Cout), one launch:
+ *   out[b, 2y+py, 2x+px, co] = bias[co] + sum_{dy,dx in {0,1}} sum_ci in_pad[b, y+py+dy, x+px+dx, ci] * W[ci, co, 3-py-2dy, 3-px-2dx]
+ * weight: bf16 [4 (phase = 2 py + px)][Cout][(dy, dx, ci)] packed on the host from torch's [Cin, Cout, 4, 4]
+ * (mem_amd pack_convt_weight); bias f32 [Cout] or NULL.  Cin a multiple of 64, Cout a multiple of 8; B == 0 is MEMHIP_OK.
+ * memhip_convt_plan: the dispatch of that call as data (Hp, Wp of the input, Ho = 2H, Wo = 2W, K = 4*Cin, off = 0,
+ * M = B*H*W, one launch MEMHIP_CONV_K_BF16_T of 4 x tiles workgroups); validates like the call (same codes and messages,
+ * pointers aside), launches nothing and needs no device. */
+int memhip_convt2d_nhwc(const void* in, const void* weight, const float* bias, void* out, int B, int H, int W, int Cin, int Cout,
+                        int relu, memhip_stream_t stream);
+int memhip_convt_plan(int B, int H, int W, int Cin, int Cout, int device_cus, memhip_conv_plan_t* out);
+/* row_kl f32 [M]: KL(softmax(logits[m]) || uniform) = sum_n q log q + log N over the N columns of logits [M, ld], in one pass
+ * over the row (no [M, N] log_softmax matrix); mode = the logits' type as in memhip_argmax_rows: MEMHIP_CONV_BF16 (N, ld
+ * multiples of 8) or MEMHIP_CONV_F32 (multiples of 4).  The reference's 'batchmean' kl_div is sum(row_kl) / batch size. */
+int memhip_kl_uniform_rows(const void* logits, int mode, int64_t ld, int M, int N, float* row_kl, memhip_stream_t stream);
 
 /* ------------------------------------------------------------------------
  * Layout / dtype movers

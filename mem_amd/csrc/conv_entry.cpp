@@ -46,3 +46,20 @@ extern "C" int memhip_argmax_rows(const void* logits, int mode, int64_t ld, int 
   static ArgmaxLaunchFn* const launch[] = {argmax_rows_bf16_launch, argmax_rows_f32_launch};
   return launch[mode](logits, ld, M, N, ids, top2_gap, row_rms, n_samples, rows_per_sample, stream);
 }
+
+// The decoder: validate -> plan -> launch, like the convolutions above (the rules are convt_validate / convt_plan in conv_plan.cpp).
+extern "C" int memhip_convt2d_nhwc(const void* in, const void* weight, const float* bias, void* out, int B, int H, int W, int Cin,
+                                   int Cout, int relu, memhip_stream_t stream) {
+  if (int rc = convt_validate(B, H, W, Cin, Cout, in && weight && out)) return rc;
+  if (B == 0) return MEMHIP_OK;
+  return convt_bf16_launch(in, weight, bias, out, B, H, W, Cin, Cout, relu, convt_plan(B, H, W, Cin, Cout), stream);
+}
+
+extern "C" int memhip_kl_uniform_rows(const void* logits, int mode, int64_t ld, int M, int N, float* row_kl, memhip_stream_t stream) {
+  MEMHIP_REQUIRE(mode == MEMHIP_CONV_BF16 || mode == MEMHIP_CONV_F32, "kl_uniform_rows: the logits are bf16 or fp32, mode %d", mode);
+  const int vec = mode == MEMHIP_CONV_BF16 ? 8 : 4;
+  MEMHIP_REQUIRE(M >= 0 && N > 0 && N % vec == 0 && ld >= N && ld % vec == 0, "kl_uniform_rows: N and ld must be multiples of %d", vec);
+  if (M == 0) return MEMHIP_OK;
+  MEMHIP_REQUIRE(logits && row_kl, "kl_uniform_rows: null pointer");
+  return kl_uniform_rows_launch(logits, mode, ld, M, N, row_kl, stream);
+}

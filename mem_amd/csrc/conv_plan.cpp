@@ -121,7 +121,38 @@ ConvPlan conv_plan(int mode, const ConvGeom& g, const ConvFlags& f, const ConvOp
   return a;
 }
 
+// ---- the transposed convolution of the decoder (bf16 only): Cin % 64 (a 64-deep k-tile lies inside one of the 2x2 taps),
+// Cout % 8 (16-byte stores); 4 M output pixels
+int convt_validate(int B, int H, int W, int Cin, int Cout, bool ptrs_ok) {
+  MEMHIP_REQUIRE(B >= 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0, "convt2d: bad shape");
+  if (B == 0) return MEMHIP_OK;
+  MEMHIP_REQUIRE(ptrs_ok, "convt2d: null pointer");
+  MEMHIP_REQUIRE(Cin % 64 == 0, "convt2d: C_in must be a multiple of 64");
+  MEMHIP_REQUIRE(Cout % 8 == 0, "convt2d: C_out must be a multiple of 8");
+  MEMHIP_REQUIRE(4 * (int64_t)B * H * W < (1LL << 31), "convt2d: too many output pixels");
+  return MEMHIP_OK;
+}
+
+ConvPlan convt_plan(int B, int H, int W, int Cin, int Cout) {
+  ConvPlan a = {};
+  a.Hp = H + 2; a.Wp = W + 2; a.Ho = 2 * H; a.Wo = 2 * W; a.K = 4 * Cin; a.off = 0; a.M = (int64_t)B * H * W;
+  if (a.M == 0) return a;
+  // one launch for the four phases: (row tile, phase, column tile), one 128 x 128 tile per workgroup
+  const long long grid = 4LL * cdiv(a.M, kConvTileM) * cdiv(Cout, kConvTileN);
+  push(a, MEMHIP_CONV_K_BF16_T, (int)grid, 256, kConvLdsBf16);
+  return a;
+}
+
 }  // namespace memhip
+
+extern "C" int memhip_convt_plan(int B, int H, int W, int Cin, int Cout, int device_cus, memhip_conv_plan_t* out) {
+  using namespace memhip;
+  MEMHIP_REQUIRE(out, "convt_plan: null pointer");
+  if (int rc = convt_validate(B, H, W, Cin, Cout, true)) return rc;
+  (void)device_cus;                                     // the one form does not depend on the device
+  *out = convt_plan(B, H, W, Cin, Cout);
+  return MEMHIP_OK;
+}
 
 extern "C" int memhip_conv_plan(const memhip_conv_args_t* args, int device_cus, memhip_conv_plan_t* out) {
   using namespace memhip;

@@ -66,4 +66,13 @@ ConvLaunchFn conv_bf16_launch, conv_f32_launch, conv_f16x2_launch;
 ToNhwc4LaunchFn to_nhwc4_bf16_launch, to_nhwc4_f32_launch, to_nhwc4_f16x2_launch;
 ArgmaxLaunchFn argmax_rows_bf16_launch, argmax_rows_f32_launch;
 
+// ---- the decoder's transposed convolution, ConvTranspose2d(4, stride 2, pad 1) as four 2x2 phase GEMMs (convt.hip; plain
+// arguments: memhip_convt2d_nhwc and memhip_convt_plan).  convt_validate is the one reader of the arguments for the call and
+// the query (ptrs_ok: the query dereferences nothing), convt_plan the one place that decides the launch; the launcher obeys.
+int convt_validate(int B, int H, int W, int Cin, int Cout, bool ptrs_ok);
+ConvPlan convt_plan(int B, int H, int W, int Cin, int Cout);
+int convt_bf16_launch(const void* in, const void* weight, const float* bias, void* out, int B, int H, int W, int Cin, int Cout,
+                      int relu, const ConvPlan& plan, memhip_stream_t stream);
+int kl_uniform_rows_launch(const void* logits, int mode, int64_t ld, int M, int N, float* row_kl, memhip_stream_t stream);
+
 }  // namespace memhip

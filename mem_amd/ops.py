@@ -8,6 +8,7 @@ import ctypes as C
 import torch
 
 from ._lib import check, declare, f32, f64, i32, i64, lib, ptr, stream_ptr, sz, vp
+from .vae_model import pack_convt_weight  # noqa: F401  (the host side of convt2d_nhwc's weight layout, next to the encoder's _pack)
 
 EPI_BIAS_BF16, EPI_BIAS_GELU, EPI_RESIDUAL, EPI_DGELU, EPI_F32, EPI_PATCH_EMBED, EPI_BIAS_GELU_DG, EPI_MUL_AUX = range(8)
 EPI_RESIDUAL_DROP = 8
@@ -306,6 +307,36 @@ def nchw_to_padded_nhwc4(x, out, mean=None, std=None):
 def argmax_rows(logits, M, N, ids, gap=None, rms=None, n_samples=None, rows_per_sample=0):
     check(lib.memhip_argmax_rows(ptr(logits), _CONV_MODE[logits.dtype], logits.stride(0), M, N, ptr(ids), ptr(gap), ptr(rms),
                                  ptr(n_samples), rows_per_sample, stream_ptr()), "argmax_rows")
+
+
+declare({
+    "memhip_convt2d_nhwc": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
+    "memhip_kl_uniform_rows": (i32, [vp, i32, i64, i32, i32, vp, vp]),
+})
+
+
+def convt2d_nhwc(x_pad, weight, bias, out, B, H, W, Cin, Cout, relu=False):
+    """ConvTranspose2d(Cin, Cout, 4, stride=2, padding=1) (+ bias, optional ReLU; vae_model.py:92) on the tokenizer's format:
+    x_pad bf16 [B, H+2, W+2, Cin] with a zero border -> the interior of out bf16 [B, 2H+2, 2W+2, Cout] (its border ring is
+    not written).  weight = pack_convt_weight(w) in bf16, bias f32 [Cout] or None.  Cin % 64 == 0, Cout % 8 == 0."""
+    assert x_pad.dtype == torch.bfloat16 and weight.dtype == torch.bfloat16 and out.dtype == torch.bfloat16
+    assert B == 0 or (x_pad.numel() >= B * (H + 2) * (W + 2) * Cin and weight.numel() == 16 * Cin * Cout and
+                      out.numel() >= B * (2 * H + 2) * (2 * W + 2) * Cout and (bias is None or bias.numel() == Cout))
+    check(lib.memhip_convt2d_nhwc(_p(x_pad), _p(weight), _p(bias), _p(out), B, H, W, Cin, Cout, int(relu), stream_ptr()),
+          "convt2d_nhwc")
+
+
+def kl_uniform_rows(logits, M, N, out=None):
+    """f32 [M]: KL(softmax(logits[m]) || uniform) = sum_n q log q + log N of the first M rows of logits (bf16 or fp32,
+    [rows, ld]) in one pass per row -- F.kl_div(log_uniform, F.log_softmax(logits, -1), reduction='none',
+    log_target=True).sum(-1) (vae_model.py:203-206) without the [M, N] log_softmax matrix."""
+    assert logits.dim() == 2 and logits.stride(1) == 1 and logits.shape[0] >= M and logits.shape[1] >= N
+    if out is None:
+        out = torch.empty((M,), dtype=torch.float32, device=logits.device)
+    assert out.dtype == torch.float32 and out.numel() >= M
+    check(lib.memhip_kl_uniform_rows(ptr(logits), _CONV_MODE[logits.dtype], logits.stride(0), M, N, ptr(out), stream_ptr()),
+          "kl_uniform_rows")
+    return out[:M]
 
 
 def tok_flag_samples(gap, rms, B, hw, kappa, lst, count, stats=None):
@@ -738,7 +769,7 @@ def mae_loss(pred, img, mask, B, Cc, H, W, patch, only_masked, row_loss, dpred, 
 # ---------------------------------------------------------------- the dispatch of the tokenizer convolutions (csrc/conv_plan.cpp)
 # kernel names of ConvLaunch.kernel (MEMHIP_CONV_K_*), as they appear in a kernel trace
 CONV_KERNELS = ("conv_gemm_kernel", "conv_gemm_f32_kernel", "conv_gemm_f32_m32_kernel", "conv_gemm_f16x2_kernel<4>",
-                "conv_gemm_f16x2_kernel<8>", "conv_gemm_f16x2_wide_kernel", "conv_gemm_f16x2_first_kernel")
+                "conv_gemm_f16x2_kernel<8>", "conv_gemm_f16x2_wide_kernel", "conv_gemm_f16x2_first_kernel", "convt_gemm_kernel")
 
 
 class ConvLaunch(C.Structure):
@@ -774,6 +805,18 @@ def conv_plan(mode, B, H, W, Cin, Cout, ksize, stride, pad, add=False, out_f32=F
                   out_padded=out_padded, out_f32=out_f32, n_active=16 if dynamic else None)
     plan = ConvPlan()
     check(lib.memhip_conv_plan(C.byref(a), -1 if device_cus is None else device_cus, C.byref(plan)), "conv_plan")
+    return plan
+
+
+declare({"memhip_convt_plan": (i32, [i32, i32, i32, i32, i32, i32, C.POINTER(ConvPlan)])})
+
+
+def convt_plan(B, H, W, Cin, Cout, device_cus=None):
+    """The ConvPlan of convt2d_nhwc for this layer: Hp, Wp of the input, Ho = 2H, Wo = 2W, K = 4 Cin, off = 0, M = B H W and one
+    launch of convt_gemm_kernel over 4 (phases) x tiles workgroups.  Validates like the call; nothing is launched and no device
+    is needed."""
+    plan = ConvPlan()
+    check(lib.memhip_convt_plan(B, H, W, Cin, Cout, -1 if device_cus is None else device_cus, C.byref(plan)), "convt_plan")
     return plan
 
 

@@ -1,13 +1,42 @@
-"""Event dVAE tokenizer, inference side -- adjacent dependency of the pretraining loop
-(/root/reference/eventvae/vae/vae_model.py:29-113,153-189; called every step at
-mem/engine_for_pretraining.py:144).  SURVEY.md section 8 row a22 / f1: v1 runs the frozen tokenizer
-through stock PyTorch-ROCm (MIOpen convs); a hand-written implicit-GEMM version is the next row.
-Same module tree => same state-dict keys as the reference checkpoints ('hparams' / 'weights').
-Training the dVAE (gumbel-softmax path, losses) is a different stage and not provided."""
+"""Event dVAE tokenizer, inference side -- adjacent dependency of the pretraining loop (reference:
+eventvae/vae/vae_model.py:29-113,153-189; called every step at mem/engine_for_pretraining.py:144).
+
+`DiscreteVAE` is the torch module with the reference's module tree, so reference checkpoints ('hparams' / 'weights') load by
+key; `HipTokenizer` runs it on the hand-written HIP path (csrc/conv*.hip, csrc/convt.hip): the encoder
+(`get_codebook_indices`: fp32, certified fp16x2 or bf16 implicit-GEMM convolutions + argmax) and the decoder (`decode`,
+`reconstruct`: bf16, the transposed convolutions as four 2x2 phase GEMMs).  mem_amd/eval_tokenizer.py evaluates a checkpoint
+with them (reconstruction loss, KL to uniform, codebook usage; vae_model.py:216-266).
+Training the dVAE (gumbel-softmax forward, any backward) is a different stage and not provided."""
 from typing import NamedTuple, Optional
 
 import torch
+import torch.nn.functional as F
 from torch import nn
+
+
+def pack_convt_weight(w, cin_pad=None, cout_pad=None):
+    """The weight layout of ops.convt2d_nhwc (csrc/convt.hip).  w: torch's ConvTranspose2d(Cin, Cout, 4, stride=2, padding=1)
+    weight [Cin, Cout, 4, 4] -> [4, Cout, 4 * Cin] in w's dtype, K-contiguous:
+
+        packed[2 * py + px, co, (2 * dy + dx) * Cin + ci] = w[ci, co, 3 - py - 2 * dy, 3 - px - 2 * dx]
+
+    Output phase (py, px) = the parity of the output pixel (2y + py, 2x + px); (dy, dx) in {0, 1}^2 walks the 2 x 2 input
+    window whose top-left pixel is PADDED position (y + py, x + px) of the one-pixel-border input, so that
+
+        out[b, 2y+py, 2x+px, co] = bias[co] + sum_{dy, dx, ci} in_pad[b, y+py+dy, x+px+dx, ci] * packed[2py+px, co, (2dy+dx) Cin + ci]
+
+    cin_pad / cout_pad: zero-pad the channel counts first (the kernel wants Cin % 64 == 0 and Cout % 8 == 0)."""
+    ci, co, kh, kw = w.shape
+    assert kh == 4 and kw == 4, "ConvTranspose2d(4, stride 2, padding 1) only"
+    cip, cop = cin_pad or ci, cout_pad or co
+    if (cip, cop) != (ci, co):
+        w = F.pad(w, (0, 0, 0, 0, 0, cop - co, 0, cip - ci))
+    phases = []
+    for py in (0, 1):
+        for px in (0, 1):
+            taps = [w[:, :, 3 - py - 2 * dy, 3 - px - 2 * dx] for dy in (0, 1) for dx in (0, 1)]     # each [Cin, Cout]
+            phases.append(torch.stack(taps).permute(2, 0, 1).reshape(cop, 4 * cip))                # [Cout, (dy, dx, ci)]
+    return torch.stack(phases).contiguous()
 
 
 class ResBlock(nn.Module):
@@ -29,6 +58,10 @@ class DiscreteVAE(nn.Module):
         self.input_H, self.input_W, self.input_size = input_H, input_W, (input_H, input_W)
         self.num_tokens, self.num_layers = num_tokens, num_layers
         self.normalization = normalization
+        self.loss, self.temperature, self.straight_through = loss, temperature, straight_through
+        self.kl_div_loss_weight = kl_div_loss_weight
+        # vae_model.py:107-108
+        self.loss_fn = {"mse": F.mse_loss, "smooth_l1": F.smooth_l1_loss, "cosine": self.cosine_reconstruction_loss}[loss]
         self.codebook = nn.Embedding(num_tokens, codebook_dim)
         has_res = num_resnet_blocks > 0
         enc_chans = [channels] + [hidden_dim] * num_layers
@@ -45,6 +78,13 @@ class DiscreteVAE(nn.Module):
         enc.append(nn.Conv2d(enc_chans[-1], num_tokens, 1))
         dec.append(nn.Conv2d(dec_chans[-1], channels, 1))
         self.encoder, self.decoder = nn.Sequential(*enc), nn.Sequential(*dec)
+
+    @staticmethod
+    def cosine_reconstruction_loss(target, rec):
+        """vae_model.py:116-119"""
+        target = target / (target.norm(dim=-1, keepdim=True) + 1e-9)
+        rec = rec / (rec.norm(dim=-1, keepdim=True) + 1e-9)
+        return (1 - (target * rec).sum(-1)).mean()
 
     def norm(self, images):
         if self.normalization is None:
@@ -64,7 +104,8 @@ class DiscreteVAE(nn.Module):
     def forward(self, img, return_logits=False, **kw):
         assert img.shape[-1] == self.input_W and img.shape[-2] == self.input_H
         if not return_logits:
-            raise NotImplementedError("dVAE training / reconstruction is a separate stage (out of scope)")
+            raise NotImplementedError("dVAE training (gumbel-softmax forward, losses with gradients) is a separate stage; "
+                                      "reconstruction: HipTokenizer.reconstruct / mem_amd.eval_tokenizer")
         return self.encoder(self.norm(img))
 
     def decode(self, img_seq):
@@ -115,7 +156,12 @@ class HipTokenizer:
       `audit_every`-th call one sample is recomputed in fp32 on the device and label mismatches are counted
       (`certification_stats()["audit_mismatches"]`, expected 0).  `certify=False` is the raw mode.
     precision="bf16" (csrc/conv.hip): bf16 operands, fp32 accumulation; ~6x faster, 97-99 % of the ids agree (the rest
-      are near ties) -- an explicit opt-in (`--tokenizer_impl hip_bf16`), never the default."""
+      are near ties) -- an explicit opt-in (`--tokenizer_impl hip_bf16`), never the default.
+
+    `decode(ids)` / `reconstruct(images)` are `DiscreteVAE.decode` on the same path, in bf16 whatever the encoder's precision
+    (the reference evaluates the decoder under autocast): codebook rows gathered into the padded NHWC format, the 1x1
+    convolution and ResBlocks through the bf16 convolutions, the ConvTranspose2d(4, s2, p1) layers through csrc/convt.hip.
+    The decoder's weights and buffers are packed / allocated on the first `decode`, for chunks of `decode_batch` samples."""
 
     # flag a token when gap <= kappa * rms(row).  kappa is calibrated per model (see the class docstring); CERT_KAPPA is the value
     # round 5 used for every model (4 x the worst deviation seen then, 1.75e-5 of the rms on the ViT-B fixture) and stays as the
@@ -124,9 +170,12 @@ class HipTokenizer:
     KAPPA_FLOOR = 1e-5
 
     def __init__(self, vae: "DiscreteVAE", max_batch=256, precision="fp32", certify=True, exact_capacity=256, kappa=None,
-                 calibration_images=None, audit_every=64):
+                 calibration_images=None, audit_every=64, decode_batch=16):
         from . import ops
         self.ops = ops
+        self._model = vae                                  # decode() packs the decoder from it on first use
+        self.decode_batch = int(decode_batch)
+        self._dec = None
         assert precision in ("fp32", "bf16", "fp16x2")
         self.precision = precision
         self.certify = bool(certify) and precision == "fp16x2"
@@ -323,3 +372,111 @@ class HipTokenizer:
         is from flipping under a different fp32 summation order."""
         h, w = self.hw_out
         return self.gap[: B * h * w].view(B, h * w).clone()
+
+    # ---------------------------------------------------------------- decoder (bf16; vae_model.py:160-171)
+    def _pack_dec(self, conv, cin_pad=None, cout_pad=None):
+        """A Conv2d of the decoder as a bf16 ConvLayer, channel counts zero-padded to cin_pad / cout_pad."""
+        w = conv.weight.detach().float()                   # [Cout, Cin, k, k]
+        co, ci, k, _ = w.shape
+        cip, cop = cin_pad or ci, cout_pad or co
+        w = F.pad(w.permute(0, 2, 3, 1), (0, cip - ci, 0, 0, 0, 0, 0, cop - co))
+        b = conv.bias.detach().float() if conv.bias is not None else torch.zeros(co, device=w.device)
+        return ConvLayer(w.reshape(cop, k * k * cip).to(torch.bfloat16).contiguous(), F.pad(b, (0, cop - co)).contiguous(),
+                         cip, cop, k, conv.stride[0], conv.padding[0])
+
+    def _decode_init(self):
+        """Pack the decoder once: the codebook as a bf16 table with its dim padded to a multiple of 64, then in order
+        ("conv1", ConvLayer) the 1x1 behind the codebook, ("res", (ConvLayer,) * 3), ("convt", ConvLayer with the phase-packed
+        weight) and ("head", ConvLayer) = the final 1x1 with its output channels padded to 8."""
+        vae = self._model
+        cb = vae.codebook.weight.detach().float()
+        cpad = -(-cb.shape[1] // 64) * 64
+        d = {"table": F.pad(cb, (0, cpad - cb.shape[1])).to(torch.bfloat16).contiguous(), "cpad": cpad, "layers": [], "n": 0}
+        cin = cpad                                         # channels (padded) the next layer reads
+        for m in vae.decoder:
+            if isinstance(m, nn.Sequential):               # ConvTranspose2d(4, s2, p1) + ReLU
+                ct = m[0]
+                assert ct.kernel_size == (4, 4) and ct.stride == (2, 2) and ct.padding == (1, 1)
+                w = pack_convt_weight(ct.weight.detach().float(), cin_pad=cin).to(torch.bfloat16).contiguous()
+                d["layers"].append(("convt", ConvLayer(w, ct.bias.detach().float().contiguous(), cin, ct.out_channels, 4, 2, 1)))
+                cin = ct.out_channels
+            elif isinstance(m, ResBlock):
+                d["layers"].append(("res", tuple(self._pack_dec(m.net[i]) for i in (0, 2, 4))))
+            elif m is vae.decoder[-1]:                     # final Conv2d(hidden, channels, 1)
+                d["channels"] = m.out_channels
+                d["layers"].append(("head", self._pack_dec(m, cout_pad=-(-m.out_channels // 8) * 8)))
+            else:                                          # Conv2d(codebook_dim, hidden, 1) in front of the ResBlocks
+                d["layers"].append(("conv1", self._pack_dec(m, cin_pad=cin)))
+                cin = m.out_channels
+        self._dec = d
+
+    def _decode_alloc(self, n):
+        """Zero-bordered bf16 buffers for chunks of n samples: the codebook level, three at the ResBlocks' level, one per
+        transposed layer, and the dense head output."""
+        d = self._dec
+        if n <= d["n"]:
+            return
+        dev, bf = self.dev, torch.bfloat16
+        h, w = self.hw_out
+        d["n"], d["x0"], d["bufs"] = n, torch.zeros((n, h + 2, w + 2, d["cpad"]), dtype=bf, device=dev), {}
+        for kind, L in d["layers"]:
+            if kind == "head":
+                d["out"] = torch.empty((n * h * w, L.cout), dtype=bf, device=dev)
+                continue
+            if kind == "convt":
+                h, w = 2 * h, 2 * w
+            cout = L[0].cout if kind == "res" else L.cout
+            pool = d["bufs"].setdefault((h, w, cout), [])
+            while len(pool) < (3 if kind == "res" else 1):
+                pool.append(torch.zeros((n, h + 2, w + 2, cout), dtype=bf, device=dev))
+
+    def _decode_chunk(self, ids):
+        d, ops = self._dec, self.ops
+        conv = ops.conv2d_nhwc
+        n = ids.shape[0]
+        h, w = self.hw_out
+        cur = d["x0"]
+        cur[:n, 1:-1, 1:-1] = d["table"][ids].view(n, h, w, d["cpad"])
+        for kind, L in d["layers"]:
+            if kind == "conv1":
+                out = d["bufs"][(h, w, L.cout)][0]
+                conv(cur, L.w, L.b, out, n, h, w, L.cin, L.cout, 1, 1, 0, relu=False)
+                cur = out
+            elif kind == "res":
+                c1, c2, c3 = L
+                pool = d["bufs"][(h, w, c1.cout)]
+                t1 = next(t for t in pool if t is not cur)
+                t2 = next(t for t in pool if t is not cur and t is not t1)
+                conv(cur, c1.w, c1.b, t1, n, h, w, c1.cin, c1.cout, c1.k, c1.stride, c1.pad, relu=True)
+                conv(t1, c2.w, c2.b, t2, n, h, w, c2.cin, c2.cout, c2.k, c2.stride, c2.pad, relu=True)
+                conv(t2, c3.w, c3.b, t1, n, h, w, c3.cin, c3.cout, c3.k, c3.stride, c3.pad, relu=False, add=cur)   # net(x) + x
+                cur = t1
+            elif kind == "convt":
+                out = d["bufs"][(2 * h, 2 * w, L.cout)][0]
+                ops.convt2d_nhwc(cur, L.w, L.b, out, n, h, w, L.cin, L.cout, relu=True)
+                cur, h, w = out, 2 * h, 2 * w
+            else:
+                conv(cur, L.w, L.b, d["out"], n, h, w, L.cin, L.cout, 1, 1, 0, relu=False, out_padded=False)
+        return d["out"][: n * h * w, : d["channels"]].view(n, h, w, d["channels"]).permute(0, 3, 1, 2).float()
+
+    @torch.no_grad()
+    def decode(self, ids, decode_batch=None):
+        """`DiscreteVAE.decode`: ids i64 [B, h*w] on the GPU -> f32 [B, C, H, W], in chunks of decode_batch samples (default:
+        the constructor's; every sample's result is independent of the chunking)."""
+        h, w = self.hw_out
+        assert ids.is_cuda and ids.dtype == torch.int64 and ids.dim() == 2 and ids.shape[1] == h * w
+        if self._dec is None:
+            self._decode_init()
+        step = max(1, int(decode_batch or self.decode_batch))
+        B = ids.shape[0]
+        self._decode_alloc(min(step, max(B, 1)))
+        out = torch.empty((B, self._dec["channels"], self.H, self.W), dtype=torch.float32, device=self.dev)
+        for i in range(0, B, step):
+            out[i:i + step] = self._decode_chunk(ids[i:i + step])
+        return out
+
+    @torch.no_grad()
+    def reconstruct(self, images):
+        """(ids, recon): `get_codebook_indices`, then `decode` (the hard reconstruction of vae_model.py:240-245)."""
+        ids = self.get_codebook_indices(images)
+        return ids, self.decode(ids)

@@ -1,5 +1,5 @@
 // Host-only exercise of conv_plan.cpp for the sanitizers: memhip_conv_plan over a few hundred thousand memhip_conv_args_t --
-// every mode and unknown ones, accepted and rejected shapes, fields the mode does not have, null in / weight / out (the query
+// every mode and unknown ones (and memhip_convt_plan over its plain arguments), accepted and rejected shapes, fields the mode does not have, null in / weight / out (the query
 // reads no pointer), every conv_waves value, 8..304 CUs -- with the invariants a launcher relies on checked on the way.  The
 // three functions of core.cpp it needs are stubbed here; no device:
 //
@@ -62,6 +62,26 @@ int main() {
     }
   }
   CHECK(ok > 30000 && rejected > 30000);
+  // memhip_convt_plan (the decoder's transposed convolution): plain arguments, one launch of 4 x tiles workgroups
+  long long t_ok = 0, t_rejected = 0;
+  CHECK(memhip_convt_plan(2, 3, 5, 64, 72, 256, nullptr) == MEMHIP_EINVAL);
+  for (int it = 0; it < 100000; ++it) {
+    const int B = rnd(0, 29) ? rnd(1, 256) : rnd(-1, 0), H = rnd(0, 29) ? rnd(1, 224) : rnd(-3, 0);
+    const int W = rnd(0, 3) ? H : rnd(1, 4096), Cin = cins[rnd(0, 7)], Cout = rnd(0, 1) ? 128 * rnd(1, 8) : 2 * rnd(0, 512);
+    const int rc = memhip_convt_plan(rnd(0, 99) ? B : 1 << 16, H, W, Cin, Cout, rnd(0, 9) ? 8 * rnd(1, 38) : -1, &plan);
+    CHECK(rc == MEMHIP_OK || rc == MEMHIP_EINVAL);
+    if (rc != MEMHIP_OK) { ++t_rejected; CHECK(memhip::g_err[0]); continue; }
+    ++t_ok;
+    CHECK(plan.count == (plan.M ? 1 : 0) && plan.K == 4 * Cin && plan.off == 0 && plan.Ho == 2 * H && plan.Wo == 2 * W);
+    if (plan.count) {
+      const memhip_conv_launch_t& l = plan.l[0];
+      const long long tiles = (plan.M + 127) / 128 * ((Cout + 127) / 128);
+      CHECK(l.kernel == MEMHIP_CONV_K_BF16_T && l.grid == 4 * tiles && l.grid >= 4 && l.block == 256 && l.lds > 0 && l.lds <= 160 * 1024);
+      ++launches;
+    }
+  }
+  CHECK(t_ok > 10000 && t_rejected > 10000);
+  ok += t_ok; rejected += t_rejected;
   std::printf("conv_plan_sanitize: %lld plans, %lld launches, %lld rejected\n", ok, launches, rejected);
   return 0;
 }
