@@ -36,7 +36,7 @@ extern "C" {
 #endif
 
 #define MEMHIP_ABI_VERSION 10  /* 10: the rasterizer takes one args struct: memhip_rasterize and memhip_rasterize_plan read the same memhip_raster_args_t; the
-                                  memhip_rasterize_f64 / _aug_f64 / _var_f64 / _binned_f64 / _workspace / _binned_workspace symbols are gone (additive since: memhip_convt2d_nhwc, memhip_convt_plan, memhip_kl_uniform_rows of the tokenizer's decoder); 9: the tokenizer takes one args struct: memhip_conv2d_nhwc and memhip_conv_plan read the same memhip_conv_args_t; one
+                                  memhip_rasterize_f64 / _aug_f64 / _var_f64 / _binned_f64 / _workspace / _binned_workspace symbols are gone (additive since: memhip_convt2d_nhwc, memhip_convt_plan, memhip_kl_uniform_rows of the tokenizer's decoder; memhip_conv_wgrad_nhwc / _plan / _workspace with memhip_conv_wgrad_args_t, memhip_relu_bwd_colsum / _workspace of dVAE training); 9: the tokenizer takes one args struct: memhip_conv2d_nhwc and memhip_conv_plan read the same memhip_conv_args_t; one
                                   memhip_nchw_to_padded_nhwc4 and one memhip_argmax_rows with a mode argument; the per-mode symbols (_bf16 / _f32 / _f32_dyn / _f32_ex / _f16x2) are gone;
                                   8: one entry point per backward family, optional features as struct fields (memhip_branch_bwd, memhip_layernorm_bwd_branch,
                                   memhip_attn_bwd take an args struct; memhip_gemm_bf16_tn takes the workspace; the *_map / *_drop / *_out / *_ws symbols are gone; additive since: the memhip_neck_* entry points of the feature-pyramid necks);
@@ -877,6 +877,68 @@ int memhip_convt_plan(int B, int H, int W, int Cin, int Cout, int device_cus, me
  * over the row (no [M, N] log_softmax matrix); mode = the logits' type as in memhip_argmax_rows: MEMHIP_CONV_BF16 (N, ld
  * multiples of 8) or MEMHIP_CONV_F32 (multiples of 4).  The reference's 'batchmean' kl_div is sum(row_kl) / batch size. */
 int memhip_kl_uniform_rows(const void* logits, int mode, int64_t ld, int M, int N, float* row_kl, memhip_stream_t stream);
+
+/* ------------------------------------------------------------------------
+ * dVAE tokenizer, training side: the weight gradient of every convolution of the model (additive at ABI 10)
+ * replaces autograd's weight gradients of  ResBlock's Conv2d(3,1,1) / Conv2d(1)           eventvae/vae/vae_model.py:29-41
+ *                                          Conv2d(4,2,1), ConvTranspose2d(4,2,1), heads  eventvae/vae/vae_model.py:86-102
+ * ------------------------------------------------------------------------
+ * memhip_conv_wgrad_nhwc: one implicit TN GEMM, the reduction over the pixels (b, y, x) of the SMALL grid Hs x Ws:
+ *   G[n, (ky, kx, c)] (+)= sum_{b,y,x} Small[b, y, x, n] * BigPad[b, s*y + ky + 1 - pad, s*x + kx + 1 - pad, c]
+ * grad   f32 [N, k*k*C], (ky, kx, c)-major: the packed layout of the forward weight (memhip_conv2d_nhwc's [Cout, k*k*Cin]).
+ * small  bf16, N channels over Hs x Ws: the one-pixel-border format [B, Hs+2, Ws+2, N] (small_padded = 1; its ring is never
+ *        read) or the dense matrix [B*Hs*Ws, N] (small_padded = 0), rows (b, y, x).
+ * big    bf16 [B, s*Hs + 2, s*Ws + 2, C], always the padded format; its ring IS read and must be zero.
+ * Forms (ksize, stride, pad): (4, 2, 1), (3, 1, 1), (1, 1, 0).  C = 4 (4x4 only: the first encoder layer) or a multiple of 8;
+ * N a multiple of 8.  small and big 16-byte aligned.
+ *   Conv2d:                  small = the gradient of the pre-activation, big = the layer's input, G = dW packed.
+ *   ConvTranspose2d(4,2,1):  small = the layer's INPUT [.., Cin], big = the gradient of its output [B, 2H+2, 2W+2, Cout]:
+ *                            torch's dW[ci, co, ky, kx] = G[ci, (ky, kx, co)].
+ *   The two 1x1 heads:       small dense (token logits [M, num_tokens], reconstruction [M, 8]).
+ * The pixel range is split over the grid (memhip_conv_wgrad_plan_t.splits slices of whole 64-pixel stages).  No atomics: with
+ * more than one slice every workgroup stores its partial tile into `workspace` ([splits][N][K] f32, all of it overwritten) and
+ * a second launch folds the slices in ascending order into grad (accumulate: onto what grad holds); two calls give the same
+ * bits.  One slice writes grad itself and needs no workspace.  workspace_bytes < the plan's ws_bytes: MEMHIP_EWORKSPACE.
+ * memhip_conv_wgrad_plan: the dispatch as data for a device of device_cus CUs (< 0: the current device's, as the call uses);
+ * it validates like the call (same codes and messages; pointers, alignment and the workspace size aside), launches nothing
+ * and needs no device.  memhip_conv_wgrad_workspace: the plan's ws_bytes (0 for a rejected struct).
+ * (The two structs are declared tag first, typedef second.) */
+struct memhip_conv_wgrad_args {
+  const void* small;          /* bf16, see above */
+  const void* big;            /* bf16 padded, zero ring */
+  float* grad;                /* f32 [N, ksize*ksize*C] */
+  void* workspace;            /* >= plan.ws_bytes, 16-byte aligned; may be NULL when the plan has one slice */
+  size_t workspace_bytes;
+  int32_t B, Hs, Ws;          /* the SMALL pixel grid; big's is stride*Hs x stride*Ws */
+  int32_t C, N;               /* channels of big / of small */
+  int32_t ksize, stride, pad;
+  int32_t small_padded;       /* 1: padded NHWC, 0: dense rows */
+  int32_t accumulate;         /* 1: grad += , 0: grad = */
+};
+typedef struct memhip_conv_wgrad_args memhip_conv_wgrad_args_t;
+struct memhip_conv_wgrad_plan {
+  int64_t M;                  /* B*Hs*Ws reduction rows */
+  int64_t ws_bytes;           /* splits > 1: splits * N * K * 4, else 0 */
+  int32_t K;                  /* ksize*ksize*C columns of grad */
+  int32_t Hbp, Wbp;           /* padded size of big */
+  int32_t tiles_n, tiles_k;   /* 128 x 128 output tiles */
+  int32_t splits, rows_per_split;   /* slices of the pixel range: slice i covers [i * rows_per_split, min(M, (i+1) * ...)) */
+  int32_t grid, block, lds_bytes;   /* the GEMM launch: tiles_n * tiles_k * splits workgroups */
+  int32_t fold_grid;          /* workgroups of the fold launch (256 threads), 0 with one slice */
+  int32_t reserved;
+};
+typedef struct memhip_conv_wgrad_plan memhip_conv_wgrad_plan_t;
+int memhip_conv_wgrad_nhwc(const memhip_conv_wgrad_args_t* args, memhip_stream_t stream);
+int memhip_conv_wgrad_plan(const memhip_conv_wgrad_args_t* args, int device_cus, memhip_conv_wgrad_plan_t* out);
+size_t memhip_conv_wgrad_workspace(const memhip_conv_wgrad_args_t* args, int device_cus);
+/* ReLU backward in place, with the bias gradient: g *= (y > 0) over the R = B*H*W pixels of a bf16 buffer of C channels
+ * (C % 8 == 0; padded = 1: g and y in the one-pixel-border format [B, H+2, W+2, C], rings untouched; 0: dense [R, C]);
+ * y NULL: no mask.  colsum f32 [C] or NULL: (+)= the column sums of the masked g -- per-workgroup partial sums as plain
+ * stores into `workspace` (memhip_relu_bwd_colsum_workspace bytes), folded in ascending order by a second launch: no
+ * atomics, two calls give the same bits.  R == 0 is MEMHIP_OK. */
+int memhip_relu_bwd_colsum(void* g, const void* y, int padded, int B, int H, int W, int C, float* colsum, int accumulate,
+                           void* workspace, size_t workspace_bytes, memhip_stream_t stream);
+size_t memhip_relu_bwd_colsum_workspace(int B, int H, int W, int C);
 
 /* ------------------------------------------------------------------------
  * Layout / dtype movers

@@ -820,6 +820,86 @@ def convt_plan(B, H, W, Cin, Cout, device_cus=None):
     return plan
 
 
+# ---------------------------------------------------------------- dVAE training: weight gradients (csrc/conv_wgrad.hip)
+class ConvWgradArgs(C.Structure):
+    """== memhip_conv_wgrad_args_t."""
+    _fields_ = [("small", vp), ("big", vp), ("grad", vp), ("workspace", vp), ("workspace_bytes", sz)] + \
+               [(n, i32) for n in ("B", "Hs", "Ws", "C", "N", "ksize", "stride", "pad", "small_padded", "accumulate")]
+
+
+class ConvWgradPlan(C.Structure):
+    """== memhip_conv_wgrad_plan_t."""
+    _fields_ = [("M", i64), ("ws_bytes", i64)] + \
+               [(n, i32) for n in ("K", "Hbp", "Wbp", "tiles_n", "tiles_k", "splits", "rows_per_split", "grid", "block",
+                                   "lds_bytes", "fold_grid", "reserved")]
+
+
+declare({
+    "memhip_conv_wgrad_nhwc": (i32, [C.POINTER(ConvWgradArgs), vp]),
+    "memhip_conv_wgrad_plan": (i32, [C.POINTER(ConvWgradArgs), i32, C.POINTER(ConvWgradPlan)]),
+    "memhip_conv_wgrad_workspace": (sz, [C.POINTER(ConvWgradArgs), i32]),
+    "memhip_relu_bwd_colsum": (i32, [vp, vp, i32, i32, i32, i32, i32, vp, i32, vp, sz, vp]),
+    "memhip_relu_bwd_colsum_workspace": (sz, [i32, i32, i32, i32]),
+})
+
+
+def conv_wgrad_args(B, Hs, Ws, C_, N, ksize, stride, pad, small=None, big=None, grad=None, small_padded=True, accumulate=False,
+                    workspace=None, workspace_bytes=0):
+    """The memhip_conv_wgrad_args_t of conv_wgrad / conv_wgrad_plan; the tensors are addresses or None."""
+    return ConvWgradArgs(small, big, grad, workspace, workspace_bytes, B, Hs, Ws, C_, N, ksize, stride, pad, int(small_padded),
+                         int(accumulate))
+
+
+def conv_wgrad_plan(B, Hs, Ws, C_, N, ksize, stride, pad, small_padded=True, device_cus=None):
+    """The ConvWgradPlan of conv_wgrad for this layer: tiles, slices of the pixel range, grid, LDS and workspace bytes.
+    Validates like the call; nothing is launched, and no device is needed when device_cus is given."""
+    plan = ConvWgradPlan()
+    a = conv_wgrad_args(B, Hs, Ws, C_, N, ksize, stride, pad, small_padded=small_padded)
+    check(lib.memhip_conv_wgrad_plan(C.byref(a), -1 if device_cus is None else device_cus, C.byref(plan)), "conv_wgrad_plan")
+    return plan
+
+
+def conv_wgrad_workspace(B, Hs, Ws, C_, N, ksize, stride, pad, small_padded=True, device_cus=None):
+    """Workspace bytes conv_wgrad needs for this layer (0: one slice, no workspace)."""
+    a = conv_wgrad_args(B, Hs, Ws, C_, N, ksize, stride, pad, small_padded=small_padded)
+    return int(lib.memhip_conv_wgrad_workspace(C.byref(a), -1 if device_cus is None else device_cus))
+
+
+def conv_wgrad(small, big, grad, B, Hs, Ws, C_, N, ksize, stride, pad, small_padded=True, accumulate=False, workspace=None):
+    """grad f32 [N, k*k*C] (+)= sum over the pixels (b, y, x) of the Hs x Ws grid of
+    small[b, y, x, n] * big_pad[b, s*y + ky + 1 - pad, s*x + kx + 1 - pad, c]: the weight gradient of Conv2d (small = g of the
+    pre-activation, big = the layer's input), of ConvTranspose2d(4, 2, 1) (small = the layer's input, big = g of its output:
+    torch's dW[ci, co, ky, kx] = grad[ci, (ky, kx, co)]) and of the 1x1 heads (small dense, small_padded=False).
+    small bf16 padded [B, Hs+2, Ws+2, N] or dense [B*Hs*Ws, N]; big bf16 padded [B, s*Hs+2, s*Ws+2, C] with a ZERO ring.
+    workspace: a 16-byte aligned tensor of >= conv_wgrad_workspace(...) bytes (None only when that is 0).  No atomics: two
+    calls give the same bits."""
+    assert small.dtype == torch.bfloat16 and big.dtype == torch.bfloat16 and grad.dtype == torch.float32
+    assert small.is_contiguous() and big.is_contiguous() and grad.is_contiguous()
+    assert small.numel() >= (B * (Hs + 2) * (Ws + 2) * N if small_padded else B * Hs * Ws * N)
+    assert big.numel() >= B * (stride * Hs + 2) * (stride * Ws + 2) * C_ and grad.numel() >= N * ksize * ksize * C_
+    ws_bytes = 0 if workspace is None else workspace.numel() * workspace.element_size()
+    a = conv_wgrad_args(B, Hs, Ws, C_, N, ksize, stride, pad, _p(small), _p(big), _p(grad), small_padded, accumulate,
+                        _p(workspace), ws_bytes)
+    check(lib.memhip_conv_wgrad_nhwc(C.byref(a), stream_ptr()), "conv_wgrad")
+
+
+def relu_bwd_colsum_workspace(B, H, W, C_):
+    return int(lib.memhip_relu_bwd_colsum_workspace(B, H, W, C_))
+
+
+def relu_bwd_colsum(g, y, B, H, W, C_, padded=True, colsum=None, accumulate=False, workspace=None):
+    """In place g *= (y > 0) over the B*H*W pixels of a bf16 buffer of C channels (padded [B, H+2, W+2, C]: the ring is not
+    touched; or dense [B*H*W, C]); y None: no mask.  colsum f32 [C] (+)= the column sums of the masked g (the bias gradient),
+    through per-workgroup partial sums in `workspace` (>= relu_bwd_colsum_workspace bytes) folded in a fixed order."""
+    assert g.dtype == torch.bfloat16 and g.is_contiguous() and (y is None or (y.dtype == torch.bfloat16 and y.is_contiguous()))
+    n = B * (H + 2) * (W + 2) * C_ if padded else B * H * W * C_
+    assert g.numel() >= n and (y is None or y.numel() >= n)
+    assert colsum is None or (colsum.dtype == torch.float32 and colsum.numel() >= C_)
+    ws_bytes = 0 if workspace is None else workspace.numel() * workspace.element_size()
+    check(lib.memhip_relu_bwd_colsum(_p(g), _p(y), int(padded), B, H, W, C_, _p(colsum), int(accumulate), _p(workspace), ws_bytes,
+                                     stream_ptr()), "relu_bwd_colsum")
+
+
 # ---------------------------------------------------------------- finetuning recipe (csrc/finetune_recipe.hip)
 declare({
     "memhip_mixup": (i32, [vp, i32, i32, i32, i32, vp, vp, vp, vp, vp]),

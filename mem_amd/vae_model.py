@@ -6,7 +6,10 @@ key; `HipTokenizer` runs it on the hand-written HIP path (csrc/conv*.hip, csrc/c
 (`get_codebook_indices`: fp32, certified fp16x2 or bf16 implicit-GEMM convolutions + argmax) and the decoder (`decode`,
 `reconstruct`: bf16, the transposed convolutions as four 2x2 phase GEMMs).  mem_amd/eval_tokenizer.py evaluates a checkpoint
 with them (reconstruction loss, KL to uniform, codebook usage; vae_model.py:216-266).
-Training the dVAE (gumbel-softmax forward, any backward) is a different stage and not provided."""
+Training the dVAE (gumbel-softmax forward, the backward, Adam) runs on `vae_train.DVAEEngine` / `python -m mem_amd.train_vae`,
+with an explicit backward on the HIP kernels; the torch module itself has no training forward.  This file holds the host side
+of that backward's weights: `dgrad_weight` / `pack_dgrad_weight` re-read a layer's weight so that its data gradient is one of
+the forward kernels."""
 from typing import NamedTuple, Optional
 
 import torch
@@ -37,6 +40,46 @@ def pack_convt_weight(w, cin_pad=None, cout_pad=None):
             taps = [w[:, :, 3 - py - 2 * dy, 3 - px - 2 * dx] for dy in (0, 1) for dx in (0, 1)]     # each [Cin, Cout]
             phases.append(torch.stack(taps).permute(2, 0, 1).reshape(cop, 4 * cip))                # [Cout, (dy, dx, ci)]
     return torch.stack(phases).contiguous()
+
+
+def pack_conv_weight(w):
+    """The weight layout of ops.conv2d_nhwc (and of ops.conv_wgrad's gradient): torch's Conv2d weight [Cout, Cin, k, k] ->
+    [Cout, k*k*Cin], (ky, kx, c)-major."""
+    return w.permute(0, 2, 3, 1).reshape(w.shape[0], -1).contiguous()
+
+
+def dgrad_weight(kind, w):
+    """Data gradients of the dVAE's layers are forward kernels with a re-read weight.  Returns (op, weight in torch layout) with
+    which dX = op(g, weight), for the layer kinds of the model:
+
+        "conv4s2"  Conv2d(4, stride 2, pad 1), w [Co, Ci, 4, 4]:  dX = conv_transpose2d(g, w, stride 2, pad 1) -- w already has
+                   ConvTranspose2d's [in = Co, out = Ci, 4, 4] layout
+        "convt"    ConvTranspose2d(4, 2, 1), w [Ci, Co, 4, 4]:    dX = conv2d(g, w, stride 2, pad 1) -- w read as [out = Ci, in = Co]
+        "conv3"    Conv2d(3, 1, 1), w [Co, Ci, 3, 3]:             dX = conv2d(g, w', pad 1), w'[ci, co, ky, kx] = w[co, ci, 2-ky, 2-kx]
+        "conv1"    Conv2d(1), w [Co, Ci, 1, 1]:                   dX = conv2d(g, w^T)
+
+    Plain torch on the weights, once per step; not on the hot path."""
+    if kind == "conv4s2":
+        return "conv_transpose2d", w
+    if kind == "convt":
+        return "conv2d", w
+    if kind == "conv3":
+        return "conv2d", w.flip(2, 3).transpose(0, 1).contiguous()
+    if kind == "conv1":
+        return "conv2d", w.transpose(0, 1).contiguous()
+    raise KeyError(kind)
+
+
+def pack_dgrad_weight(kind, w, cin_pad=None, cout_pad=None):
+    """dgrad_weight in the layout of the kernel that runs it: ops.convt2d_nhwc's phase-packed [4, Ci, 4*Co] for "conv4s2",
+    ops.conv2d_nhwc's [out, k*k*in] for the others.  cin_pad / cout_pad zero-pad the channels of g / of dX."""
+    op, wd = dgrad_weight(kind, w)
+    if op == "conv_transpose2d":
+        return pack_convt_weight(wd, cin_pad=cin_pad, cout_pad=cout_pad)
+    co, ci = wd.shape[:2]
+    if (cin_pad or ci, cout_pad or co) != (ci, co):
+        wd = F.pad(wd, (0, 0, 0, 0, 0, (cin_pad or ci) - ci, 0, (cout_pad or co) - co))
+    return pack_conv_weight(wd)
 
 
 class ResBlock(nn.Module):
@@ -104,7 +147,8 @@ class DiscreteVAE(nn.Module):
     def forward(self, img, return_logits=False, **kw):
         assert img.shape[-1] == self.input_W and img.shape[-2] == self.input_H
         if not return_logits:
-            raise NotImplementedError("dVAE training (gumbel-softmax forward, losses with gradients) is a separate stage; "
+            raise NotImplementedError("the torch module has no training forward: dVAE training (gumbel-softmax forward, losses, "
+                                      "explicit backward) is mem_amd.vae_train.DVAEEngine / python -m mem_amd.train_vae; "
                                       "reconstruction: HipTokenizer.reconstruct / mem_amd.eval_tokenizer")
         return self.encoder(self.norm(img))
 
