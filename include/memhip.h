@@ -36,7 +36,7 @@ extern "C" {
 #endif
 
 #define MEMHIP_ABI_VERSION 10  /* 10: the rasterizer takes one args struct: memhip_rasterize and memhip_rasterize_plan read the same memhip_raster_args_t; the
-                                  memhip_rasterize_f64 / _aug_f64 / _var_f64 / _binned_f64 / _workspace / _binned_workspace symbols are gone (additive since: memhip_convt2d_nhwc, memhip_convt_plan, memhip_kl_uniform_rows of the tokenizer's decoder; memhip_conv_wgrad_nhwc / _plan / _workspace with memhip_conv_wgrad_args_t, memhip_relu_bwd_colsum / _workspace of dVAE training); 9: the tokenizer takes one args struct: memhip_conv2d_nhwc and memhip_conv_plan read the same memhip_conv_args_t; one
+                                  memhip_rasterize_f64 / _aug_f64 / _var_f64 / _binned_f64 / _workspace / _binned_workspace symbols are gone (additive since: memhip_convt2d_nhwc, memhip_convt_plan, memhip_kl_uniform_rows of the tokenizer's decoder; memhip_conv_wgrad_nhwc / _plan / _workspace with memhip_conv_wgrad_args_t, memhip_relu_bwd_colsum / _workspace of dVAE training; memhip_seg_axis_table / _seg_plan / _seg_ce / _seg_confusion with memhip_seg_args_t of the segmentation loss); 9: the tokenizer takes one args struct: memhip_conv2d_nhwc and memhip_conv_plan read the same memhip_conv_args_t; one
                                   memhip_nchw_to_padded_nhwc4 and one memhip_argmax_rows with a mode argument; the per-mode symbols (_bf16 / _f32 / _f32_dyn / _f32_ex / _f16x2) are gone;
                                   8: one entry point per backward family, optional features as struct fields (memhip_branch_bwd, memhip_layernorm_bwd_branch,
                                   memhip_attn_bwd take an args struct; memhip_gemm_bf16_tn takes the workspace; the *_map / *_drop / *_out / *_ws symbols are gone; additive since: the memhip_neck_* entry points of the feature-pyramid necks);
@@ -1112,6 +1112,76 @@ int memhip_neck_bn_gelu_bwd_sums(const void* da_bf16, const void* y_bf16, int64_
 int memhip_neck_bn_gelu_bwd_apply(const void* da_bf16, const void* y_bf16, int64_t R, int D, const float* mean, const float* rstd,
                                   const float* gamma, const float* beta, const float* sums, float inv_n, void* dy_bf16,
                                   memhip_stream_t stream);
+
+/* ------------------------------------------------------------------------
+ * Segmentation loss and metrics (seg_loss.hip, seg_plan.cpp; additive to ABI 10)
+ * replaces the end of every mmseg 0.30 decode head: resize(seg_logit, size=seg_label.shape[2:], mode='bilinear') ->
+ *          cross_entropy(ignore_index=255) / accuracy (training) and resize -> argmax -> intersect_and_union (evaluation)
+ *          mem/semantic_segmentation/configs/_base_/models/upernet_beit.py:25-50
+ * ------------------------------------------------------------------------
+ * The upsampled [B, C, H, W] tensor is never written.  Both calls and the plan query read one host struct.
+ *
+ * Axis tables: the bilinear weights of one axis (in -> out samples, out >= in), torch's upsample_bilinear2d arithmetic in
+ * fp32: scale = in / out (align_corners: (in - 1) / (out - 1), 0 when out == 1), src = max(scale (y + 0.5) - 0.5, 0)
+ * (align_corners: scale y), i0 = min(floor(src), in - 1), i1 = min(i0 + 1, in - 1), w1 = src - i0, w0 = 1 - w1.
+ * lo[i] .. hi[i] is the inclusive range of outputs that read input i through i0 or i1.  memhip_seg_axis_table fills HOST
+ * arrays i0[out], w1[out], lo[in], hi[in]; the caller uploads them and the kernels read the weights from there, so loss and
+ * gradient agree on every weight.  A pixel's logit is w0y (w0x a + w1x b) + w1y (w0x c + w1x d). */
+int memhip_seg_axis_table(int in, int out, int align_corners, int32_t* i0, float* w1, int32_t* lo, int32_t* hi);
+
+/* (declared as a tagged struct with its typedef behind it, like memhip_seg_plan below) */
+struct memhip_seg_args {
+  const float* logits;               /* device f32, logical [B, C, h, w] at element strides sb, sc, sy, sx (NCHW of a torch
+                                        head, or pixel rows [B h w, ld]: sb = h w ld, sc = 1, sy = w ld, sx = ld) */
+  int64_t sb, sc, sy, sx;
+  const uint8_t* labels;             /* device u8 [B, H, W] contiguous */
+  int32_t B, C, h, w, H, W;          /* B >= 1, 2 <= C <= 32, H >= h >= 1, W >= w >= 1 */
+  int32_t ignore_index;              /* the label that does not count (mmseg: 255); -1: none.  A label >= C that is not
+                                        ignore_index is counted in n_bad and otherwise treated as ignored */
+  int32_t align_corners;             /* 0 / 1 */
+  int32_t avg_non_ignore;            /* 0: loss = loss_weight * sum / (B H W) (mmseg 0.30); 1: / max(n_valid, 1) */
+  float loss_weight;
+  const int32_t* y_i0; const float* y_w1; const int32_t* y_lo; const int32_t* y_hi;   /* device: the table (h -> H) */
+  const int32_t* x_i0; const float* x_w1; const int32_t* x_lo; const int32_t* x_hi;   /* device: the table (w -> W) */
+  /* memhip_seg_ce only */
+  float* dz;                         /* device f32, logical [B, C, h, w] at element strides db, dc, dy, dx (no two elements
+                                        at one address): sum over the outputs of weight * (softmax - onehot), UNSCALED;
+                                        every element is written exactly once */
+  int64_t db, dc, dy, dx;
+  float* loss;                       /* device f32 [3]: loss, loss_weight / N (the factor of dz in the backward), loss_sum */
+  int64_t* stats;                    /* device i64 [3]: n_valid, n_correct (argmax == label, ties to the lowest class), n_bad */
+  void* workspace;                   /* device, workspace_bytes >= memhip_seg_plan_t.ws_bytes, 8-byte aligned */
+  size_t workspace_bytes;
+  /* memhip_seg_confusion only */
+  int64_t* confusion;                /* device i64 [C, C], row = label, column = prediction: ADDED to */
+};
+typedef struct memhip_seg_args memhip_seg_args_t;
+
+/* Training: one kernel (a workgroup per tile of low-resolution pixels recomputes the outputs in its footprint, takes loss and
+ * counts of the outputs it is home to, gathers dz in a fixed order) + a one-workgroup finish kernel.  No float atomics:
+ * the same inputs give the same bits.  All labels ignored: loss 0, dz 0. */
+int memhip_seg_ce(const memhip_seg_args_t* args, memhip_stream_t stream);
+/* Evaluation: one thread per output pixel, argmax of the interpolated logits (ties to the lowest class), a C x C histogram
+ * per workgroup in LDS, flushed with integer atomics.  Ignored and bad labels are skipped. */
+int memhip_seg_confusion(const memhip_seg_args_t* args, memhip_stream_t stream);
+
+/* The launches of both calls as data.  memhip_seg_plan validates the struct like the calls do, except that pointers may
+ * be NULL (workspace_bytes is compared only when there is a workspace).  Host arithmetic only. */
+struct memhip_seg_plan {
+  int32_t tile_h, tile_w;            /* low-resolution pixels per workgroup; tile (ty, tx) starts at (ty tile_h, tx tile_w) */
+  int32_t tiles_y, tiles_x;
+  int32_t grid, block;               /* memhip_seg_ce: grid = B tiles_y tiles_x workgroups, one workspace slot each */
+  int32_t chunk;                     /* outputs of a footprint per pass */
+  int32_t max_fh, max_fw;            /* the largest footprint (y_lo[first] .. y_hi[last] of a tile) over the tiles */
+  int32_t tables_in_lds;             /* the footprint's slices of the tables are staged in LDS (else read from memory) */
+  int32_t lds_bytes;                 /* per workgroup, <= 64 KiB */
+  int32_t slot_bytes;                /* workspace bytes per workgroup */
+  int32_t conf_grid, conf_block, conf_lds_bytes;   /* memhip_seg_confusion */
+  int32_t reserved;
+  uint64_t ws_bytes;
+};
+typedef struct memhip_seg_plan memhip_seg_plan_t;
+int memhip_seg_plan(const memhip_seg_args_t* args, memhip_seg_plan_t* out);
 
 #ifdef __cplusplus
 }

@@ -1113,3 +1113,116 @@ def neck_bn_gelu_bwd_apply(da, y, mean, rstd, gamma, beta, sums, inv_n, out=None
     check(lib.memhip_neck_bn_gelu_bwd_apply(ptr(da), ptr(y), R, D, ptr(mean), ptr(rstd), ptr(gamma), ptr(beta), ptr(sums),
                                             float(inv_n), ptr(out), stream_ptr()), "neck_bn_gelu_bwd_apply")
     return out
+
+
+# ---------------------------------------------------------------- segmentation loss and metrics (csrc/seg_loss.hip, seg_plan.cpp)
+class SegArgs(C.Structure):
+    """== memhip_seg_args_t."""
+    _fields_ = [("logits", vp), ("sb", i64), ("sc", i64), ("sy", i64), ("sx", i64), ("labels", vp)] + \
+               [(n, i32) for n in ("B", "C", "h", "w", "H", "W", "ignore_index", "align_corners", "avg_non_ignore")] + \
+               [("loss_weight", f32)] + \
+               [(n, vp) for n in ("y_i0", "y_w1", "y_lo", "y_hi", "x_i0", "x_w1", "x_lo", "x_hi", "dz")] + \
+               [(n, i64) for n in ("db", "dc", "dy", "dx")] + \
+               [("loss", vp), ("stats", vp), ("workspace", vp), ("workspace_bytes", sz), ("confusion", vp)]
+
+
+class SegPlan(C.Structure):
+    """== memhip_seg_plan_t."""
+    _fields_ = [(n, i32) for n in ("tile_h", "tile_w", "tiles_y", "tiles_x", "grid", "block", "chunk", "max_fh", "max_fw",
+                                   "tables_in_lds", "lds_bytes", "slot_bytes", "conf_grid", "conf_block", "conf_lds_bytes",
+                                   "reserved")] + [("ws_bytes", C.c_uint64)]
+
+
+declare({
+    "memhip_seg_axis_table": (i32, [i32, i32, i32, vp, vp, vp, vp]),
+    "memhip_seg_plan": (i32, [C.POINTER(SegArgs), C.POINTER(SegPlan)]),
+    "memhip_seg_ce": (i32, [C.POINTER(SegArgs), vp]),
+    "memhip_seg_confusion": (i32, [C.POINTER(SegArgs), vp]),
+})
+
+
+def seg_axis_table(n_in, n_out, align_corners):
+    """The bilinear table of one axis as host arrays (i0 i32 [out], w1 f32 [out], lo i32 [in], hi i32 [in]): output y reads
+    inputs i0[y] and min(i0[y] + 1, in - 1) with weights 1 - w1[y] and w1[y]; lo[i] .. hi[i] are the outputs that read input i.
+    No device needed."""
+    import numpy as np
+    i0, w1 = np.empty(max(n_out, 0), np.int32), np.empty(max(n_out, 0), np.float32)
+    lo, hi = np.empty(max(n_in, 0), np.int32), np.empty(max(n_in, 0), np.int32)
+    check(lib.memhip_seg_axis_table(n_in, n_out, int(align_corners), i0.ctypes.data, w1.ctypes.data, lo.ctypes.data,
+                                    hi.ctypes.data), "seg_axis_table")
+    return i0, w1, lo, hi
+
+
+_SEG_TABLES = {}
+
+
+def seg_tables(n_in, n_out, align_corners, device):
+    """The table of seg_axis_table on the device: one i32 tensor [2 out + 2 in] = i0 | bits of w1 | lo | hi, uploaded once
+    per (in, out, align_corners, device) and kept."""
+    key = (n_in, n_out, bool(align_corners), str(device))
+    t = _SEG_TABLES.get(key)
+    if t is None:
+        import numpy as np
+        i0, w1, lo, hi = seg_axis_table(n_in, n_out, align_corners)
+        t = _SEG_TABLES[key] = torch.from_numpy(np.concatenate([i0, w1.view(np.int32), lo, hi])).to(device)
+    return t
+
+
+def _table_ptrs(t, n_in, n_out):
+    p = t.data_ptr()
+    return p, p + 4 * n_out, p + 8 * n_out, p + 8 * n_out + 4 * n_in
+
+
+def seg_args(B, C_, h, w, H, W, ignore_index=255, align_corners=False, avg_non_ignore=False, loss_weight=1.0, **fields):
+    """The memhip_seg_args_t of seg_ce / seg_confusion / seg_plan; pointer fields are addresses or None."""
+    a = SegArgs(B=B, C=C_, h=h, w=w, H=H, W=W, ignore_index=-1 if ignore_index is None else int(ignore_index),
+                align_corners=int(align_corners), avg_non_ignore=int(avg_non_ignore), loss_weight=float(loss_weight))
+    for k, v in fields.items():
+        setattr(a, k, v)
+    return a
+
+
+def seg_plan(B, C_, h, w, H, W, align_corners=False):
+    """The SegPlan of a call with these shapes: tiles, grid, LDS bytes, workspace bytes.  Validates like the call; no device."""
+    plan = SegPlan()
+    check(lib.memhip_seg_plan(C.byref(seg_args(B, C_, h, w, H, W, align_corners=align_corners)), C.byref(plan)), "seg_plan")
+    return plan
+
+
+def _seg_common(logits, labels, ignore_index, align_corners, **kw):
+    assert logits.is_cuda and logits.dtype == torch.float32 and logits.dim() == 4, "logits: a CUDA f32 tensor [B, C, h, w] (any strides)"
+    assert labels.is_cuda and labels.dtype == torch.uint8 and labels.dim() == 3 and labels.is_contiguous(), \
+        "labels: a contiguous CUDA u8 tensor [B, H, W]"
+    B, C_, h, w = logits.shape
+    assert labels.shape[0] == B, (tuple(logits.shape), tuple(labels.shape))
+    H, W = labels.shape[1:]
+    a = seg_args(B, C_, h, w, H, W, ignore_index, align_corners, logits=logits.data_ptr(), labels=labels.data_ptr(), **kw)
+    a.sb, a.sc, a.sy, a.sx = logits.stride()
+    ty, tx = seg_tables(h, H, align_corners, logits.device), seg_tables(w, W, align_corners, logits.device)
+    a.y_i0, a.y_w1, a.y_lo, a.y_hi = _table_ptrs(ty, h, H)
+    a.x_i0, a.x_w1, a.x_lo, a.x_hi = _table_ptrs(tx, w, W)
+    return a, (ty, tx)
+
+
+def seg_ce(logits, labels, dz, loss, stats, workspace, ignore_index=255, align_corners=False, avg_non_ignore=False, loss_weight=1.0):
+    """Bilinear resize of logits f32 [B, C, h, w] (any strides) to the labels' size + cross entropy, nothing upsampled in
+    memory.  labels u8 [B, H, W]; dz f32 [B, C, h, w] (any non-overlapping strides) <- the UNSCALED gradient sum of weight *
+    (softmax - onehot); loss f32 [3] <- loss, loss_weight / N, loss_sum; stats i64 [3] <- n_valid, n_correct, n_bad;
+    workspace: >= seg_plan(...).ws_bytes bytes.  The gradient of `loss` with respect to the logits is dz * loss[1]."""
+    assert dz.dtype == torch.float32 and tuple(dz.shape) == tuple(logits.shape) and dz.is_cuda
+    assert loss.dtype == torch.float32 and loss.numel() >= 3 and loss.is_contiguous()
+    assert stats.dtype == torch.int64 and stats.numel() >= 3 and stats.is_contiguous()
+    a, keep = _seg_common(logits, labels, ignore_index, align_corners, avg_non_ignore=int(avg_non_ignore),
+                          loss_weight=float(loss_weight), dz=dz.data_ptr(), loss=loss.data_ptr(), stats=stats.data_ptr(),
+                          workspace=workspace.data_ptr(), workspace_bytes=workspace.numel() * workspace.element_size())
+    a.db, a.dc, a.dy, a.dx = dz.stride()
+    check(lib.memhip_seg_ce(C.byref(a), stream_ptr()), "seg_ce")
+
+
+def seg_confusion(logits, labels, confusion, ignore_index=255, align_corners=False):
+    """confusion i64 [C, C] (row = label, column = argmax of the resized logits, ties to the lowest class) += the counts of
+    this batch; ignored labels and labels >= C are skipped."""
+    C_ = logits.shape[1]
+    assert confusion.dtype == torch.int64 and tuple(confusion.shape) == (C_, C_) and confusion.is_contiguous() and confusion.is_cuda
+    a, keep = _seg_common(logits, labels, ignore_index, align_corners, confusion=confusion.data_ptr())
+    check(lib.memhip_seg_confusion(C.byref(a), stream_ptr()), "seg_confusion")
