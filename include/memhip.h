@@ -353,7 +353,8 @@ int memhip_mask_random_location(uint32_t* mt_state, int H, int W, int num_maskin
  *         work-skipping index or a row of a split half): masks do not depend on work skipping, stream splits or b0 / b1.
  *         A call that addresses a buffer whose row 0 is residual-stream row r0 passes row0 = r0.
  *   col   in [0, D), D a multiple of 8.
- *   site  block i's attention branch 2i, its MLP branch 2i + 1, pos_drop 2 * depth.
+ *   site  block i's attention branch 2i, its MLP branch 2i + 1, pos_drop 2 * depth.  Decode heads (Dropout2d: row = sample,
+ *         col = channel) take MEMHIP_DROPOUT_SITE_HEAD = 0x48454144 + the head's number, far above 2 * depth for any depth.
  * One Philox4x32-10 call per 8 columns: key = (key0, key1), counter = (row, col / 8, site, 0).  Column 8 * (col / 8) + j takes
  * the 16-bit half (j & 1) of output word (j >> 1), low half first; the element is KEPT iff that half >= thr = round(p * 65536),
  * and a kept value is multiplied by scale = 1 / (1 - p) (torch's scale).  The keep rate is 1 - thr / 65536 (within 7.6e-6
@@ -1182,6 +1183,110 @@ struct memhip_seg_plan {
 };
 typedef struct memhip_seg_plan memhip_seg_plan_t;
 int memhip_seg_plan(const memhip_seg_args_t* args, memhip_seg_plan_t* out);
+
+/* ------------------------------------------------------------------------
+ * FCN decode head (seg_head.hip, seg_head_plan.cpp; additive to ABI 10)
+ * replaces auxiliary_head = dict(type='FCNHead', in_index=2, channels=256, num_convs=1, concat_input=False, dropout_ratio=0.1,
+ *          norm_cfg=SyncBN, align_corners=False)   mem/semantic_segmentation/configs/_base_/models/upernet_beit.py:38-50
+ *                                                  mem/semantic_segmentation/configs/mem/upernet/mem_224_160k.py:64-77
+ *          mmseg 0.30 FCNHead.forward: output = self.convs(x) [ConvModule: Conv2d(3, padding 1, bias=False) -> SyncBN -> ReLU];
+ *          BaseDecodeHead.cls_seg: self.conv_seg(self.dropout(feat)) [Dropout2d -> Conv2d(channels, num_classes, 1)]
+ * ------------------------------------------------------------------------
+ * The 3x3 convolution, its data gradient and its weight gradient are memhip_conv2d_nhwc (MEMHIP_CONV_BF16) and
+ * memhip_conv_wgrad_nhwc on the activation format of the tokenizer: bf16 [B, h+2, w+2, C], a one-pixel zero border.  What
+ * is declared here is everything around them; every kernel streams, 16 bytes per lane, no float atomics (two calls give the
+ * same bits), nothing reads the environment.  B == 0 is MEMHIP_OK everywhere, nothing is read.
+ *
+ * Movers between the engine's fp32 maps and that format, through a padded 64 x 64 LDS tile like memhip_tokens_to_maps:
+ * memhip_map_to_nhwc_pad: map f32 [B, D, h, w] -> the INTERIOR of out bf16 [B, h+2, w+2, D] (round to nearest even; the
+ *   ring is never written: the caller zeroes the buffer once).  memhip_nhwc_pad_to_map: the inverse, bf16 -> f32 (exact).
+ * D % 64 == 0, any h, w >= 1 (ragged tiles are neither read nor written); the bf16 buffer 16-byte aligned; the map side
+ * moves 16 bytes per lane when h w % 4 == 0 and the map is 16-byte aligned, single floats otherwise. */
+int memhip_map_to_nhwc_pad(const float* map, int B, int D, int h, int w, void* out_bf16, memhip_stream_t stream);
+int memhip_nhwc_pad_to_map(const void* in_bf16, int B, int D, int h, int w, float* map, memhip_stream_t stream);
+/* Batch statistics of a bf16 activation of C channels (C % 64 == 0) over its R = B h w pixels: padded = 1: the
+ * one-pixel-border format [B, h+2, w+2, C], only interiors are read; 0: dense rows [R, C].  shift f32 [C] or NULL (zero).
+ *   out f32 [3, C] = count (R), sum (x - shift), sum (x - shift)^2 per channel
+ * Two stages: G = min(ceil(R / 32), MEMHIP_BN_GROUPS) workgroups per 64 channels, each thread a fixed-order chain over its
+ * rows r = 32 g + j, + 32 G, .., the 32 row lanes folded in LDS in order, one partial per workgroup stored plainly to
+ * `workspace` (memhip_bn_stats_workspace(C) bytes), and a finish kernel that adds the G partials in order.  The longest
+ * chain of fp32 roundings behind one output (the subtraction and the square included) is ceil(R / (32 G)) + 32 + G. */
+#define MEMHIP_BN_GROUPS 128
+size_t memhip_bn_stats_workspace(int C);
+int memhip_bn_stats_nhwc(const void* x_bf16, int padded, int B, int h, int w, int C, const float* shift, float* workspace,
+                         size_t workspace_bytes, float* out, memhip_stream_t stream);
+
+/* The site of memhip_dropout_t's mask contract for decode heads: Dropout2d drops a whole channel of a sample, element
+ * (site = MEMHIP_DROPOUT_SITE_HEAD + head number, row = sample b, col = channel c), so that
+ * memhip_dropout_mask(d, 0, B, C) reproduces the bits.  The trunk's sites are 0 .. 2 depth; this constant is above 2 depth
+ * for any depth (a depth is far below 2^30). */
+#define MEMHIP_DROPOUT_SITE_HEAD 0x48454144u
+
+/* The fused tail of the head over the convolution's output y (bf16 padded, C channels; C % 64 == 0, C <= 512) and the 1x1
+ * classifier wcls f32 [K, C], 2 <= K <= 32 (the segmentation loss's limit).  With xhat = (y - mean) rstd,
+ * u = gamma xhat + beta, keep = the Dropout2d bit of (sample, channel) and scale = 1 / (1 - p) (dropout NULL: 1, 1), all fp32:
+ *   memhip_bnhead_fwd:       z = relu(u) keep scale (not stored); logits[r, k] = bias[k] + sum_c z[c] wcls[k, c] as f32 pixel
+ *                            rows [R, ld], ld >= K: memhip_seg_args_t's layout with sb = h w ld, sc = 1, sy = w ld, sx = ld.
+ *                            The classifier weight is staged in LDS once per workgroup (K C 4 <= 64 KiB).
+ *   memhip_bnhead_bwd_sums:  from dlogit f32, logical [B, K, h, w] at element strides db, dk, dy, dx (memhip_seg_args_t.dz as
+ *                            it is), dz[c] = sum_k dlogit[k] wcls[k, c], g = dz keep scale (u > 0):
+ *                            sums f32 [2, C] = sum g (= dbeta), sum g xhat (= dgamma); dwcls f32 [K, C] = sum_pixels dlogit[k] z[c];
+ *                            dbias f32 [K] = sum_pixels dlogit[k].  Per-workgroup partials as plain stores into `workspace`
+ *                            (memhip_bnhead_plan_t.ws_bytes), folded in ascending order by a second launch; all four overwritten.
+ *   memhip_bnhead_bwd_apply: dy bf16 = gamma rstd (g - tot[0, c] inv_n - xhat tot[1, c] inv_n) into the INTERIOR of the padded
+ *                            format (the ring is never written), where the dgrad convolution reads it and
+ *                            memhip_conv_wgrad_nhwc takes it as small_padded = 1.  tot f32 [2, C] = the (all-reduced) sums and
+ *                            inv_n = 1 / (elements per channel over all ranks) are arguments, so that a SyncBN exchange sits
+ *                            between the two calls; tot NULL: eval statistics (running stats, a frozen BN), no correction terms.
+ * mean / rstd / gamma / beta f32 [C]; they, wcls, y and dy 16-byte aligned.  A field another call owns is ignored.
+ * (The structs are declared tag first, typedef second.) */
+struct memhip_bnhead_args {
+  const void* y;                     /* device bf16 [B, h+2, w+2, C] */
+  const float* mean; const float* rstd; const float* gamma; const float* beta;   /* device f32 [C] */
+  const float* wcls;                 /* device f32 [K, C] */
+  const float* bias;                 /* device f32 [K], or NULL (memhip_bnhead_fwd only) */
+  const memhip_dropout_t* dropout;   /* HOST struct read at the call, or NULL: nothing dropped */
+  int32_t B, C, K, h, w;
+  int32_t reserved0;
+  /* memhip_bnhead_fwd */
+  float* logits;                     /* device f32 [B h w, ld] */
+  int64_t ld;                        /* >= K (the plan query: 0 = not given) */
+  /* memhip_bnhead_bwd_sums and _apply */
+  const float* dlogit;               /* device f32, logical [B, K, h, w] at element strides db, dk, dy, dx */
+  int64_t db, dk, dy, dx;
+  /* memhip_bnhead_bwd_sums */
+  float* sums;                       /* device f32 [2, C] */
+  float* dwcls;                      /* device f32 [K, C] */
+  float* dbias;                      /* device f32 [K] */
+  void* workspace;                   /* device, workspace_bytes >= memhip_bnhead_plan_t.ws_bytes, 16-byte aligned */
+  size_t workspace_bytes;
+  /* memhip_bnhead_bwd_apply */
+  const float* tot;                  /* device f32 [2, C], or NULL: eval statistics */
+  float inv_n;                       /* > 0 when tot is given */
+  int32_t reserved1;
+  void* dy_out;                      /* device bf16 [B, h+2, w+2, C] */
+};
+typedef struct memhip_bnhead_args memhip_bnhead_args_t;
+int memhip_bnhead_fwd(const memhip_bnhead_args_t* args, memhip_stream_t stream);
+int memhip_bnhead_bwd_sums(const memhip_bnhead_args_t* args, memhip_stream_t stream);
+int memhip_bnhead_bwd_apply(const memhip_bnhead_args_t* args, memhip_stream_t stream);
+
+/* The launches of the three calls as data.  memhip_bnhead_plan validates the struct like the calls do (same codes and
+ * messages), except that pointers may be NULL (workspace_bytes is compared only when there is a workspace; ld only when it
+ * is not 0).  Host arithmetic only. */
+struct memhip_bnhead_plan {
+  int64_t R;                         /* B h w pixels (0: nothing to do) */
+  int32_t kp;                        /* classifier rows held per thread: K rounded up to a multiple of 8 */
+  int32_t block;                     /* threads of every launch */
+  int32_t fwd_grid, fwd_lds_bytes;   /* tiles of 32 pixels, strided over by at most 512 workgroups; the weight [kp, C] */
+  int32_t sums_grid_x, sums_grid_y, sums_lds_bytes;   /* x: pixel groups (tiles of 64 pixels, at most MEMHIP_BN_GROUPS), y: C / 64 */
+  int32_t apply_grid_x, apply_grid_y, apply_lds_bytes;   /* x: tiles of 32 pixels, y: C / 64 */
+  int32_t slot_floats;               /* workspace floats per pixel group: 2 C + K C + K */
+  int32_t fold_grid;                 /* workgroups of the fold launch */
+  uint64_t ws_bytes;
+};
+typedef struct memhip_bnhead_plan memhip_bnhead_plan_t;
+int memhip_bnhead_plan(const memhip_bnhead_args_t* args, memhip_bnhead_plan_t* out);
 
 #ifdef __cplusplus
 }

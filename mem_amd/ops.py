@@ -1226,3 +1226,148 @@ def seg_confusion(logits, labels, confusion, ignore_index=255, align_corners=Fal
     assert confusion.dtype == torch.int64 and tuple(confusion.shape) == (C_, C_) and confusion.is_contiguous() and confusion.is_cuda
     a, keep = _seg_common(logits, labels, ignore_index, align_corners, confusion=confusion.data_ptr())
     check(lib.memhip_seg_confusion(C.byref(a), stream_ptr()), "seg_confusion")
+
+
+# ---------------------------------------------------------------- FCN decode head (csrc/seg_head.hip, seg_head_plan.cpp)
+DROPOUT_SITE_HEAD = 0x48454144       # == MEMHIP_DROPOUT_SITE_HEAD: Dropout2d of decode head i is site DROPOUT_SITE_HEAD + i
+BN_GROUPS = 128                      # == MEMHIP_BN_GROUPS
+
+
+class BnHeadArgs(C.Structure):
+    """== memhip_bnhead_args_t."""
+    _fields_ = [(n, vp) for n in ("y", "mean", "rstd", "gamma", "beta", "wcls", "bias")] + [("dropout", C.POINTER(Dropout))] + \
+               [(n, i32) for n in ("B", "C", "K", "h", "w", "reserved0")] + \
+               [("logits", vp), ("ld", i64), ("dlogit", vp), ("db", i64), ("dk", i64), ("dy", i64), ("dx", i64),
+                ("sums", vp), ("dwcls", vp), ("dbias", vp), ("workspace", vp), ("workspace_bytes", sz),
+                ("tot", vp), ("inv_n", f32), ("reserved1", i32), ("dy_out", vp)]
+
+
+class BnHeadPlan(C.Structure):
+    """== memhip_bnhead_plan_t."""
+    _fields_ = [("R", i64)] + \
+               [(n, i32) for n in ("kp", "block", "fwd_grid", "fwd_lds_bytes", "sums_grid_x", "sums_grid_y", "sums_lds_bytes",
+                                   "apply_grid_x", "apply_grid_y", "apply_lds_bytes", "slot_floats", "fold_grid")] + \
+               [("ws_bytes", C.c_uint64)]
+
+
+declare({
+    "memhip_map_to_nhwc_pad": (i32, [vp, i32, i32, i32, i32, vp, vp]),
+    "memhip_nhwc_pad_to_map": (i32, [vp, i32, i32, i32, i32, vp, vp]),
+    "memhip_bn_stats_workspace": (sz, [i32]),
+    "memhip_bn_stats_nhwc": (i32, [vp, i32, i32, i32, i32, i32, vp, vp, sz, vp, vp]),
+    "memhip_bnhead_fwd": (i32, [C.POINTER(BnHeadArgs), vp]),
+    "memhip_bnhead_bwd_sums": (i32, [C.POINTER(BnHeadArgs), vp]),
+    "memhip_bnhead_bwd_apply": (i32, [C.POINTER(BnHeadArgs), vp]),
+    "memhip_bnhead_plan": (i32, [C.POINTER(BnHeadArgs), C.POINTER(BnHeadPlan)]),
+})
+
+
+def map_to_nhwc_pad(x, out):
+    """x f32 [B, D, h, w] contiguous -> the interior of out bf16 [B, h+2, w+2, D] (round to nearest even; the ring is not
+    written)."""
+    assert x.dtype == torch.float32 and x.dim() == 4 and x.is_contiguous()
+    B, D, h, w = x.shape
+    assert out.dtype == torch.bfloat16 and out.is_contiguous() and tuple(out.shape) == (B, h + 2, w + 2, D)
+    check(lib.memhip_map_to_nhwc_pad(ptr(x), B, D, h, w, ptr(out), stream_ptr()), "map_to_nhwc_pad")
+    return out
+
+
+def nhwc_pad_to_map(x_pad, out=None):
+    """The inverse: the interior of x_pad bf16 [B, h+2, w+2, D] -> f32 [B, D, h, w] (exact)."""
+    assert x_pad.dtype == torch.bfloat16 and x_pad.dim() == 4 and x_pad.is_contiguous()
+    B, h, w, D = x_pad.shape[0], x_pad.shape[1] - 2, x_pad.shape[2] - 2, x_pad.shape[3]
+    if out is None:
+        out = torch.empty((B, D, h, w), dtype=torch.float32, device=x_pad.device)
+    assert out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (B, D, h, w)
+    check(lib.memhip_nhwc_pad_to_map(ptr(x_pad), B, D, h, w, ptr(out), stream_ptr()), "nhwc_pad_to_map")
+    return out
+
+
+def bn_stats_workspace(C_, device):
+    return torch.empty(int(lib.memhip_bn_stats_workspace(C_)) // 4, dtype=torch.float32, device=device)
+
+
+def bn_stats_chain(R):
+    """The longest chain of fp32 roundings behind one output of bn_stats_nhwc over R pixels (include/memhip.h)."""
+    G = min(-(-R // 32), BN_GROUPS)
+    return -(-R // (32 * G)) + 32 + G
+
+
+def bn_stats_nhwc(x, B, h, w, C_, ws, shift=None, padded=True, out=None):
+    """x bf16 padded [B, h+2, w+2, C] (interiors only) or dense [B h w, C] -> out f32 [3, C]: count, sum (x - shift),
+    sum (x - shift)^2 per channel; shift f32 [C] or None (zero)."""
+    assert x.dtype == torch.bfloat16 and x.is_contiguous()
+    assert x.numel() >= (B * (h + 2) * (w + 2) * C_ if padded else B * h * w * C_)
+    assert shift is None or (shift.dtype == torch.float32 and shift.numel() == C_ and shift.is_contiguous())
+    if out is None:
+        out = torch.empty((3, C_), dtype=torch.float32, device=x.device)
+    assert out.dtype == torch.float32 and out.is_contiguous() and out.numel() == 3 * C_
+    check(lib.memhip_bn_stats_nhwc(ptr(x), int(padded), B, h, w, C_, ptr(shift), ptr(ws), ws.numel() * 4, ptr(out), stream_ptr()),
+          "bn_stats_nhwc")
+    return out
+
+
+def bnhead_args(B, C_, K, h, w, dropout=None, **fields):
+    """The memhip_bnhead_args_t of bnhead_fwd / _bwd_sums / _bwd_apply / bnhead_plan; pointer fields are addresses or None,
+    dropout a Dropout struct or None."""
+    a = BnHeadArgs(B=B, C=C_, K=K, h=h, w=w)
+    if dropout is not None:
+        a.dropout = C.pointer(dropout)
+    for k, v in fields.items():
+        setattr(a, k, v)
+    return a
+
+
+def bnhead_plan(B, C_, K, h, w, **fields):
+    """The BnHeadPlan of the three calls at these shapes: grids, LDS bytes, workspace bytes.  Validates like the calls; no
+    device."""
+    plan = BnHeadPlan()
+    check(lib.memhip_bnhead_plan(C.byref(bnhead_args(B, C_, K, h, w, **fields)), C.byref(plan)), "bnhead_plan")
+    return plan
+
+
+def _bnhead_common(y, B, C_, K, h, w, mean, rstd, gamma, beta, wcls, dropout):
+    assert y.dtype == torch.bfloat16 and y.is_contiguous() and y.numel() >= B * (h + 2) * (w + 2) * C_
+    assert all(v.dtype == torch.float32 and v.numel() == C_ and v.is_contiguous() for v in (mean, rstd, gamma, beta))
+    assert wcls.dtype == torch.float32 and wcls.is_contiguous() and wcls.numel() == K * C_
+    return bnhead_args(B, C_, K, h, w, dropout, y=y.data_ptr(), mean=mean.data_ptr(), rstd=rstd.data_ptr(), gamma=gamma.data_ptr(),
+                       beta=beta.data_ptr(), wcls=wcls.data_ptr())
+
+
+def _dlogit_fields(a, dlogit, B, K, h, w):
+    assert dlogit.dtype == torch.float32 and tuple(dlogit.shape) == (B, K, h, w) and dlogit.is_cuda
+    a.dlogit = dlogit.data_ptr()
+    a.db, a.dk, a.dy, a.dx = dlogit.stride()
+
+
+def bnhead_fwd(y, B, C_, K, h, w, mean, rstd, gamma, beta, wcls, bias, logits, dropout=None):
+    """logits f32 [B h w, ld] = bias + relu(gamma (y - mean) rstd + beta) keep scale @ wcls^T over y bf16 [B, h+2, w+2, C]."""
+    a = _bnhead_common(y, B, C_, K, h, w, mean, rstd, gamma, beta, wcls, dropout)
+    assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.stride(1) == 1 and logits.shape[0] >= B * h * w
+    assert bias is None or (bias.dtype == torch.float32 and bias.numel() == K and bias.is_contiguous())
+    a.bias, a.logits, a.ld = _p(bias), logits.data_ptr(), logits.stride(0)
+    check(lib.memhip_bnhead_fwd(C.byref(a), stream_ptr()), "bnhead_fwd")
+    return logits
+
+
+def bnhead_bwd_sums(dlogit, y, B, C_, K, h, w, mean, rstd, gamma, beta, wcls, sums, dwcls, dbias, workspace, dropout=None):
+    """sums f32 [2, C] = sum g, sum g xhat; dwcls f32 [K, C]; dbias f32 [K] from dlogit f32 [B, K, h, w] (any strides)."""
+    a = _bnhead_common(y, B, C_, K, h, w, mean, rstd, gamma, beta, wcls, dropout)
+    _dlogit_fields(a, dlogit, B, K, h, w)
+    for v, n in ((sums, 2 * C_), (dwcls, K * C_), (dbias, K)):
+        assert v.dtype == torch.float32 and v.is_contiguous() and v.numel() == n
+    a.sums, a.dwcls, a.dbias = sums.data_ptr(), dwcls.data_ptr(), dbias.data_ptr()
+    a.workspace, a.workspace_bytes = workspace.data_ptr(), workspace.numel() * workspace.element_size()
+    check(lib.memhip_bnhead_bwd_sums(C.byref(a), stream_ptr()), "bnhead_bwd_sums")
+
+
+def bnhead_bwd_apply(dlogit, y, B, C_, K, h, w, mean, rstd, gamma, beta, wcls, tot, inv_n, dy_out, dropout=None):
+    """The interior of dy_out bf16 [B, h+2, w+2, C] = gamma rstd (g - tot[0] inv_n - xhat tot[1] inv_n); tot None: eval
+    statistics, no correction terms."""
+    a = _bnhead_common(y, B, C_, K, h, w, mean, rstd, gamma, beta, wcls, dropout)
+    _dlogit_fields(a, dlogit, B, K, h, w)
+    assert dy_out.dtype == torch.bfloat16 and dy_out.is_contiguous() and dy_out.numel() >= B * (h + 2) * (w + 2) * C_
+    assert tot is None or (tot.dtype == torch.float32 and tot.is_contiguous() and tot.numel() == 2 * C_)
+    a.tot, a.inv_n, a.dy_out = _p(tot), float(inv_n), dy_out.data_ptr()
+    check(lib.memhip_bnhead_bwd_apply(C.byref(a), stream_ptr()), "bnhead_bwd_apply")
+    return dy_out

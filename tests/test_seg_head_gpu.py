@@ -1,0 +1,539 @@
+"""-m gpu: the FCN decode head on the device -- the movers bit-exact against the torch expression that specifies them, the
+batch statistics against float64 under the bound their summation structure gives, and FCNHead(impl="hip") forward and backward
+against the float64 oracle of tests/test_seg_head_cpu.py fed the same bf16-rounded map, the same bf16-rounded convolution
+weight and the same Dropout2d mask, under the project's yardstick:
+
+    error(hip) <= 2 x error(torch arm under bf16 autocast on the GPU, same inputs) + 2^-20 x max |float64 result|
+
+(max-abs errors; both sides round at bf16 in different places and orders, hence the factor; the yardstick's error can be
+exactly zero, hence the floor).  Measured ratios per shape: DESIGN.md section 2c, "FCN decode head"."""
+import functools
+
+import pytest
+import torch
+import torch.nn.functional as F
+
+from test_seg_head_cpu import CASES, oracle_head
+
+pytestmark = pytest.mark.gpu
+
+FLOOR = 2.0 ** -20
+U = 2.0 ** -24            # unit roundoff of fp32
+GUARD = 256
+KEY = (0x1234, 0x9e37)
+NAMES = ["x", "convs.0.conv.weight", "convs.0.bn.weight", "convs.0.bn.bias", "conv_seg.weight", "conv_seg.bias"]
+
+
+def held(name, got, yard, ref, figures):
+    """error(got) <= 2 error(yard) + 2^-20 max |ref|; the figures are appended to `figures`"""
+    got, yard, ref = got.detach().double().cpu(), yard.detach().double().cpu(), ref.detach().double().cpu()
+    e_got, e_yard = float((got - ref).abs().max()), float((yard - ref).abs().max())
+    bound = 2.0 * e_yard + FLOOR * float(ref.abs().max())
+    figures.append((name, e_got, e_yard, bound))
+    return e_got <= bound
+
+
+def report(tag, figures):
+    for name, e_got, e_yard, bound in figures:
+        print("%s %-22s hip %.3e  torch bf16 %.3e  bound %.3e  ratio %.3f" % (tag, name, e_got, e_yard, bound, e_got / max(e_yard, 1e-300)))
+
+
+def _guarded(n, dtype, fill=float("nan")):
+    big = torch.full((n + 2 * GUARD,), fill, device="cuda", dtype=dtype)
+    return big, big[GUARD:GUARD + n]
+
+
+def _guards_intact(big):
+    return bool(torch.isnan(big[:GUARD]).all() and torch.isnan(big[-GUARD:]).all())
+
+
+# ---------------------------------------------------------------------------------------------- movers
+@pytest.mark.parametrize("B,D,h,w", [(2, 64, 5, 7), (3, 128, 6, 10), (1, 768, 4, 6), (2, 64, 1, 1), (1, 64, 9, 8), (2, 64, 96, 97)])
+def test_movers_are_bit_exact_and_leave_the_ring(B, D, h, w):
+    from mem_amd import ops
+    gen = torch.Generator().manual_seed(B * 1000 + h * 10 + w)
+    x = (torch.randn(B, D, h, w, generator=gen) * 3.0).cuda()
+    big, flat = _guarded(B * (h + 2) * (w + 2) * D, torch.bfloat16)
+    flat.fill_(-7.0)                                                      # the sentinel of the ring
+    out = ops.map_to_nhwc_pad(x, flat.view(B, h + 2, w + 2, D))
+    want = x.permute(0, 2, 3, 1).to(torch.bfloat16)
+    ring = torch.ones(B, h + 2, w + 2, dtype=torch.bool, device="cuda")
+    ring[:, 1:-1, 1:-1] = False
+    print("map_to_nhwc_pad", (B, D, h, w), "interior equal:", torch.equal(out[:, 1:-1, 1:-1], want), "ring untouched:",
+          bool((out[ring] == -7.0).all()))
+    assert torch.equal(out[:, 1:-1, 1:-1], want)
+    assert bool((out[ring] == -7.0).all()) and _guards_intact(big)
+    bigm, flatm = _guarded(B * D * h * w, torch.float32)
+    back = ops.nhwc_pad_to_map(out, out=flatm.view(B, D, h, w))
+    assert torch.equal(back, want.permute(0, 3, 1, 2).float()) and _guards_intact(bigm)
+    if h * w > 1:                                                         # a map that is not 16-byte aligned: the single-float path
+        bigo, flato = _guarded(B * D * h * w + 1, torch.float32)
+        xo = flato[1:].view(B, D, h, w).copy_(x)
+        out2 = ops.map_to_nhwc_pad(xo, torch.full_like(out, -7.0))
+        assert torch.equal(out2[:, 1:-1, 1:-1], want) and bool((out2[ring] == -7.0).all())
+        flato.fill_(float("nan"))
+        assert torch.equal(ops.nhwc_pad_to_map(out, out=flato[1:].view(B, D, h, w)), back) and _guards_intact(bigo)
+        assert bool(torch.isnan(flato[0]))
+
+
+# ---------------------------------------------------------------------------------------------- batch statistics
+@pytest.mark.parametrize("B,C,h,w", [(2, 64, 5, 7), (3, 128, 6, 10), (1, 256, 4, 6), (2, 64, 48, 49)])
+@pytest.mark.parametrize("padded", [True, False])
+@pytest.mark.parametrize("shifted", [False, True])
+def test_bn_stats_against_float64(B, C, h, w, padded, shifted):
+    """The bound is the summation structure's: an output is behind at most L = bn_stats_chain(R) fp32 roundings (the
+    subtraction and the square included), so |error| <= L 2^-24 sum |x - shift| (first moment) and L 2^-24 sum (x - shift)^2."""
+    from mem_amd import ops
+    gen = torch.Generator().manual_seed(C + h)
+    R = B * h * w
+    vals = (torch.randn(B, h, w, C, generator=gen) * 2.0 + torch.randn(C, generator=gen)).to(torch.bfloat16).cuda()
+    if padded:
+        buf = torch.full((B, h + 2, w + 2, C), float("nan"), dtype=torch.bfloat16, device="cuda")       # a ring that must not be read
+        buf[:, 1:-1, 1:-1] = vals
+    else:
+        buf = vals.reshape(R, C).contiguous()
+    shift = (torch.randn(C, generator=gen) * 0.5).cuda() if shifted else None
+    ws = ops.bn_stats_workspace(C, "cuda")
+    big, flat = _guarded(3 * C, torch.float32)
+    out = ops.bn_stats_nhwc(buf, B, h, w, C, ws, shift, padded, out=flat.view(3, C))
+    first = out.clone()
+    d = vals.double().reshape(R, C) - (shift.double() if shifted else 0.0)
+    L = ops.bn_stats_chain(R)
+    b1, b2 = L * U * d.abs().sum(0), L * U * (d * d).sum(0)
+    e1, e2 = (out[1].double() - d.sum(0)).abs(), (out[2].double() - (d * d).sum(0)).abs()
+    print("bn_stats", (B, C, h, w), "padded" if padded else "dense", "shift" if shifted else "no shift", "chain", L,
+          "worst error / bound: sum %.3f, squares %.3f" % (float((e1 / b1).max()), float((e2 / b2).max())))
+    assert bool((out[0] == float(R)).all()) and _guards_intact(big)
+    assert bool((e1 <= b1).all()) and bool((e2 <= b2).all())
+    ws.fill_(float("nan"))
+    again = ops.bn_stats_nhwc(buf, B, h, w, C, ws, shift, padded)
+    assert torch.equal(again, first)                                      # two calls, the same bits
+
+
+# ---------------------------------------------------------------------------------------------- the fused tail on a given y
+@pytest.mark.parametrize("case", ["S1", "S2", "BIG"])
+@pytest.mark.parametrize("layout", ["rows", "nchw"])
+def test_fused_tail_against_float64_on_the_same_y(case, layout):
+    """bnhead_fwd / _bwd_sums / _bwd_apply fed one stored bf16 y, against float64 on those same values: no rounding point is
+    left between the two but fp32 arithmetic, so an output is held to (its longest chain of fp32 roundings) x 2^-24 x the sum
+    of the magnitudes of its terms, the chains read off the kernels: a logit C / 8 products per lane, the butterfly and the bias;
+    g its K products and the normalisation; a channel sum 2 pixels per tile of its workgroup, the 32 row lanes and the G
+    partials; dWcls 64 pixels per tile and the G partials -- each with 12 more for the roundings inside xhat, u, z and g.  dy is
+    held to bf16 round-to-nearest (2^-8 relative at most).  An element whose u is within fp32 rounding of zero may take either gate: its whole |dz| is added
+    to the bounds it enters.  BIG has more tiles than workgroups in all three kernels."""
+    from mem_amd import ops
+    B, Cin, C, K, h, w = CASES[case]
+    R = B * h * w
+    gen = torch.Generator().manual_seed(77 + R)
+    y = torch.zeros(B, h + 2, w + 2, C, dtype=torch.bfloat16)
+    y[:, 1:-1, 1:-1] = (torch.randn(B, h, w, C, generator=gen) * 1.5 + 0.3).to(torch.bfloat16)
+    mean, rstd = 0.3 + 0.2 * torch.randn(C, generator=gen), 0.5 + torch.rand(C, generator=gen)
+    gamma, beta = 1.0 + 0.3 * torch.randn(C, generator=gen), 0.3 * torch.randn(C, generator=gen)
+    wcls, bias = torch.randn(K, C, generator=gen) * C ** -0.5, 0.1 * torch.randn(K, generator=gen)
+    dl = torch.randn(B, K, h, w, generator=gen)
+    dl_dev = dl.cuda() if layout == "nchw" else dl.permute(0, 2, 3, 1).contiguous().cuda().permute(0, 3, 1, 2)
+    tot = torch.randn(2, C, generator=gen)
+    p = 0.25
+    d = ops.dropout_params(KEY[0], KEY[1], ops.DROPOUT_SITE_HEAD, p)
+    keep = _mask(B, C, p).cpu().double() / (1.0 - p)
+    dev = [t.cuda() for t in (mean, rstd, gamma, beta, wcls)]
+    yd = y.cuda()
+    # float64 on the same values
+    y64 = y[:, 1:-1, 1:-1].double()                                                   # [B, h, w, C]
+    xh = (y64 - mean.double()) * rstd.double()
+    u = gamma.double() * xh + beta.double()
+    km = keep[:, None, None, :]
+    z = u.clamp(min=0.0) * km
+    dl64 = dl.double().permute(0, 2, 3, 1)                                            # [B, h, w, K]
+    dz = dl64 @ wcls.double()
+    g = dz * km * (u > 0)
+    amb = (u.abs() < 2.0 ** -20 * ((gamma.double() * xh).abs() + beta.double().abs())).double()        # either gate
+    slack = amb * dz.abs() * km
+    want = {"logits": z @ wcls.double().t() + bias.double(), "sums": torch.stack([g.sum((0, 1, 2)), (g * xh).sum((0, 1, 2))]),
+            "dwcls": torch.einsum("bhwk,bhwc->kc", dl64, z), "dbias": dl64.sum((0, 1, 2)),
+            "dy": gamma.double() * rstd.double() * (g - tot[0].double() / R - xh * tot[1].double() / R)}
+    mags = {"logits": z.abs() @ wcls.double().abs().t() + bias.double().abs(),
+            "sums": torch.stack([g.abs().sum((0, 1, 2)), (g * xh).abs().sum((0, 1, 2))]),
+            "slack": torch.stack([slack.sum((0, 1, 2)), (slack * xh.abs()).sum((0, 1, 2))]),
+            "dwcls": torch.einsum("bhwk,bhwc->kc", dl64.abs(), z.abs()), "dbias": dl64.abs().sum((0, 1, 2))}
+    # the kernels
+    big, flat = _guarded(R * K, torch.float32)
+    rows = ops.bnhead_fwd(yd, B, C, K, h, w, *dev, bias.cuda(), flat.view(R, K), dropout=d)
+    plan = ops.bnhead_plan(B, C, K, h, w)
+    sums, dwcls, dbias = (torch.full(s, float("nan"), device="cuda") for s in ((2, C), (K, C), (K,)))
+    ws = torch.full((int(plan.ws_bytes) // 4,), float("nan"), device="cuda")
+    ops.bnhead_bwd_sums(dl_dev, yd, B, C, K, h, w, *dev, sums, dwcls, dbias, ws, dropout=d)
+    dy = torch.full((B, h + 2, w + 2, C), -7.0, dtype=torch.bfloat16, device="cuda")
+    ops.bnhead_bwd_apply(dl_dev, yd, B, C, K, h, w, *dev, tot.cuda(), 1.0 / R, dy, dropout=d)
+    got = {"logits": rows.view(B, h, w, K), "sums": sums, "dwcls": dwcls, "dbias": dbias}
+    G = plan.sums_grid_x
+    per = -(-(-(-R // 64)) // G)                                                      # tiles of 64 pixels per workgroup of the sums
+    depth = {"logits": C // 8 + 4 + 12, "sums": 2 * per + 32 + G + K + 12, "dwcls": 64 * per + G + 12, "dbias": 64 * per + G}
+    print("%s %s: %d ambiguous gates; chains %s" % (case, layout, int(amb.sum()), depth))
+    assert _guards_intact(big)
+    for name, t in got.items():
+        err = (t.double().cpu() - want[name]).abs()
+        worst = float((err / (depth[name] * U * mags[name] + (mags["slack"] if name == "sums" else 0.0) + 1e-30)).max())
+        print("%s %s %-7s worst error / bound %.4f (largest error %.3e)" % (case, layout, name, worst, float(err.max())))
+        assert worst <= 1.0, name
+    ring = torch.ones(B, h + 2, w + 2, dtype=torch.bool)
+    ring[:, 1:-1, 1:-1] = False
+    dyc = dy.cpu()
+    e = (dyc[:, 1:-1, 1:-1].double() - want["dy"]).abs()
+    scale = (gamma.double() * rstd.double()).abs()
+    step = 2.0 ** -8 * want["dy"].abs() + (K + 12) * U * scale * (dl64.abs() @ wcls.double().abs() * km + (tot[0].abs() + xh.abs() * tot[1].abs()) / R) + scale * slack
+    print("%s %s dy      worst error / (2^-8 relative + fp32 terms) %.4f" % (case, layout, float((e / (step + 1e-30)).max())))
+    assert bool((e <= step).all()) and bool((dyc[ring] == -7.0).all())
+    # eval statistics: no correction terms
+    ops.bnhead_bwd_apply(dl_dev, yd, B, C, K, h, w, *dev, None, 1.0, dy, dropout=d)
+    want0 = gamma.double() * rstd.double() * g
+    e0 = (dy.cpu()[:, 1:-1, 1:-1].double() - want0).abs()
+    assert bool((e0 <= 2.0 ** -8 * want0.abs() + (K + 12) * U * scale * (dl64.abs() @ wcls.double().abs()) * km + scale * slack).all())
+
+
+# ---------------------------------------------------------------------------------------------- the head against the oracle
+def _state(case, seed=0):
+    """x f32 of bf16 values, a state dict with a bf16-valued convolution weight and non-trivial running statistics"""
+    B, Cin, C, K, h, w = CASES[case]
+    gen = torch.Generator().manual_seed(1000 + seed + sum(map(ord, case)))
+    x = (torch.randn(B, Cin, h, w, generator=gen) * 1.5).to(torch.bfloat16).float()
+    sd = {"convs.0.conv.weight": (torch.randn(C, Cin, 3, 3, generator=gen) * (2.0 / (9 * Cin)) ** 0.5).to(torch.bfloat16).float(),
+          "convs.0.bn.weight": 1.0 + 0.3 * torch.randn(C, generator=gen), "convs.0.bn.bias": 0.3 * torch.randn(C, generator=gen),
+          "convs.0.bn.running_mean": 0.2 * torch.randn(C, generator=gen), "convs.0.bn.running_var": 0.5 + torch.rand(C, generator=gen),
+          "convs.0.bn.num_batches_tracked": torch.tensor(3),
+          "conv_seg.weight": torch.randn(K, C, 1, 1, generator=gen) * (1.0 / C) ** 0.5, "conv_seg.bias": 0.1 * torch.randn(K, generator=gen)}
+    gout = torch.randn(B, K, h, w, generator=gen)
+    return x, sd, gout
+
+
+def _head(case, impl, sd, p, train=True):
+    from mem_amd.seg_heads import FCNHead
+    B, Cin, C, K, h, w = CASES[case]
+    head = FCNHead(in_channels=Cin, channels=C, num_classes=K, in_index=0, dropout_ratio=p, impl=impl)
+    head.load_state_dict(sd, strict=True)
+    head.drop_key = KEY
+    return head.cuda().train(train)
+
+
+def _mask(B, C, p):
+    """the keep bits the mask contract gives (site of head 0, row = sample, column = channel), u8 [B, C]"""
+    from mem_amd import ops
+    out = torch.empty((B, C), dtype=torch.uint8, device="cuda")
+    ops.dropout_mask(ops.dropout_params(KEY[0], KEY[1], ops.DROPOUT_SITE_HEAD, p), 0, B, C, out)
+    return out
+
+
+def _run(head, x, gout, autocast=False):
+    """logits and the gradients NAMES of one forward + backward"""
+    head.zero_grad(set_to_none=True)
+    xg = x.cuda().requires_grad_()
+    with torch.autocast("cuda", dtype=torch.bfloat16, enabled=autocast):
+        out = head((xg,))
+    out.float().backward(gout.cuda())
+    grads = [xg.grad] + [dict(head.named_parameters())[n].grad for n in NAMES[1:]]
+    return out.detach().float().clone(), [g.detach().float().clone() for g in grads]
+
+
+@functools.lru_cache(maxsize=None)
+def _reference(case, p, train=True):
+    """float64 on the CPU, once per case: logits and gradients, with the mask of the contract"""
+    B, Cin, C, K, h, w = CASES[case]
+    x, sd, gout = _state(case)
+    keep = _mask(B, C, p).cpu() if (train and p > 0.0) else None
+    leaves = [x.double().requires_grad_()] + [sd[n].double().requires_grad_() for n in NAMES[1:]]
+    running = None if train else (sd["convs.0.bn.running_mean"].double(), sd["convs.0.bn.running_var"].double())
+    out = oracle_head(leaves[0], leaves[1], leaves[2], leaves[3], leaves[4].reshape(K, C), leaves[5], keep, p if keep is not None else 0.0,
+                      1e-5, running)
+    grads = torch.autograd.grad(out, leaves, gout.double())
+    return out.detach(), [g.detach() for g in grads], keep
+
+
+def _against_oracle(case, p, train=True):
+    x, sd, gout = _state(case)
+    ref_out, ref_grads, keep = _reference(case, p, train)
+    hip_out, hip_grads = _run(_head(case, "hip", sd, p, train), x, gout)
+    yard = _head(case, "torch", sd, p, train)
+    yard.keep_mask = None if keep is None else keep.cuda()
+    yard_out, yard_grads = _run(yard, x, gout, autocast=True)
+    figures = []
+    ok = [held("logits", hip_out, yard_out, ref_out, figures)]
+    ok += [held("d " + n, a, b, c.reshape(a.shape), figures) for n, a, b, c in zip(NAMES, hip_grads, yard_grads, ref_grads)]
+    report("%s p=%.1f %s" % (case, p, "train" if train else "eval"), figures)
+    return ok, figures, (hip_out, ref_out, keep)
+
+
+@pytest.mark.parametrize("case", ["S1", "S2", "S3", "S1K2", "S1K32", "MAX"])
+def test_forward_and_backward_within_twice_torchs_own_error(case):
+    """(BIG is not held to this yardstick: at 96 x 97 torch's bf16 convolution does not round its output to nearest -- half of
+    its 1.19 M outputs differ from bf16(float64 convolution), 137 of the hip arm's do -- so the ReLU gates that flip against
+    float64 are independent draws in the two arms and the ratio of their errors, 0.2 - 1.7 when measured, says nothing about the
+    code.  Its many-tile paths are held to float64 directly in test_fused_tail_against_float64_on_the_same_y.)"""
+    ok, figures, _ = _against_oracle(case, 0.1)
+    assert all(ok), [f for f, o in zip(figures, ok) if not o]
+
+
+def test_dropout2d_follows_the_mask_contract():
+    """p = 0.5: the logits agree with the oracle fed memhip_dropout_mask(d, 0, B, C)'s bits -- one wrong channel of one sample
+    moves every pixel of that sample; p = 0 and eval(): nothing is dropped."""
+    case = "S2"
+    B, Cin, C, K, h, w = CASES[case]
+    ok, figures, (hip_out, ref_out, keep) = _against_oracle(case, 0.5)
+    kept = float(keep.float().mean())
+    print("keep rate %.3f over %d (sample, channel) pairs" % (kept, B * C))
+    assert all(ok), [f for f, o in zip(figures, ok) if not o]
+    assert 0.35 < kept < 0.65 and not bool((keep[0] == keep[1]).all())
+    # the comparison sees a single wrong bit
+    x, sd, gout = _state(case)
+    wrong = keep.clone()
+    wrong[1, 5] ^= 1
+    leaves = [x.double()] + [sd[n].double() for n in NAMES[1:]]
+    off = oracle_head(leaves[0], leaves[1], leaves[2], leaves[3], leaves[4].reshape(K, C), leaves[5], wrong, 0.5)
+    bound = figures[0][3]
+    moved = (off - ref_out).abs().amax(dim=(1, 2, 3))
+    print("one flipped bit moves sample 1 by %.3e (bound of the comparison %.3e), the others by %.3e" % (float(moved[1]), bound, float(moved[[0, 2]].max())))
+    assert float(moved[1]) > 4 * bound and float(moved[[0, 2]].max()) == 0.0
+    # nothing dropped at p = 0 and in eval()
+    for p, train in ((0.0, True), (0.5, False)):
+        ok, figures, (_, _, keep) = _against_oracle(case, p, train)
+        assert keep is None and all(ok), [f for f, o in zip(figures, ok) if not o]
+
+
+def test_two_calls_give_the_same_bits():
+    case = "S2"
+    x, sd, gout = _state(case)
+    head = _head(case, "hip", sd, 0.1)
+    a_out, a_grads = _run(head, x, gout)
+    b_out, b_grads = _run(head, x, gout)
+    assert torch.equal(a_out, b_out) and all(torch.equal(a, b) for a, b in zip(a_grads, b_grads))
+    assert all(bool(torch.isfinite(g).all()) for g in a_grads)
+
+
+def test_eval_mode_uses_the_running_statistics_and_touches_nothing_else():
+    case = "S1"
+    x, sd, gout = _state(case)
+    ok, figures, _ = _against_oracle(case, 0.1, train=False)
+    assert all(ok), [f for f, o in zip(figures, ok) if not o]
+    head = _head(case, "hip", sd, 0.1, train=False)
+    with torch.no_grad():
+        out = head((x.cuda(),))
+    ref_out = _reference(case, 0.1, False)[0]
+    print("eval, no_grad: max error %.3e" % float((out.double().cpu() - ref_out).abs().max()))
+    assert not out.requires_grad and float((out.double().cpu() - ref_out).abs().max()) <= 2.0 ** -7 * float(ref_out.abs().max())
+    bn = head.convs[0].bn
+    assert torch.equal(bn.running_mean.cpu(), sd["convs.0.bn.running_mean"]) and torch.equal(bn.running_var.cpu(), sd["convs.0.bn.running_var"])
+    assert int(bn.num_batches_tracked) == 3
+    used = sorted(k[0] for k in head._bufs)
+    print("buffers of an eval forward:", used)
+    assert used == ["logits", "xp", "y"]                                  # no statistics, no backward buffers
+    head.train()
+    head((x.cuda().requires_grad_(),))
+    assert int(bn.num_batches_tracked) == 4 and not torch.equal(bn.running_mean.cpu(), sd["convs.0.bn.running_mean"])
+
+
+def test_running_statistics_match_batchnorm2d():
+    """two training forwards: the running statistics of the hip arm against nn.BatchNorm2d on the float64 convolution output
+    (fp32 statistics of bf16-rounded values: 2^-9 relative on every value at most, so 2^-8 of the spread is ample)"""
+    case = "S2"
+    B, Cin, C, K, h, w = CASES[case]
+    x, sd, gout = _state(case)
+    head = _head(case, "hip", sd, 0.1)
+    ref = torch.nn.BatchNorm2d(C).double().train()
+    ref.load_state_dict({k[len("convs.0.bn."):]: v.double() if v.dtype.is_floating_point else v for k, v in sd.items() if ".bn." in k})
+    for i in range(2):
+        xi = (x * (1.0 + i)).to(torch.bfloat16).float()
+        with torch.no_grad():
+            head((xi.cuda(),))
+        ref(F.conv2d(xi.double(), sd["convs.0.conv.weight"].double(), None, padding=1))
+    bn = head.convs[0].bn
+    em = float((bn.running_mean.double().cpu() - ref.running_mean).abs().max())
+    ev = float((bn.running_var.double().cpu() - ref.running_var).abs().max())
+    print("running mean error %.3e, running var error %.3e" % (em, ev))
+    assert int(bn.num_batches_tracked) == 5 == int(ref.num_batches_tracked)
+    assert em <= 2.0 ** -8 * float(ref.running_var.sqrt().max()) and ev <= 2.0 ** -8 * float(ref.running_var.max())
+
+
+# ---------------------------------------------------------------------------------------------- with the loss
+def _labels(gen, B, K, H, W):
+    lab = torch.randint(0, K, (B, H, W), generator=gen)
+    lab[torch.rand((B, H, W), generator=gen) < 0.2] = 255
+    return lab.to(torch.uint8)
+
+
+@pytest.mark.parametrize("case", ["S1", "S3"])
+def test_forward_train_with_the_loss(case, monkeypatch):
+    from mem_amd import ops
+    B, Cin, C, K, h, w = CASES[case]
+    H, W = 16 * h, 16 * w
+    x, sd, _ = _state(case)
+    lab = _labels(torch.Generator().manual_seed(5), B, K, H, W)
+    p, lw = 0.1, 0.4
+    keep = _mask(B, C, p).cpu()
+
+    def expression(head_out, lab_long):
+        up = F.interpolate(head_out, size=(H, W), mode="bilinear", align_corners=False)
+        return lw * F.cross_entropy(up, lab_long, ignore_index=255, reduction="sum") / (B * H * W), up
+
+    # float64
+    x64 = x.double().requires_grad_()
+    leaves = [sd[n].double() for n in NAMES[1:]]
+    loss64, _ = expression(oracle_head(x64, leaves[0], leaves[1], leaves[2], leaves[3].reshape(K, C), leaves[4], keep, p), lab.long())
+    loss64.backward()
+    # the yardstick
+    yard = _head(case, "torch", sd, p)
+    yard.keep_mask = keep.cuda()
+    xy = x.cuda().requires_grad_()
+    with torch.autocast("cuda", dtype=torch.bfloat16):
+        loss_y, _ = expression(yard((xy,)), lab.cuda().long())
+    loss_y.float().backward()
+    # the hip arm, watching what its backward is handed
+    head = _head(case, "hip", sd, p)
+    seen = {}
+    real = ops.bnhead_bwd_sums
+
+    def spy(dlogit, *a, **kw):
+        seen["ops"] = (dlogit.data_ptr(), dlogit.stride())
+        return real(dlogit, *a, **kw)
+
+    monkeypatch.setattr(ops, "bnhead_bwd_sums", spy)
+    xh = x.cuda().requires_grad_()
+    feats = (xh,)
+    logits = head(feats)
+    logits.register_hook(lambda g: seen.__setitem__("autograd", (g.data_ptr(), g.stride())))
+    res = {"loss_seg": head.loss_decode(logits, lab.cuda()), "acc_seg": head.loss_decode.acc_seg()}
+    res["loss_seg"].backward()
+    figures = []
+    ok = [held("loss_seg", res["loss_seg"], loss_y, loss64, figures), held("d map", xh.grad, xy.grad, x64.grad, figures)]
+    report("%s with the loss" % case, figures)
+    assert all(ok), [f for f, o in zip(figures, ok) if not o]
+    print("dlogit as autograd delivered it", seen["autograd"], "as the kernel took it", seen["ops"])
+    live = [i for i, n in enumerate(logits.shape) if n > 1]                # (the stride of a dimension of size 1 says nothing)
+    assert seen["ops"][0] == seen["autograd"][0]                          # pixel rows as the loss left them, no copy
+    assert [seen["ops"][1][i] for i in live] == [seen["autograd"][1][i] for i in live] == [(h * w * K, 1, w * K, K)[i] for i in live]
+    # forward_train is the same call; acc_seg to the count, from the head's own logits
+    again = _head(case, "hip", sd, p)
+    out = again.forward_train((x.cuda(),), lab.cuda())
+    assert sorted(out) == ["acc_seg", "loss_seg"] and torch.equal(out["loss_seg"], res["loss_seg"].detach())
+    up = F.interpolate(logits.detach().double().cpu(), size=(H, W), mode="bilinear", align_corners=False)
+    valid = lab != 255
+    n_correct = int(((up.argmax(1) == lab.long()) & valid).sum())
+    stats = again.loss_decode.last_stats
+    print("n_valid %d, n_correct %d (float64 on the head's logits: %d)" % (int(stats["n_valid"]), int(stats["n_correct"]), n_correct))
+    assert int(stats["n_valid"]) == int(valid.sum()) and int(stats["n_correct"]) == n_correct
+    assert float(out["acc_seg"]) == 100.0 * n_correct / int(valid.sum())
+
+
+# ---------------------------------------------------------------------------------------------- SyncBN hook
+def test_syncbn_hook_two_identical_ranks():
+    """reduce doubles the sums (two ranks holding the same batch): the result is the single-rank run on the batch
+    concatenated with itself.  Statistics and backward sums of the two runs are added in different orders (fp32, relative
+    differences of a few 2^-24 on mean and rstd), so fp32 results agree to 1e-5 of their largest value; the gradient of the
+    convolution's output is rounded to bf16, where such a difference can move single elements by one bf16 step (2^-8
+    relative): what passes through it (map and convolution-weight gradients) agrees to 2^-7 of its largest value."""
+    case = "S2"
+    B, Cin, C, K, h, w = CASES[case]
+    x, sd, gout = _state(case)
+    calls = []
+
+    def doubled(vec, tag):
+        calls.append(tag)
+        return vec * 2.0
+
+    rank = _head(case, "hip", sd, 0.0)
+    rank.reduce = doubled
+    r_out, r_grads = _run(rank, x, gout)
+    full = _head(case, "hip", sd, 0.0)
+    f_out, f_grads = _run(full, torch.cat([x, x]), torch.cat([gout, gout]))
+    assert calls == ["stats", "bwd"]
+    tol = {"x": 2.0 ** -7, "convs.0.conv.weight": 2.0 ** -7}
+    e = float((f_out[:B] - r_out).abs().max() / r_out.abs().max())
+    print("logits: rel %.3e" % e)
+    assert e <= 1e-5 and torch.equal(f_out[:B], f_out[B:])
+    for n, a, b in zip(NAMES, f_grads, r_grads):
+        want = b if n == "x" else 2.0 * b                                 # a parameter's gradient is the sum over both ranks
+        a = a[:B] if n == "x" else a
+        e = float((a - want).abs().max() / want.abs().max())
+        print("d %-22s rel %.3e (tolerance %.3e)" % (n, e, tol.get(n, 1e-5)))
+        assert e <= tol.get(n, 1e-5), n
+    n = 2.0 * B * h * w                                                   # the count went through the hook too
+    rv_rank, rv_full = rank.convs[0].bn.running_var, full.convs[0].bn.running_var
+    alone = _head(case, "hip", sd, 0.0)
+    _run(alone, x, gout)
+    print("running_var: two ranks vs concatenated %.3e, vs one rank alone %.3e" % (float((rv_rank - rv_full).abs().max()),
+                                                                                  float((rv_rank - alone.convs[0].bn.running_var).abs().max())))
+    assert float((rv_rank - rv_full).abs().max()) <= 1e-5 * float(rv_full.max())
+    assert float((rv_rank - alone.convs[0].bn.running_var).abs().max()) > 0.0       # n / (n - 1) of 2R pixels, not R
+    assert n > 0
+
+
+# ---------------------------------------------------------------------------------------------- through the backbone
+CFG = dict(img_size=(64, 96), patch_size=16, in_chans=3, embed_dim=128, depth=4, num_heads=2, out_indices=(0, 1, 2, 3),
+           use_rel_pos_bias=True, use_abs_pos_emb=False, init_values=0.1, drop_path_rate=0.0)
+
+
+def _seg_model(impl, sd=None):
+    from mem_amd.seg_heads import FCNHead, SegModel
+    from mem_amd.semseg_backbone import EvBEiT
+    from oracle.vit_ref import fill_by_name
+    m = SegModel(EvBEiT(**CFG), FCNHead(in_channels=128, channels=64, num_classes=11, in_index=2, dropout_ratio=0.1, loss_weight=1.0, impl=impl))
+    if sd is None:
+        trunk = {k: v for k, v in m.backbone.state_dict().items() if not k.startswith("fpn")}
+        m.backbone.load_state_dict(fill_by_name(trunk, seed=5), strict=False)
+        gen = torch.Generator().manual_seed(9)
+        with torch.no_grad():
+            w = m.decode_head.convs[0].conv.weight
+            w.copy_((torch.randn(w.shape, generator=gen) * (2.0 / (9 * 128)) ** 0.5).to(torch.bfloat16).float())
+            m.decode_head.conv_seg.weight.copy_(torch.randn(11, 64, 1, 1, generator=gen) * 0.125)
+        sd = {k: v.clone() for k, v in m.state_dict().items()}
+    m.load_state_dict(sd, strict=True)
+    m.decode_head.drop_key = KEY
+    return m.cuda().train(), sd
+
+
+def _trunk_step(m, x, lab, autocast=False):
+    """the trunk as it is, the (torch) head alone under autocast"""
+    m.zero_grad(set_to_none=True)
+    feats = m.extract_feat(x)
+    with torch.autocast("cuda", dtype=torch.bfloat16, enabled=autocast):
+        out = m.decode_head.forward_train(feats, lab)
+    out["loss_seg"].float().backward()
+    return out, {k: p.grad.detach().float().clone() for k, p in m.named_parameters() if p.grad is not None}
+
+
+def test_through_the_backbone():
+    """SegModel(EvBEiT, FCNHead(hip)): one forward_train + backward; the trunk's gradients against the same model with the torch
+    head in fp32 (the reference here: there is no float64 trunk), held to the yardstick by the torch head under bf16 autocast
+    behind the same trunk.  The three share the state dict and the Dropout2d mask."""
+    from oracle.gen_golden_ft import ft_inputs
+    x = ft_inputs(dict(in_chans=3, img_size=(64, 96), num_classes=2), 4, 3)[0].cuda()
+    lab = _labels(torch.Generator().manual_seed(6), 4, 11, 64, 96).cuda()
+    mh, sd = _seg_model("hip")
+    mt, _ = _seg_model("torch", sd)
+    my, _ = _seg_model("torch", sd)
+    keep = _mask(4, 64, 0.1)
+    mt.decode_head.keep_mask = my.decode_head.keep_mask = keep
+    out_h = mh.forward_train(x, lab)
+    assert sorted(out_h) == ["decode.acc_seg", "decode.loss_seg"]
+    mh.zero_grad(set_to_none=True)
+    out_h["decode.loss_seg"].backward()
+    g_h = {k: p.grad.detach().float().clone() for k, p in mh.named_parameters() if p.grad is not None}
+    out_t, g_t = _trunk_step(mt, x, lab)
+    out_y, g_y = _trunk_step(my, x, lab, autocast=True)
+    trunk = [k for k, _ in mh.named_parameters() if k.startswith("backbone.") and not k.startswith("backbone.fpn")]
+    heads = [k for k, _ in mh.named_parameters() if k.startswith("decode_head.")]
+    assert len(trunk) > 40 and len(heads) == 5
+    for k in trunk + heads:
+        assert (k in g_h or k not in g_t) and (k not in g_h or bool(torch.isfinite(g_h[k]).all())), k
+    assert all(k in g_h for k in heads)
+    pe = float(g_h["backbone.patch_embed.proj.weight"].abs().max())
+    print("loss hip %.6f torch fp32 %.6f torch bf16 %.6f; |d patch_embed| max %.3e" % (float(out_h["decode.loss_seg"].detach()), float(out_t["loss_seg"].detach()),
+                                                                                       float(out_y["loss_seg"].detach()), pe))
+    assert pe > 0.0
+    figures = []
+    ok = [held("loss_seg", out_h["decode.loss_seg"], out_y["loss_seg"], out_t["loss_seg"], figures)]
+    used = [k for k in trunk if k in g_t and float(g_t[k].abs().max()) > 0.0]          # blocks behind the exit of in_index = 2 get no gradient
+    ok += [held("d " + k[len("backbone."):], g_h[k], g_y[k], g_t[k], figures) for k in used]
+    report("through the backbone", figures)
+    assert len(used) > 30 and all(ok), [f for f, o in zip(figures, ok) if not o]
+    for k in trunk:
+        if k not in used and k in g_h:
+            assert float(g_h[k].abs().max()) == 0.0, k
