@@ -22,64 +22,21 @@
 // LDS accesses are 4-byte (ds_read_b32 / ds_write_b32, banks of a 32-lane half): the Z side and the I side are at worst
 // 2-way conflicted, which a ds_write_b32 absorbs and costs a ds_read_b32 one extra cycle; the kernels are HBM-bound.
 //
-// Column sums (batch statistics, the two sums of the batch-norm backward) are two-stage: a grid of G x D/64 workgroups, each
-// thread a fixed-order chain over its rows, 8 partials per channel folded in LDS in fixed order, one partial per workgroup
-// stored plainly to the workspace, and a finish kernel that adds the G partials in order.  No atomics: bit-reproducible.
+// The Z side, the k = 0 map side and the two-stage column sums (batch statistics, the two sums of the batch-norm backward: 8 row
+// lanes per workgroup here) are bn_tile.hpp's, shared with seg_head.hip.
 #include "common.h"
+#include "bn_tile.hpp"
 #include "gemm_epilogue.hpp"   // gelu_f / gelu_grad_f: the project's exact-erf GELU
 
 namespace {
 
 using namespace memhip;
-
-constexpr int kT = 256;
-constexpr int kTile = 64;            // fine rows and channels per tile
-constexpr int kPitch = kTile + 1;    // floats per LDS row
-constexpr int kGroups = MEMHIP_NECK_GROUPS;
-
-typedef float f4 __attribute__((ext_vector_type(4)));
-typedef float f2 __attribute__((ext_vector_type(2)));
-typedef unsigned short us8 __attribute__((ext_vector_type(8)));
-typedef unsigned short bf16_t;       // storage
-
-__device__ __forceinline__ float bf2f(bf16_t u) { return __uint_as_float((unsigned)u << 16); }
-__device__ __forceinline__ bf16_t f2bf(float v) { return __builtin_bit_cast(bf16_t, (__bf16)v); }   // round to nearest even
+using namespace memhip::bn;
 
 struct Geom {
   int D, Hp, Wp;
   long long R0;      // base pixels: B * Hp * Wp
 };
-
-// ---------------------------------------------------------------- Z side: plain bf16 rows [nz, D]
-__device__ __forceinline__ void z_load(const bf16_t* __restrict__ rows, long long nz, int D, long long z0, int c0, float* tile) {
-  const int t = threadIdx.x, c = 8 * (t & 7);
-  us8 v[2];
-#pragma unroll
-  for (int h = 0; h < 2; ++h) {
-    const int zl = (t >> 3) + 32 * h;
-    v[h] = 0;
-    if (z0 + zl < nz) v[h] = *reinterpret_cast<const us8*>(rows + (z0 + zl) * D + c0 + c);
-  }
-#pragma unroll
-  for (int h = 0; h < 2; ++h) {
-    float* dst = tile + ((t >> 3) + 32 * h) * kPitch + c;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) dst[e] = bf2f(v[h][e]);
-  }
-}
-
-__device__ __forceinline__ void z_store(bf16_t* __restrict__ rows, long long nz, int D, long long z0, int c0, const float* tile) {
-  const int t = threadIdx.x, c = 8 * (t & 7);
-#pragma unroll
-  for (int h = 0; h < 2; ++h) {
-    const int zl = (t >> 3) + 32 * h;
-    const float* src = tile + zl * kPitch + c;
-    us8 v;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) v[e] = f2bf(src[e]);
-    if (z0 + zl < nz) *reinterpret_cast<us8*>(rows + (z0 + zl) * D + c0 + c) = v;
-  }
-}
 
 // ---------------------------------------------------------------- I side: interleaved bf16 rows [R, 4D]
 // lane (row rl = t / 32 + 8 h of the tile's 16, channel pair cl = 2 (t % 32)): element e is channel cl + e / 4, q = e % 4,
@@ -169,39 +126,7 @@ __device__ __forceinline__ void map_side(float* __restrict__ map, const Geom& g,
       }
     }
   } else {
-    const int q = t & 15;
-    const long long z = z0 + 4 * q;                                  // element e: fine row (= pixel row) z + e
-#pragma unroll
-    for (int h = 0; h < 4; ++h) {
-      const int cl = (t >> 4) + 16 * h;
-      if constexpr (VEC) {                                           // P % 4 == 0: the four pixels lie in one sample
-        const bool ok = z < g.R0;
-        float* ptr = map + ((z / P) * g.D + c0 + cl) * P + z % P;
-        if (LOAD) {
-          f4 v = 0.f;
-          if (ok) v = *reinterpret_cast<const f4*>(ptr);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) tile[(4 * q + e) * kPitch + cl] = v[e];
-        } else {
-          f4 v;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) v[e] = tile[(4 * q + e) * kPitch + cl];
-          if (ok) *reinterpret_cast<f4*>(ptr) = v;
-        }
-      } else {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const long long ze = z + e;
-          const bool ok = ze < g.R0;
-          float* ptr = map + ((ze / P) * g.D + c0 + cl) * P + ze % P;
-          if (LOAD) {
-            tile[(4 * q + e) * kPitch + cl] = ok ? *ptr : 0.f;
-          } else if (ok) {
-            *ptr = tile[(4 * q + e) * kPitch + cl];
-          }
-        }
-      }
-    }
+    bn::map_side<VEC, LOAD>(map, g.D, P, g.R0, z0, c0, tile);      // the map itself: 64 pixels of [B, D, P]
   }
 }
 
@@ -214,7 +139,7 @@ __global__ __launch_bounds__(kT) void maps_to_rows_kernel(const float* __restric
   const long long nz = g.R0 << (2 * K);
   map_side<K, VEC, true>(const_cast<float*>(map), g, z0, c0, tile);
   __syncthreads();
-  if constexpr (K == 0) z_store(rows, nz, g.D, z0, c0, tile);
+  if constexpr (K == 0) row_side<false>(rows, nz, PlainRows{g.D}, z0, c0, tile);
   else i_store(rows, nz / 4, g.D, z0, c0, tile);
 }
 
@@ -224,45 +149,13 @@ __global__ __launch_bounds__(kT) void rows_to_maps_kernel(const bf16_t* __restri
   const long long z0 = (long long)blockIdx.x * kTile;
   const int c0 = blockIdx.y * kTile;
   const long long nz = g.R0 << (2 * K);
-  if constexpr (K == 0) z_load(rows, nz, g.D, z0, c0, tile);
+  if constexpr (K == 0) row_side<true>(rows, nz, PlainRows{g.D}, z0, c0, tile);
   else i_load(rows, nz / 4, g.D, z0, c0, tile);
   __syncthreads();
   map_side<K, VEC, false>(map, g, z0, c0, tile);
 }
 
-// ---------------------------------------------------------------- column sums, stage 1 tail and stage 2
-// the workgroup's 8 row groups (t / 32) hold two sums for each of their 2 channels; fold them in fixed order and store
-// the workgroup's partial: ws[(blockIdx.x * 2 + which) * D + channel]
-__device__ __forceinline__ void fold_and_store(const float (&a1)[2], const float (&a2)[2], float* red, float* __restrict__ ws,
-                                               int D, int c0) {
-  const int t = threadIdx.x, cl = 2 * (t & 31), j = t >> 5;
-#pragma unroll
-  for (int c = 0; c < 2; ++c) {
-    red[j * 64 + cl + c] = a1[c];
-    red[512 + j * 64 + cl + c] = a2[c];
-  }
-  __syncthreads();
-  if (t < 128) {
-    const int which = t >> 6, c = t & 63;
-    float s = red[which * 512 + c];
-#pragma unroll
-    for (int k = 1; k < 8; ++k) s += red[which * 512 + k * 64 + c];
-    ws[((long long)blockIdx.x * 2 + which) * D + c0 + c] = s;
-  }
-}
-
-// out[(row0 + which) * D + c] = sum over g < G of ws[(g * 2 + which) * D + c], in order; row0 == 1: out[c] = count
-__global__ __launch_bounds__(kT) void sums_finish_kernel(const float* __restrict__ ws, int G, int D, int row0, float count,
-                                                         float* __restrict__ out) {
-  const int i = blockIdx.x * kT + threadIdx.x;
-  if (i >= 2 * D) return;
-  const int which = i / D, c = i % D;
-  float s = 0.f;
-  for (int g = 0; g < G; ++g) s += ws[((long long)g * 2 + which) * D + c];
-  out[(long long)(row0 + which) * D + c] = s;
-  if (row0 == 1 && which == 0) out[c] = count;
-}
-
+// ---------------------------------------------------------------- column sums (bn_tile.hpp: 8 row lanes x 2 channels per thread)
 // per channel over y [R, 4D] interleaved: sum (x - s), sum (x - s)^2
 __global__ __launch_bounds__(kT) void colstats_kernel(const bf16_t* __restrict__ y, long long R, int D,
                                                       const float* __restrict__ shift, float* __restrict__ ws) {
@@ -280,13 +173,10 @@ __global__ __launch_bounds__(kT) void colstats_kernel(const bf16_t* __restrict__
       a2[e >> 2] = fmaf(d, d, a2[e >> 2]);
     }
   }
-  fold_and_store(a1, a2, red, ws, D, c0);
+  fold_rows_and_store<8, 2>(a1, a2, red, ws + (long long)blockIdx.x * 2 * D, D, c0);
 }
 
 // ---------------------------------------------------------------- batch norm + GELU
-struct BnParams {
-  const float* mean; const float* rstd; const float* gamma; const float* beta;
-};
 struct BnChan { float m[2], rs[2], ga[2], be[2]; };
 __device__ __forceinline__ BnChan bn_chan(const BnParams& p, int c) {
   BnChan k;
@@ -320,7 +210,7 @@ __global__ __launch_bounds__(kT) void bn_gelu_fwd_kernel(const bf16_t* __restric
     }
   }
   __syncthreads();
-  z_store(z, 4 * R, D, z0, c0, tile);
+  row_side<false>(z, 4 * R, PlainRows{D}, z0, c0, tile);
 }
 
 // stage 1 of the backward sums: g = da * gelu'(u), per channel sum g and sum g * xhat; workgroup blockIdx.x takes the tiles
@@ -335,7 +225,7 @@ __global__ __launch_bounds__(kT) void bn_gelu_bwd_sums_kernel(const bf16_t* __re
   for (long long ti = blockIdx.x; ti < tiles; ti += gridDim.x) {
     const long long z0 = ti * kTile;
     __syncthreads();                                   // the previous tile's readers are done
-    z_load(da, 4 * R, D, z0, c0, tile);                // zero past the end: those rows add nothing
+    row_side<true>(da, 4 * R, PlainRows{D}, z0, c0, tile);   // zero past the end: those rows add nothing
     us8 v[2];
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
@@ -358,7 +248,7 @@ __global__ __launch_bounds__(kT) void bn_gelu_bwd_sums_kernel(const bf16_t* __re
     }
   }
   __syncthreads();
-  fold_and_store(a1, a2, tile, ws, D, c0);
+  fold_rows_and_store<8, 2>(a1, a2, tile, ws + (long long)blockIdx.x * 2 * D, D, c0);
 }
 
 // dy [R, 4D] interleaved = bf16(gamma * rstd * (g - sum_g / N - xhat * sum_gx / N))
@@ -371,7 +261,7 @@ __global__ __launch_bounds__(kT) void bn_gelu_bwd_apply_kernel(const bf16_t* __r
   const BnChan k = bn_chan(p, c0 + cl);
   const float m1[2] = {sums[c0 + cl] * inv_n, sums[c0 + cl + 1] * inv_n};
   const float m2[2] = {sums[D + c0 + cl] * inv_n, sums[D + c0 + cl + 1] * inv_n};
-  z_load(da, 4 * R, D, z0, c0, tile);
+  row_side<true>(da, 4 * R, PlainRows{D}, z0, c0, tile);
   us8 v[2];
 #pragma unroll
   for (int h = 0; h < 2; ++h) {
@@ -397,8 +287,6 @@ __global__ __launch_bounds__(kT) void bn_gelu_bwd_apply_kernel(const bf16_t* __r
 }
 
 // ---------------------------------------------------------------- host side
-bool aligned(const void* p, int n) { return (reinterpret_cast<uintptr_t>(p) & (uintptr_t)(n - 1)) == 0; }
-
 int check_geom(const char* what, int B, int D, int Hp, int Wp, int level, Geom& g) {
   MEMHIP_REQUIRE(B > 0 && Hp > 0 && Wp > 0 && D > 0 && D % kTile == 0 && D / kTile <= 65535,
                  "%s: bad shape B=%d D=%d Hp=%d Wp=%d (all positive, D a multiple of 64)", what, B, D, Hp, Wp);
@@ -413,11 +301,6 @@ int check_geom(const char* what, int B, int D, int Hp, int Wp, int level, Geom& 
 int check_rows(const char* what, long long R, int D) {
   MEMHIP_REQUIRE(R > 0 && R <= (1LL << 34) && D > 0 && D % kTile == 0 && D / kTile <= 65535,
                  "%s: bad shape R=%lld D=%d (R positive, D a positive multiple of 64)", what, R, D);
-  return MEMHIP_OK;
-}
-
-int check_bn(const char* what, const float* mean, const float* rstd, const float* gamma, const float* beta) {
-  MEMHIP_REQUIRE(mean && rstd && gamma && beta, "%s: null pointer (mean, rstd, gamma, beta)", what);
   return MEMHIP_OK;
 }
 
@@ -477,8 +360,8 @@ extern "C" int memhip_neck_colstats(const void* y, int64_t R, int D, const float
   const int G = groups_of((R + 7) / 8);
   hipLaunchKernelGGL(colstats_kernel, dim3(G, D / kTile), dim3(kT), 0, as_stream(stream), static_cast<const bf16_t*>(y),
                      (long long)R, D, shift, workspace);
-  hipLaunchKernelGGL(sums_finish_kernel, dim3(cdiv(2 * D, kT)), dim3(kT), 0, as_stream(stream), workspace, G, D, 1,
-                     (float)(4 * R), out);
+  launch_fold(workspace, G, 2 * D, fold_grid(2 * D), FoldOut{{out + D, nullptr, nullptr}, {2 * D, 0, 0}, out, D, (float)(4 * R)},
+              as_stream(stream));
   return check_launch("neck_colstats");
 }
 
@@ -506,7 +389,7 @@ extern "C" int memhip_neck_bn_gelu_bwd_sums(const void* da, const void* y, int64
   hipLaunchKernelGGL(bn_gelu_bwd_sums_kernel, dim3(G, D / kTile), dim3(kT), 0, as_stream(stream),
                      static_cast<const bf16_t*>(da), static_cast<const bf16_t*>(y), (long long)R, D,
                      BnParams{mean, rstd, gamma, beta}, workspace);
-  hipLaunchKernelGGL(sums_finish_kernel, dim3(cdiv(2 * D, kT)), dim3(kT), 0, as_stream(stream), workspace, G, D, 0, 0.f, out);
+  launch_fold(workspace, G, 2 * D, fold_grid(2 * D), FoldOut{{out, nullptr, nullptr}, {2 * D, 0, 0}, nullptr, 0, 0.f}, as_stream(stream));
   return check_launch("neck_bn_gelu_bwd_sums");
 }
 

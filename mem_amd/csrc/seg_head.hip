@@ -9,10 +9,10 @@
 // rings are neither read nor written.  No float atomics: sums are per-workgroup partials stored plainly and folded in
 // ascending order by a second launch, so two calls give the same bits.
 //
-//   movers       a 64 pixel x 64 channel tile through LDS (pitch 65 floats, 4-byte LDS accesses, conflict-free on both
-//                sides as in dense.hip); the map side moves 16 bytes per lane when h w % 4 == 0, single floats otherwise
+//   movers       bn_tile.hpp's map side and row side (shared with necks.hip) around one 64 pixel x 64 channel LDS tile; the
+//                rows are those of the padded format
 //   bn_stats     thread (row lane j = t / 8, channels 8 (t % 8)..): a chain over the rows 32 g + j, + 32 G, ..; the 32 row
-//                lanes folded in LDS in order
+//                lanes folded in LDS in order (bn_tile.hpp), the partials by the library's one ordered fold (fold.hip)
 //   bnhead_fwd   the classifier weight [KP, C] fp32 in LDS once per workgroup (KP = K rounded up to 8, zero rows behind K);
 //                a tile is 32 pixels, the 8 lanes of a pixel walk the channels in chunks of 64 with KP accumulators each
 //                (weights as ds_read_b128, broadcast over the pixels) and add up in a 3-step butterfly; lane i of the 8
@@ -23,6 +23,7 @@
 //                channel t % 64, classes t / 64 + 4 j) adds dlogit[p, k] z[p, c] over the tile's pixels
 //   bwd_apply    phase B again with the two correction terms, written as bf16 into the padded interior
 #include "common.h"
+#include "bn_tile.hpp"
 #include "dropout.hpp"
 #include "seg_head_plan.hpp"
 
@@ -30,17 +31,8 @@ namespace {
 
 using namespace memhip;
 using namespace memhip::seghead;
-
-constexpr int kT = kThreads;
-constexpr int kTile = 64;            // pixels and channels per mover tile
-constexpr int kPitch = kTile + 1;    // floats per LDS row
-
-typedef float f4 __attribute__((ext_vector_type(4)));
-typedef unsigned short us8 __attribute__((ext_vector_type(8)));
-typedef unsigned short bf16_t;       // storage
-
-__device__ __forceinline__ float bf2f(bf16_t u) { return __uint_as_float((unsigned)u << 16); }
-__device__ __forceinline__ bf16_t f2bf(float v) { return __builtin_bit_cast(bf16_t, (__bf16)v); }   // round to nearest even
+using bn::kT, bn::kTile, bn::kPitch, bn::f4, bn::us8, bn::bf16_t, bn::bf2f, bn::f2bf, bn::BnParams, bn::FoldOut, bn::aligned;
+static_assert(kThreads == kT && kChunk == kTile && seghead::kGroups == bn::kGroups, "the plan's constants are the tile's");
 
 struct Geom {
   int C, h, w, P;    // P = h * w
@@ -55,76 +47,20 @@ __device__ __forceinline__ long long pad_off(const Geom& g, long long r) {
 }
 
 // ---------------------------------------------------------------- movers
-// M side: fp32 maps [B, C, P]; lane (q = t % 16, channel t / 16 + 16 k) takes the pixels z0 + 4 q .. + 3 of one channel
-template <bool VEC, bool LOAD>
-__device__ __forceinline__ void map_side(float* __restrict__ map, const Geom& g, long long z0, int c0, float* tile) {
-  const int t = threadIdx.x, q = t & 15;
-  const long long z = z0 + 4 * q;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const int cl = (t >> 4) + 16 * k;
-    if constexpr (VEC) {                                             // P % 4 == 0: the four pixels lie in one sample
-      const bool ok = z < g.R;
-      float* ptr = map + ((z / g.P) * g.C + c0 + cl) * g.P + z % g.P;
-      if (LOAD) {
-        f4 v = 0.f;
-        if (ok) v = *reinterpret_cast<const f4*>(ptr);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) tile[(4 * q + e) * kPitch + cl] = v[e];
-      } else {
-        f4 v;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = tile[(4 * q + e) * kPitch + cl];
-        if (ok) *reinterpret_cast<f4*>(ptr) = v;
-      }
-    } else {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const long long ze = z + e;
-        const bool ok = ze < g.R;
-        float* ptr = map + ((ze / g.P) * g.C + c0 + cl) * g.P + ze % g.P;
-        if (LOAD) {
-          tile[(4 * q + e) * kPitch + cl] = ok ? *ptr : 0.f;
-        } else if (ok) {
-          *ptr = tile[(4 * q + e) * kPitch + cl];
-        }
-      }
-    }
-  }
-}
-
-// N side: the padded bf16 format; lane (pixel t / 8 + 32 k, channels 8 (t % 8)..) moves 16 bytes
-template <bool LOAD>
-__device__ __forceinline__ void pad_side(bf16_t* __restrict__ buf, const Geom& g, long long z0, int c0, float* tile) {
-  const int t = threadIdx.x, c = 8 * (t & 7);
-#pragma unroll
-  for (int k = 0; k < 2; ++k) {
-    const int zl = (t >> 3) + 32 * k;
-    const bool ok = z0 + zl < g.R;
-    bf16_t* ptr = buf + (ok ? pad_off(g, z0 + zl) : 0) + c0 + c;
-    float* row = tile + zl * kPitch + c;
-    if (LOAD) {
-      us8 v = 0;
-      if (ok) v = *reinterpret_cast<const us8*>(ptr);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) row[e] = bf2f(v[e]);
-    } else {
-      us8 v;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) v[e] = f2bf(row[e]);
-      if (ok) *reinterpret_cast<us8*>(ptr) = v;
-    }
-  }
-}
+// where the rows of the padded format lie (bn_tile.hpp: row_side)
+struct PadRows {
+  Geom g;
+  __device__ __forceinline__ long long operator()(long long r) const { return pad_off(g, r); }
+};
 
 template <bool VEC>
 __global__ __launch_bounds__(kT) void map_to_nhwc_pad_kernel(const float* __restrict__ map, Geom g, bf16_t* __restrict__ out) {
   __shared__ float tile[kTile * kPitch];
   const long long z0 = (long long)blockIdx.x * kTile;
   const int c0 = blockIdx.y * kTile;
-  map_side<VEC, true>(const_cast<float*>(map), g, z0, c0, tile);
+  bn::map_side<VEC, true>(map, g.C, g.P, g.R, z0, c0, tile);
   __syncthreads();
-  pad_side<false>(out, g, z0, c0, tile);
+  bn::row_side<false>(out, g.R, PadRows{g}, z0, c0, tile);
 }
 
 template <bool VEC>
@@ -132,62 +68,9 @@ __global__ __launch_bounds__(kT) void nhwc_pad_to_map_kernel(const bf16_t* __res
   __shared__ float tile[kTile * kPitch];
   const long long z0 = (long long)blockIdx.x * kTile;
   const int c0 = blockIdx.y * kTile;
-  pad_side<true>(const_cast<bf16_t*>(in), g, z0, c0, tile);
+  bn::row_side<true>(in, g.R, PadRows{g}, z0, c0, tile);
   __syncthreads();
-  map_side<VEC, false>(map, g, z0, c0, tile);
-}
-
-// ---------------------------------------------------------------- ordered fold of per-workgroup partials
-// s[i] = sum over g < G of ws[g * slot + i], in order, i < slot; the slot is cut into up to three outputs; count_out[i] =
-// count for i < n_count
-struct FoldOut {
-  float* p[3];
-  int n[3];
-  float* count_out;
-  int n_count;
-  float count;
-};
-
-__global__ __launch_bounds__(kT) void fold_kernel(const float* __restrict__ ws, int G, int slot, FoldOut o) {
-  const int i = blockIdx.x * kT + threadIdx.x;
-  if (i < o.n_count) o.count_out[i] = o.count;
-  if (i >= slot) return;
-  float s = 0.f;
-  int g = 0;
-  for (; g + 8 <= G; g += 8) {                       // eight loads in flight, added in the same ascending order
-    float v[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) v[j] = ws[(long long)(g + j) * slot + i];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) s += v[j];
-  }
-  for (; g < G; ++g) s += ws[(long long)g * slot + i];
-  int j = i;
-#pragma unroll
-  for (int q = 0; q < 3; ++q) {
-    if (j < o.n[q]) { o.p[q][j] = s; return; }
-    j -= o.n[q];
-  }
-}
-
-// the 32 row lanes (t / 8) hold two sums for each of their 8 channels: fold them in order and store the workgroup's partial
-// ws_slot[which * C + c0 + channel].  red: 2 * 32 * 64 floats
-__device__ __forceinline__ void fold32_and_store(const float (&a1)[8], const float (&a2)[8], float* red, float* __restrict__ ws_slot,
-                                                 int C, int c0) {
-  const int t = threadIdx.x, c = 8 * (t & 7), j = t >> 3;
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    red[j * 64 + c + e] = a1[e];
-    red[2048 + j * 64 + c + e] = a2[e];
-  }
-  __syncthreads();
-  if (t < 128) {
-    const int which = t >> 6, cc = t & 63;
-    float s = red[which * 2048 + cc];
-#pragma unroll
-    for (int k = 1; k < 32; ++k) s += red[which * 2048 + k * 64 + cc];
-    ws_slot[which * C + c0 + cc] = s;
-  }
+  bn::map_side<VEC, false>(map, g.C, g.P, g.R, z0, c0, tile);
 }
 
 // ---------------------------------------------------------------- batch statistics
@@ -212,13 +95,10 @@ __global__ __launch_bounds__(kT) void bn_stats_kernel(const bf16_t* __restrict__
       a2[e] = fmaf(d, d, a2[e]);
     }
   }
-  fold32_and_store(a1, a2, red, ws + (long long)blockIdx.x * 2 * g.C, g.C, c0);
+  bn::fold_rows_and_store<32, 8>(a1, a2, red, ws + (long long)blockIdx.x * 2 * g.C, g.C, c0);
 }
 
 // ---------------------------------------------------------------- batch norm + ReLU + Dropout2d + classifier
-struct BnParams {
-  const float* mean; const float* rstd; const float* gamma; const float* beta;
-};
 struct Chan8 { float m[8], rs[8], ga[8], be[8]; };
 
 __device__ __forceinline__ void load8(const float* __restrict__ p, float (&o)[8]) {
@@ -436,7 +316,7 @@ __global__ __launch_bounds__(kT) void bnhead_bwd_sums_kernel(const float* __rest
     if (blockIdx.y == 0 && t < K) ws_slot[2 * g.C + K * g.C + t] = dbs;
   }
   __syncthreads();                                   // the last tile's readers of zt are done
-  fold32_and_store(a1, a2, zt, ws_slot, g.C, c0);
+  bn::fold_rows_and_store<32, 8>(a1, a2, zt, ws_slot, g.C, c0);
 }
 
 template <int KP>
@@ -473,8 +353,6 @@ __global__ __launch_bounds__(kT) void bnhead_bwd_apply_kernel(const float* __res
 }
 
 // ---------------------------------------------------------------- host side
-bool aligned(const void* p, int n) { return (reinterpret_cast<uintptr_t>(p) & (uintptr_t)(n - 1)) == 0; }
-
 int check_geom(const char* what, int B, int C, int h, int w, Geom& g) {
   MEMHIP_REQUIRE(B >= 0 && h >= 1 && w >= 1 && C > 0 && C % kChunk == 0 && C / kChunk <= 65535,
                  "%s: bad shape B=%d C=%d h=%d w=%d (B >= 0, h and w positive, C a positive multiple of 64)", what, B, C, h, w);
@@ -552,8 +430,8 @@ extern "C" int memhip_bn_stats_nhwc(const void* x, int padded, int B, int h, int
     hipLaunchKernelGGL(bn_stats_kernel<true>, dim3(G, C / kChunk), dim3(kT), 0, as_stream(stream), xb, g, shift, workspace);
   else
     hipLaunchKernelGGL(bn_stats_kernel<false>, dim3(G, C / kChunk), dim3(kT), 0, as_stream(stream), xb, g, shift, workspace);
-  const FoldOut o{{out + C, nullptr, nullptr}, {2 * C, 0, 0}, out, C, (float)g.R};
-  hipLaunchKernelGGL(fold_kernel, dim3(cdiv(2 * C, kT)), dim3(kT), 0, as_stream(stream), workspace, G, 2 * C, o);
+  bn::launch_fold(workspace, G, 2 * C, bn::fold_grid(2 * C), FoldOut{{out + C, nullptr, nullptr}, {2 * C, 0, 0}, out, C, (float)g.R},
+                  as_stream(stream));
   return check_launch("bn_stats_nhwc");
 }
 
@@ -586,8 +464,8 @@ extern "C" int memhip_bnhead_bwd_sums(const memhip_bnhead_args_t* a, memhip_stre
                        as_stream(stream), a->dlogit, ds, static_cast<const bf16_t*>(a->y), g, bp, a->wcls, a->K, dr, ws, p.slot_floats);
     return 0;
   });
-  const FoldOut o{{a->sums, a->dwcls, a->dbias}, {2 * a->C, a->K * a->C, a->K}, nullptr, 0, 0.f};
-  hipLaunchKernelGGL(fold_kernel, dim3(p.fold_grid), dim3(kT), 0, as_stream(stream), ws, p.sums_grid_x, p.slot_floats, o);
+  bn::launch_fold(ws, p.sums_grid_x, p.slot_floats, p.fold_grid,
+                  FoldOut{{a->sums, a->dwcls, a->dbias}, {2 * a->C, a->K * a->C, a->K}, nullptr, 0, 0.f}, as_stream(stream));
   return check_launch("bnhead_bwd_sums");
 }
 

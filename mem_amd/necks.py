@@ -21,6 +21,7 @@ returned maps fp32.
 import torch
 
 from . import ops
+from .syncbn import BufferCache, add_affine_grads, all_reduce_sum, backward_totals, batch_vectors
 
 # ---------------------------------------------------------------------------------------------- packing (pure torch)
 def weight_matrix(weight):
@@ -61,17 +62,6 @@ def rows_to_map(rows, B, D, Hp, Wp, level):
     return rows.reshape(B, Hp, Wp, 2, 2, D, 2, 2).permute(0, 5, 1, 3, 6, 2, 4, 7).reshape(B, D, 4 * Hp, 4 * Wp)
 
 
-# ---------------------------------------------------------------------------------------------- SyncBN exchange
-def all_reduce_sum(vec, tag):
-    """Sum ``vec`` over the ranks when torch.distributed runs with more than one; ``tag`` is "stats" (the [count, sum,
-    sum of squares] rows of the batch statistics) or "bwd" (the [sum g, sum g xhat] rows of the batch-norm backward).  Both
-    are tiny.  ``FusedNecks.reduce`` holds this function; a test replaces it."""
-    import torch.distributed as dist
-    if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
-        dist.all_reduce(vec)
-    return vec
-
-
 # ---------------------------------------------------------------------------------------------- autograd entry points
 class _Fpn2Function(torch.autograd.Function):
     """fpn2: the engine's fp32 map [B, D, Hp, Wp] -> fp32 [B, D, 2Hp, 2Wp].  The parameters are inputs so that a call
@@ -102,7 +92,7 @@ class _Fpn1Function(torch.autograd.Function):
         return (None, ctx.necks._fpn1_backward(ctx.saved, dout, ctx.needs_input_grad[1])) + (None,) * 6
 
 
-class FusedNecks:
+class FusedNecks(BufferCache):
     """fpn1 and fpn2 of an EvBEiT on the HIP path.  Holds no parameter of its own: it reads the torch modules' parameters
     and buffers (``fpn1.0`` ConvTranspose2d, ``fpn1.1`` SyncBatchNorm, ``fpn1.3`` ConvTranspose2d, ``fpn2.0``
     ConvTranspose2d) and, when the model has an engine, the engine's bf16 shadow ``flat_w16`` of the weights.
@@ -121,12 +111,8 @@ class FusedNecks:
         self._tn_ws = None
 
     # ------------------------------------------------------------------ buffers and weights
-    def _buf(self, name, shape, dtype=torch.bfloat16):
-        key = (name, tuple(shape), dtype)
-        b = self._bufs.get(key)
-        if b is None:
-            b = self._bufs[key] = torch.empty(shape, dtype=dtype, device=self.fpn2[0].weight.device)
-        return b
+    def _buf_device(self):
+        return self.fpn2[0].weight.device
 
     def _convs(self):
         return ((self.prefix[0] + "0", self.fpn1[0]), (self.prefix[0] + "3", self.fpn1[3]), (self.prefix[1] + "0", self.fpn2[0]))
@@ -164,11 +150,6 @@ class FusedNecks:
     def refresh(self):
         """Drop the bf16 weight copies (a caller that changed the weights behind torch's version counters)."""
         self._stamp = None
-
-    def _grad(self, p):
-        if p.grad is None:
-            p.grad = torch.zeros_like(p)
-        return p.grad
 
     def _wgrad(self, conv, X, dY, R, D):
         """Accumulate the gradients of a transposed convolution from its input rows X [R, D] and dY [R, 4D]."""
@@ -225,24 +206,9 @@ class FusedNecks:
         return self._fpn2_forward(x.detach())[0]
 
     # ------------------------------------------------------------------ fpn1
-    def _bn_vectors(self, bn, Y1, R, D, bias):
-        """(mean, rstd, 1 / n) of the batch norm over Y1 [R, 4D]: the batch statistics in train() over the n elements per
-        channel of every rank (running statistics updated as nn.SyncBatchNorm does: momentum, unbiased variance,
-        num_batches_tracked), the running ones in eval() (no n)."""
-        if not bn.training:
-            return bn.running_mean.contiguous(), torch.rsqrt(bn.running_var + bn.eps), None
+    def _colstats(self, Y1, D, bias):
         ws = self._buf("sums.ws", (ops.NECK_GROUPS * 2 * D,), torch.float32)
-        st = self.reduce(ops.neck_colstats(Y1, bias, ws, out=self._buf("stats", (3, D), torch.float32)), "stats")
-        n = st[0]
-        m1 = st[1] / n
-        mean = bias + m1                                   # the shift of the sums was the convolution's bias
-        var = (st[2] / n - m1 * m1).clamp_(min=0.0)
-        with torch.no_grad():
-            assert bn.momentum is not None, "the necks' batch norm has momentum 0.1 (no cumulative average)"
-            bn.running_mean.mul_(1.0 - bn.momentum).add_(mean, alpha=bn.momentum)
-            bn.running_var.mul_(1.0 - bn.momentum).add_(var * (n / (n - 1.0)), alpha=bn.momentum)
-            bn.num_batches_tracked += 1
-        return mean, torch.rsqrt(var + bn.eps), 1.0 / n
+        return ops.neck_colstats(Y1, bias, ws, out=self._buf("stats", (3, D), torch.float32))
 
     def _fpn1_forward(self, x, keep):
         B, D, Hp, Wp = x.shape
@@ -253,7 +219,8 @@ class FusedNecks:
         Y1 = self._buf("f1.y1", (R, 4 * D))
         ops.gemm_nt(X0, w[self.prefix[0] + "0"][1], R, 4 * D, D, ops.EPI_BIAS_BF16, out0=Y1, bias=w[self.prefix[0] + "0"][2])
         with torch.no_grad():
-            mean, rstd, inv_n = self._bn_vectors(bn, Y1, R, D, c0.bias.detach())
+            bias = c0.bias.detach()                            # the shift of the sums is the convolution's bias
+            mean, rstd, inv_n = batch_vectors(bn, lambda: self._colstats(Y1, D, bias), self.reduce, shift=bias)
             gamma, beta = bn.weight.detach().contiguous(), bn.bias.detach().contiguous()
         Z1 = ops.neck_bn_gelu_fwd(Y1, mean, rstd, gamma, beta, out=self._buf("f1.z1", (4 * R, D)))
         Y2 = self._buf("f1.y2", (4 * R, 4 * D))
@@ -274,12 +241,8 @@ class FusedNecks:
         ops.gemm_nt(dY2, w[self.prefix[0] + "3"][0], 4 * R, D, 4 * D, ops.EPI_BIAS_BF16, out0=da)
         ws = self._buf("sums.ws", (ops.NECK_GROUPS * 2 * D,), torch.float32)
         sums = ops.neck_bn_gelu_bwd_sums(da, Y1, mean, rstd, gamma, beta, ws, out=self._buf("bwd.sums", (2, D), torch.float32))
-        if bn.bias.requires_grad:
-            self._grad(bn.bias).add_(sums[0])
-        if bn.weight.requires_grad:
-            self._grad(bn.weight).add_(sums[1])
-        # the two sums over every rank, divided on the device by the element count the forward's statistics had (no read-back)
-        tot = (self.reduce(sums.clone(), "bwd") * inv_n).contiguous()
+        add_affine_grads(bn, sums)
+        tot = backward_totals(sums, inv_n, self.reduce)
         dY1 = ops.neck_bn_gelu_bwd_apply(da, Y1, mean, rstd, gamma, beta, tot, 1.0, out=self._buf("f1.dy1", (R, 4 * D)))
         self._wgrad(c0, X0, dY1, R, D)
         if not need_dx:

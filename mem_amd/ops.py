@@ -1059,6 +1059,14 @@ def neck_rows_to_maps(rows, B, D, Hp, Wp, level, out=None):
     return out
 
 
+def _sums_out(out, rows, C_, device):
+    """The f32 [rows, C] output of a two-stage column sum ([3, C]: count, sum, sum of squares; [2, C]: sum g, sum g xhat)."""
+    if out is None:
+        out = torch.empty((rows, C_), dtype=torch.float32, device=device)
+    assert out.dtype == torch.float32 and out.is_contiguous() and out.numel() == rows * C_
+    return out
+
+
 def neck_sums_workspace(D, device):
     return torch.empty(int(lib.memhip_neck_sums_workspace(D)) // 4, dtype=torch.float32, device=device)
 
@@ -1067,9 +1075,7 @@ def neck_colstats(y, shift, ws, out=None):
     """y bf16 [R, 4D] interleaved, shift f32 [D] -> out f32 [3, D]: count, sum (x - shift), sum (x - shift)^2 per channel."""
     R, D = y.shape[0], y.shape[1] // 4
     assert y.dtype == torch.bfloat16 and y.is_contiguous() and shift.dtype == torch.float32 and shift.numel() == D
-    if out is None:
-        out = torch.empty((3, D), dtype=torch.float32, device=y.device)
-    assert out.dtype == torch.float32 and out.is_contiguous() and out.numel() == 3 * D
+    out = _sums_out(out, 3, D, y.device)
     check(lib.memhip_neck_colstats(ptr(y), R, D, ptr(shift), ptr(ws), ws.numel() * 4, ptr(out), stream_ptr()), "neck_colstats")
     return out
 
@@ -1093,9 +1099,7 @@ def neck_bn_gelu_bwd_sums(da, y, mean, rstd, gamma, beta, ws, out=None):
     assert y.dtype == torch.bfloat16 and y.is_contiguous() and da.dtype == torch.bfloat16 and da.is_contiguous()
     assert tuple(da.shape) == (4 * R, D)
     assert all(v.dtype == torch.float32 and v.numel() == D and v.is_contiguous() for v in (mean, rstd, gamma, beta))
-    if out is None:
-        out = torch.empty((2, D), dtype=torch.float32, device=y.device)
-    assert out.dtype == torch.float32 and out.is_contiguous() and out.numel() == 2 * D
+    out = _sums_out(out, 2, D, y.device)
     check(lib.memhip_neck_bn_gelu_bwd_sums(ptr(da), ptr(y), R, D, ptr(mean), ptr(rstd), ptr(gamma), ptr(beta), ptr(ws),
                                            ws.numel() * 4, ptr(out), stream_ptr()), "neck_bn_gelu_bwd_sums")
     return out
@@ -1299,9 +1303,7 @@ def bn_stats_nhwc(x, B, h, w, C_, ws, shift=None, padded=True, out=None):
     assert x.dtype == torch.bfloat16 and x.is_contiguous()
     assert x.numel() >= (B * (h + 2) * (w + 2) * C_ if padded else B * h * w * C_)
     assert shift is None or (shift.dtype == torch.float32 and shift.numel() == C_ and shift.is_contiguous())
-    if out is None:
-        out = torch.empty((3, C_), dtype=torch.float32, device=x.device)
-    assert out.dtype == torch.float32 and out.is_contiguous() and out.numel() == 3 * C_
+    out = _sums_out(out, 3, C_, x.device)
     check(lib.memhip_bn_stats_nhwc(ptr(x), int(padded), B, h, w, C_, ptr(shift), ptr(ws), ws.numel() * 4, ptr(out), stream_ptr()),
           "bn_stats_nhwc")
     return out

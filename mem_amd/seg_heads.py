@@ -27,16 +27,7 @@ import torch.nn.functional as F
 
 from . import ops
 from .seg_loss import SegCrossEntropy
-
-
-def all_reduce_sum(vec, tag):
-    """Sum ``vec`` over the ranks when torch.distributed runs with more than one; ``tag`` is "stats" (the [count, sum,
-    sum of squares] rows of the batch statistics) or "bwd" (the [sum g, sum g xhat] rows of the batch-norm backward).
-    ``FCNHead.reduce`` holds this function; a test replaces it."""
-    import torch.distributed as dist
-    if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
-        dist.all_reduce(vec)
-    return vec
+from .syncbn import BufferCache, add_affine_grads, all_reduce_sum, backward_totals, batch_vectors
 
 
 class ConvModule(nn.Module):
@@ -63,7 +54,7 @@ class _FCNHeadFunction(torch.autograd.Function):
         return (None, ctx.head._hip_backward(ctx.saved, dlogit, ctx.needs_input_grad[1])) + (None,) * 5
 
 
-class FCNHead(nn.Module):
+class FCNHead(BufferCache, nn.Module):
     """mmseg 0.30 ``FCNHead(num_convs=1, concat_input=False)`` with its loss.
 
     ``forward(inputs)``: the backbone's tuple of maps -> logits ``[B, num_classes, h, w]`` from ``inputs[in_index]`` (the hip
@@ -140,13 +131,8 @@ class FCNHead(nn.Module):
         return F.conv2d(z, self.conv_seg.weight, self.conv_seg.bias)
 
     # ------------------------------------------------------------------ the hip arm: buffers and weights
-    def _buf(self, name, shape, dtype=torch.bfloat16, zero=False):
-        key = (name, tuple(shape), dtype)
-        b = self._bufs.get(key)
-        if b is None:
-            make = torch.zeros if zero else torch.empty
-            b = self._bufs[key] = make(shape, dtype=dtype, device=self.conv_seg.weight.device)
-        return b
+    def _buf_device(self):
+        return self.conv_seg.weight.device
 
     def _weights(self):
         """(w16 [C, 9 Cin], wd16 [Cin, 9 C]): the bf16 operands of the forward and of the data gradient (the same kernel on
@@ -164,12 +150,6 @@ class FCNHead(nn.Module):
         """Drop the bf16 weight copies (a caller that changed the weight behind torch's version counter)."""
         self._stamp = None
 
-    @staticmethod
-    def _grad(p):
-        if p.grad is None:
-            p.grad = torch.zeros_like(p)
-        return p.grad
-
     def _dropout(self):
         if not (self.training and self.dropout_ratio > 0.0):
             return None
@@ -180,24 +160,10 @@ class FCNHead(nn.Module):
         site = ops.DROPOUT_SITE_HEAD if self.dropout_site is None else self.dropout_site
         return ops.dropout_params(key[0], key[1], site, self.dropout_ratio)
 
-    def _bn_vectors(self, Y, B, h, w):
-        """(mean, rstd, 1 / n) of the batch norm over the convolution's output: the batch statistics in train() over the n
-        pixels of every rank (running statistics updated as nn.SyncBatchNorm does: momentum, unbiased variance,
-        num_batches_tracked), the running ones in eval() (no n)."""
-        bn, C = self.convs[0].bn, self.channels
-        if not bn.training:
-            return bn.running_mean.contiguous(), torch.rsqrt(bn.running_var + bn.eps), None
+    def _stats(self, Y, B, h, w):
+        C = self.channels
         ws = self._buf("stats.ws", (ops.BN_GROUPS * 2 * C,), torch.float32)
-        st = self.reduce(ops.bn_stats_nhwc(Y, B, h, w, C, ws, None, True, out=self._buf("stats", (3, C), torch.float32)), "stats")
-        n = st[0]
-        mean = st[1] / n                                   # the convolution has no bias: the sums are unshifted
-        var = (st[2] / n - mean * mean).clamp_(min=0.0)
-        with torch.no_grad():
-            assert bn.momentum is not None, "the head's batch norm has momentum 0.1 (no cumulative average)"
-            bn.running_mean.mul_(1.0 - bn.momentum).add_(mean, alpha=bn.momentum)
-            bn.running_var.mul_(1.0 - bn.momentum).add_(var * (n / (n - 1.0)), alpha=bn.momentum)
-            bn.num_batches_tracked += 1
-        return mean, torch.rsqrt(var + bn.eps), 1.0 / n
+        return ops.bn_stats_nhwc(Y, B, h, w, C, ws, None, True, out=self._buf("stats", (3, C), torch.float32))
 
     def _vectors(self):
         bn, cs = self.convs[0].bn, self.conv_seg
@@ -213,7 +179,8 @@ class FCNHead(nn.Module):
         Y = self._buf("y", (B, h + 2, w + 2, C), zero=True)
         ops.conv2d_nhwc(Xp, w16, None, Y, B, h, w, Cin, C, 3, 1, 1)
         with torch.no_grad():
-            mean, rstd, inv_n = self._bn_vectors(Y, B, h, w)
+            # the convolution has no bias: the sums are unshifted
+            mean, rstd, inv_n = batch_vectors(self.convs[0].bn, lambda: self._stats(Y, B, h, w), self.reduce)
             gamma, beta, wcls, bcls = self._vectors()
         d = self._dropout()
         rows = self._buf("logits", (B * h * w, K), torch.float32)
@@ -234,16 +201,12 @@ class FCNHead(nn.Module):
         dbias = self._buf("bwd.dbias", (K,), torch.float32)
         ws = self._buf("bwd.ws", (int(plan.ws_bytes) // 4,), torch.float32)
         ops.bnhead_bwd_sums(dlogit, Y, B, C, K, h, w, mean, rstd, gamma, beta, wcls, sums, dwcls, dbias, ws, dropout=d)
-        if bn.bias.requires_grad:
-            self._grad(bn.bias).add_(sums[0])
-        if bn.weight.requires_grad:
-            self._grad(bn.weight).add_(sums[1])
+        add_affine_grads(bn, sums)
         if cs.weight.requires_grad:
             self._grad(cs.weight).add_(dwcls.view(K, C, 1, 1))
         if cs.bias.requires_grad:
             self._grad(cs.bias).add_(dbias)
-        # batch statistics: the two sums over every rank, divided on the device by the pixel count the forward's statistics had
-        tot = None if inv_n is None else (self.reduce(sums.clone(), "bwd") * inv_n).contiguous()
+        tot = backward_totals(sums, inv_n, self.reduce)
         dY = ops.bnhead_bwd_apply(dlogit, Y, B, C, K, h, w, mean, rstd, gamma, beta, wcls, tot, 1.0,
                                   self._buf("dy", (B, h + 2, w + 2, C), zero=True), dropout=d)
         if conv.weight.requires_grad:

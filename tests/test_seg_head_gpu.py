@@ -76,6 +76,27 @@ def test_movers_are_bit_exact_and_leave_the_ring(B, D, h, w):
         assert bool(torch.isnan(flato[0]))
 
 
+@pytest.mark.parametrize("B,D,h,w", [(3, 128, 5, 7),       # P = 35: the scalar map form; R = 105: a ragged last tile; two channel tiles
+                                     (2, 64, 6, 6),        # the vector form; R = 72: a ragged last tile
+                                     (1, 64, 1, 1)])
+def test_the_shared_movers_agree_with_the_necks(B, D, h, w):
+    """The necks' level-0 movers and the head's are one map side and one row side (csrc/bn_tile.hpp) on two row layouts: the
+    same bits in the plain rows and in the interior of the padded format, both ways; the ring stays as it was."""
+    from mem_amd import ops
+    gen = torch.Generator().manual_seed(B * 100 + h * 10 + w)
+    x = (torch.randn(B, D, h, w, generator=gen) * 3.0).cuda()
+    rows = ops.neck_maps_to_rows(x, 0)
+    pad = ops.map_to_nhwc_pad(x, torch.zeros((B, h + 2, w + 2, D), dtype=torch.bfloat16, device="cuda"))
+    ring = torch.ones(B, h + 2, w + 2, dtype=torch.bool, device="cuda")
+    ring[:, 1:-1, 1:-1] = False
+    assert torch.equal(rows.view(B, h, w, D), pad[:, 1:-1, 1:-1])
+    assert bool((pad[ring] == 0).all())
+    back = (torch.randn(B * h * w, D, generator=gen) * 3.0).to(torch.bfloat16).cuda()
+    padded = torch.zeros_like(pad)
+    padded[:, 1:-1, 1:-1] = back.view(B, h, w, D)
+    assert torch.equal(ops.neck_rows_to_maps(back, B, D, h, w, 0), ops.nhwc_pad_to_map(padded))
+
+
 # ---------------------------------------------------------------------------------------------- batch statistics
 @pytest.mark.parametrize("B,C,h,w", [(2, 64, 5, 7), (3, 128, 6, 10), (1, 256, 4, 6), (2, 64, 48, 49)])
 @pytest.mark.parametrize("padded", [True, False])
