@@ -1288,6 +1288,98 @@ struct memhip_bnhead_plan {
 typedef struct memhip_bnhead_plan memhip_bnhead_plan_t;
 int memhip_bnhead_plan(const memhip_bnhead_args_t* args, memhip_bnhead_plan_t* out);
 
+/* ------------------------------------------------------------------------
+ * Pyramid pooling of the PSP decode head (ppm.hip, ppm_plan.cpp; additive to ABI 10)
+ * replaces mmseg 0.30 PSPHead.forward / UPerHead.psp_forward up to the bottleneck's operand
+ *          (mmseg/models/decode_heads/psp_head.py: PPM = per pool scale AdaptiveAvgPool2d(s) -> ConvModule(1x1, no bias,
+ *          SyncBN, ReLU) -> resize(bilinear, size of the input); psp_outs = cat([x] + ppm_outs, dim=1) -> bottleneck)
+ *          decode_head = dict(type='UPerHead', pool_scales=(1, 2, 3, 6), channels=512, ...)
+ *          mem/semantic_segmentation/configs/_base_/models/upernet_beit.py:25-37
+ * ------------------------------------------------------------------------
+ * Everything is on the activation format of the FCN head above: bf16 [B, m+2, m'+2, channels] with a zero ring that is never
+ * written.  n <= MEMHIP_PPM_MAX_SCALES pool scales, 1 <= s <= MEMHIP_PPM_MAX_SCALE, s <= min(h, w).  Per scale i:
+ *   P_i  bf16 [B, s+2, s+2, Cin]  the pooled map, operand of the 1x1 convolution (memhip_conv2d_nhwc) and of its weight gradient
+ *   Y_i  bf16 [B, s+2, s+2, C]    the 1x1 convolution's output; its batch statistics are memhip_bn_stats_nhwc
+ * and Xcat bf16 [B, h+2, w+2, Cin + n C] is the operand of the bottleneck's 3x3 convolution: channels [0, Cin) the map,
+ * channels Cin + i C + c the upsampled activation of scale i.  Neither relu(bn(Y_i)) nor an upsampled map nor an fp32 concat
+ * is ever stored.  mean / rstd / gamma / beta / sums / tot are f32 [n, C] resp. [n, 2, C], scale-major.
+ *
+ * Pool bins: bin i of s over n pixels is [floor(i n / s), ceil((i + 1) n / s)), integer arithmetic; memhip_ppm_bins fills
+ * HOST arrays start[s], end[s] with the arithmetic the kernels use.  With s <= n a pixel lies in at most two bins per axis.
+ * Bilinear weights: memhip_seg_axis_table(s, h, ...) and (s, w, ...) of the segmentation loss, uploaded by the caller; forward
+ * and backward read the same tables.  Taps combine as w0y (w0x a + w1x b) + w1y (w0x c + w1x d).
+ *
+ *   memhip_ppm_pool:             map f32 [B, Cin, h, w], read once -> the interiors of all P_i in one launch: the fp32 sum of a
+ *                                bin in row-major order, divided by the bin's pixel count, rounded to bf16 (nearest even).  A
+ *                                bin of one pixel holds the bits of memhip_map_to_nhwc_pad.
+ *   memhip_ppm_concat_fwd:       the interior of Xcat in one launch: channels [0, Cin) the bits of memhip_map_to_nhwc_pad; channel
+ *                                Cin + i C + c = bf16(bilinear(relu(gamma xhat + beta))), xhat = (Y_i - mean) rstd at the four taps.
+ *   memhip_ppm_concat_bwd_sums:  from dXcat (channels >= Cin): dA[b, bin, c] = the sum over the outputs lo .. hi of both axes
+ *                                of (wy wx) dXcat, rows then columns ascending; g_i f32 [B s^2, C] = dA (u > 0); sums f32
+ *                                [n, 2, C] = sum g, sum g xhat over (b, bin): 32 row lanes, each an ascending chain, folded in
+ *                                order by the one workgroup that owns the 64 channels.
+ *   memhip_ppm_bwd_apply:        the interiors of dY_i bf16 = gamma rstd (g - tot[i, 0] inv_n[i] - xhat tot[i, 1] inv_n[i]);
+ *                                tot NULL: eval statistics, no correction terms.
+ *   memhip_ppm_dmap:             dmap f32 [B, Cin, h, w], overwritten = f32(dXcat[.., c < Cin]) + for each scale, bin row and bin
+ *                                column holding the pixel (in that order, at most 2 x 2 per scale) f32(dP_i) / count(bin).
+ * No float atomics, no workspace: every sum is a gather in an order fixed by the shapes alone, so two calls give the same
+ * bits.  Every bf16 buffer and vector 16-byte aligned.  One host struct for the five calls and the plan; a field another call
+ * owns is ignored.  B == 0 is MEMHIP_OK, nothing is read. */
+#define MEMHIP_PPM_MAX_SCALES 4
+#define MEMHIP_PPM_MAX_SCALE 8
+int memhip_ppm_bins(int n, int s, int32_t* start, int32_t* end);
+
+struct memhip_ppm_args {
+  int32_t B, Cin, C, h, w;
+  int32_t n;                         /* pool scales, 1 .. MEMHIP_PPM_MAX_SCALES */
+  int32_t scales[MEMHIP_PPM_MAX_SCALES];
+  const float* map;                  /* device f32 [B, Cin, h, w] (_pool, _concat_fwd) */
+  void* P[MEMHIP_PPM_MAX_SCALES];    /* device bf16 [B, s+2, s+2, Cin] (_pool writes the interiors) */
+  const void* Y[MEMHIP_PPM_MAX_SCALES];   /* device bf16 [B, s+2, s+2, C] (_concat_fwd, _concat_bwd_sums, _bwd_apply) */
+  const float* mean; const float* rstd; const float* gamma; const float* beta;   /* device f32 [n, C] */
+  /* device: the tables (s -> h) and (s -> w) of memhip_seg_axis_table per scale (_concat_fwd, _concat_bwd_sums) */
+  const int32_t* y_i0[MEMHIP_PPM_MAX_SCALES]; const float* y_w1[MEMHIP_PPM_MAX_SCALES];
+  const int32_t* y_lo[MEMHIP_PPM_MAX_SCALES]; const int32_t* y_hi[MEMHIP_PPM_MAX_SCALES];
+  const int32_t* x_i0[MEMHIP_PPM_MAX_SCALES]; const float* x_w1[MEMHIP_PPM_MAX_SCALES];
+  const int32_t* x_lo[MEMHIP_PPM_MAX_SCALES]; const int32_t* x_hi[MEMHIP_PPM_MAX_SCALES];
+  void* xcat;                        /* device bf16 [B, h+2, w+2, Cin + n C] (_concat_fwd writes the interior) */
+  const void* dxcat;                 /* device bf16, the same shape (_concat_bwd_sums: channels >= Cin, _dmap: channels < Cin) */
+  float* g[MEMHIP_PPM_MAX_SCALES];   /* device f32 [B s^2, C] (_concat_bwd_sums writes, _bwd_apply reads) */
+  float* sums;                       /* device f32 [n, 2, C] (_concat_bwd_sums) */
+  const float* tot;                  /* device f32 [n, 2, C], or NULL: eval statistics (_bwd_apply) */
+  float inv_n[MEMHIP_PPM_MAX_SCALES];     /* > 0 when tot is given */
+  void* dY[MEMHIP_PPM_MAX_SCALES];   /* device bf16 [B, s+2, s+2, C] (_bwd_apply writes the interiors) */
+  const void* dP[MEMHIP_PPM_MAX_SCALES];  /* device bf16 [B, s+2, s+2, Cin] (_dmap) */
+  float* dmap;                       /* device f32 [B, Cin, h, w] (_dmap) */
+};
+typedef struct memhip_ppm_args memhip_ppm_args_t;
+int memhip_ppm_pool(const memhip_ppm_args_t* args, memhip_stream_t stream);
+int memhip_ppm_concat_fwd(const memhip_ppm_args_t* args, memhip_stream_t stream);
+int memhip_ppm_concat_bwd_sums(const memhip_ppm_args_t* args, memhip_stream_t stream);
+int memhip_ppm_bwd_apply(const memhip_ppm_args_t* args, memhip_stream_t stream);
+int memhip_ppm_dmap(const memhip_ppm_args_t* args, memhip_stream_t stream);
+
+/* The launches of the five calls as data.  memhip_ppm_plan validates the struct like the calls do (same codes and messages),
+ * except that pointers may be NULL.  Host arithmetic only. */
+struct memhip_ppm_plan {
+  int64_t R;                         /* B h w pixels (0: nothing to do) */
+  int32_t block;                     /* threads of every launch */
+  int32_t ct;                        /* channels of Xcat: Cin + n C */
+  int32_t bins;                      /* sum of s^2 */
+  int32_t rows[MEMHIP_PPM_MAX_SCALES];        /* B s^2 */
+  int32_t row_tile0[MEMHIP_PPM_MAX_SCALES];   /* the first tile of 32 rows of scale i in the (scale, row) grids */
+  int32_t pool_grid, pool_lds_bytes;          /* a workgroup per (sample, 64 channels): the tile and the bins' accumulators */
+  int32_t concat_grid_x, concat_grid_y;       /* x: tiles of 64 pixels, y: Cin / 64 map tiles, then n C / 64 pyramid tiles */
+  int32_t gather_grid_x, gather_grid_y;       /* _concat_bwd_sums, first launch, and _bwd_apply: x: tiles of 32 rows over the
+                                                 scales, y: C / 64 */
+  int32_t sums_grid_x, sums_grid_y;           /* _concat_bwd_sums, second launch: x: n, y: C / 64 */
+  int32_t dmap_grid_x, dmap_grid_y;           /* x: tiles of 64 pixels, y: Cin / 64 */
+  int32_t tile_lds_bytes;                     /* the 64 x 64 fp32 tile of _concat_fwd and _dmap; the fold's scratch of the sums */
+  uint64_t ws_bytes;                          /* 0: no call takes a workspace */
+};
+typedef struct memhip_ppm_plan memhip_ppm_plan_t;
+int memhip_ppm_plan(const memhip_ppm_args_t* args, memhip_ppm_plan_t* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1373,3 +1373,163 @@ def bnhead_bwd_apply(dlogit, y, B, C_, K, h, w, mean, rstd, gamma, beta, wcls, t
     a.tot, a.inv_n, a.dy_out = _p(tot), float(inv_n), dy_out.data_ptr()
     check(lib.memhip_bnhead_bwd_apply(C.byref(a), stream_ptr()), "bnhead_bwd_apply")
     return dy_out
+
+
+# ---------------------------------------------------------------- pyramid pooling of the PSP head (csrc/ppm.hip, ppm_plan.cpp)
+PPM_MAX_SCALES = 4                   # == MEMHIP_PPM_MAX_SCALES
+PPM_MAX_SCALE = 8                    # == MEMHIP_PPM_MAX_SCALE
+_vp4, _i32x4 = vp * PPM_MAX_SCALES, i32 * PPM_MAX_SCALES
+
+
+class PpmArgs(C.Structure):
+    """== memhip_ppm_args_t."""
+    _fields_ = [(n, i32) for n in ("B", "Cin", "C", "h", "w", "n")] + [("scales", _i32x4), ("map", vp), ("P", _vp4), ("Y", _vp4)] + \
+               [(n, vp) for n in ("mean", "rstd", "gamma", "beta")] + \
+               [(n, _vp4) for n in ("y_i0", "y_w1", "y_lo", "y_hi", "x_i0", "x_w1", "x_lo", "x_hi")] + \
+               [("xcat", vp), ("dxcat", vp), ("g", _vp4), ("sums", vp), ("tot", vp), ("inv_n", f32 * PPM_MAX_SCALES),
+                ("dY", _vp4), ("dP", _vp4), ("dmap", vp)]
+
+
+class PpmPlan(C.Structure):
+    """== memhip_ppm_plan_t."""
+    _fields_ = [("R", i64), ("block", i32), ("ct", i32), ("bins", i32), ("rows", _i32x4), ("row_tile0", _i32x4)] + \
+               [(n, i32) for n in ("pool_grid", "pool_lds_bytes", "concat_grid_x", "concat_grid_y", "gather_grid_x", "gather_grid_y",
+                                   "sums_grid_x", "sums_grid_y", "dmap_grid_x", "dmap_grid_y", "tile_lds_bytes")] + \
+               [("ws_bytes", C.c_uint64)]
+
+
+declare({
+    "memhip_ppm_bins": (i32, [i32, i32, vp, vp]),
+    "memhip_ppm_plan": (i32, [C.POINTER(PpmArgs), C.POINTER(PpmPlan)]),
+    "memhip_ppm_pool": (i32, [C.POINTER(PpmArgs), vp]),
+    "memhip_ppm_concat_fwd": (i32, [C.POINTER(PpmArgs), vp]),
+    "memhip_ppm_concat_bwd_sums": (i32, [C.POINTER(PpmArgs), vp]),
+    "memhip_ppm_bwd_apply": (i32, [C.POINTER(PpmArgs), vp]),
+    "memhip_ppm_dmap": (i32, [C.POINTER(PpmArgs), vp]),
+})
+
+
+def ppm_bins(n, s):
+    """The adaptive-average-pooling bins of s over n pixels as host arrays (start i32 [s], end i32 [s]): bin i is
+    [floor(i n / s), ceil((i + 1) n / s)), the kernels' own arithmetic.  No device needed."""
+    import numpy as np
+    start, end = np.empty(max(s, 0), np.int32), np.empty(max(s, 0), np.int32)
+    check(lib.memhip_ppm_bins(n, s, start.ctypes.data, end.ctypes.data), "ppm_bins")
+    return start, end
+
+
+def ppm_args(B, Cin, C_, h, w, scales, **fields):
+    """The memhip_ppm_args_t of the five ppm calls and ppm_plan.  Fields: a pointer field takes an address or None, a
+    per-scale field a sequence of them (or of floats: inv_n)."""
+    a = PpmArgs(B=B, Cin=Cin, C=C_, h=h, w=w, n=len(scales))
+    if len(scales) <= PPM_MAX_SCALES:                      # (more: the plan refuses n)
+        a.scales = _i32x4(*[int(s) for s in scales])
+    for k, v in fields.items():
+        if isinstance(v, (list, tuple)):
+            v = type(getattr(a, k))(*v)
+        setattr(a, k, v)
+    return a
+
+
+def ppm_plan(B, Cin, C_, h, w, scales, **fields):
+    """The PpmPlan of the five calls at these shapes: grids, LDS bytes.  Validates like the calls; no device."""
+    plan = PpmPlan()
+    check(lib.memhip_ppm_plan(C.byref(ppm_args(B, Cin, C_, h, w, scales, **fields)), C.byref(plan)), "ppm_plan")
+    return plan
+
+
+def _ppm_pads(bufs, B, scales, ch):
+    for t, s in zip(bufs, scales):
+        assert t.dtype == torch.bfloat16 and t.is_contiguous() and t.is_cuda and tuple(t.shape) == (B, s + 2, s + 2, ch), (tuple(t.shape), s, ch)
+    return [t.data_ptr() for t in bufs]
+
+
+def _ppm_vectors(a, vecs, n, C_):
+    for name, v in zip(("mean", "rstd", "gamma", "beta"), vecs):
+        assert v.dtype == torch.float32 and v.is_contiguous() and v.is_cuda and tuple(v.shape) == (n, C_), name
+        setattr(a, name, v.data_ptr())
+
+
+def _ppm_tables(a, scales, h, w, align_corners, device):
+    """the axis tables of every scale, (s -> h) and (s -> w), as seg_tables keeps them"""
+    keep = []
+    for name, n_out in (("y", h), ("x", w)):
+        ptrs = []
+        for s in scales:
+            t = seg_tables(s, n_out, align_corners, device)
+            keep.append(t)
+            ptrs.append(_table_ptrs(t, s, n_out))
+        for j, f in enumerate(("i0", "w1", "lo", "hi")):
+            setattr(a, name + "_" + f, _vp4(*[p[j] for p in ptrs]))
+    return keep
+
+
+def ppm_pool(x, scales, P):
+    """x f32 [B, Cin, h, w] contiguous -> the interiors of P[i] bf16 [B, s+2, s+2, Cin], every scale in one launch: the mean
+    over the bin (fp32 sum in row-major order / the count), rounded to bf16."""
+    assert x.dtype == torch.float32 and x.dim() == 4 and x.is_contiguous() and x.is_cuda
+    B, Cin, h, w = x.shape
+    a = ppm_args(B, Cin, 64, h, w, scales, map=x.data_ptr(), P=_ppm_pads(P, B, scales, Cin))
+    check(lib.memhip_ppm_pool(C.byref(a), stream_ptr()), "ppm_pool")
+    return P
+
+
+def ppm_concat_fwd(x, scales, Y, mean, rstd, gamma, beta, xcat, align_corners=False):
+    """The interior of xcat bf16 [B, h+2, w+2, Cin + n C]: channels < Cin the map (the bits of map_to_nhwc_pad), channel
+    Cin + i C + c the bilinear resize of relu(gamma (Y[i] - mean) rstd + beta); vectors f32 [n, C]."""
+    assert x.dtype == torch.float32 and x.dim() == 4 and x.is_contiguous() and x.is_cuda
+    B, Cin, h, w = x.shape
+    n, C_ = len(scales), Y[0].shape[-1]
+    assert xcat.dtype == torch.bfloat16 and xcat.is_contiguous() and tuple(xcat.shape) == (B, h + 2, w + 2, Cin + n * C_)
+    a = ppm_args(B, Cin, C_, h, w, scales, map=x.data_ptr(), Y=_ppm_pads(Y, B, scales, C_), xcat=xcat.data_ptr())
+    _ppm_vectors(a, (mean, rstd, gamma, beta), n, C_)
+    keep = _ppm_tables(a, scales, h, w, align_corners, x.device)
+    check(lib.memhip_ppm_concat_fwd(C.byref(a), stream_ptr()), "ppm_concat_fwd")
+    del keep
+    return xcat
+
+
+def ppm_concat_bwd_sums(dxcat, Cin, scales, Y, mean, rstd, gamma, beta, g, sums, align_corners=False):
+    """From dxcat bf16 [B, h+2, w+2, Cin + n C] (channels >= Cin): g[i] f32 [B s^2, C] = the transposed resize, gated by
+    u > 0; sums f32 [n, 2, C] = sum g, sum g xhat."""
+    B, h, w = dxcat.shape[0], dxcat.shape[1] - 2, dxcat.shape[2] - 2
+    n, C_ = len(scales), Y[0].shape[-1]
+    assert dxcat.dtype == torch.bfloat16 and dxcat.is_contiguous() and dxcat.is_cuda and dxcat.shape[3] == Cin + n * C_
+    for t, s in zip(g, scales):
+        assert t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (B * s * s, C_)
+    assert sums.dtype == torch.float32 and sums.is_contiguous() and tuple(sums.shape) == (n, 2, C_)
+    a = ppm_args(B, Cin, C_, h, w, scales, dxcat=dxcat.data_ptr(), Y=_ppm_pads(Y, B, scales, C_), g=[t.data_ptr() for t in g],
+                 sums=sums.data_ptr())
+    _ppm_vectors(a, (mean, rstd, gamma, beta), n, C_)
+    keep = _ppm_tables(a, scales, h, w, align_corners, dxcat.device)
+    check(lib.memhip_ppm_concat_bwd_sums(C.byref(a), stream_ptr()), "ppm_concat_bwd_sums")
+    del keep
+    return g, sums
+
+
+def ppm_bwd_apply(g, scales, Y, mean, rstd, gamma, beta, tot, inv_n, dY, hw):
+    """The interiors of dY[i] bf16 [B, s+2, s+2, C] = gamma rstd (g - tot[i, 0] inv_n[i] - xhat tot[i, 1] inv_n[i]); tot f32
+    [n, 2, C] or None: eval statistics, no correction terms; inv_n: a float per scale; hw = (h, w) of the map."""
+    n, C_ = len(scales), Y[0].shape[-1]
+    B = Y[0].shape[0]
+    for t, s in zip(g, scales):
+        assert t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (B * s * s, C_)
+    assert tot is None or (tot.dtype == torch.float32 and tot.is_contiguous() and tuple(tot.shape) == (n, 2, C_))
+    a = ppm_args(B, 64, C_, hw[0], hw[1], scales, Y=_ppm_pads(Y, B, scales, C_), g=[t.data_ptr() for t in g], tot=_p(tot),
+                 inv_n=[float(v) for v in inv_n], dY=_ppm_pads(dY, B, scales, C_))
+    _ppm_vectors(a, (mean, rstd, gamma, beta), n, C_)
+    check(lib.memhip_ppm_bwd_apply(C.byref(a), stream_ptr()), "ppm_bwd_apply")
+    return dY
+
+
+def ppm_dmap(dxcat, Cin, scales, dP, out):
+    """out f32 [B, Cin, h, w] = dxcat[.., :Cin] + the transposed pooling of dP[i] bf16 [B, s+2, s+2, Cin] (each bin's value
+    / its pixel count to every pixel of the bin), added in the order scale, bin row, bin column."""
+    B, h, w = dxcat.shape[0], dxcat.shape[1] - 2, dxcat.shape[2] - 2
+    assert dxcat.dtype == torch.bfloat16 and dxcat.is_contiguous() and dxcat.is_cuda and dxcat.shape[3] >= Cin
+    assert out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (B, Cin, h, w)
+    C_ = (dxcat.shape[3] - Cin) // len(scales)
+    assert C_ * len(scales) == dxcat.shape[3] - Cin
+    a = ppm_args(B, Cin, C_, h, w, scales, dxcat=dxcat.data_ptr(), dP=_ppm_pads(dP, B, scales, Cin), dmap=out.data_ptr())
+    check(lib.memhip_ppm_dmap(C.byref(a), stream_ptr()), "ppm_dmap")
+    return out

@@ -1,25 +1,36 @@
 """Segmentation decode heads: mmseg 0.30's ``FCNHead`` -- the reference's auxiliary head
 (mem/semantic_segmentation/configs/_base_/models/upernet_beit.py:38-50, configs/mem/upernet/mem_224_160k.py:64-77:
-``in_index=2, channels=256, num_convs=1, concat_input=False, dropout_ratio=0.1``) -- and ``SegModel``, the thin
+``in_index=2, channels=256, num_convs=1, concat_input=False, dropout_ratio=0.1``) --, mmseg 0.30's ``PSPHead``
+(mmseg/models/decode_heads/psp_head.py; its layers are ``UPerHead.psp_forward`` + ``cls_seg``, the pyramid branch of the
+reference's decode head, upernet_beit.py:25-37: ``pool_scales=(1, 2, 3, 6), channels=512``) and ``SegModel``, the thin
 ``EncoderDecoder`` that joins a backbone, a decode head and an optional auxiliary head::
 
-    feat      = ReLU(SyncBN(Conv2d(in_channels, channels, 3, padding=1, bias=False)(inputs[in_index])))   # mmcv ConvModule
-    seg_logit = Conv2d(channels, num_classes, 1)(Dropout2d(dropout_ratio)(feat))                           # cls_seg
+    FCNHead   feat = ReLU(SyncBN(Conv2d(in_channels, channels, 3, padding=1, bias=False)(inputs[in_index])))   # mmcv ConvModule
+    PSPHead   outs = [resize(ReLU(SyncBN(Conv2d(in_channels, channels, 1, bias=False)(AdaptiveAvgPool2d(s)(x)))), size of x)
+                      for s in pool_scales]                                                                    # PPM
+              feat = ReLU(SyncBN(Conv2d(in_channels + len(pool_scales) channels, channels, 3, padding=1, bias=False)(
+                         cat([x] + outs, dim=1))))                                                             # bottleneck
+    both      seg_logit = Conv2d(channels, num_classes, 1)(Dropout2d(dropout_ratio)(feat))                     # cls_seg
 
 ``impl="torch"`` runs these layers as plain torch ops on any device and dtype (the reference arm of tests and benchmark).
 ``impl="hip"`` runs them on the library: the engine's fp32 map moves into the tokenizer's activation format (bf16
-``[B, h+2, w+2, C]``, a zero ring), the 3x3 convolution, its data gradient and its weight gradient are the dVAE trainer's
-kernels, and everything between the convolution and the loss is one pass each way (csrc/seg_head.hip): batch statistics,
+``[B, h+2, w+2, C]``, a zero ring), the convolutions, their data gradients and their weight gradients are the dVAE trainer's
+kernels, and everything between the 3x3 convolution and the loss is one pass each way (csrc/seg_head.hip): batch statistics,
 then batch norm + ReLU + Dropout2d + classifier fused (the activation ``feat`` is never stored), and the backward split in
-``sums`` and ``apply`` so that the SyncBN exchange (``reduce``) sits between them.  Both arms own the same parameters and
-buffers under mmseg's keys, so a reference checkpoint's ``auxiliary_head.*`` loads with ``strict=True`` and moves freely
-between the arms.
+``sums`` and ``apply`` so that the SyncBN exchange (``reduce``) sits between them.  That walk is one piece of code for both
+heads (``_BnClsHead``).  ``PSPHead`` puts ``PyramidPooling`` in front of it (csrc/ppm.hip): all scales pooled in one pass over
+the map, and batch norm + ReLU + bilinear resize + concat written straight as the bottleneck's operand -- the branch
+activations, their upsampled maps and an fp32 concat are never stored.  Both arms own the same parameters and buffers under
+mmseg's keys, so a reference checkpoint's ``auxiliary_head.*`` (``FCNHead``) and the ``psp_modules.*`` / ``bottleneck.*`` entries
+of its ``decode_head.*`` (``PSPHead``) load with ``strict=True`` and move freely between the arms.
 
 Precision of the hip arm: the placement torch's bf16 autocast would use.  Convolution operands bf16 with fp32 accumulation,
-its output rounded to bf16 once; statistics, normalise -> affine -> ReLU -> dropout -> classifier in fp32 on fp32 parameters;
-the gradient of the convolution's output rounded to bf16 once; logits, parameter gradients and the returned map gradient fp32.
+each convolution output rounded to bf16 once; pooling sums, statistics, normalise -> affine -> ReLU -> interpolation -> dropout
+-> classifier in fp32 on fp32 parameters; a value is rounded to bf16 once where it becomes a convolution operand or the
+gradient of a convolution's output; logits, parameter gradients and the returned map gradient fp32.
 
-Out of scope: ``UPerHead``, ``num_convs != 1``, ``concat_input``, dilation, class weights, OHEM samplers, more than 32 classes.
+Out of scope: the rest of ``UPerHead`` (laterals, top-down path, FPN convolutions, ``fpn_bottleneck``; its pyramid branch is
+``PyramidPooling``), ``num_convs != 1``, ``concat_input``, dilation, class weights, OHEM samplers, more than 32 classes.
 """
 import torch
 import torch.nn as nn
@@ -27,81 +38,43 @@ import torch.nn.functional as F
 
 from . import ops
 from .seg_loss import SegCrossEntropy
-from .syncbn import BufferCache, add_affine_grads, all_reduce_sum, backward_totals, batch_vectors
+from .syncbn import BufferCache, add_affine_grads, all_reduce_sum, backward_totals, batch_vectors, batch_vectors_stacked, grad_of
 
 
 class ConvModule(nn.Module):
-    """mmcv's ConvModule as the head uses it: ``conv`` (no bias) -> ``bn`` -> ReLU, under mmcv's attribute names."""
+    """mmcv's ConvModule as the heads use it: ``conv`` (no bias) -> ``bn`` -> ReLU, under mmcv's attribute names."""
 
-    def __init__(self, in_channels, out_channels):
+    def __init__(self, in_channels, out_channels, kernel_size=3):
         super().__init__()
-        self.conv = nn.Conv2d(in_channels, out_channels, 3, padding=1, bias=False)
+        self.conv = nn.Conv2d(in_channels, out_channels, kernel_size, padding=kernel_size // 2, bias=False)
         self.bn = nn.BatchNorm2d(out_channels)
 
 
-class _FCNHeadFunction(torch.autograd.Function):
+class _HeadFunction(torch.autograd.Function):
     """The hip arm: fp32 map [B, Cin, h, w] -> logits, a [B, K, h, w] view of fp32 pixel rows.  The parameters are inputs so
     that a call under a frozen trunk still records; their gradients are accumulated into ``p.grad`` by the backward itself."""
 
     @staticmethod
-    def forward(ctx, head, x, w, gamma, beta, wcls, bcls):
-        ctx.head = head
+    def forward(ctx, head, x, *params):
+        ctx.head, ctx.n_params = head, len(params)
         out, ctx.saved = head._hip_forward(x, keep=True)
         return out
 
     @staticmethod
     def backward(ctx, dlogit):
-        return (None, ctx.head._hip_backward(ctx.saved, dlogit, ctx.needs_input_grad[1])) + (None,) * 5
+        return (None, ctx.head._hip_backward(ctx.saved, dlogit, ctx.needs_input_grad[1])) + (None,) * ctx.n_params
 
 
-class FCNHead(BufferCache, nn.Module):
-    """mmseg 0.30 ``FCNHead(num_convs=1, concat_input=False)`` with its loss.
+class _BnClsHead(BufferCache, nn.Module):
+    """What the decode heads share: the walk from the padded bf16 operand of a head's last 3x3 ConvModule (``_cm()``) to the
+    logits and back (``_tail_forward`` / ``_tail_backward``), the bf16 weight copies, Dropout2d's keys, and mmseg's interface."""
 
-    ``forward(inputs)``: the backbone's tuple of maps -> logits ``[B, num_classes, h, w]`` from ``inputs[in_index]`` (the hip
-    arm returns a strided view of pixel rows ``[B h w, num_classes]``, valid until this head's next call with that shape).
-    ``forward_train(inputs, seg_label)`` -> ``{"loss_seg", "acc_seg"}`` (mmseg's ``losses``), ``forward_test(inputs)`` -> logits.
-
-    The hip arm takes the engine's CUDA fp32 maps; ``in_channels`` and ``channels`` multiples of 64, ``channels <= 512``,
-    ``2 <= num_classes <= 32``.  Everything runs on the current stream, nothing synchronises with the host; buffers are
-    per shape and reused.  ``eval()`` uses the running statistics and drops nothing; under ``torch.no_grad()`` nothing is
-    saved.  ``reduce`` is the SyncBN exchange (``all_reduce_sum``).  Dropout2d follows the mask contract of ``ops.Dropout``
-    at site ``dropout_site``, row = sample, column = channel; the key of a training forward is ``drop_key`` when the caller
-    sets one (a ``(key0, key1)`` per step, like the engine's), else ``(torch.initial_seed(), number of the call)``."""
-
-    def __init__(self, in_channels=768, channels=256, num_classes=11, in_index=2, dropout_ratio=0.1, align_corners=False,
-                 loss_weight=0.4, ignore_index=255, impl="hip", num_convs=1, concat_input=False, kernel_size=3, dilation=1,
-                 class_weight=None, sampler=None, **kwargs):
-        super().__init__()
-        if num_convs != 1:
-            raise NotImplementedError("num_convs: FCNHead mirrors num_convs=1 only (one conv + BN + ReLU block)")
-        if concat_input:
-            raise NotImplementedError("concat_input: FCNHead mirrors concat_input=False only")
-        if kernel_size != 3:
-            raise NotImplementedError("kernel_size: FCNHead mirrors the 3x3 convolution only")
-        if dilation != 1:
-            raise NotImplementedError("dilation: FCNHead mirrors dilation=1 only")
-        if class_weight is not None:
-            raise NotImplementedError("class_weight: class weights are not part of mem_amd.seg_loss")
-        if sampler is not None:
-            raise NotImplementedError("sampler: pixel samplers (OHEM) are not part of mem_amd.seg_loss")
-        if kwargs:
-            raise TypeError(f"FCNHead: unsupported arguments {sorted(kwargs)}")
-        if impl not in ("hip", "torch"):
-            raise ValueError(f'impl: "hip" or "torch", got {impl!r}')
-        if not 0.0 <= dropout_ratio < 1.0:
-            raise ValueError(f"dropout_ratio: 0 <= p < 1, got {dropout_ratio!r}")
-        if impl == "hip":
-            if in_channels % 64 or channels % 64 or channels > 512:
-                raise ValueError(f"FCNHead(impl='hip'): in_channels={in_channels} and channels={channels} must be multiples of "
-                                 "64 and channels <= 512")
-            if not 2 <= num_classes <= 32:
-                raise ValueError(f"FCNHead(impl='hip'): 2 <= num_classes <= 32, got {num_classes}")
-        self.in_channels, self.channels, self.num_classes, self.in_index = in_channels, channels, num_classes, in_index
+    def _init_tail(self, channels, num_classes, in_index, dropout_ratio, align_corners, loss_weight, ignore_index, impl):
+        self.channels, self.num_classes, self.in_index = channels, num_classes, in_index
         self.dropout_ratio = float(dropout_ratio)
         self.align_corners = bool(align_corners)
         self.ignore_index = ignore_index
         self.impl = impl
-        self.convs = nn.Sequential(ConvModule(in_channels, channels))
         self.conv_seg = nn.Conv2d(channels, num_classes, 1)
         nn.init.normal_(self.conv_seg.weight, mean=0.0, std=0.01)          # mmseg: normal_init(self.conv_seg, mean=0, std=0.01)
         nn.init.constant_(self.conv_seg.bias, 0.0)
@@ -112,12 +85,39 @@ class FCNHead(BufferCache, nn.Module):
         self.keep_mask = None                # torch arm only: a [B, channels] 0/1 tensor in place of Dropout2d's own draw (tests)
         self._calls = 0
         self._bufs = {}
-        self._w = None
-        self._stamp = None
+        self._w = {}
+
+    @classmethod
+    def _check_common(cls, impl, dropout_ratio, in_channels, channels, num_classes, class_weight, sampler, kwargs):
+        name = cls.__name__
+        if class_weight is not None:
+            raise NotImplementedError("class_weight: class weights are not part of mem_amd.seg_loss")
+        if sampler is not None:
+            raise NotImplementedError("sampler: pixel samplers (OHEM) are not part of mem_amd.seg_loss")
+        if kwargs:
+            raise TypeError(f"{name}: unsupported arguments {sorted(kwargs)}")
+        if impl not in ("hip", "torch"):
+            raise ValueError(f'impl: "hip" or "torch", got {impl!r}')
+        if not 0.0 <= dropout_ratio < 1.0:
+            raise ValueError(f"dropout_ratio: 0 <= p < 1, got {dropout_ratio!r}")
+        if impl == "hip":
+            if in_channels % 64 or channels % 64 or channels > 512:
+                raise ValueError(f"{name}(impl='hip'): in_channels={in_channels} and channels={channels} must be multiples of "
+                                 "64 and channels <= 512")
+            if not 2 <= num_classes <= 32:
+                raise ValueError(f"{name}(impl='hip'): 2 <= num_classes <= 32, got {num_classes}")
+
+    def _cm(self):
+        """the ConvModule (3x3) in front of ``cls_seg``"""
+        raise NotImplementedError
+
+    def _params(self):
+        """the parameters the hip arm's backward feeds, in a fixed order"""
+        raise NotImplementedError
 
     # ------------------------------------------------------------------ the torch arm
-    def _torch_forward(self, x):
-        conv, bn = self.convs[0].conv, self.convs[0].bn
+    def _torch_tail(self, x):
+        conv, bn = self._cm().conv, self._cm().bn
         y = F.conv2d(x, conv.weight, None, padding=1)
         if bn.training:
             with torch.no_grad():
@@ -134,21 +134,26 @@ class FCNHead(BufferCache, nn.Module):
     def _buf_device(self):
         return self.conv_seg.weight.device
 
-    def _weights(self):
-        """(w16 [C, 9 Cin], wd16 [Cin, 9 C]): the bf16 operands of the forward and of the data gradient (the same kernel on
-        the flipped, transposed weight), packed (ky, kx, c)-major.  Refreshed when the parameter has changed, never per forward."""
+    def _packed(self, conv, kind):
+        """(w16 [N, k k Cin], wd16 [Cin, k k N]) of ``conv`` ("conv3" / "conv1"): the bf16 operands of the forward and of the data
+        gradient (the same kernel on the flipped, transposed weight), packed (ky, kx, c)-major.  Refreshed when the parameter
+        has changed, never per forward."""
         from .vae_model import pack_conv_weight, pack_dgrad_weight
-        w = self.convs[0].conv.weight
+        w = conv.weight
         stamp = (w._version, w.data_ptr())
-        if self._w is None or stamp != self._stamp:
+        got = self._w.get(id(conv))
+        if got is None or got[0] != stamp:
             wd = w.detach().float()
-            self._w = (pack_conv_weight(wd).to(torch.bfloat16).contiguous(), pack_dgrad_weight("conv3", wd).to(torch.bfloat16).contiguous())
-            self._stamp = stamp
-        return self._w
+            got = self._w[id(conv)] = (stamp, (pack_conv_weight(wd).to(torch.bfloat16).contiguous(),
+                                               pack_dgrad_weight(kind, wd).to(torch.bfloat16).contiguous()))
+        return got[1]
+
+    def _weights(self):
+        return self._packed(self._cm().conv, "conv3")
 
     def refresh(self):
-        """Drop the bf16 weight copies (a caller that changed the weight behind torch's version counter)."""
-        self._stamp = None
+        """Drop the bf16 weight copies (a caller that changed a weight behind torch's version counter)."""
+        self._w = {}
 
     def _dropout(self):
         if not (self.training and self.dropout_ratio > 0.0):
@@ -166,21 +171,20 @@ class FCNHead(BufferCache, nn.Module):
         return ops.bn_stats_nhwc(Y, B, h, w, C, ws, None, True, out=self._buf("stats", (3, C), torch.float32))
 
     def _vectors(self):
-        bn, cs = self.convs[0].bn, self.conv_seg
+        bn, cs = self._cm().bn, self.conv_seg
         return (bn.weight.detach().contiguous(), bn.bias.detach().contiguous(),
                 cs.weight.detach().reshape(self.num_classes, self.channels), cs.bias.detach().contiguous())
 
-    # ------------------------------------------------------------------ the hip arm: the two walks
-    def _hip_forward(self, x, keep):
-        B, Cin, h, w = x.shape
+    # ------------------------------------------------------------------ the hip arm: the shared walk
+    def _tail_forward(self, Xp, B, Cin, h, w, keep):
+        """Xp bf16 [B, h+2, w+2, Cin] -> (logits, what the backward needs)"""
         C, K = self.channels, self.num_classes
         w16, _ = self._weights()
-        Xp = ops.map_to_nhwc_pad(x, self._buf("xp", (B, h + 2, w + 2, Cin), zero=True))
         Y = self._buf("y", (B, h + 2, w + 2, C), zero=True)
         ops.conv2d_nhwc(Xp, w16, None, Y, B, h, w, Cin, C, 3, 1, 1)
         with torch.no_grad():
             # the convolution has no bias: the sums are unshifted
-            mean, rstd, inv_n = batch_vectors(self.convs[0].bn, lambda: self._stats(Y, B, h, w), self.reduce)
+            mean, rstd, inv_n = batch_vectors(self._cm().bn, lambda: self._stats(Y, B, h, w), self.reduce)
             gamma, beta, wcls, bcls = self._vectors()
         d = self._dropout()
         rows = self._buf("logits", (B * h * w, K), torch.float32)
@@ -188,10 +192,12 @@ class FCNHead(BufferCache, nn.Module):
         out = rows.view(B, h, w, K).permute(0, 3, 1, 2).detach()       # a fresh tensor on the buffer
         return out, ((Xp, Y, mean, rstd, inv_n, d, (B, Cin, h, w)) if keep else None)
 
-    def _hip_backward(self, saved, dlogit, need_dx):
+    def _tail_backward(self, saved, dlogit, need_dx):
+        """dlogit [B, K, h, w] -> dXp bf16 [B, h+2, w+2, Cin] (interiors; None when nobody needs it); the gradients of the
+        3x3 ConvModule and of ``conv_seg`` are added to ``p.grad``"""
         Xp, Y, mean, rstd, inv_n, d, (B, Cin, h, w) = saved
         C, K = self.channels, self.num_classes
-        conv, bn, cs = self.convs[0].conv, self.convs[0].bn, self.conv_seg
+        conv, bn, cs = self._cm().conv, self._cm().bn, self.conv_seg
         gamma, beta, wcls, _ = self._vectors()
         if dlogit.dtype != torch.float32:
             dlogit = dlogit.float()
@@ -219,7 +225,7 @@ class FCNHead(BufferCache, nn.Module):
             return None
         dXp = self._buf("dxp", (B, h + 2, w + 2, Cin))
         ops.conv2d_nhwc(dY, self._weights()[1], None, dXp, B, h, w, C, Cin, 3, 1, 1)
-        return ops.nhwc_pad_to_map(dXp, out=self._buf("dmap", (B, Cin, h, w), torch.float32)).detach()
+        return dXp
 
     # ------------------------------------------------------------------ mmseg's interface
     def forward(self, inputs):
@@ -228,12 +234,12 @@ class FCNHead(BufferCache, nn.Module):
             return self._torch_forward(x)
         if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.shape[1] == self.in_channels):
             from ._lib import MemhipError
-            raise MemhipError("FCNHead(impl='hip') takes the engine's CUDA fp32 map [B, %d, h, w] (no CPU fallback)" % self.in_channels)
+            raise MemhipError("%s(impl='hip') takes the engine's CUDA fp32 map [B, %d, h, w] (no CPU fallback)"
+                              % (type(self).__name__, self.in_channels))
         x = x.contiguous()
-        conv, bn, cs = self.convs[0].conv, self.convs[0].bn, self.conv_seg
-        params = [conv.weight, bn.weight, bn.bias, cs.weight, cs.bias]
+        params = self._params()
         if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params)):
-            return _FCNHeadFunction.apply(self, x, *params)
+            return _HeadFunction.apply(self, x, *params)
         return self._hip_forward(x.detach(), keep=False)[0]
 
     def forward_train(self, inputs, seg_label):
@@ -245,11 +251,215 @@ class FCNHead(BufferCache, nn.Module):
         return self.forward(inputs)
 
 
+class FCNHead(_BnClsHead):
+    """mmseg 0.30 ``FCNHead(num_convs=1, concat_input=False)`` with its loss.
+
+    ``forward(inputs)``: the backbone's tuple of maps -> logits ``[B, num_classes, h, w]`` from ``inputs[in_index]`` (the hip
+    arm returns a strided view of pixel rows ``[B h w, num_classes]``, valid until this head's next call with that shape).
+    ``forward_train(inputs, seg_label)`` -> ``{"loss_seg", "acc_seg"}`` (mmseg's ``losses``), ``forward_test(inputs)`` -> logits.
+
+    The hip arm takes the engine's CUDA fp32 maps; ``in_channels`` and ``channels`` multiples of 64, ``channels <= 512``,
+    ``2 <= num_classes <= 32``.  Everything runs on the current stream, nothing synchronises with the host; buffers are
+    per shape and reused.  ``eval()`` uses the running statistics and drops nothing; under ``torch.no_grad()`` nothing is
+    saved.  ``reduce`` is the SyncBN exchange (``all_reduce_sum``).  Dropout2d follows the mask contract of ``ops.Dropout``
+    at site ``dropout_site``, row = sample, column = channel; the key of a training forward is ``drop_key`` when the caller
+    sets one (a ``(key0, key1)`` per step, like the engine's), else ``(torch.initial_seed(), number of the call)``."""
+
+    def __init__(self, in_channels=768, channels=256, num_classes=11, in_index=2, dropout_ratio=0.1, align_corners=False,
+                 loss_weight=0.4, ignore_index=255, impl="hip", num_convs=1, concat_input=False, kernel_size=3, dilation=1,
+                 class_weight=None, sampler=None, **kwargs):
+        super().__init__()
+        if num_convs != 1:
+            raise NotImplementedError("num_convs: FCNHead mirrors num_convs=1 only (one conv + BN + ReLU block)")
+        if concat_input:
+            raise NotImplementedError("concat_input: FCNHead mirrors concat_input=False only")
+        if kernel_size != 3:
+            raise NotImplementedError("kernel_size: FCNHead mirrors the 3x3 convolution only")
+        if dilation != 1:
+            raise NotImplementedError("dilation: FCNHead mirrors dilation=1 only")
+        self._check_common(impl, dropout_ratio, in_channels, channels, num_classes, class_weight, sampler, kwargs)
+        self.in_channels = in_channels
+        self.convs = nn.Sequential(ConvModule(in_channels, channels))
+        self._init_tail(channels, num_classes, in_index, dropout_ratio, align_corners, loss_weight, ignore_index, impl)
+
+    def _cm(self):
+        return self.convs[0]
+
+    def _params(self):
+        conv, bn, cs = self.convs[0].conv, self.convs[0].bn, self.conv_seg
+        return [conv.weight, bn.weight, bn.bias, cs.weight, cs.bias]
+
+    def _torch_forward(self, x):
+        return self._torch_tail(x)
+
+    # ------------------------------------------------------------------ the hip arm: the movers around the shared walk
+    def _hip_forward(self, x, keep):
+        B, Cin, h, w = x.shape
+        Xp = ops.map_to_nhwc_pad(x, self._buf("xp", (B, h + 2, w + 2, Cin), zero=True))
+        return self._tail_forward(Xp, B, Cin, h, w, keep)
+
+    def _hip_backward(self, saved, dlogit, need_dx):
+        dXp = self._tail_backward(saved, dlogit, need_dx)
+        if dXp is None:
+            return None
+        B, Cin, h, w = saved[-1]
+        return ops.nhwc_pad_to_map(dXp, out=self._buf("dmap", (B, Cin, h, w), torch.float32)).detach()
+
+
+class PyramidPooling:
+    """The pyramid branch of ``PSPHead`` (and of a later ``UPerHead``) on the hip path: fp32 map ``[B, Cin, h, w]`` -> the
+    interior of ``Xcat`` bf16 ``[B, h+2, w+2, Cin + n C]`` (``forward``), and ``dXcat`` -> the fp32 map gradient (``backward``);
+    who consumes ``Xcat`` is the caller's business.  ``modules``: the 1x1 ``ConvModule`` per pool scale; ``owner``: whose buffer
+    cache (``_buf``, names under ``ppm.``), bf16 weight copies (``_packed``) and SyncBN hook (``reduce``) it uses.
+
+    Per training step one ``reduce(., "stats")`` for the statistics of all scales ([n, 3, C]) and one ``reduce(., "bwd")`` for
+    their backward sums ([n, 2, C])."""
+
+    def __init__(self, owner, modules, pool_scales, in_channels, channels, align_corners=False):
+        self.owner, self.modules, self.scales = owner, list(modules), tuple(int(s) for s in pool_scales)
+        self.in_channels, self.channels, self.align_corners = in_channels, channels, bool(align_corners)
+
+    def check(self, B, h, w, training):
+        """refuse what the kernels' tables and torch's batch norm refuse, by name"""
+        if min(h, w) < max(self.scales):
+            raise ValueError("pool_scales=%r on a map of %dx%d: the hip arm resizes upwards only, min(h, w) >= max(pool_scales)"
+                             % (self.scales, h, w))
+        if training:
+            import torch.distributed as dist
+            alone = not (dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1)
+            for s in self.scales:
+                if B * s * s == 1 and alone:
+                    raise ValueError("Expected more than 1 value per channel when training: pool scale %d of a batch of %d gives "
+                                     "its batch norm one value (torch's batch norm refuses it too)" % (s, B))
+
+    def _stats(self, Y, B):
+        C, o = self.channels, self.owner
+        ws = o._buf("ppm.stats.ws", (ops.BN_GROUPS * 2 * C,), torch.float32)
+        out = o._buf("ppm.stats", (len(self.scales), 3, C), torch.float32)
+        for i, s in enumerate(self.scales):
+            ops.bn_stats_nhwc(Y[i], B, s, s, C, ws, None, True, out=out[i])
+        return out
+
+    def forward(self, x, xcat, keep):
+        B, Cin, h, w = x.shape
+        C, o, sc = self.channels, self.owner, self.scales
+        P = [o._buf("ppm.p%d" % i, (B, s + 2, s + 2, Cin), zero=True) for i, s in enumerate(sc)]
+        ops.ppm_pool(x, sc, P)
+        Y = [o._buf("ppm.y%d" % i, (B, s + 2, s + 2, C), zero=True) for i, s in enumerate(sc)]
+        for i, s in enumerate(sc):
+            ops.conv2d_nhwc(P[i], o._packed(self.modules[i].conv, "conv1")[0], None, Y[i], B, s, s, Cin, C, 1, 1, 0)
+        with torch.no_grad():
+            bns = [m.bn for m in self.modules]
+            mean, rstd, inv_n = batch_vectors_stacked(bns, lambda: self._stats(Y, B), o.reduce)
+            gamma, beta = torch.stack([bn.weight.detach() for bn in bns]), torch.stack([bn.bias.detach() for bn in bns])
+        ops.ppm_concat_fwd(x, sc, Y, mean, rstd, gamma, beta, xcat, self.align_corners)
+        return (P, Y, mean, rstd, gamma, beta, inv_n, (B, Cin, h, w)) if keep else None
+
+    def backward(self, saved, dxcat, need_dx):
+        P, Y, mean, rstd, gamma, beta, inv_n, (B, Cin, h, w) = saved
+        C, o, sc = self.channels, self.owner, self.scales
+        n = len(sc)
+        g = [o._buf("ppm.g%d" % i, (B * s * s, C), torch.float32) for i, s in enumerate(sc)]
+        sums = o._buf("ppm.sums", (n, 2, C), torch.float32)
+        ops.ppm_concat_bwd_sums(dxcat, Cin, sc, Y, mean, rstd, gamma, beta, g, sums, self.align_corners)
+        for i, m in enumerate(self.modules):
+            add_affine_grads(m.bn, sums[i])
+        # the sums of every rank, divided on the device by the counts the forward's statistics had; eval statistics: none
+        tot = None if inv_n is None else (o.reduce(sums.clone(), "bwd") * inv_n[:, None, :]).contiguous()
+        dY = [o._buf("ppm.dy%d" % i, (B, s + 2, s + 2, C), zero=True) for i, s in enumerate(sc)]
+        ops.ppm_bwd_apply(g, sc, Y, mean, rstd, gamma, beta, tot, [1.0] * n, dY, (h, w))
+        for i, (s, m) in enumerate(zip(sc, self.modules)):
+            if m.conv.weight.requires_grad:
+                need = ops.conv_wgrad_workspace(B, s, s, Cin, C, 1, 1, 0)
+                wws = o._buf("ppm.wgrad.ws", (need,), torch.uint8) if need else None
+                gw = o._buf("ppm.wgrad", (C, Cin), torch.float32)
+                ops.conv_wgrad(dY[i], P[i], gw, B, s, s, Cin, C, 1, 1, 0, small_padded=True, accumulate=False, workspace=wws)
+                grad_of(m.conv.weight).add_(gw.view(C, Cin, 1, 1))
+        if not need_dx:
+            return None
+        dP = [o._buf("ppm.dp%d" % i, (B, s + 2, s + 2, Cin)) for i, s in enumerate(sc)]
+        for i, s in enumerate(sc):
+            ops.conv2d_nhwc(dY[i], o._packed(self.modules[i].conv, "conv1")[1], None, dP[i], B, s, s, C, Cin, 1, 1, 0)
+        return ops.ppm_dmap(dxcat, Cin, sc, dP, o._buf("ppm.dmap", (B, Cin, h, w), torch.float32)).detach()
+
+
+class PSPHead(_BnClsHead):
+    """mmseg 0.30 ``PSPHead`` (mmseg/models/decode_heads/psp_head.py) with its loss: pyramid pooling at ``pool_scales``, a 1x1
+    ConvModule per scale, bilinear resize back, concat with the input, a 3x3 bottleneck ConvModule, ``cls_seg`` -- the
+    layers, and under ``psp_modules.{i}.1.*`` / ``bottleneck.*`` the state-dict keys and shapes, of ``UPerHead.psp_forward`` in the
+    reference's decode head (mem/semantic_segmentation/configs/_base_/models/upernet_beit.py:25-37).
+
+    The interface, the hip arm's inputs and limits, Dropout2d's keys and ``reduce`` are ``FCNHead``'s.  In addition the hip
+    arm takes at most 4 pool scales, each ``1 <= s <= 8``, and maps with ``min(h, w) >= max(pool_scales)`` (7x7 at 224^2, 14x20
+    at 440x640); a training call in which a scale's batch norm would see one value (``B s^2 == 1``, no process group) is refused
+    as torch's batch norm refuses it.  ``reduce`` is called with the tags "stats", "stats" (pyramid, bottleneck) in a training
+    forward and "bwd", "bwd" (bottleneck, pyramid) in its backward."""
+
+    def __init__(self, in_channels=768, channels=512, num_classes=11, in_index=3, pool_scales=(1, 2, 3, 6), dropout_ratio=0.1,
+                 align_corners=False, loss_weight=1.0, ignore_index=255, impl="hip", class_weight=None, sampler=None, **kwargs):
+        super().__init__()
+        self._check_common(impl, dropout_ratio, in_channels, channels, num_classes, class_weight, sampler, kwargs)
+        pool_scales = tuple(pool_scales)
+        if not pool_scales or any(int(s) != s or s < 1 for s in pool_scales):
+            raise ValueError(f"pool_scales: positive integers, got {pool_scales!r}")
+        if impl == "hip":
+            if len(pool_scales) > ops.PPM_MAX_SCALES:
+                raise ValueError(f"PSPHead(impl='hip'): at most {ops.PPM_MAX_SCALES} pool_scales, got {pool_scales!r}")
+            if any(not 1 <= s <= ops.PPM_MAX_SCALE for s in pool_scales):
+                raise ValueError(f"PSPHead(impl='hip'): 1 <= s <= {ops.PPM_MAX_SCALE} for every s of pool_scales, got {pool_scales!r}")
+        self.in_channels, self.pool_scales = in_channels, tuple(int(s) for s in pool_scales)
+        self.psp_modules = nn.ModuleList(nn.Sequential(nn.AdaptiveAvgPool2d(s), ConvModule(in_channels, channels, 1))
+                                         for s in self.pool_scales)
+        self.bottleneck = ConvModule(in_channels + len(self.pool_scales) * channels, channels)
+        self._init_tail(channels, num_classes, in_index, dropout_ratio, align_corners, loss_weight, ignore_index, impl)
+        self.ppm = PyramidPooling(self, [seq[1] for seq in self.psp_modules], self.pool_scales, in_channels, channels, align_corners)
+
+    def _cm(self):
+        return self.bottleneck
+
+    def _params(self):
+        ps = []
+        for seq in self.psp_modules:
+            ps += [seq[1].conv.weight, seq[1].bn.weight, seq[1].bn.bias]
+        return ps + [self.bottleneck.conv.weight, self.bottleneck.bn.weight, self.bottleneck.bn.bias, self.conv_seg.weight, self.conv_seg.bias]
+
+    # ------------------------------------------------------------------ the torch arm: psp_head.py, line by line
+    def _torch_forward(self, x):
+        outs = [x]
+        for s, seq in zip(self.pool_scales, self.psp_modules):
+            conv, bn = seq[1].conv, seq[1].bn
+            y = F.conv2d(F.adaptive_avg_pool2d(x, s), conv.weight)
+            if bn.training:
+                with torch.no_grad():
+                    bn.num_batches_tracked += 1
+            z = F.relu(F.batch_norm(y, bn.running_mean, bn.running_var, bn.weight, bn.bias, bn.training, bn.momentum, bn.eps))
+            outs.append(F.interpolate(z, size=x.shape[2:], mode="bilinear", align_corners=self.align_corners))
+        return self._torch_tail(torch.cat(outs, 1))
+
+    # ------------------------------------------------------------------ the hip arm: the pyramid around the shared walk
+    def _hip_forward(self, x, keep):
+        B, Cin, h, w = x.shape
+        self.ppm.check(B, h, w, self.training)
+        ct = Cin + len(self.pool_scales) * self.channels
+        xcat = self._buf("xcat", (B, h + 2, w + 2, ct), zero=True)
+        pyramid = self.ppm.forward(x, xcat, keep)
+        out, tail = self._tail_forward(xcat, B, ct, h, w, keep)
+        return out, ((pyramid, tail) if keep else None)
+
+    def _hip_backward(self, saved, dlogit, need_dx):
+        pyramid, tail = saved
+        branches = any(p.requires_grad for seq in self.psp_modules for p in seq[1].parameters())
+        dxcat = self._tail_backward(tail, dlogit, need_dx or branches)
+        if dxcat is None:
+            return None
+        return self.ppm.backward(pyramid, dxcat, need_dx)
+
+
 class SegModel(nn.Module):
     """mmseg's ``EncoderDecoder``, thin: ``backbone`` (an ``EvBEiT``: images -> a tuple of maps), ``decode_head`` and an optional
-    ``auxiliary_head`` (``FCNHead``s).  ``forward_train(img, seg_label)`` -> ``{"decode.loss_seg", "decode.acc_seg", "aux.loss_seg",
-    "aux.acc_seg"}``; ``encode_decode(img)`` -> the decode head's logits at the head's resolution (``test_cfg.mode='whole'``:
-    the resize to the label's size is ``SegEvaluator``'s).  One object for an optimizer and an evaluator."""
+    ``auxiliary_head`` (``FCNHead`` or ``PSPHead``).  ``forward_train(img, seg_label)`` -> ``{"decode.loss_seg", "decode.acc_seg",
+    "aux.loss_seg", "aux.acc_seg"}``; ``encode_decode(img)`` -> the decode head's logits at the head's resolution
+    (``test_cfg.mode='whole'``: the resize to the label's size is ``SegEvaluator``'s).  One object for an optimizer and an evaluator."""
 
     def __init__(self, backbone, decode_head, auxiliary_head=None):
         super().__init__()

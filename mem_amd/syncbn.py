@@ -35,6 +35,26 @@ def batch_vectors(bn, stats, reduce, shift=None):
     return mean, torch.rsqrt(var + bn.eps), 1.0 / n
 
 
+def batch_vectors_stacked(bns, stats, reduce):
+    """``batch_vectors`` for several batch norms of one width whose statistics travel in ONE exchange (the pyramid branches of
+    ``PSPHead``): ``stats()`` -> f32 [len(bns), 3, C], unshifted, one ``reduce(., "stats")`` for all of them.  Returns (mean
+    [n, C], rstd [n, C], 1 / n [n, C]); the arithmetic and the bookkeeping per batch norm are ``batch_vectors``'s.  eval(): the
+    running statistics, no 1 / n; neither ``stats`` nor ``reduce`` is called."""
+    if not bns[0].training:
+        return (torch.stack([bn.running_mean for bn in bns]), torch.stack([torch.rsqrt(bn.running_var + bn.eps) for bn in bns]), None)
+    st = reduce(stats(), "stats")
+    n = st[:, 0]
+    mean = st[:, 1] / n
+    var = (st[:, 2] / n - mean * mean).clamp_(min=0.0)
+    with torch.no_grad():
+        for i, bn in enumerate(bns):
+            assert bn.momentum is not None, "the batch norm %r has momentum 0.1 (no cumulative average)" % (bn,)
+            bn.running_mean.mul_(1.0 - bn.momentum).add_(mean[i], alpha=bn.momentum)
+            bn.running_var.mul_(1.0 - bn.momentum).add_(var[i] * (n[i] / (n[i] - 1.0)), alpha=bn.momentum)
+            bn.num_batches_tracked += 1
+    return mean, torch.stack([torch.rsqrt(var[i] + bn.eps) for i, bn in enumerate(bns)]), 1.0 / n
+
+
 def grad_of(p):
     """``p.grad``, zeros at first use: the backward walks accumulate into it themselves."""
     if p.grad is None:
