@@ -961,7 +961,11 @@ int memhip_transpose_cast_f32_bf16(const float* in, int64_t ldin, int R, int Cc,
 /* n weight transposes (fp32 [R,C] -> bf16 [C, ldout], rows beyond R zero-filled up to min(ldout, 64-padded R))
  * in one launch: desc = device array of n records {const float* in; int64 ldin; int64 R; int64 C; bf16* out;
  * int64 ldout} (48 bytes each), tile_prefix = device i32 [n+1] with the first 64x64 tile index of every matrix
- * (tile_prefix[n] = total_tiles).  Same result as n calls of memhip_transpose_cast_f32_bf16. */
+ * (tile_prefix[n] = total_tiles).  Same result as n calls of memhip_transpose_cast_f32_bf16.
+ * The descriptors live on the device, so the entry cannot validate them.  Preconditions on every record, which the
+ * kernel's 16-byte stores rely on: ldout % 8 == 0 and ldout >= R, and `out` 16-byte aligned.  (`in` and ldin are free:
+ * a source that is not 16-byte aligned, or ldin % 4 != 0, takes the scalar load path.)  A launch on a slice
+ * desc + k0 takes a tile_prefix that starts at 0 for record k0. */
 int memhip_transpose_cast_batched(const void* desc, const int32_t* tile_prefix, int n, int total_tiles,
                                   memhip_stream_t stream);
 
@@ -1000,7 +1004,9 @@ int memhip_adamw(float* p, const float* g, float* m, float* v, int64_t n, const 
 /* The same step with per-group learning rates / weight decay (layer-wise lr decay of finetuning:
  * replaces get_parameter_groups + LayerDecayValueAssigner   mem/optim_factory.py:31-100 feeding optim.AdamW).
  * group_of_chunk u8 [n/1024]; group_table f32 [n_groups][2] (device) = {1 - lr_g*wd_g, lr_g / (1 - beta1^step)},
- * computed by the caller in double and rounded once, like torch's Python-side scalars. */
+ * computed by the caller in double and rounded once, like torch's Python-side scalars.
+ * Precondition the entry cannot check (group_of_chunk lives on the device): every group_of_chunk[c] < n_groups; a
+ * larger id reads beyond the table.  A group {1, 0} is frozen: its parameters keep their bits, its moments still move. */
 int memhip_adamw_groups(float* p, const float* g, float* m, float* v, int64_t n, const uint8_t* group_of_chunk,
                         const float* group_table, int n_groups, double beta1, double beta2, double eps, int step,
                         const float* gnorm, double max_norm, memhip_stream_t stream);
