@@ -1386,6 +1386,119 @@ struct memhip_ppm_plan {
 typedef struct memhip_ppm_plan memhip_ppm_plan_t;
 int memhip_ppm_plan(const memhip_ppm_args_t* args, memhip_ppm_plan_t* out);
 
+/* ------------------------------------------------------------------------
+ * The FPN part of the UPerNet decode head (fpn.hip, fpn_plan.cpp; additive to ABI 10)
+ * replaces mmseg 0.30 UPerHead.forward between the convolutions (mmseg/models/decode_heads/uper_head.py): the top-down
+ *          path laterals[i - 1] += resize(laterals[i], size of i - 1, bilinear), and fpn_outs[i] = resize(fpn_outs[i], size
+ *          of level 0); cat(fpn_outs, dim=1) -> fpn_bottleneck; every ConvModule Conv2d(no bias) -> SyncBN -> ReLU
+ *          decode_head = dict(type='UPerHead', in_index=[0, 1, 2, 3], channels=512, ...)
+ *          mem/semantic_segmentation/configs/_base_/models/upernet_beit.py:25-37
+ * ------------------------------------------------------------------------
+ * L levels (2 .. MEMHIP_FPN_MAX_LEVELS) of h[l] x w[l] pixels, finest first, non-increasing in both axes (the tables resize
+ * upwards only; equal sizes are allowed), all of C channels (C % 64 == 0, C <= 512).  Everything is on the activation format
+ * of the heads above: bf16 [B, h_l+2, w_l+2, channels] with a ring that is neither read nor written.  The 1x1 / 3x3
+ * convolutions, their data and weight gradients and the batch statistics are memhip_conv2d_nhwc / memhip_conv_wgrad_nhwc /
+ * memhip_bn_stats_nhwc.  Per level l:
+ *   Y[l]   bf16  a stored convolution output whose ReLU(SyncBN(.)) a call evaluates on the fly: which one is the caller's
+ *                business (the lateral's, the FPN convolution's, at l = L - 1 the pyramid bottleneck's "Ypsp")
+ *   T_l    bf16  the top-down sum, operand of FPN convolution l
+ * BN vectors mean / rstd / gamma / beta are f32 [L, C], level-major: row l belongs to Y[l].
+ * Bilinear weights: memhip_seg_axis_table(n_in, n_out, ...) uploaded by the caller, two families: "c" (h_l -> h_0, w_l ->
+ * w_0: the concat) and "t" (h_{l+1} -> h_l, w_{l+1} -> w_l, stored at index l: the top-down step).  Forward and backward read
+ * the same tables; taps combine as w0y (w0x a + w1x b) + w1y (w0x c + w1x d), u = gamma xhat + beta with xhat = (Y - mean) rstd.
+ *
+ *   memhip_fpn_topdown_fwd:  level = l <= L - 2.  The interior of T (= T_l) = bf16(relu(u(Y[l])) + bilinear_{l+1 -> l}(src)),
+ *                            src = the stored T_{l+1} (`src`, plain bf16), or with src NULL (l == L - 2 only) relu(u(Y[l+1]))
+ *                            evaluated in fp32 at the four taps: the activated coarsest lateral is never stored.
+ *   memhip_fpn_concat_fwd:   the interior of xcat bf16 [B, h_0+2, w_0+2, L C] in one launch: channel l C + c =
+ *                            bf16(bilinear_{l -> 0}(relu(u(Y[l])))).  An identity table (every w1 == 0, level 0 always)
+ *                            gives exactly bf16(relu(u(Y[l]))).
+ *   memhip_fpn_resize_bwd:   level = the destination d.  rows f32 [B h_d w_d, C] = the sum, in this order, of
+ *                            own (bf16 padded map of the destination's size, or NULL), the transposed resize of channel
+ *                            slice `slice` of dxcat (bf16, pitch L C, table c[d]; or NULL) and the transposed resize of
+ *                            fine_rows f32 [B h_{d-1} w_{d-1}, C] (table t[d-1]; or NULL; d >= 1).  A transposed resize is
+ *                            a gather over the outputs lo .. hi of both axes, rows then columns ascending, one fused
+ *                            multiply-add each.  The rows are ungated.
+ *   memhip_fpn_bn_bwd_sums:  level = l.  sums f32 [2, C] = sum g, sum g xhat over the B h_l w_l pixels, g = rows (u(Y[l]) > 0).
+ *                            Two stages as memhip_bn_stats_nhwc: G = min(ceil(R / 32), MEMHIP_BN_GROUPS) workgroups per 64
+ *                            channels, a fixed-order chain per thread over the rows r = 32 g + j, + 32 G, .., the 32 row
+ *                            lanes folded in LDS in order, one partial per workgroup stored plainly into `workspace`
+ *                            (memhip_fpn_plan_t.ws_bytes), the G partials added in ascending order by a second launch.
+ *   memhip_fpn_bn_bwd_apply: level = l.  The interior of dY bf16 = gamma rstd (g - tot[0] inv_n - xhat tot[1] inv_n), g as
+ *                            above; tot f32 [2, C], or NULL: eval statistics, no correction terms.
+ * No float atomics: two calls give the same bits.  Every bf16 buffer, vector and f32 row buffer 16-byte aligned.  One host
+ * struct for the five calls and the plan; NULL / 0 = off; a field another call owns is ignored.  B == 0 is MEMHIP_OK, nothing
+ * is read. */
+#define MEMHIP_FPN_MAX_LEVELS 4
+
+struct memhip_fpn_args {
+  int32_t B, C, L;
+  int32_t level;                     /* 0 .. L - 1: the level of a per-level call (every call but _concat_fwd) */
+  int32_t h[MEMHIP_FPN_MAX_LEVELS];
+  int32_t w[MEMHIP_FPN_MAX_LEVELS];
+  const void* Y[MEMHIP_FPN_MAX_LEVELS];   /* device bf16 [B, h_l+2, w_l+2, C] */
+  const float* mean; const float* rstd; const float* gamma; const float* beta;   /* device f32 [L, C] */
+  /* device: the tables (h_l -> h_0) and (w_l -> w_0) per level (_concat_fwd: all; _resize_bwd: of `level`, with dxcat) */
+  const int32_t* cy_i0[MEMHIP_FPN_MAX_LEVELS]; const float* cy_w1[MEMHIP_FPN_MAX_LEVELS];
+  const int32_t* cy_lo[MEMHIP_FPN_MAX_LEVELS]; const int32_t* cy_hi[MEMHIP_FPN_MAX_LEVELS];
+  const int32_t* cx_i0[MEMHIP_FPN_MAX_LEVELS]; const float* cx_w1[MEMHIP_FPN_MAX_LEVELS];
+  const int32_t* cx_lo[MEMHIP_FPN_MAX_LEVELS]; const int32_t* cx_hi[MEMHIP_FPN_MAX_LEVELS];
+  /* device: the tables (h_{l+1} -> h_l) and (w_{l+1} -> w_l) at index l (_topdown_fwd: of `level`; _resize_bwd: of
+     `level` - 1, with fine_rows) */
+  const int32_t* ty_i0[MEMHIP_FPN_MAX_LEVELS]; const float* ty_w1[MEMHIP_FPN_MAX_LEVELS];
+  const int32_t* ty_lo[MEMHIP_FPN_MAX_LEVELS]; const int32_t* ty_hi[MEMHIP_FPN_MAX_LEVELS];
+  const int32_t* tx_i0[MEMHIP_FPN_MAX_LEVELS]; const float* tx_w1[MEMHIP_FPN_MAX_LEVELS];
+  const int32_t* tx_lo[MEMHIP_FPN_MAX_LEVELS]; const int32_t* tx_hi[MEMHIP_FPN_MAX_LEVELS];
+  /* memhip_fpn_topdown_fwd */
+  const void* src;                   /* device bf16 [B, h_{l+1}+2, w_{l+1}+2, C]: T_{l+1}; NULL: relu(u(Y[l+1])), l == L - 2 */
+  void* T;                           /* device bf16 [B, h_l+2, w_l+2, C] */
+  /* memhip_fpn_concat_fwd */
+  void* xcat;                        /* device bf16 [B, h_0+2, w_0+2, L C] */
+  /* memhip_fpn_resize_bwd */
+  const void* own;                   /* device bf16 [B, h_d+2, w_d+2, C], or NULL */
+  const void* dxcat;                 /* device bf16 [B, h_0+2, w_0+2, L C], or NULL */
+  const float* fine_rows;            /* device f32 [B h_{d-1} w_{d-1}, C], or NULL */
+  int32_t slice;                     /* 0 .. L - 1: the channel slice of dxcat */
+  int32_t reserved0;
+  float* rows;                       /* device f32 [B h_d w_d, C]: _resize_bwd writes, _bn_bwd_sums and _bn_bwd_apply read */
+  /* memhip_fpn_bn_bwd_sums */
+  float* sums;                       /* device f32 [2, C] */
+  void* workspace;                   /* device, workspace_bytes >= memhip_fpn_plan_t.ws_bytes, 16-byte aligned */
+  size_t workspace_bytes;
+  /* memhip_fpn_bn_bwd_apply */
+  const float* tot;                  /* device f32 [2, C], or NULL: eval statistics */
+  float inv_n;                       /* > 0 when tot is given */
+  int32_t reserved1;
+  void* dY;                          /* device bf16 [B, h_l+2, w_l+2, C] */
+};
+typedef struct memhip_fpn_args memhip_fpn_args_t;
+int memhip_fpn_topdown_fwd(const memhip_fpn_args_t* args, memhip_stream_t stream);
+int memhip_fpn_concat_fwd(const memhip_fpn_args_t* args, memhip_stream_t stream);
+int memhip_fpn_resize_bwd(const memhip_fpn_args_t* args, memhip_stream_t stream);
+int memhip_fpn_bn_bwd_sums(const memhip_fpn_args_t* args, memhip_stream_t stream);
+int memhip_fpn_bn_bwd_apply(const memhip_fpn_args_t* args, memhip_stream_t stream);
+
+/* The launches of the five calls as data, for every level at once.  memhip_fpn_plan validates the struct like the calls do
+ * (same codes and messages), except that pointers may be NULL (workspace_bytes is compared only when there is a workspace).
+ * Host arithmetic only. */
+struct memhip_fpn_plan {
+  int64_t R[MEMHIP_FPN_MAX_LEVELS];           /* B h_l w_l pixels (0: nothing to do) */
+  int32_t block;                              /* threads of every launch */
+  int32_t ct;                                 /* channels of xcat: L C */
+  int32_t grid_y;                             /* C / 64: every per-level launch */
+  int32_t concat_grid_x, concat_grid_y;       /* x: tiles of 64 pixels of level 0, y: L C / 64 */
+  int32_t topdown_grid_x[MEMHIP_FPN_MAX_LEVELS];   /* tiles of 64 pixels of level l (0 at l = L - 1) */
+  int32_t resize_grid_x[MEMHIP_FPN_MAX_LEVELS];    /* tiles of 32 pixels of the destination l */
+  int32_t sums_grid_x[MEMHIP_FPN_MAX_LEVELS];      /* G_l = min(ceil(R_l / 32), MEMHIP_BN_GROUPS) */
+  int32_t apply_grid_x[MEMHIP_FPN_MAX_LEVELS];     /* tiles of 64 pixels of level l */
+  int32_t sums_lds_bytes;                     /* the fold's scratch: 2 x 32 x 64 floats */
+  int32_t slot_floats;                        /* workspace floats per workgroup of the sums: 2 C */
+  int32_t fold_grid;                          /* workgroups of the second launch of the sums */
+  uint64_t ws_bytes;                          /* MEMHIP_BN_GROUPS slots */
+};
+typedef struct memhip_fpn_plan memhip_fpn_plan_t;
+int memhip_fpn_plan(const memhip_fpn_args_t* args, memhip_fpn_plan_t* out);
+
 #ifdef __cplusplus
 }
 #endif

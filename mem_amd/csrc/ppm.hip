@@ -22,7 +22,7 @@
 //   dmap         tile of 64 pixels x 64 channels: dXcat's map channels plus the at most 2 x 2 bins per scale that hold the
 //                pixel, through the LDS tile to bn_tile.hpp's map side
 #include "common.h"
-#include "bn_tile.hpp"
+#include "bn_taps.hpp"
 #include "ppm_plan.hpp"
 
 namespace {
@@ -30,6 +30,7 @@ namespace {
 using namespace memhip;
 using namespace memhip::ppm;
 using bn::kT, bn::kTile, bn::kPitch, bn::f4, bn::us8, bn::bf16_t, bn::bf2f, bn::f2bf;
+using bn::clampi, bn::pad_at, bn::weight_of, bn::Chan8, bn::load8, bn::bn8;     // bn_taps.hpp: shared with fpn.hip
 static_assert(kThreads == kT && kChunk == kTile && kPixels == kTile && kTileLdsBytes == kTile * kPitch * 4, "the plan's constants are the tile's");
 constexpr int kN = MEMHIP_PPM_MAX_SCALES;
 
@@ -47,13 +48,6 @@ struct Dev {
   float* sums; const float* tot; float inv_n[kN];
 };
 
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
-// element offset of channel 0 of pixel (b, y, x) in a padded buffer of m x m' pixels and `pitch` channels
-__device__ __forceinline__ long long pad_at(long long b, int y, int x, int m, int mm, int pitch) {
-  return ((b * (m + 2) + y + 1) * (mm + 2) + x + 1) * pitch;
-}
-
 // where the rows of Xcat lie (bn_tile.hpp: row_side)
 struct CatRows {
   int h, w, P, CT;
@@ -64,34 +58,9 @@ struct CatRows {
   }
 };
 
-// the weight with which output (i0, i1 = min(i0 + 1, n - 1), w1) reads input i (seg_loss.hip)
-__device__ __forceinline__ float weight_of(int i, int i0, int i1, float w1) {
-  return (i0 == i ? 1.f - w1 : 0.f) + (i1 == i ? w1 : 0.f);
-}
-
-struct Chan8 { float m[8], rs[8], ga[8], be[8]; };
-
-__device__ __forceinline__ void load8(const float* __restrict__ p, float (&o)[8]) {
-  const f4 a = *reinterpret_cast<const f4*>(p), b = *reinterpret_cast<const f4*>(p + 4);
-#pragma unroll
-  for (int e = 0; e < 4; ++e) { o[e] = a[e]; o[4 + e] = b[e]; }
-}
-
 // the vectors of channels c .. c + 7 of scale i
 __device__ __forceinline__ Chan8 chan8(const Dev& d, int i, int c) {
-  Chan8 k;
-  const int o = i * d.C + c;
-  load8(d.mean + o, k.m); load8(d.rstd + o, k.rs); load8(d.gamma + o, k.ga); load8(d.beta + o, k.be);
-  return k;
-}
-
-// xhat, u = gamma xhat + beta of 8 channels of one pixel
-__device__ __forceinline__ void bn8(const us8& v, const Chan8& k, float (&xh)[8], float (&u)[8]) {
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    xh[e] = (bf2f(v[e]) - k.m[e]) * k.rs[e];
-    u[e] = fmaf(xh[e], k.ga[e], k.be[e]);
-  }
+  return bn::chan8(bn::BnParams{d.mean, d.rstd, d.gamma, d.beta}, i, d.C, c);
 }
 
 // ---------------------------------------------------------------- pool

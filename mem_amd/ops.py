@@ -1533,3 +1533,175 @@ def ppm_dmap(dxcat, Cin, scales, dP, out):
     a = ppm_args(B, Cin, C_, h, w, scales, dxcat=dxcat.data_ptr(), dP=_ppm_pads(dP, B, scales, Cin), dmap=out.data_ptr())
     check(lib.memhip_ppm_dmap(C.byref(a), stream_ptr()), "ppm_dmap")
     return out
+
+
+# ---------------------------------------------------------------- the FPN part of the UPerNet head (csrc/fpn.hip, fpn_plan.cpp)
+FPN_MAX_LEVELS = 4                   # == MEMHIP_FPN_MAX_LEVELS
+_FPN_TABLES = [ax + "_" + f for ax in ("cy", "cx", "ty", "tx") for f in ("i0", "w1", "lo", "hi")]
+
+
+class FpnArgs(C.Structure):
+    """== memhip_fpn_args_t."""
+    _fields_ = [(n, i32) for n in ("B", "C", "L", "level")] + [("h", _i32x4), ("w", _i32x4), ("Y", _vp4)] + \
+               [(n, vp) for n in ("mean", "rstd", "gamma", "beta")] + [(n, _vp4) for n in _FPN_TABLES] + \
+               [(n, vp) for n in ("src", "T", "xcat", "own", "dxcat", "fine_rows")] + [("slice", i32), ("reserved0", i32)] + \
+               [("rows", vp), ("sums", vp), ("workspace", vp), ("workspace_bytes", sz), ("tot", vp), ("inv_n", f32),
+                ("reserved1", i32), ("dY", vp)]
+
+
+class FpnPlan(C.Structure):
+    """== memhip_fpn_plan_t."""
+    _fields_ = [("R", i64 * FPN_MAX_LEVELS)] + [(n, i32) for n in ("block", "ct", "grid_y", "concat_grid_x", "concat_grid_y")] + \
+               [(n, _i32x4) for n in ("topdown_grid_x", "resize_grid_x", "sums_grid_x", "apply_grid_x")] + \
+               [(n, i32) for n in ("sums_lds_bytes", "slot_floats", "fold_grid")] + [("ws_bytes", C.c_uint64)]
+
+
+declare({
+    "memhip_fpn_plan": (i32, [C.POINTER(FpnArgs), C.POINTER(FpnPlan)]),
+    "memhip_fpn_topdown_fwd": (i32, [C.POINTER(FpnArgs), vp]),
+    "memhip_fpn_concat_fwd": (i32, [C.POINTER(FpnArgs), vp]),
+    "memhip_fpn_resize_bwd": (i32, [C.POINTER(FpnArgs), vp]),
+    "memhip_fpn_bn_bwd_sums": (i32, [C.POINTER(FpnArgs), vp]),
+    "memhip_fpn_bn_bwd_apply": (i32, [C.POINTER(FpnArgs), vp]),
+})
+
+
+def fpn_args(B, C_, sizes, level=0, **fields):
+    """The memhip_fpn_args_t of the five fpn calls and fpn_plan; sizes = [(h_l, w_l)], finest first.  Fields: a pointer field
+    takes an address or None, a per-level field a sequence of them."""
+    a = FpnArgs(B=B, C=C_, L=len(sizes), level=level)
+    if len(sizes) <= FPN_MAX_LEVELS:                       # (more: the plan refuses L)
+        a.h, a.w = _i32x4(*[int(s[0]) for s in sizes]), _i32x4(*[int(s[1]) for s in sizes])
+    for k, v in fields.items():
+        if isinstance(v, (list, tuple)):
+            v = type(getattr(a, k))(*v)
+        setattr(a, k, v)
+    return a
+
+
+def fpn_plan(B, C_, sizes, level=0, **fields):
+    """The FpnPlan of the five calls at these shapes, every level: grids, workspace bytes.  Validates like the calls; no device."""
+    plan = FpnPlan()
+    check(lib.memhip_fpn_plan(C.byref(fpn_args(B, C_, sizes, level, **fields)), C.byref(plan)), "fpn_plan")
+    return plan
+
+
+def fpn_sums_workspace(C_, device):
+    """the workspace of fpn_bn_bwd_sums: BN_GROUPS partials of [2, C], whatever the level"""
+    return torch.empty(BN_GROUPS * 2 * C_, dtype=torch.float32, device=device)
+
+
+def _fpn_pad(t, B, hw, ch, name):
+    assert t.dtype == torch.bfloat16 and t.is_contiguous() and t.is_cuda and tuple(t.shape) == (B, hw[0] + 2, hw[1] + 2, ch), \
+        (name, tuple(t.shape), B, hw, ch)
+    return t.data_ptr()
+
+
+def _fpn_vectors(a, vecs, L, C_):
+    for name, v in zip(("mean", "rstd", "gamma", "beta"), vecs):
+        assert v.dtype == torch.float32 and v.is_contiguous() and v.is_cuda and tuple(v.shape) == (L, C_), name
+        setattr(a, name, v.data_ptr())
+
+
+def _fpn_tables(a, family, sizes, levels, align_corners, device):
+    """family "c": the tables (level l -> level 0) at index l; "t": (level l + 1 -> level l) at index l, as seg_tables keeps
+    them; only the indices in ``levels`` are set"""
+    keep = []
+    for j, ax in enumerate("yx"):
+        ptrs = [(None,) * 4] * FPN_MAX_LEVELS
+        for l in levels:
+            n_in, n_out = (sizes[l][j], sizes[0][j]) if family == "c" else (sizes[l + 1][j], sizes[l][j])
+            t = seg_tables(n_in, n_out, align_corners, device)
+            keep.append(t)
+            ptrs[l] = _table_ptrs(t, n_in, n_out)
+        for k, f in enumerate(("i0", "w1", "lo", "hi")):
+            setattr(a, "%s%s_%s" % (family, ax, f), _vp4(*[p[k] for p in ptrs]))
+    return keep
+
+
+def _fpn_rows(t, n, C_, name):
+    assert t.dtype == torch.float32 and t.is_contiguous() and t.is_cuda and tuple(t.shape) == (n, C_), (name, tuple(t.shape), n, C_)
+    return t.data_ptr()
+
+
+def fpn_topdown_fwd(level, sizes, Y, vecs, src, T, align_corners=False):
+    """The interior of T bf16 [B, h_l+2, w_l+2, C] = bf16(relu(bn(Y)) + bilinear(level + 1 -> level)(src)); Y the lateral's
+    stored output of ``level``; src the stored T of level + 1, or (level == L - 2) a tuple ``(Ysrc,)``: the stored output whose
+    relu(bn(.)) with row level + 1 of the vectors is the source.  vecs = (mean, rstd, gamma, beta) f32 [L, C]."""
+    B, C_, L = Y.shape[0], Y.shape[-1], len(sizes)
+    a = fpn_args(B, C_, sizes, level, T=_fpn_pad(T, B, sizes[level], C_, "T"))
+    ys = [None] * FPN_MAX_LEVELS
+    ys[level] = _fpn_pad(Y, B, sizes[level], C_, "Y")
+    if isinstance(src, tuple):
+        ys[level + 1] = _fpn_pad(src[0], B, sizes[level + 1], C_, "Ysrc")
+    else:
+        a.src = _fpn_pad(src, B, sizes[level + 1], C_, "src")
+    a.Y = _vp4(*ys)
+    _fpn_vectors(a, vecs, L, C_)
+    keep = _fpn_tables(a, "t", sizes, [level], align_corners, Y.device)
+    check(lib.memhip_fpn_topdown_fwd(C.byref(a), stream_ptr()), "fpn_topdown_fwd")
+    del keep
+    return T
+
+
+def fpn_concat_fwd(sizes, Y, vecs, xcat, align_corners=False):
+    """The interior of xcat bf16 [B, h_0+2, w_0+2, L C]: channel l C + c = bf16(bilinear(level l -> level 0)(relu(bn_l(Y[l]))))."""
+    B, C_, L = Y[0].shape[0], Y[0].shape[-1], len(sizes)
+    a = fpn_args(B, C_, sizes, 0, xcat=_fpn_pad(xcat, B, sizes[0], L * C_, "xcat"),
+                 Y=[_fpn_pad(y, B, s, C_, "Y") for y, s in zip(Y, sizes)])
+    _fpn_vectors(a, vecs, L, C_)
+    keep = _fpn_tables(a, "c", sizes, range(L), align_corners, xcat.device)
+    check(lib.memhip_fpn_concat_fwd(C.byref(a), stream_ptr()), "fpn_concat_fwd")
+    del keep
+    return xcat
+
+
+def fpn_resize_bwd(level, sizes, C_, rows, own=None, dxcat=None, slice_=0, fine_rows=None, align_corners=False):
+    """rows f32 [B h_d w_d, C] (d = level) = own (bf16 padded, the destination's size) + the transposed resize of channel slice
+    ``slice_`` of dxcat bf16 [B, h_0+2, w_0+2, L C] + the transposed resize of fine_rows f32 [B h_{d-1} w_{d-1}, C], in that
+    order; each term optional.  Ungated."""
+    L, (h, w) = len(sizes), sizes[level]
+    B = rows.shape[0] // (h * w)
+    a = fpn_args(B, C_, sizes, level, rows=_fpn_rows(rows, B * h * w, C_, "rows"), slice=slice_)
+    keep = []
+    if own is not None:
+        a.own = _fpn_pad(own, B, sizes[level], C_, "own")
+    if dxcat is not None:
+        a.dxcat = _fpn_pad(dxcat, B, sizes[0], L * C_, "dxcat")
+        keep += _fpn_tables(a, "c", sizes, [level], align_corners, rows.device)
+    if fine_rows is not None:
+        a.fine_rows = _fpn_rows(fine_rows, B * sizes[level - 1][0] * sizes[level - 1][1], C_, "fine_rows")
+        keep += _fpn_tables(a, "t", sizes, [level - 1], align_corners, rows.device)
+    check(lib.memhip_fpn_resize_bwd(C.byref(a), stream_ptr()), "fpn_resize_bwd")
+    del keep
+    return rows
+
+
+def _fpn_bn_common(level, sizes, Y, vecs, rows):
+    B, C_, L, (h, w) = Y.shape[0], Y.shape[-1], len(sizes), sizes[level]
+    ys = [None] * FPN_MAX_LEVELS
+    ys[level] = _fpn_pad(Y, B, sizes[level], C_, "Y")
+    a = fpn_args(B, C_, sizes, level, Y=ys, rows=_fpn_rows(rows, B * h * w, C_, "rows"))
+    _fpn_vectors(a, vecs, L, C_)
+    return a, C_
+
+
+def fpn_bn_bwd_sums(level, sizes, Y, vecs, rows, sums, workspace):
+    """sums f32 [2, C] = sum g, sum g xhat over the level's pixels, g = rows (u > 0), u and xhat from Y and row ``level`` of
+    the vectors; workspace: fpn_sums_workspace."""
+    a, C_ = _fpn_bn_common(level, sizes, Y, vecs, rows)
+    assert sums.dtype == torch.float32 and sums.is_contiguous() and sums.is_cuda and tuple(sums.shape) == (2, C_)
+    assert workspace.is_cuda and workspace.is_contiguous()
+    a.sums, a.workspace, a.workspace_bytes = sums.data_ptr(), workspace.data_ptr(), workspace.numel() * workspace.element_size()
+    check(lib.memhip_fpn_bn_bwd_sums(C.byref(a), stream_ptr()), "fpn_bn_bwd_sums")
+    return sums
+
+
+def fpn_bn_bwd_apply(level, sizes, Y, vecs, rows, tot, inv_n, dY):
+    """The interior of dY bf16 [B, h_l+2, w_l+2, C] = gamma rstd (g - tot[0] inv_n - xhat tot[1] inv_n); tot f32 [2, C] or
+    None: eval statistics, no correction terms."""
+    a, C_ = _fpn_bn_common(level, sizes, Y, vecs, rows)
+    assert tot is None or (tot.dtype == torch.float32 and tot.is_contiguous() and tot.is_cuda and tuple(tot.shape) == (2, C_))
+    a.tot, a.inv_n, a.dY = _p(tot), float(inv_n), _fpn_pad(dY, Y.shape[0], sizes[level], C_, "dY")
+    check(lib.memhip_fpn_bn_bwd_apply(C.byref(a), stream_ptr()), "fpn_bn_bwd_apply")
+    return dY

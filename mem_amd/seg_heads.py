@@ -2,7 +2,8 @@
 (mem/semantic_segmentation/configs/_base_/models/upernet_beit.py:38-50, configs/mem/upernet/mem_224_160k.py:64-77:
 ``in_index=2, channels=256, num_convs=1, concat_input=False, dropout_ratio=0.1``) --, mmseg 0.30's ``PSPHead``
 (mmseg/models/decode_heads/psp_head.py; its layers are ``UPerHead.psp_forward`` + ``cls_seg``, the pyramid branch of the
-reference's decode head, upernet_beit.py:25-37: ``pool_scales=(1, 2, 3, 6), channels=512``) and ``SegModel``, the thin
+reference's decode head, upernet_beit.py:25-37: ``pool_scales=(1, 2, 3, 6), channels=512``), mmseg 0.30's ``UPerHead``
+(mmseg/models/decode_heads/uper_head.py: that decode head itself, ``in_index=[0, 1, 2, 3]``) and ``SegModel``, the thin
 ``EncoderDecoder`` that joins a backbone, a decode head and an optional auxiliary head::
 
     FCNHead   feat = ReLU(SyncBN(Conv2d(in_channels, channels, 3, padding=1, bias=False)(inputs[in_index])))   # mmcv ConvModule
@@ -10,7 +11,10 @@ reference's decode head, upernet_beit.py:25-37: ``pool_scales=(1, 2, 3, 6), chan
                       for s in pool_scales]                                                                    # PPM
               feat = ReLU(SyncBN(Conv2d(in_channels + len(pool_scales) channels, channels, 3, padding=1, bias=False)(
                          cat([x] + outs, dim=1))))                                                             # bottleneck
-    both      seg_logit = Conv2d(channels, num_classes, 1)(Dropout2d(dropout_ratio)(feat))                     # cls_seg
+    UPerHead  lat_l = ReLU(SyncBN(Conv2d(in_channels[l], channels, 1, bias=False)(inputs[in_index[l]]))), l < L - 1; lat_L-1 = PSPHead's
+              feat on the last level; top-down lat_l-1 += resize(lat_l); out_l = ReLU(SyncBN(Conv2d(channels, channels, 3, ..)(lat_l)));
+              feat = ReLU(SyncBN(Conv2d(L channels, channels, 3, padding=1, bias=False)(cat([out_0] + [resize(out_l)], 1))))  # fpn_bottleneck
+    all       seg_logit = Conv2d(channels, num_classes, 1)(Dropout2d(dropout_ratio)(feat))                     # cls_seg
 
 ``impl="torch"`` runs these layers as plain torch ops on any device and dtype (the reference arm of tests and benchmark).
 ``impl="hip"`` runs them on the library: the engine's fp32 map moves into the tokenizer's activation format (bf16
@@ -20,17 +24,20 @@ then batch norm + ReLU + Dropout2d + classifier fused (the activation ``feat`` i
 ``sums`` and ``apply`` so that the SyncBN exchange (``reduce``) sits between them.  That walk is one piece of code for both
 heads (``_BnClsHead``).  ``PSPHead`` puts ``PyramidPooling`` in front of it (csrc/ppm.hip): all scales pooled in one pass over
 the map, and batch norm + ReLU + bilinear resize + concat written straight as the bottleneck's operand -- the branch
-activations, their upsampled maps and an fp32 concat are never stored.  Both arms own the same parameters and buffers under
-mmseg's keys, so a reference checkpoint's ``auxiliary_head.*`` (``FCNHead``) and the ``psp_modules.*`` / ``bottleneck.*`` entries
-of its ``decode_head.*`` (``PSPHead``) load with ``strict=True`` and move freely between the arms.
+activations, their upsampled maps and an fp32 concat are never stored.  ``UPerHead`` puts the FPN part between the two
+(csrc/fpn.hip): the laterals and FPN convolutions are the library's, the top-down sums and ``fpn_bottleneck``'s operand are
+written with batch norm + ReLU + resize fused, and the backward transposes both as ordered gathers.  Both arms own the same
+parameters and buffers under mmseg's keys, so a reference checkpoint's ``auxiliary_head.*`` (``FCNHead``) and ``decode_head.*``
+(``UPerHead``; its ``psp_modules.*`` / ``bottleneck.*`` entries: ``PSPHead``) load with ``strict=True`` and move freely between
+the arms.
 
 Precision of the hip arm: the placement torch's bf16 autocast would use.  Convolution operands bf16 with fp32 accumulation,
 each convolution output rounded to bf16 once; pooling sums, statistics, normalise -> affine -> ReLU -> interpolation -> dropout
 -> classifier in fp32 on fp32 parameters; a value is rounded to bf16 once where it becomes a convolution operand or the
 gradient of a convolution's output; logits, parameter gradients and the returned map gradient fp32.
 
-Out of scope: the rest of ``UPerHead`` (laterals, top-down path, FPN convolutions, ``fpn_bottleneck``; its pyramid branch is
-``PyramidPooling``), ``num_convs != 1``, ``concat_input``, dilation, class weights, OHEM samplers, more than 32 classes.
+Out of scope: the mmseg runner, schedules and data pipeline, sliding-window test mode, ``num_convs != 1``, ``concat_input``,
+dilation, class weights, OHEM samplers, more than 32 classes, ``channels > 512``, more than 4 levels on the hip arm.
 """
 import torch
 import torch.nn as nn
@@ -63,6 +70,22 @@ class _HeadFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dlogit):
         return (None, ctx.head._hip_backward(ctx.saved, dlogit, ctx.needs_input_grad[1])) + (None,) * ctx.n_params
+
+
+class _LevelsFunction(torch.autograd.Function):
+    """``_HeadFunction`` for a head that reads several maps (``UPerHead``): ``n`` fp32 maps -> logits; the backward returns a
+    gradient per map (None where nobody asked)."""
+
+    @staticmethod
+    def forward(ctx, head, n, *args):
+        ctx.head, ctx.n, ctx.n_params = head, n, len(args) - n
+        out, ctx.saved = head._hip_forward(args[:n], keep=True)
+        return out
+
+    @staticmethod
+    def backward(ctx, dlogit):
+        grads = ctx.head._hip_backward(ctx.saved, dlogit, ctx.needs_input_grad[2:2 + ctx.n])
+        return (None, None) + tuple(grads) + (None,) * ctx.n_params
 
 
 class _BnClsHead(BufferCache, nn.Module):
@@ -116,6 +139,16 @@ class _BnClsHead(BufferCache, nn.Module):
         raise NotImplementedError
 
     # ------------------------------------------------------------------ the torch arm
+    @staticmethod
+    def _torch_cm(m, x):
+        """a ``ConvModule`` on plain torch ops: conv -> batch norm (with its bookkeeping) -> ReLU"""
+        y = F.conv2d(x, m.conv.weight, None, padding=m.conv.padding)
+        bn = m.bn
+        if bn.training:
+            with torch.no_grad():
+                bn.num_batches_tracked += 1
+        return F.relu(F.batch_norm(y, bn.running_mean, bn.running_var, bn.weight, bn.bias, bn.training, bn.momentum, bn.eps))
+
     def _torch_tail(self, x):
         conv, bn = self._cm().conv, self._cm().bn
         y = F.conv2d(x, conv.weight, None, padding=1)
@@ -307,7 +340,7 @@ class FCNHead(_BnClsHead):
 
 
 class PyramidPooling:
-    """The pyramid branch of ``PSPHead`` (and of a later ``UPerHead``) on the hip path: fp32 map ``[B, Cin, h, w]`` -> the
+    """The pyramid branch of ``PSPHead`` and of ``UPerHead`` on the hip path: fp32 map ``[B, Cin, h, w]`` -> the
     interior of ``Xcat`` bf16 ``[B, h+2, w+2, Cin + n C]`` (``forward``), and ``dXcat`` -> the fp32 map gradient (``backward``);
     who consumes ``Xcat`` is the caller's business.  ``modules``: the 1x1 ``ConvModule`` per pool scale; ``owner``: whose buffer
     cache (``_buf``, names under ``ppm.``), bf16 weight copies (``_packed``) and SyncBN hook (``reduce``) it uses.
@@ -455,11 +488,274 @@ class PSPHead(_BnClsHead):
         return self.ppm.backward(pyramid, dxcat, need_dx)
 
 
+class UPerHead(_BnClsHead):
+    """mmseg 0.30 ``UPerHead`` (mmseg/models/decode_heads/uper_head.py) with its loss -- the reference's decode head
+    (mem/semantic_segmentation/configs/_base_/models/upernet_beit.py:25-37: ``in_index=[0, 1, 2, 3], pool_scales=(1, 2, 3, 6),
+    channels=512``).  With L = len(in_channels) levels, finest first, ``x_l = inputs[in_index[l]]``::
+
+        lat_l   = ReLU(SyncBN(Conv2d(in_channels[l], channels, 1, bias=False)(x_l)))        l < L - 1     lateral_convs.{l}
+        lat_L-1 = PSPHead's pyramid and bottleneck on x_L-1                                               psp_modules, bottleneck
+        lat_l-1 = lat_l-1 + resize(lat_l, size of level l - 1)                              l = L - 1 .. 1
+        out_l   = ReLU(SyncBN(Conv2d(channels, channels, 3, padding=1, bias=False)(lat_l))) l < L - 1     fpn_convs.{l}
+        feat    = ReLU(SyncBN(Conv2d(L channels, channels, 3, padding=1, bias=False)(
+                      cat([out_0] + [resize(out_l, size of level 0)] + [resize(lat_L-1, size of level 0)], 1))))   fpn_bottleneck
+        logits  = conv_seg(Dropout2d(feat))
+
+    under mmseg's state-dict keys and shapes: a reference checkpoint's ``decode_head.*`` loads with ``strict=True``.
+
+    The interface, Dropout2d's keys and ``reduce`` are ``FCNHead``'s; ``forward`` takes the backbone's tuple and returns logits
+    at level 0's size.  The hip arm (csrc/fpn.hip around the library's convolutions, ``PyramidPooling`` and the shared tail)
+    takes CUDA fp32 maps whose sizes do not increase from level to level in either axis (equal sizes are fine), 2 <= L <= 4,
+    every ``in_channels[l]`` and ``channels`` a multiple of 64, ``channels <= 512``, and ``PSPHead``'s pool scales.  Stored per
+    level: the convolution outputs (bf16) and the top-down sums T_l (bf16, the FPN convolutions' operands); the activations
+    ``lat_l``, ``out_l``, their upsampled maps and an fp32 concat never are.  ``reduce`` is called with "stats" five times in a
+    training forward (laterals stacked [L-1, 3, C]; pyramid; bottleneck; fpn convs stacked; fpn_bottleneck) and with "bwd"
+    four times in its backward (fpn_bottleneck; fpn convs stacked [L-1, 2, C]; laterals + bottleneck stacked [L, 2, C];
+    pyramid)."""
+
+    def __init__(self, in_channels=(768,) * 4, channels=512, num_classes=11, in_index=(0, 1, 2, 3), pool_scales=(1, 2, 3, 6),
+                 dropout_ratio=0.1, align_corners=False, loss_weight=1.0, ignore_index=255, impl="hip", class_weight=None,
+                 sampler=None, **kwargs):
+        super().__init__()
+        in_channels, in_index = tuple(in_channels), tuple(in_index)
+        if len(in_channels) != len(in_index):
+            raise ValueError(f"UPerHead: len(in_channels)={len(in_channels)} != len(in_index)={len(in_index)}")
+        if not in_channels:
+            raise ValueError("UPerHead: in_channels is empty")
+        for c in in_channels:
+            self._check_common(impl, dropout_ratio, c, channels, num_classes, class_weight, sampler, kwargs)
+        pool_scales = tuple(pool_scales)
+        if not pool_scales or any(int(s) != s or s < 1 for s in pool_scales):
+            raise ValueError(f"pool_scales: positive integers, got {pool_scales!r}")
+        if impl == "hip":
+            if not 2 <= len(in_channels) <= ops.FPN_MAX_LEVELS:
+                raise ValueError(f"UPerHead(impl='hip'): 2 <= levels <= {ops.FPN_MAX_LEVELS}, got in_channels={in_channels!r}")
+            if len(pool_scales) > ops.PPM_MAX_SCALES:
+                raise ValueError(f"UPerHead(impl='hip'): at most {ops.PPM_MAX_SCALES} pool_scales, got {pool_scales!r}")
+            if any(not 1 <= s <= ops.PPM_MAX_SCALE for s in pool_scales):
+                raise ValueError(f"UPerHead(impl='hip'): 1 <= s <= {ops.PPM_MAX_SCALE} for every s of pool_scales, got {pool_scales!r}")
+        self.in_channels, self.pool_scales, self.levels = in_channels, tuple(int(s) for s in pool_scales), len(in_channels)
+        self.psp_modules = nn.ModuleList(nn.Sequential(nn.AdaptiveAvgPool2d(s), ConvModule(in_channels[-1], channels, 1))
+                                         for s in self.pool_scales)
+        self.bottleneck = ConvModule(in_channels[-1] + len(self.pool_scales) * channels, channels)
+        self.lateral_convs = nn.ModuleList(ConvModule(c, channels, 1) for c in in_channels[:-1])
+        self.fpn_convs = nn.ModuleList(ConvModule(channels, channels) for _ in in_channels[:-1])
+        self.fpn_bottleneck = ConvModule(len(in_channels) * channels, channels)
+        self._init_tail(channels, num_classes, in_index, dropout_ratio, align_corners, loss_weight, ignore_index, impl)
+        self.ppm = PyramidPooling(self, [seq[1] for seq in self.psp_modules], self.pool_scales, in_channels[-1], channels, align_corners)
+
+    def _cm(self):
+        return self.fpn_bottleneck
+
+    def _upstream(self):
+        """the ConvModules in front of ``fpn_bottleneck``'s operand"""
+        return [seq[1] for seq in self.psp_modules] + [self.bottleneck] + list(self.lateral_convs) + list(self.fpn_convs)
+
+    def _params(self):
+        ps = []
+        for m in self._upstream() + [self.fpn_bottleneck]:
+            ps += [m.conv.weight, m.bn.weight, m.bn.bias]
+        return ps + [self.conv_seg.weight, self.conv_seg.bias]
+
+    # ------------------------------------------------------------------ the torch arm: uper_head.py, line by line
+    def _torch_forward(self, xs):
+        resize = lambda t, size: F.interpolate(t, size=size, mode="bilinear", align_corners=self.align_corners)
+        laterals = [self._torch_cm(m, x) for m, x in zip(self.lateral_convs, xs)]
+        x = xs[-1]
+        psp = [x] + [resize(self._torch_cm(seq[1], F.adaptive_avg_pool2d(x, s)), x.shape[2:]) for s, seq in zip(self.pool_scales, self.psp_modules)]
+        laterals.append(self._torch_cm(self.bottleneck, torch.cat(psp, 1)))
+        for l in range(self.levels - 1, 0, -1):
+            laterals[l - 1] = laterals[l - 1] + resize(laterals[l], laterals[l - 1].shape[2:])
+        outs = [self._torch_cm(m, lat) for m, lat in zip(self.fpn_convs, laterals)] + [laterals[-1]]
+        outs = [outs[0]] + [resize(o, outs[0].shape[2:]) for o in outs[1:]]
+        return self._torch_tail(torch.cat(outs, 1))
+
+    # ------------------------------------------------------------------ the hip arm
+    def check(self, B, sizes, training):
+        """refuse what the tables refuse, by name: level sizes that grow; and what the pyramid refuses on the last level"""
+        for l in range(1, len(sizes)):
+            if sizes[l][0] > sizes[l - 1][0] or sizes[l][1] > sizes[l - 1][1]:
+                raise ValueError("UPerHead(impl='hip'): level %d of %dx%d is larger than level %d of %dx%d: the hip arm resizes upwards "
+                                 "only, level sizes must not increase" % (l, sizes[l][0], sizes[l][1], l - 1, sizes[l - 1][0], sizes[l - 1][1]))
+        self.ppm.check(B, sizes[-1][0], sizes[-1][1], training)
+
+    def _stats_stacked(self, name, Y, B, sizes):
+        C = self.channels
+        ws = self._buf("stats.ws", (ops.BN_GROUPS * 2 * C,), torch.float32)
+        out = self._buf(name, (len(Y), 3, C), torch.float32)
+        for l, y in enumerate(Y):
+            ops.bn_stats_nhwc(y, B, sizes[l][0], sizes[l][1], C, ws, None, True, out=out[l])
+        return out
+
+    def _level_vectors(self, name, mods, mean, rstd, mean_p, rstd_p):
+        """(mean, rstd, gamma, beta) f32 [L, C] in the head's buffers ``name``: a row per level (``mods``: the lateral / FPN
+        ConvModules, their vectors [L - 1, C]) and the pyramid bottleneck's as the last"""
+        L, C, bp = self.levels, self.channels, self.bottleneck.bn
+        out = [self._buf("%s.%s" % (name, k), (L, C), torch.float32) for k in ("mean", "rstd", "gamma", "beta")]
+        out[0][:L - 1].copy_(mean)
+        out[0][L - 1].copy_(mean_p)
+        out[1][:L - 1].copy_(rstd)
+        out[1][L - 1].copy_(rstd_p)
+        for l, bn in enumerate([m.bn for m in mods] + [bp]):
+            out[2][l].copy_(bn.weight.detach())
+            out[3][l].copy_(bn.bias.detach())
+        return tuple(out)
+
+    def _totals(self, name, sums, inv_n):
+        """``backward_totals`` for stacked sums [k, 2, C] with 1 / n [k, C], in the head's buffers: one ``reduce(., "bwd")``"""
+        if inv_n is None:
+            return None
+        sent = self.reduce(self._buf(name + ".sent", tuple(sums.shape), torch.float32).copy_(sums), "bwd")
+        return torch.mul(sent, inv_n[:, None, :], out=self._buf(name + ".tot", tuple(sums.shape), torch.float32))
+
+    def _hip_forward(self, xs, keep):
+        L, C, ac = self.levels, self.channels, self.align_corners
+        B = xs[0].shape[0]
+        sizes = [(int(x.shape[2]), int(x.shape[3])) for x in xs]
+        self.check(B, sizes, self.training)
+        Xp, Yl = [], []
+        for l in range(L - 1):
+            (h, w), Cin = sizes[l], self.in_channels[l]
+            Xp.append(ops.map_to_nhwc_pad(xs[l], self._buf("lat.xp%d" % l, (B, h + 2, w + 2, Cin), zero=True)))
+            Yl.append(self._buf("lat.y%d" % l, (B, h + 2, w + 2, C), zero=True))
+            ops.conv2d_nhwc(Xp[l], self._packed(self.lateral_convs[l].conv, "conv1")[0], None, Yl[l], B, h, w, Cin, C, 1, 1, 0)
+        with torch.no_grad():
+            mean_l, rstd_l, inv_l = batch_vectors_stacked([m.bn for m in self.lateral_convs],
+                                                          lambda: self._stats_stacked("lat.stats", Yl, B, sizes), self.reduce)
+        (hL, wL), CinL = sizes[-1], self.in_channels[-1]
+        ct = CinL + len(self.pool_scales) * C
+        pxcat = self._buf("psp.xcat", (B, hL + 2, wL + 2, ct), zero=True)
+        pyramid = self.ppm.forward(xs[-1], pxcat, keep)
+        Yp = self._buf("psp.y", (B, hL + 2, wL + 2, C), zero=True)
+        ops.conv2d_nhwc(pxcat, self._packed(self.bottleneck.conv, "conv3")[0], None, Yp, B, hL, wL, ct, C, 3, 1, 1)
+        with torch.no_grad():
+            mean_p, rstd_p, inv_p = batch_vectors(self.bottleneck.bn,
+                                                  lambda: self._stats_stacked("psp.stats", [Yp], B, sizes[-1:])[0], self.reduce)
+            lat_vecs = self._level_vectors("lat.vec", self.lateral_convs, mean_l, rstd_l, mean_p, rstd_p)
+        # the top-down path: T_l = lat_l + resize(T_l+1); the coarsest lateral is read through its batch norm, never stored
+        T = [None] * L
+        for l in range(L - 2, -1, -1):
+            T[l] = self._buf("fpn.t%d" % l, (B, sizes[l][0] + 2, sizes[l][1] + 2, C), zero=True)
+            ops.fpn_topdown_fwd(l, sizes, Yl[l], lat_vecs, (Yp,) if l == L - 2 else T[l + 1], T[l], ac)
+        Yf = []
+        for l in range(L - 1):
+            h, w = sizes[l]
+            Yf.append(self._buf("fpn.y%d" % l, (B, h + 2, w + 2, C), zero=True))
+            ops.conv2d_nhwc(T[l], self._packed(self.fpn_convs[l].conv, "conv3")[0], None, Yf[l], B, h, w, C, C, 3, 1, 1)
+        with torch.no_grad():
+            mean_f, rstd_f, inv_f = batch_vectors_stacked([m.bn for m in self.fpn_convs],
+                                                          lambda: self._stats_stacked("fpn.stats", Yf, B, sizes), self.reduce)
+            fpn_vecs = self._level_vectors("fpn.vec", self.fpn_convs, mean_f, rstd_f, mean_p, rstd_p)
+        h0, w0 = sizes[0]
+        xcat = self._buf("xcat", (B, h0 + 2, w0 + 2, L * C), zero=True)
+        ops.fpn_concat_fwd(sizes, Yf + [Yp], fpn_vecs, xcat, ac)
+        out, tail = self._tail_forward(xcat, B, L * C, h0, w0, keep)
+        if not keep:
+            return out, None
+        return out, ((Xp, Yl, Yp, T, Yf, pxcat, pyramid, lat_vecs, fpn_vecs, inv_l, inv_p, inv_f, sizes, B), tail)
+
+    def _wgrad(self, name, conv, dY, X, B, h, w, Cin, k):
+        """the weight gradient of a k x k ConvModule's convolution from dY and its operand X, added to ``conv.weight.grad``"""
+        if not conv.weight.requires_grad:
+            return
+        C = self.channels
+        need = ops.conv_wgrad_workspace(B, h, w, Cin, C, k, 1, k // 2)
+        wws = self._buf(name + ".ws", (need,), torch.uint8) if need else None
+        gw = self._buf(name, (C, k * k * Cin), torch.float32)
+        ops.conv_wgrad(dY, X, gw, B, h, w, Cin, C, k, 1, k // 2, small_padded=True, accumulate=False, workspace=wws)
+        self._grad(conv.weight).add_(gw.view(C, k, k, Cin).permute(0, 3, 1, 2))
+
+    def _hip_backward(self, saved, dlogit, needs):
+        (Xp, Yl, Yp, T, Yf, pxcat, pyramid, lat_vecs, fpn_vecs, inv_l, inv_p, inv_f, sizes, B), tail = saved
+        L, C, ac = self.levels, self.channels, self.align_corners
+        upstream = any(p.requires_grad for m in self._upstream() for p in m.parameters())
+        dxcat = self._tail_backward(tail, dlogit, any(needs) or upstream)
+        grads = [None] * L
+        if dxcat is None:
+            return grads
+        ws = self._buf("fpn.bwd.ws", (ops.BN_GROUPS * 2 * C,), torch.float32)
+        # the FPN ConvModules: A_l = the transposed resize of dXcat's slice l
+        sums_f = self._buf("fpn.sums", (L - 1, 2, C), torch.float32)
+        A = []
+        for l in range(L - 1):
+            A.append(self._buf("fpn.a%d" % l, (B * sizes[l][0] * sizes[l][1], C), torch.float32))
+            ops.fpn_resize_bwd(l, sizes, C, A[l], dxcat=dxcat, slice_=l, align_corners=ac)
+            ops.fpn_bn_bwd_sums(l, sizes, Yf[l], fpn_vecs, A[l], sums_f[l], ws)
+            add_affine_grads(self.fpn_convs[l].bn, sums_f[l])
+        tot_f = self._totals("fpn.sums", sums_f, inv_f)
+        dT_own = []
+        for l in range(L - 1):
+            h, w = sizes[l]
+            dY = ops.fpn_bn_bwd_apply(l, sizes, Yf[l], fpn_vecs, A[l], None if tot_f is None else tot_f[l], 1.0,
+                                      self._buf("fpn.dy%d" % l, (B, h + 2, w + 2, C), zero=True))
+            self._wgrad("fpn.wgrad%d" % l, self.fpn_convs[l].conv, dY, T[l], B, h, w, C, 3)
+            dT_own.append(self._buf("fpn.dt%d" % l, (B, h + 2, w + 2, C)))
+            ops.conv2d_nhwc(dY, self._packed(self.fpn_convs[l].conv, "conv3")[1], None, dT_own[l], B, h, w, C, C, 3, 1, 1)
+        # the top-down path backwards: dT_l = own + the transposed resize of dT_l-1; the coarsest level's own term is dXcat's
+        dT = []
+        for l in range(L):
+            dT.append(self._buf("fpn.dlat%d" % l, (B * sizes[l][0] * sizes[l][1], C), torch.float32))
+            fine = dT[l - 1] if l else None
+            if l < L - 1:
+                ops.fpn_resize_bwd(l, sizes, C, dT[l], own=dT_own[l], fine_rows=fine, align_corners=ac)
+            else:
+                ops.fpn_resize_bwd(l, sizes, C, dT[l], dxcat=dxcat, slice_=l, fine_rows=fine, align_corners=ac)
+        # the laterals and the pyramid's bottleneck: one exchange
+        sums_l = self._buf("lat.sums", (L, 2, C), torch.float32)
+        Ys, mods = Yl + [Yp], list(self.lateral_convs) + [self.bottleneck]
+        for l in range(L):
+            ops.fpn_bn_bwd_sums(l, sizes, Ys[l], lat_vecs, dT[l], sums_l[l], ws)
+            add_affine_grads(mods[l].bn, sums_l[l])
+        inv = None
+        if inv_l is not None:
+            inv = self._buf("lat.inv_n", (L, C), torch.float32)
+            inv[:L - 1].copy_(inv_l)
+            inv[L - 1].copy_(inv_p)
+        tot_l = self._totals("lat.sums", sums_l, inv)
+        for l in range(L - 1):
+            (h, w), Cin, conv = sizes[l], self.in_channels[l], self.lateral_convs[l].conv
+            dY = ops.fpn_bn_bwd_apply(l, sizes, Yl[l], lat_vecs, dT[l], None if tot_l is None else tot_l[l], 1.0,
+                                      self._buf("lat.dy%d" % l, (B, h + 2, w + 2, C), zero=True))
+            self._wgrad("lat.wgrad%d" % l, conv, dY, Xp[l], B, h, w, Cin, 1)
+            if needs[l]:
+                dXp = self._buf("lat.dxp%d" % l, (B, h + 2, w + 2, Cin))
+                ops.conv2d_nhwc(dY, self._packed(conv, "conv1")[1], None, dXp, B, h, w, C, Cin, 1, 1, 0)
+                grads[l] = ops.nhwc_pad_to_map(dXp, out=self._buf("lat.dmap%d" % l, (B, Cin, h, w), torch.float32)).detach()
+        (hL, wL), ct = sizes[-1], pxcat.shape[3]
+        dY = ops.fpn_bn_bwd_apply(L - 1, sizes, Yp, lat_vecs, dT[L - 1], None if tot_l is None else tot_l[L - 1], 1.0,
+                                  self._buf("psp.dy", (B, hL + 2, wL + 2, C), zero=True))
+        self._wgrad("psp.wgrad", self.bottleneck.conv, dY, pxcat, B, hL, wL, ct, 3)
+        branches = any(p.requires_grad for seq in self.psp_modules for p in seq[1].parameters())
+        if needs[L - 1] or branches:
+            dpx = self._buf("psp.dxcat", (B, hL + 2, wL + 2, ct))
+            ops.conv2d_nhwc(dY, self._packed(self.bottleneck.conv, "conv3")[1], None, dpx, B, hL, wL, C, ct, 3, 1, 1)
+            grads[L - 1] = self.ppm.backward(pyramid, dpx, needs[L - 1])
+        return grads
+
+    # ------------------------------------------------------------------ mmseg's interface: the backbone's tuple
+    def forward(self, inputs):
+        xs = [inputs[i] for i in self.in_index]
+        if self.impl == "torch":
+            return self._torch_forward(xs)
+        for l, x in enumerate(xs):
+            if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.shape[1] == self.in_channels[l]
+                    and x.shape[0] == xs[0].shape[0]):
+                from ._lib import MemhipError
+                raise MemhipError("UPerHead(impl='hip') takes the engine's CUDA fp32 maps [B, %d, h, w] at level %d (no CPU fallback)"
+                                  % (self.in_channels[l], l))
+        xs = [x.contiguous() for x in xs]
+        params = self._params()
+        if torch.is_grad_enabled() and (any(x.requires_grad for x in xs) or any(p.requires_grad for p in params)):
+            return _LevelsFunction.apply(self, len(xs), *xs, *params)
+        return self._hip_forward([x.detach() for x in xs], keep=False)[0]
+
+
 class SegModel(nn.Module):
     """mmseg's ``EncoderDecoder``, thin: ``backbone`` (an ``EvBEiT``: images -> a tuple of maps), ``decode_head`` and an optional
-    ``auxiliary_head`` (``FCNHead`` or ``PSPHead``).  ``forward_train(img, seg_label)`` -> ``{"decode.loss_seg", "decode.acc_seg",
-    "aux.loss_seg", "aux.acc_seg"}``; ``encode_decode(img)`` -> the decode head's logits at the head's resolution
-    (``test_cfg.mode='whole'``: the resize to the label's size is ``SegEvaluator``'s).  One object for an optimizer and an evaluator."""
+    ``auxiliary_head`` (each a ``UPerHead``, ``PSPHead`` or ``FCNHead``; the reference's model is ``SegModel(EvBEiT, UPerHead,
+    FCNHead)``).  ``forward_train(img, seg_label)`` -> ``{"decode.loss_seg", "decode.acc_seg", "aux.loss_seg", "aux.acc_seg"}``;
+    ``encode_decode(img)`` -> the decode head's logits at the head's resolution (``test_cfg.mode='whole'``: the resize to the
+    label's size is ``SegEvaluator``'s).  One object for an optimizer and an evaluator."""
 
     def __init__(self, backbone, decode_head, auxiliary_head=None):
         super().__init__()

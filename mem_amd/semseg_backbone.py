@@ -13,8 +13,8 @@ GELU in fp32, the movement kernels of csrc/necks.hip around them, forward and ba
 the two.  ``fpn3`` (identity) and ``fpn4`` (max pooling) are torch's in both.
 
 Not mirrored: ``resize_in`` (feed the model its ``img_size``), the patch-8 necks, gradient checkpointing, the mmseg / mmcv
-registry and runner, ``UPerHead`` beyond its pyramid branch; that branch with its bottleneck (mmseg's ``PSPHead``), the auxiliary
-``FCNHead`` and the thin ``EncoderDecoder`` are in ``mem_amd.seg_heads``, the heads' loss and metrics in ``mem_amd.seg_loss``.
+registry and runner; the decode head ``UPerHead`` (and its pyramid branch alone, mmseg's ``PSPHead``), the auxiliary ``FCNHead``
+and the thin ``EncoderDecoder`` are in ``mem_amd.seg_heads``, the heads' loss and metrics in ``mem_amd.seg_loss``.
 """
 from functools import partial
 
