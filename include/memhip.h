@@ -36,7 +36,7 @@ extern "C" {
 #endif
 
 #define MEMHIP_ABI_VERSION 10  /* 10: the rasterizer takes one args struct: memhip_rasterize and memhip_rasterize_plan read the same memhip_raster_args_t; the
-                                  memhip_rasterize_f64 / _aug_f64 / _var_f64 / _binned_f64 / _workspace / _binned_workspace symbols are gone (additive since: memhip_convt2d_nhwc, memhip_convt_plan, memhip_kl_uniform_rows of the tokenizer's decoder; memhip_conv_wgrad_nhwc / _plan / _workspace with memhip_conv_wgrad_args_t, memhip_relu_bwd_colsum / _workspace of dVAE training; memhip_seg_axis_table / _seg_plan / _seg_ce / _seg_confusion with memhip_seg_args_t of the segmentation loss); 9: the tokenizer takes one args struct: memhip_conv2d_nhwc and memhip_conv_plan read the same memhip_conv_args_t; one
+                                  memhip_rasterize_f64 / _aug_f64 / _var_f64 / _binned_f64 / _workspace / _binned_workspace symbols are gone (additive since: memhip_convt2d_nhwc, memhip_convt_plan, memhip_kl_uniform_rows of the tokenizer's decoder; memhip_conv_wgrad_nhwc / _plan / _workspace with memhip_conv_wgrad_args_t, memhip_relu_bwd_colsum / _workspace of dVAE training; memhip_seg_axis_table / _seg_plan / _seg_ce / _seg_confusion with memhip_seg_args_t of the segmentation loss; memhip_segdata_resize_hist / _norm / _geom with memhip_segdata_args_t of the segmentation data chain); 9: the tokenizer takes one args struct: memhip_conv2d_nhwc and memhip_conv_plan read the same memhip_conv_args_t; one
                                   memhip_nchw_to_padded_nhwc4 and one memhip_argmax_rows with a mode argument; the per-mode symbols (_bf16 / _f32 / _f32_dyn / _f32_ex / _f16x2) are gone;
                                   8: one entry point per backward family, optional features as struct fields (memhip_branch_bwd, memhip_layernorm_bwd_branch,
                                   memhip_attn_bwd take an args struct; memhip_gemm_bf16_tn takes the workspace; the *_map / *_drop / *_out / *_ws symbols are gone; additive since: the memhip_neck_* entry points of the feature-pyramid necks);
@@ -1498,6 +1498,73 @@ struct memhip_fpn_plan {
 };
 typedef struct memhip_fpn_plan memhip_fpn_plan_t;
 int memhip_fpn_plan(const memhip_fpn_args_t* args, memhip_fpn_plan_t* out);
+
+/* ------------------------------------------------------------------------
+ * Segmentation data chain (DSEC), image and label, batched with per-sample sizes (host draws, device arithmetic)
+ * replaces Resize(ratio_range) on the image and on the label   mem/semantic_segmentation/configs/_base_/datasets/dsec.py:14
+ *          RemoveHotPixelsEvs                                   mem/semantic_segmentation/backbone/EventDataset.py:566-596
+ *          NormalizeEvs, ToUnit8Evs                             EventDataset.py:1339-1354, 1526-1535
+ *          RandomCrop, RandomFlip, Normalize(to_rgb), Pad       dsec.py:21-24 (train), 41-44 (test)
+ *          the backbone's resize_in                             mem/semantic_segmentation/backbone/mem.py:294,420
+ * ------------------------------------------------------------------------
+ * The resized image of sample b has its own size dims[b] = (h_b, w_b), 1 <= h_b <= max_h, 1 <= w_b <= max_w, and is stored
+ * densely as [3, h_b, w_b] at element offs[b] of the working buffer: a byte offset into img_u8, a float offset into img_f32,
+ * offs[b] + 3 h_b w_b <= img_elems.  A sample whose dims or offs break these rules is skipped by every kernel (nothing of it is
+ * read or written).  Three entries on the caller's stream, one host struct; NULL / 0 = off; a field another entry owns is
+ * ignored.  No float atomics, no host synchronisation, no allocation; B == 0 is MEMHIP_OK, nothing is read.
+ *
+ *   memhip_segdata_resize_hist: planes u8 [B, 3, H, W] (the rasterizer's [pos, 0, neg]) -> img_u8 at offs / dims, bilinear with
+ *     half-pixel centres and clamped edges in exact integer arithmetic: output x reads the source position
+ *     ((2 x + 1) W - w_b) / (2 w_b) clamped to [0, W - 1]; the two taps carry the integer weights nx, 2 w_b - nx (rows: ny of
+ *     2 h_b) and the value is (sum v nx ny + 2 w_b h_b) / (4 w_b h_b), round half up, in 64-bit integers.
+ *     Equal sizes give an exact copy.  hist u32 [B, 2, 256] is cleared by the call and then holds H_val, the counts of the values
+ *     of channels 0 and 2 of the RESIZED image, and H_pmax, the counts of max(ch0, ch2) per pixel (integer atomics: sums do not
+ *     depend on their order).  OpenCV's 8-bit INTER_LINEAR, which mmcv's imresize calls, uses 11-bit fixed-point coefficients
+ *     and may differ from this exact rational form by one count in isolated pixels: unmeasured, OpenCV is not available here.
+ *   memhip_segdata_norm: the three whole-image reductions of RemoveHotPixelsEvs and NormalizeEvs come from the 256 bins, which
+ *     every workgroup re-reads: n, sum v, sum v^2 exactly from H_val (int64), thr = mean + num_stds * unbiased std in double;
+ *     a pixel is hot iff max(ch0, ch2) > thr (strict; the reference's unravel_index on the (3, H, W) shape lands on the same
+ *     (y, x) for both polarities), hot pixels are zeroed in channels 0 and 2; m = the largest non-empty bin of H_pmax not above
+ *     thr, 1 when that is 0; every channel becomes (v / m) * 255.f: a correctly rounded fp32 division, then a multiply.
+ *     out_f32 == 0: truncated to u8 in place in img_u8 (NormalizeEvs, ToUnit8Evs: the train chain); out_f32 == 1: stored
+ *     unrounded to img_f32 at the same offs (the test chain).  Channel 1 is the rasterizer's zero plane: it is scaled like the
+ *     others and is not part of the maximum.
+ *   memhip_segdata_geom: crop i32 [B, 3] = {top, left, flip} (clamped into the image).  Image: in_f32 ? img_f32 : img_u8 at
+ *     offs / dims -> out f32 [B, 3, net_h, net_w] in one gather: crop to (crop_h, crop_w), horizontal flip of the cropped
+ *     window, swap of channels 0 and 2 (Normalize(mean 0, std 1, to_rgb=True) is only that), zero pad right / bottom to the
+ *     crop size, then bilinear resize to the net size with align_corners=False and no antialias (F.interpolate's function:
+ *     src = (in / out) (dst + 0.5) - 0.5 clamped at 0, taken exactly as ((2 dst + 1) in - out) / (2 out): the tap is the integer
+ *     quotient, the weight the remainder rounded once to fp32, then w0y (w0x a + w1x b) + w1y (w0x c + w1x d) in fp32; aten's
+ *     fp32 evaluation of src is off by up to in * 2^-23, and the weight with it).  torchvision >= 0.17 would antialias this downscale; the tensor
+ *     behaviour current when the reference was written is taken.  Labels: labels u8 [B, H, W] -> label_out u8 [B, crop_h,
+ *     crop_w]: nearest resize to dims[b] (source index min(dst * src / dst_size, src - 1), integer; OpenCV's INTER_NEAREST
+ *     computes the index in double: unmeasured as above), the same crop and flip, pad 255.  out NULL or label_out NULL: that
+ *     half is off. */
+struct memhip_segdata_args {
+  int32_t B, H, W;                   /* the source canvas of planes and labels */
+  int32_t max_h, max_w;              /* upper bounds of dims */
+  int32_t crop_h, crop_w;            /* _geom */
+  int32_t net_h, net_w;              /* _geom */
+  int32_t out_f32;                   /* _norm: 0 = u8 in place, 1 = f32 to img_f32 */
+  int32_t in_f32;                    /* _geom: the image is read from img_f32 */
+  int32_t reserved0;
+  double num_stds;                   /* _norm */
+  const uint8_t* planes;             /* device u8 [B, 3, H, W]: _resize_hist */
+  const int64_t* offs;               /* device i64 [B] */
+  const int32_t* dims;               /* device i32 [B, 2] */
+  uint8_t* img_u8;                   /* device: the working image, u8 */
+  float* img_f32;                    /* device: the working image, f32 */
+  int64_t img_elems;                 /* elements of the working buffer in use */
+  uint32_t* hist;                    /* device u32 [B, 2, 256] */
+  const int32_t* crop;               /* device i32 [B, 3]: _geom */
+  float* out;                        /* device f32 [B, 3, net_h, net_w]: _geom */
+  const uint8_t* labels;             /* device u8 [B, H, W]: _geom */
+  uint8_t* label_out;                /* device u8 [B, crop_h, crop_w]: _geom */
+};
+typedef struct memhip_segdata_args memhip_segdata_args_t;
+int memhip_segdata_resize_hist(const memhip_segdata_args_t* args, memhip_stream_t stream);
+int memhip_segdata_norm(const memhip_segdata_args_t* args, memhip_stream_t stream);
+int memhip_segdata_geom(const memhip_segdata_args_t* args, memhip_stream_t stream);
 
 #ifdef __cplusplus
 }

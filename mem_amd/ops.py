@@ -1705,3 +1705,90 @@ def fpn_bn_bwd_apply(level, sizes, Y, vecs, rows, tot, inv_n, dY):
     a.tot, a.inv_n, a.dY = _p(tot), float(inv_n), _fpn_pad(dY, Y.shape[0], sizes[level], C_, "dY")
     check(lib.memhip_fpn_bn_bwd_apply(C.byref(a), stream_ptr()), "fpn_bn_bwd_apply")
     return dY
+
+
+# ---------------------------------------------------------------- segmentation data chain (csrc/seg_data.hip)
+class SegDataArgs(C.Structure):
+    """== memhip_segdata_args_t."""
+    _fields_ = [(n, i32) for n in ("B", "H", "W", "max_h", "max_w", "crop_h", "crop_w", "net_h", "net_w", "out_f32", "in_f32",
+                                   "reserved0")] + \
+               [("num_stds", f64), ("planes", vp), ("offs", vp), ("dims", vp), ("img_u8", vp), ("img_f32", vp), ("img_elems", i64),
+                ("hist", vp), ("crop", vp), ("out", vp), ("labels", vp), ("label_out", vp)]
+
+
+declare({
+    "memhip_segdata_resize_hist": (i32, [C.POINTER(SegDataArgs), vp]),
+    "memhip_segdata_norm": (i32, [C.POINTER(SegDataArgs), vp]),
+    "memhip_segdata_geom": (i32, [C.POINTER(SegDataArgs), vp]),
+})
+
+
+def _segdata_common(offs, dims, max_hw, **fields):
+    B = dims.shape[0]
+    assert dims.is_cuda and dims.dtype == torch.int32 and dims.is_contiguous() and tuple(dims.shape) == (B, 2), "dims: CUDA i32 [B, 2]"
+    assert offs.is_cuda and offs.dtype == torch.int64 and offs.is_contiguous() and tuple(offs.shape) == (B,), "offs: CUDA i64 [B]"
+    a = SegDataArgs(B=B, max_h=int(max_hw[0]), max_w=int(max_hw[1]), offs=offs.data_ptr(), dims=dims.data_ptr())
+    for k, v in fields.items():
+        setattr(a, k, v)
+    return a
+
+
+def _segdata_buf(t, dtype, name):
+    assert t.is_cuda and t.dtype == dtype and t.is_contiguous() and t.dim() == 1, f"{name}: a flat contiguous CUDA {dtype} tensor"
+    return t.data_ptr()
+
+
+def segdata_resize_hist(planes, offs, dims, max_hw, img_u8, hist):
+    """planes u8 [B, 3, H, W] -> the exact-integer bilinear resize of sample b to dims[b] = (h_b, w_b) (<= max_hw), stored
+    densely as [3, h_b, w_b] at byte offs[b] of the flat u8 buffer img_u8; hist u32 [B, 2, 256] <- H_val (values of channels
+    0 and 2 of the resized image), H_pmax (max(ch0, ch2) per pixel)."""
+    B, _, H, W = planes.shape
+    assert planes.is_cuda and planes.dtype == torch.uint8 and planes.is_contiguous() and planes.shape[1] == 3
+    assert hist.is_cuda and hist.dtype == torch.int32 and hist.is_contiguous() and tuple(hist.shape) == (B, 2, 256), \
+        "hist: CUDA i32 [B, 2, 256] (the u32 counts)"
+    a = _segdata_common(offs, dims, max_hw, H=H, W=W, planes=planes.data_ptr(), img_u8=_segdata_buf(img_u8, torch.uint8, "img_u8"),
+                        img_elems=img_u8.numel(), hist=hist.data_ptr())
+    check(lib.memhip_segdata_resize_hist(C.byref(a), stream_ptr()), "segdata_resize_hist")
+
+
+def segdata_norm(offs, dims, max_hw, img_u8, hist, num_stds=10.0, img_f32=None):
+    """Hot-pixel removal and (v / m) * 255 from the histograms of segdata_resize_hist: in place in img_u8 (truncated), or with
+    img_f32 (a flat f32 buffer of as many elements) unrounded to img_f32 at the same element offsets."""
+    B = dims.shape[0]
+    assert hist.is_cuda and hist.dtype == torch.int32 and hist.is_contiguous() and tuple(hist.shape) == (B, 2, 256)
+    a = _segdata_common(offs, dims, max_hw, img_u8=_segdata_buf(img_u8, torch.uint8, "img_u8"), img_elems=img_u8.numel(),
+                        hist=hist.data_ptr(), num_stds=float(num_stds))
+    if img_f32 is not None:
+        assert img_f32.numel() >= img_u8.numel()
+        a.img_f32, a.out_f32 = _segdata_buf(img_f32, torch.float32, "img_f32"), 1
+    check(lib.memhip_segdata_norm(C.byref(a), stream_ptr()), "segdata_norm")
+
+
+def segdata_geom(offs, dims, max_hw, img, crop, crop_size, net_size=None, out=None, labels=None, label_out=None):
+    """crop i32 [B, 3] = {top, left, flip}.  Image: img (flat u8 or f32 buffer, samples at offs / dims) -> out f32
+    [B, 3, net_h, net_w]: crop, flip, channel swap, zero pad to crop_size, bilinear resize to net_size.  Labels: labels u8
+    [B, H, W] -> label_out u8 [B, crop_h, crop_w]: nearest resize to dims[b], the same crop and flip, pad 255."""
+    B = dims.shape[0]
+    assert crop.is_cuda and crop.dtype == torch.int32 and crop.is_contiguous() and tuple(crop.shape) == (B, 3), "crop: CUDA i32 [B, 3]"
+    a = _segdata_common(offs, dims, max_hw, crop=crop.data_ptr(), crop_h=int(crop_size[0]), crop_w=int(crop_size[1]))
+    if out is not None:
+        assert img.dtype in (torch.uint8, torch.float32)
+        a.in_f32 = int(img.dtype == torch.float32)
+        p = _segdata_buf(img, img.dtype, "img")
+        if a.in_f32:
+            a.img_f32 = p
+        else:
+            a.img_u8 = p
+        a.img_elems = img.numel()
+        a.net_h, a.net_w = int(net_size[0]), int(net_size[1])
+        assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (B, 3, a.net_h, a.net_w)
+        a.out = out.data_ptr()
+    else:
+        a.img_elems = int(img.numel()) if img is not None else (1 << 62)     # labels only: offs are not dereferenced
+    if label_out is not None:
+        assert labels.is_cuda and labels.dtype == torch.uint8 and labels.is_contiguous() and labels.dim() == 3 and labels.shape[0] == B
+        assert label_out.is_cuda and label_out.dtype == torch.uint8 and label_out.is_contiguous() \
+            and tuple(label_out.shape) == (B, a.crop_h, a.crop_w)
+        a.H, a.W = int(labels.shape[1]), int(labels.shape[2])
+        a.labels, a.label_out = labels.data_ptr(), label_out.data_ptr()
+    check(lib.memhip_segdata_geom(C.byref(a), stream_ptr()), "segdata_geom")

@@ -12,8 +12,9 @@ on the same parameters and buffers -- bf16 GEMMs of this library with fp32 accum
 GELU in fp32, the movement kernels of csrc/necks.hip around them, forward and backward.  A checkpoint moves freely between
 the two.  ``fpn3`` (identity) and ``fpn4`` (max pooling) are torch's in both.
 
-Not mirrored: ``resize_in`` (feed the model its ``img_size``), the patch-8 necks, gradient checkpointing, the mmseg / mmcv
-registry and runner; the decode head ``UPerHead`` (and its pyramid branch alone, mmseg's ``PSPHead``), the auxiliary ``FCNHead``
+Not mirrored here: ``resize_in`` (feed the model its ``img_size``: ``mem_amd.seg_data`` fuses that resize into the data chain's
+last kernel), the patch-8 necks, gradient checkpointing, the mmseg / mmcv registry and runner (``mem_amd.run_semseg`` restates
+what they decide); the decode head ``UPerHead`` (and its pyramid branch alone, mmseg's ``PSPHead``), the auxiliary ``FCNHead``
 and the thin ``EncoderDecoder`` are in ``mem_amd.seg_heads``, the heads' loss and metrics in ``mem_amd.seg_loss``.
 """
 from functools import partial
