@@ -1191,6 +1191,80 @@ typedef struct memhip_seg_plan memhip_seg_plan_t;
 int memhip_seg_plan(const memhip_seg_args_t* args, memhip_seg_plan_t* out);
 
 /* ------------------------------------------------------------------------
+ * Segmentation inference: logits of V views -> label map (seg_predict.hip, seg_predict_plan.cpp; additive to ABI 10)
+ * replaces mmseg 0.30 EncoderDecoder.slide_inference / whole_inference / inference / aug_test behind encode_decode
+ *          (mmseg/models/segmentors/encoder_decoder.py), reached from
+ *          mem/semantic_segmentation/configs/_base_/models/upernet_beit.py:53 (test_cfg) and
+ *          mem/semantic_segmentation/tools/test.py:94-99 (single_gpu_test / multi_gpu_test)
+ * ------------------------------------------------------------------------
+ * A view is one run of the model on one window of one flip state of the canvas [H, W].  All views share the window size
+ * (hc, wc) and the logits size (h, w), and with them one pair of axis tables (h -> hc, w -> wc) of memhip_seg_axis_table,
+ * of which i0 and w1 are read.  One gather kernel, a thread per four consecutive output pixels of a row; no upsampled tensor
+ * and no per-window canvas is written.  rects is a HOST array i32 [V, 3] = {y1, x1, flip}, copied into the kernel's
+ * arguments; with flip = 1 the rectangle is in the coordinates of the horizontally flipped canvas.
+ *
+ * For pass f among the flip values present (one or two passes):
+ *   L_f(y, x, c) = sum over the views of pass f whose rectangle holds (y, x), in the order of rects, of the bilinear logit at
+ *                  (y - y1, x - x1) -- w0y (w0x a + w1x b) + w1y (w0x c + w1x d) in fp32 -- divided by their number
+ *                  (slide_inference: preds += F.pad(crop_seg_logit, ...); count_mat += 1; preds / count_mat)
+ *   P_f = softmax_c(L_f), the maximum subtracted                                       (inference: F.softmax(seg_logit, dim=1))
+ *   output pixel (y, x) reads pass 1 at (y, W - 1 - x)                                 (inference: output.flip(dims=(3,)))
+ *   P = mean of P_f over the passes; pred = argmax_c P, ties to the lowest class       (aug_test: seg_logit /= len(imgs))
+ * With one pass the argmax is taken on L_f itself (softmax keeps an argmax), so one view that covers the canvas gives the
+ * labels of memhip_seg_confusion bit for bit.  Whole-image mode is V = 1, rectangle (0, 0), (hc, wc) = (H, W).
+ *
+ * Outputs, each optional (NULL = off), at least one: pred u8 [B, H, W]; prob f32 [B, C, H, W] = P; labels u8 [B, H, W] with
+ * confusion i64 [C, C] (row = label, column = pred; ADDED to; labels equal to ignore_index or >= C are skipped, as in
+ * memhip_seg_confusion; both set or both NULL).  The histogram of a workgroup lives in LDS and is flushed with 64-bit integer
+ * atomics.  No float atomics: two calls give the same bits.  No host synchronisation, no allocation, nothing is written
+ * outside the outputs.
+ *
+ * Rejected with MEMHIP_EINVAL before any launch, by the call and by the plan query alike: V outside 1 .. 64; C outside
+ * 2 .. 32; hc < h, wc < w, h < 1, w < 1; hc > H, wc > W; a rectangle that leaves the canvas; a flip value other than 0 / 1;
+ * a pass in which a pixel of the canvas is covered by no view (host arithmetic over the rectangles); labels without confusion
+ * or the reverse; no output.  B == 0 is MEMHIP_OK, nothing is read.  Not carried: vertical flips, multi-scale views (views
+ * of different sizes), more than 64 views per call.
+ * (Tagged structs with the typedef behind them, like memhip_seg_args; the tags say segpredict, as memhip_segdata_args says
+ * segdata: the `struct memhip_seg_*` of this header are the loss's two.) */
+struct memhip_segpredict_args {
+  const float* logits;               /* device f32, logical [V, B, C, h, w] at element strides sv, sb, sc, sy, sx (the views
+                                        stacked in the batch of the model call: sv = B sb; NCHW, or the heads' pixel rows
+                                        [V B h w, ld]: sb = h w ld, sc = 1, sy = w ld, sx = ld) */
+  int64_t sv, sb, sc, sy, sx;
+  const int32_t* rects;              /* HOST i32 [V, 3] = {y1, x1, flip}, read during the call */
+  int32_t V, B, C, h, w;             /* 1 <= V <= 64, 2 <= C <= 32, h, w >= 1 */
+  int32_t hc, wc;                    /* the window: hc >= h, wc >= w */
+  int32_t H, W;                      /* the canvas: H >= hc, W >= wc */
+  int32_t align_corners;             /* 0 / 1: what the tables were made with */
+  int32_t ignore_index;              /* labels: the value that does not count (mmseg: 255); -1: none */
+  int32_t reserved0;
+  const int32_t* y_i0; const float* y_w1;   /* device: the table (h -> hc) */
+  const int32_t* x_i0; const float* x_w1;   /* device: the table (w -> wc) */
+  uint8_t* pred;                     /* device u8 [B, H, W] or NULL */
+  float* prob;                       /* device f32 [B, C, H, W] or NULL */
+  const uint8_t* labels;             /* device u8 [B, H, W] or NULL */
+  int64_t* confusion;                /* device i64 [C, C] or NULL: ADDED to */
+};
+typedef struct memhip_segpredict_args memhip_segpredict_args_t;
+int memhip_seg_predict(const memhip_segpredict_args_t* args, memhip_stream_t stream);
+
+/* The launch as data.  memhip_seg_predict_plan validates the struct like the call does, except that the device pointers of
+ * logits and tables may be NULL (rects is host memory and is read).  Host arithmetic only. */
+struct memhip_segpredict_plan {
+  int32_t tile_h, tile_w;            /* output pixels per workgroup; tile (ty, tx) starts at (ty tile_h, tx tile_w) */
+  int32_t tiles_y, tiles_x;
+  int32_t grid, block;               /* grid = B tiles_y tiles_x */
+  int32_t lds_bytes;                 /* the workgroup's histogram */
+  int32_t pixels_per_thread;         /* consecutive x of one row */
+  int32_t padded_classes;            /* the instantiation: 8, 12, .. 32 */
+  int32_t passes;                    /* 1 or 2: the flip values present */
+  int32_t max_count;                 /* the largest number of views of one pass that cover one pixel */
+  int32_t pred_dwords;               /* pred leaves as whole dwords (W a multiple of 4 and pred 4-byte aligned) */
+};
+typedef struct memhip_segpredict_plan memhip_segpredict_plan_t;
+int memhip_seg_predict_plan(const memhip_segpredict_args_t* args, memhip_segpredict_plan_t* out);
+
+/* ------------------------------------------------------------------------
  * FCN decode head (seg_head.hip, seg_head_plan.cpp; additive to ABI 10)
  * replaces auxiliary_head = dict(type='FCNHead', in_index=2, channels=256, num_convs=1, concat_input=False, dropout_ratio=0.1,
  *          norm_cfg=SyncBN, align_corners=False)   mem/semantic_segmentation/configs/_base_/models/upernet_beit.py:38-50

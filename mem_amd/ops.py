@@ -1232,6 +1232,96 @@ def seg_confusion(logits, labels, confusion, ignore_index=255, align_corners=Fal
     check(lib.memhip_seg_confusion(C.byref(a), stream_ptr()), "seg_confusion")
 
 
+# ---------------------------------------------------------------- segmentation inference (csrc/seg_predict.hip, seg_predict_plan.cpp)
+class SegPredictArgs(C.Structure):
+    """== memhip_segpredict_args_t."""
+    _fields_ = [("logits", vp)] + [(n, i64) for n in ("sv", "sb", "sc", "sy", "sx")] + [("rects", vp)] + \
+               [(n, i32) for n in ("V", "B", "C", "h", "w", "hc", "wc", "H", "W", "align_corners", "ignore_index", "reserved0")] + \
+               [(n, vp) for n in ("y_i0", "y_w1", "x_i0", "x_w1", "pred", "prob", "labels", "confusion")]
+
+
+class SegPredictPlan(C.Structure):
+    """== memhip_segpredict_plan_t."""
+    _fields_ = [(n, i32) for n in ("tile_h", "tile_w", "tiles_y", "tiles_x", "grid", "block", "lds_bytes", "pixels_per_thread",
+                                   "padded_classes", "passes", "max_count", "pred_dwords")]
+
+
+declare({
+    "memhip_seg_predict": (i32, [C.POINTER(SegPredictArgs), vp]),
+    "memhip_seg_predict_plan": (i32, [C.POINTER(SegPredictArgs), C.POINTER(SegPredictPlan)]),
+})
+
+
+def seg_predict_args(rects, B, C_, hw, window, out_size, align_corners=False, ignore_index=255, **fields):
+    """The memhip_segpredict_args_t of seg_predict / seg_predict_plan.  rects: [(y1, x1, flip)] per view, kept in HOST memory
+    (the returned ``keep`` must outlive the call); pointer fields are addresses or None."""
+    import numpy as np
+    r = np.ascontiguousarray(np.asarray(rects, dtype=np.int32).reshape(-1, 3))
+    a = SegPredictArgs(V=int(r.shape[0]), B=B, C=C_, h=int(hw[0]), w=int(hw[1]), hc=int(window[0]), wc=int(window[1]),
+                       H=int(out_size[0]), W=int(out_size[1]), align_corners=int(align_corners),
+                       ignore_index=-1 if ignore_index is None else int(ignore_index), rects=r.ctypes.data)
+    for k, v in fields.items():
+        setattr(a, k, v)
+    return a, r
+
+
+def seg_predict_plan(rects, B, C_, hw, window, out_size, align_corners=False, **fields):
+    """The SegPredictPlan of a call with these shapes and rectangles: tiles, grid, LDS bytes, passes and the largest count.
+    Validates like the call (outputs included: pass dummy addresses as ``pred=...``); no device."""
+    a, keep = seg_predict_args(rects, B, C_, hw, window, out_size, align_corners, **fields)
+    plan = SegPredictPlan()
+    check(lib.memhip_seg_predict_plan(C.byref(a), C.byref(plan)), "seg_predict_plan")
+    return plan
+
+
+def seg_predict(logits, rects, window, out_size, pred=None, prob=None, labels=None, confusion=None, align_corners=False,
+                ignore_index=255):
+    """The label map of a segmentation model from the logits of V views (mmseg's slide_inference / whole_inference ->
+    softmax -> flip -> mean over the passes -> argmax), nothing upsampled in memory.
+
+    logits f32 [V, B, C, h, w], or [V B, C, h, w] with the views stacked in the batch (any strides: NCHW or the heads' pixel
+    rows); rects [(y1, x1, flip)] per view, flipped views in the coordinates of the flipped canvas; window (hc, wc) of every
+    view; out_size (H, W).  Outputs, each optional: pred u8 [B, H, W]; prob f32 [B, C, H, W]; labels u8 [B, H, W] with
+    confusion i64 [C, C] (+= the counts, ignore_index and labels >= C skipped).  Returns pred."""
+    V = len(rects)
+    assert logits.is_cuda and logits.dtype == torch.float32 and logits.dim() in (4, 5), "logits: a CUDA f32 tensor [V, B, C, h, w] or [V B, C, h, w]"
+    if logits.dim() == 5:
+        assert logits.shape[0] == V, (tuple(logits.shape), V)
+        B, C_, h, w = logits.shape[1:]
+        sv, (sb, sc, sy, sx) = logits.stride(0), logits.stride()[1:]
+    else:
+        assert V >= 1 and logits.shape[0] % V == 0, (tuple(logits.shape), V)
+        B, C_, h, w = logits.shape[0] // V, logits.shape[1], logits.shape[2], logits.shape[3]
+        sb, sc, sy, sx = logits.stride()
+        sv = B * sb
+    H, W = int(out_size[0]), int(out_size[1])
+    dev = logits.device
+    f = {}
+    if pred is not None:
+        assert pred.is_cuda and pred.dtype == torch.uint8 and pred.is_contiguous() and tuple(pred.shape) == (B, H, W), "pred: CUDA u8 [B, H, W]"
+        f["pred"] = pred.data_ptr()
+    if prob is not None:
+        assert prob.is_cuda and prob.dtype == torch.float32 and prob.is_contiguous() and tuple(prob.shape) == (B, C_, H, W), \
+            "prob: CUDA f32 [B, C, H, W]"
+        f["prob"] = prob.data_ptr()
+    if labels is not None:
+        assert labels.is_cuda and labels.dtype == torch.uint8 and labels.is_contiguous() and tuple(labels.shape) == (B, H, W), \
+            "labels: CUDA u8 [B, H, W]"
+        f["labels"] = labels.data_ptr()
+    if confusion is not None:
+        assert confusion.is_cuda and confusion.dtype == torch.int64 and confusion.is_contiguous() and tuple(confusion.shape) == (C_, C_), \
+            "confusion: CUDA i64 [C, C]"
+        f["confusion"] = confusion.data_ptr()
+    a, keep = seg_predict_args(rects, B, C_, (h, w), window, (H, W), align_corners, ignore_index, logits=logits.data_ptr(), **f)
+    a.sv, a.sb, a.sc, a.sy, a.sx = sv, sb, sc, sy, sx
+    if B > 0 and 1 <= h <= a.hc and 1 <= w <= a.wc:        # (a shape the tables cannot be made for is rejected by the call)
+        ty, tx = seg_tables(h, a.hc, align_corners, dev), seg_tables(w, a.wc, align_corners, dev)
+        a.y_i0, a.y_w1 = _table_ptrs(ty, h, a.hc)[:2]
+        a.x_i0, a.x_w1 = _table_ptrs(tx, w, a.wc)[:2]
+    check(lib.memhip_seg_predict(C.byref(a), stream_ptr()), "seg_predict")
+    return pred
+
+
 # ---------------------------------------------------------------- FCN decode head (csrc/seg_head.hip, seg_head_plan.cpp)
 DROPOUT_SITE_HEAD = 0x48454144       # == MEMHIP_DROPOUT_SITE_HEAD: Dropout2d of decode head i is site DROPOUT_SITE_HEAD + i
 BN_GROUPS = 128                      # == MEMHIP_BN_GROUPS

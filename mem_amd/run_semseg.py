@@ -46,8 +46,8 @@ REFUSED = {
 }
 
 
-def get_args(argv=None):
-    p = argparse.ArgumentParser("mem_amd semantic segmentation (stage 4)", allow_abbrev=False)
+def add_model_data_flags(p):
+    """The source, model and data flags, shared with ``mem_amd.infer_semseg``."""
     p.add_argument("--data_root", default="synthetic", help="folder with imgs/<split>, anns/<split>, labels.txt, or 'synthetic'")
     p.add_argument("--train_split", default="train")
     p.add_argument("--val_split", default="val")
@@ -80,6 +80,20 @@ def get_args(argv=None):
     p.add_argument("--slice_max_evs", default=180000, type=int)
     p.add_argument("--cat_max_ratio", default=1.0, type=float)
     p.add_argument("--samples_per_gpu", default=16, type=int)
+
+
+def resolve_model_args(args):
+    """The values that follow from others: the width and heads of --vit, the last four blocks."""
+    dim, heads = VIT_SIZES[args.vit]
+    args.embed_dim, args.num_heads = args.embed_dim or dim, args.num_heads or heads
+    if args.out_indices is None:
+        args.out_indices = list(range(args.depth - 4, args.depth))
+    return args
+
+
+def get_args(argv=None):
+    p = argparse.ArgumentParser("mem_amd semantic segmentation (stage 4)", allow_abbrev=False)
+    add_model_data_flags(p)
     # optimizer and schedule (mem_224_160k.py, schedule_160k.py)
     p.add_argument("--lr", default=5e-4, type=float)
     p.add_argument("--betas", default=[0.9, 0.999], type=float, nargs=2)
@@ -112,11 +126,8 @@ def get_args(argv=None):
             raise NotImplementedError(f"--{flag} {getattr(args, flag)}: {why}")
     if args.cat_max_ratio < 1.0:
         raise NotImplementedError(f"--cat_max_ratio {args.cat_max_ratio}: class-balanced crops are not mirrored (dsec.py sets 1.0)")
-    dim, heads = VIT_SIZES[args.vit]
-    args.embed_dim, args.num_heads = args.embed_dim or dim, args.num_heads or heads
+    resolve_model_args(args)
     args.num_layers = args.num_layers or args.depth
-    if args.out_indices is None:
-        args.out_indices = list(range(args.depth - 4, args.depth))
     return args
 
 
