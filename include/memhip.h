@@ -36,7 +36,7 @@ extern "C" {
 #endif
 
 #define MEMHIP_ABI_VERSION 10  /* 10: the rasterizer takes one args struct: memhip_rasterize and memhip_rasterize_plan read the same memhip_raster_args_t; the
-                                  memhip_rasterize_f64 / _aug_f64 / _var_f64 / _binned_f64 / _workspace / _binned_workspace symbols are gone (additive since: memhip_convt2d_nhwc, memhip_convt_plan, memhip_kl_uniform_rows of the tokenizer's decoder; memhip_conv_wgrad_nhwc / _plan / _workspace with memhip_conv_wgrad_args_t, memhip_relu_bwd_colsum / _workspace of dVAE training; memhip_seg_axis_table / _seg_plan / _seg_ce / _seg_confusion with memhip_seg_args_t of the segmentation loss; memhip_segdata_resize_hist / _norm / _geom with memhip_segdata_args_t of the segmentation data chain); 9: the tokenizer takes one args struct: memhip_conv2d_nhwc and memhip_conv_plan read the same memhip_conv_args_t; one
+                                  memhip_rasterize_f64 / _aug_f64 / _var_f64 / _binned_f64 / _workspace / _binned_workspace symbols are gone (additive since: memhip_convt2d_nhwc, memhip_convt_plan, memhip_kl_uniform_rows of the tokenizer's decoder; memhip_conv_wgrad_nhwc / _plan / _workspace with memhip_conv_wgrad_args_t, memhip_relu_bwd_colsum / _workspace of dVAE training; memhip_seg_axis_table / _seg_plan / _seg_ce / _seg_confusion with memhip_seg_args_t of the segmentation loss; memhip_segdata_resize_hist / _norm / _geom with memhip_segdata_args_t of the segmentation data chain; memhip_seg_ohem_keys / _seg_ohem_select / _seg_ce_w / _seg_ohem_plan with memhip_segohem_args_t of class weights and OHEM in the segmentation loss); 9: the tokenizer takes one args struct: memhip_conv2d_nhwc and memhip_conv_plan read the same memhip_conv_args_t; one
                                   memhip_nchw_to_padded_nhwc4 and one memhip_argmax_rows with a mode argument; the per-mode symbols (_bf16 / _f32 / _f32_dyn / _f32_ex / _f16x2) are gone;
                                   8: one entry point per backward family, optional features as struct fields (memhip_branch_bwd, memhip_layernorm_bwd_branch,
                                   memhip_attn_bwd take an args struct; memhip_gemm_bf16_tn takes the workspace; the *_map / *_drop / *_out / *_ws symbols are gone; additive since: the memhip_neck_* entry points of the feature-pyramid necks);
@@ -1189,6 +1189,82 @@ struct memhip_seg_plan {
 };
 typedef struct memhip_seg_plan memhip_seg_plan_t;
 int memhip_seg_plan(const memhip_seg_args_t* args, memhip_seg_plan_t* out);
+
+/* ------------------------------------------------------------------------
+ * Class weights and OHEM pixel sampling inside the fused loss (seg_ohem.hip, seg_loss.hip, seg_plan.cpp; additive to ABI 10)
+ * replaces mmseg 0.30 CrossEntropyLoss(class_weight=...) and OHEMPixelSampler(thresh, min_kept)
+ *          (mmseg/models/losses/cross_entropy_loss.py, mmseg/core/seg/sampler/ohem_pixel_sampler.py)
+ * ------------------------------------------------------------------------
+ * With z_p the resized logits of output pixel p (the tables above), l_p its label, valid as above, nll_p = logsumexp(z_p) -
+ * z_p[l_p], cw the class weights (all ones when class_weight is NULL) and s_p in {0, 1} the sampler's pixel weight:
+ *   loss = loss_weight / N * sum over valid p of cw[l_p] s_p nll_p,  N = B H W, or max(n_valid, 1) with avg_non_ignore
+ *   dz   = sum over the outputs of weight * cw[l_p] s_p (softmax - onehot), UNSCALED as in memhip_seg_ce
+ * N, n_valid, n_correct and n_bad depend on neither cw nor s (mmseg does not divide by the sum of the weights).
+ *
+ * The sampler is not differentiated through.  Its keys are fp32, computed once and stored as a [B, H, W] map; every keep
+ * decision is taken on the stored keys, so the selection and the loss kernel cannot disagree about a pixel.  A key k counts
+ * when k >= 0.0f (a NaN does not; -0.0f is 0.0f); memhip_seg_ohem_keys stores -1.0f at pixels that are not valid.  With n the
+ * number of keys that count and K = min_kept * B:
+ *   sampler 1 (thresh T):  key = softmax(z_p)[l_p].  n == 0: nothing kept.  Else, keys ascending a_0 <= .. <= a_n-1,
+ *                          t = max(a_min(K, n-1), T) and s_p = [key_p < t].          *threshold = t;  -inf = keep none
+ *   sampler 2 (top-k):     key = cw[l_p] nll_p.  K' = min(K, n); K' == 0: nothing kept.  Else, keys descending b_0 >= ..,
+ *                          v = b_K'-1 and s_p = [key_p >= v].                        *threshold = v;  +inf = keep none
+ *                          EVERY key equal to v is kept (mmseg keeps exactly K, by the order its sort leaves among ties).
+ * "Keep all" has no value of its own: it is a t above every key (sampler 1), or v = the smallest key (sampler 2).
+ * K is per process, as in mmseg: nothing is exchanged between ranks.
+ *
+ *   memhip_seg_ohem_keys:   logits, labels -> keys.  A thread per output pixel, max-subtracted softmax in fp32, the same
+ *                           interpolation arithmetic as the loss kernel.  Reads class_weight with sampler 2.  The three calls
+ *                           validate one struct alike: this call touches neither threshold nor the workspace, yet a NULL
+ *                           threshold is rejected, and so is a workspace that is given and too small (NULL is fine).  A caller
+ *                           that wants the key map alone passes any f32 [1] as threshold.
+ *   memhip_seg_ohem_select: keys (which the caller may have written) -> *threshold and seg.stats[3] = n_kept, the number of
+ *                           keys that count and pass the comparison.  An exact radix select on the keys' bit patterns
+ *                           (non-negative floats order like their bits): three histogram passes over bits 31..21 / 20..10 / 9..0 (bit 31 is
+ *                           zero in a key that counts, so the 31 value bits split 10 / 11 / 10 and the first pass fills 1024 of its bins), a
+ *                           histogram per workgroup in LDS, nonzero bins flushed with 64-bit integer atomics, a
+ *                           one-workgroup scan after each pass that finds the bin of rank r (n and r are derived on the device:
+ *                           r = min(K, n - 1) ascending, or n - K'), then a counting pass.  No float atomics, no host read, no sort.
+ *                           The call clears its part of the workspace on the stream before it counts: the caller prepares nothing.
+ *   memhip_seg_ce_w:        memhip_seg_ce's kernel with q_c and the loss term multiplied by cw[l_p] s_p; cw is staged once per
+ *                           workgroup, s_p is read from keys and *threshold; seg.stats is i64 [4]: n_valid, n_correct, n_bad,
+ *                           n_kept (= n_valid without a sampler), counted at the pixel's home tile.  With class_weight NULL
+ *                           and sampler 0, or with all weights 1.0f, loss, dz and stats[0..2] are memhip_seg_ce's bit for bit.
+ * All three validate before any launch; memhip_seg_ohem_plan gives the same code and message, except that the device
+ * pointers of seg may be NULL.  Rejected with MEMHIP_EINVAL: everything memhip_seg_plan rejects; a sampler other than 0, 1, 2;
+ * with sampler 1 a thresh outside (0, 1]; with a sampler min_kept < 0 or > 2^40, or keys or threshold NULL; sampler 0 in
+ * memhip_seg_ohem_keys / _select.  A workspace of fewer than ws_bytes bytes is MEMHIP_EWORKSPACE.  class_weight's entries must be
+ * finite and >= 0: device memory, not read by the validation.
+ * (Tagged structs with the typedef behind them; the tags say segohem, as memhip_segpredict_args says segpredict.) */
+struct memhip_segohem_args {
+  memhip_seg_args_t seg;             /* as for memhip_seg_ce; stats: device i64 [4]; workspace_bytes >= memhip_segohem_plan_t.ws_bytes;
+                                        confusion is not read */
+  const float* class_weight;         /* device f32 [C], or NULL: all ones */
+  int32_t sampler;                   /* 0 none, 1 thresh, 2 top-k */
+  float thresh;                      /* T, sampler 1 */
+  int64_t min_kept;                  /* m */
+  float* keys;                       /* device f32 [B, H, W], caller-provided */
+  float* threshold;                  /* device f32 [1]: t or v */
+};
+typedef struct memhip_segohem_args memhip_segohem_args_t;
+int memhip_seg_ohem_keys(const memhip_segohem_args_t* args, memhip_stream_t stream);
+int memhip_seg_ohem_select(const memhip_segohem_args_t* args, memhip_stream_t stream);
+int memhip_seg_ce_w(const memhip_segohem_args_t* args, memhip_stream_t stream);
+
+/* The launches of the three calls as data.  Host arithmetic only. */
+struct memhip_segohem_plan {
+  memhip_seg_plan_t seg;             /* memhip_seg_ce_w's kernel: memhip_seg_ce's plan, lds_bytes with the staged class weights */
+  int32_t keys_grid, keys_block;     /* memhip_seg_ohem_keys: strides over the pixels beyond keys_grid workgroups */
+  int32_t select_grid, select_block; /* the histogram and counting passes of memhip_seg_ohem_select */
+  int32_t select_passes, select_bins;/* 3 passes, 2048 bins (the last pass uses 1024) */
+  int32_t select_lds_bytes;          /* a workgroup's histogram */
+  int32_t reserved;
+  uint64_t select_ws_offset;         /* the selection's part of the workspace: [offset, offset + bytes), cleared by the call */
+  uint64_t select_ws_bytes;          /* 0 without a sampler */
+  uint64_t ws_bytes;                 /* seg.ws_bytes (the partials, rounded up to 8) + select_ws_bytes */
+};
+typedef struct memhip_segohem_plan memhip_segohem_plan_t;
+int memhip_seg_ohem_plan(const memhip_segohem_args_t* args, memhip_segohem_plan_t* out);
 
 /* ------------------------------------------------------------------------
  * Segmentation inference: logits of V views -> label map (seg_predict.hip, seg_predict_plan.cpp; additive to ABI 10)

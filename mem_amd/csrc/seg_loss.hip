@@ -18,6 +18,11 @@
 //
 // Evaluation (seg_confusion_kernel): a thread per output pixel with a counted label, logits read through the cache, running
 // argmax, an LDS histogram per workgroup, nonzero cells flushed with 64-bit integer atomics.
+//
+// Class weights and OHEM (memhip_seg_ce_w, memhip_seg_ohem_keys; the selection between them is seg_ohem.hip): the training
+// kernel's WEIGHTED instantiation multiplies q and the loss term by cw[label] * s, with cw staged in LDS once per workgroup and
+// s decided on the key that seg_ohem_keys_kernel stored (a thread per output pixel, like the confusion kernel) against the
+// threshold the selection left in device memory.
 #include "common.h"
 #include "seg_plan.hpp"
 
@@ -37,6 +42,12 @@ struct SegK {
   int tiles_y, tiles_x, max_fh, max_fw, tab_lds;
 };
 
+// what memhip_seg_ce_w adds: the class weights (NULL: ones) and the sampler's stored keys and threshold (sampler 0: none)
+struct SegW {
+  const float* cw; const float* keys; const float* threshold;
+  int sampler;
+};
+
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 // the weight with which output (i0, i1 = min(i0 + 1, n - 1), w1) reads input i
@@ -44,13 +55,16 @@ __device__ __forceinline__ float weight_of(int i, int i0, int i1, float w1) {
   return (i0 == i ? 1.f - w1 : 0.f) + (i1 == i ? w1 : 0.f);
 }
 
-template <int CP>
-__global__ __launch_bounds__(kThreads) void seg_ce_kernel(SegK k) {
+// WEIGHTED: memhip_seg_ce_w -- q and the loss term times f = cw[label] * s, s from the stored key and *threshold; with f = 1.0f
+// every product is exact and the bits are those of the plain instantiation
+template <int CP, bool WEIGHTED>
+__global__ __launch_bounds__(kThreads) void seg_ce_kernel(SegK k, SegW sw) {
   extern __shared__ __align__(16) unsigned char smem[];
   constexpr int kPitch = CP + 1;
   float* zt = reinterpret_cast<float*>(smem);                 // [kHalo * kHalo][kPitch]
   float* qs = zt + kHalo * kHalo * kPitch;                    // [CP][kChunk]
-  int* s_yi0 = reinterpret_cast<int*>(qs + CP * kChunk);      // [max_fh], then w1 [max_fh], then the x axis
+  float* s_cw = qs + CP * kChunk;                             // [kMaxC], WEIGHTED only
+  int* s_yi0 = reinterpret_cast<int*>(s_cw + (WEIGHTED ? kMaxC : 0));   // [max_fh], then w1 [max_fh], then the x axis
   float* s_yw1 = reinterpret_cast<float*>(s_yi0 + k.max_fh);
   int* s_xi0 = reinterpret_cast<int*>(s_yw1 + k.max_fh);
   float* s_xw1 = reinterpret_cast<float*>(s_xi0 + k.max_fw);
@@ -79,6 +93,11 @@ __global__ __launch_bounds__(kThreads) void seg_ce_kernel(SegK k) {
     for (int e = t; e < fw; e += kThreads) { s_xi0[e] = k.x_i0[X0 + e]; s_xw1[e] = k.x_w1[X0 + e]; }
     yi0 = s_yi0 - Y0; yw1 = s_yw1 - Y0; xi0 = s_xi0 - X0; xw1 = s_xw1 - X0;
   }
+  float thr = 0.f;
+  if constexpr (WEIGHTED) {
+    if (t < kMaxC) s_cw[t] = (sw.cw && t < C) ? sw.cw[t] : 1.f;
+    if (sw.sampler) thr = *sw.threshold;
+  }
   // the halo tile; neighbouring threads take neighbouring addresses in either layout
   {
     const float* src = k.logits + (long long)b * k.sb;
@@ -105,7 +124,7 @@ __global__ __launch_bounds__(kThreads) void seg_ce_kernel(SegK k) {
   for (int m = 0; m < CP / 4; ++m) acc[m] = 0.f;
 
   double loss = 0.0;
-  int n_valid = 0, n_correct = 0, n_bad = 0;
+  int n_valid = 0, n_correct = 0, n_bad = 0, n_kept = 0;
   const uint8_t* lab_b = k.labels + (long long)b * k.H * k.W;
 
   for (int base = 0; base < nfp; base += kChunk) {
@@ -142,11 +161,26 @@ __global__ __launch_bounds__(kThreads) void seg_ce_kernel(SegK k) {
         s += z[c];
       }
       const float inv = valid ? 1.f / s : 0.f;
-#pragma unroll
-      for (int c = 0; c < CP; ++c) qs[c * kChunk + t] = valid ? z[c] * inv - (c == lab ? 1.f : 0.f) : 0.f;
       const bool home = a0 >= i_first && a0 <= i_last && b0 >= j_first && b0 <= j_last;
+      if constexpr (WEIGHTED) {
+        bool keep = valid;
+        if (valid && sw.sampler) {                             // the decision is taken on the stored key, never recomputed
+          const float key = sw.keys[((long long)b * k.H + y) * k.W + x];
+          keep = key >= 0.f && (sw.sampler == 1 ? key < thr : key >= thr);
+        }
+        const float f = keep ? s_cw[valid ? lab : 0] : 0.f;
+#pragma unroll
+        for (int c = 0; c < CP; ++c) qs[c * kChunk + t] = valid ? (z[c] * inv - (c == lab ? 1.f : 0.f)) * f : 0.f;
+        if (home && valid) {
+          loss += (double)f * (double)(logf(s) - (zl - mx));
+          n_kept += keep;
+        }
+      } else {
+#pragma unroll
+        for (int c = 0; c < CP; ++c) qs[c * kChunk + t] = valid ? z[c] * inv - (c == lab ? 1.f : 0.f) : 0.f;
+        if (home && valid) loss += (double)(logf(s) - (zl - mx));
+      }
       if (home && valid) {
-        loss += (double)(logf(s) - (zl - mx));
         n_valid += 1;
         n_correct += am == lab;
       } else if (home && counted) {
@@ -191,36 +225,40 @@ __global__ __launch_bounds__(kThreads) void seg_ce_kernel(SegK k) {
   int* r_cnt = reinterpret_cast<int*>(r_loss + kThreads);
   r_loss[t] = loss;
   r_cnt[t] = n_valid; r_cnt[kThreads + t] = n_correct; r_cnt[2 * kThreads + t] = n_bad;
+  if constexpr (WEIGHTED) r_cnt[3 * kThreads + t] = n_kept;   // 6 KiB of the 8 KiB that eight channels of q give
   __syncthreads();
   for (int s = kThreads / 2; s > 0; s >>= 1) {
     if (t < s) {
       r_loss[t] += r_loss[t + s];
       r_cnt[t] += r_cnt[t + s]; r_cnt[kThreads + t] += r_cnt[kThreads + t + s]; r_cnt[2 * kThreads + t] += r_cnt[2 * kThreads + t + s];
+      if constexpr (WEIGHTED) r_cnt[3 * kThreads + t] += r_cnt[3 * kThreads + t + s];
     }
     __syncthreads();
   }
-  if (t == 0) k.ws[blockIdx.x] = Partial{r_loss[0], r_cnt[0], r_cnt[kThreads], r_cnt[2 * kThreads], 0};
+  if (t == 0) k.ws[blockIdx.x] = Partial{r_loss[0], r_cnt[0], r_cnt[kThreads], r_cnt[2 * kThreads], WEIGHTED ? r_cnt[3 * kThreads] : 0};
 }
 
-// one workgroup: the G partials in a fixed order -> loss [3] = loss, loss_weight / N, loss_sum; stats [3]
+// one workgroup: the G partials in a fixed order -> loss [3] = loss, loss_weight / N, loss_sum; stats [3], or [4] with_kept
 __global__ __launch_bounds__(kThreads) void seg_finish_kernel(const Partial* __restrict__ ws, int G, long long pixels, int avg_non_ignore,
-                                                              float loss_weight, float* __restrict__ loss, long long* __restrict__ stats) {
+                                                              float loss_weight, float* __restrict__ loss, long long* __restrict__ stats,
+                                                              int with_kept) {
   __shared__ double r_loss[kThreads];
-  __shared__ long long r_cnt[3 * kThreads];
+  __shared__ long long r_cnt[4 * kThreads];
   const int t = threadIdx.x;
   double l = 0.0;
-  long long v = 0, c = 0, bad = 0;
+  long long v = 0, c = 0, bad = 0, kept = 0;
   for (int gi = t; gi < G; gi += kThreads) {
     const Partial p = ws[gi];
-    l += p.loss; v += p.valid; c += p.correct; bad += p.bad;
+    l += p.loss; v += p.valid; c += p.correct; bad += p.bad; kept += p.kept;
   }
   r_loss[t] = l;
-  r_cnt[t] = v; r_cnt[kThreads + t] = c; r_cnt[2 * kThreads + t] = bad;
+  r_cnt[t] = v; r_cnt[kThreads + t] = c; r_cnt[2 * kThreads + t] = bad; r_cnt[3 * kThreads + t] = kept;
   __syncthreads();
   for (int s = kThreads / 2; s > 0; s >>= 1) {
     if (t < s) {
       r_loss[t] += r_loss[t + s];
       r_cnt[t] += r_cnt[t + s]; r_cnt[kThreads + t] += r_cnt[kThreads + t + s]; r_cnt[2 * kThreads + t] += r_cnt[2 * kThreads + t + s];
+      r_cnt[3 * kThreads + t] += r_cnt[3 * kThreads + t + s];
     }
     __syncthreads();
   }
@@ -231,6 +269,7 @@ __global__ __launch_bounds__(kThreads) void seg_finish_kernel(const Partial* __r
     loss[1] = (float)((double)loss_weight / N);
     loss[2] = (float)r_loss[0];
     stats[0] = nv; stats[1] = r_cnt[kThreads]; stats[2] = r_cnt[2 * kThreads];
+    if (with_kept) stats[3] = r_cnt[3 * kThreads];
   }
 }
 
@@ -267,6 +306,49 @@ __global__ __launch_bounds__(kConfThreads) void seg_confusion_kernel(SegK k, lon
     if (hist[e]) atomicAdd(conf + e, (unsigned long long)hist[e]);
 }
 
+// The sampler's keys: a thread per output pixel, the interpolation of the kernels above, two walks over the channels (the
+// maximum and the label's logit, then the sum of expf(z - max): the same fp32 chain as the training kernel's).
+// mode 1: softmax[label]; mode 2: cw[label] * nll.  Pixels that are not valid store -1.0f.
+__global__ __launch_bounds__(kConfThreads) void seg_ohem_keys_kernel(SegK k, long long total, int mode, const float* __restrict__ cw,
+                                                                     float* __restrict__ keys) {
+  const int C = k.C;
+  const long long HW = (long long)k.H * k.W;
+  for (long long n = (long long)blockIdx.x * kConfThreads + threadIdx.x; n < total; n += (long long)gridDim.x * kConfThreads) {
+    const int lab = k.labels[n];
+    if (lab == k.ignore || lab >= C) { keys[n] = -1.f; continue; }
+    const long long b = n / HW;
+    const int r = (int)(n - b * HW), y = r / k.W, x = r - y * k.W;
+    const int a0 = clampi(k.y_i0[y], 0, k.h - 1), a1 = min(a0 + 1, k.h - 1);
+    const int b0 = clampi(k.x_i0[x], 0, k.w - 1), b1 = min(b0 + 1, k.w - 1);
+    const float wy1 = k.y_w1[y], wy0 = 1.f - wy1, wx1 = k.x_w1[x], wx0 = 1.f - wx1;
+    const float* src = k.logits + b * k.sb;
+    const float* p00 = src + a0 * k.sy + b0 * k.sx;
+    const float* p01 = src + a0 * k.sy + b1 * k.sx;
+    const float* p10 = src + a1 * k.sy + b0 * k.sx;
+    const float* p11 = src + a1 * k.sy + b1 * k.sx;
+    float mx = 0.f, zl = 0.f;
+    for (int c = 0; c < C; ++c) {
+      const long long o = c * k.sc;
+      const float z = wy0 * (wx0 * p00[o] + wx1 * p01[o]) + wy1 * (wx0 * p10[o] + wx1 * p11[o]);
+      if (c == 0 || z > mx) mx = z;
+      if (c == lab) zl = z;
+    }
+    float s = 0.f;
+    for (int c = 0; c < C; ++c) {
+      const long long o = c * k.sc;
+      const float z = wy0 * (wx0 * p00[o] + wx1 * p01[o]) + wy1 * (wx0 * p10[o] + wx1 * p11[o]);
+      s += expf(z - mx);
+    }
+    float key;
+    if (mode == 1) {
+      key = expf(zl - mx) / s;
+    } else {
+      key = (logf(s) - (zl - mx)) * (cw ? cw[lab] : 1.f);
+    }
+    keys[n] = key > 0.f ? key : 0.f;                          // never -0.0f, never below the smallest key that counts
+  }
+}
+
 SegK kernel_args(const memhip_seg_args_t* a, const memhip_seg_plan_t& p) {
   SegK k{};
   k.logits = a->logits; k.sb = a->sb; k.sc = a->sc; k.sy = a->sy; k.sx = a->sx;
@@ -280,25 +362,38 @@ SegK kernel_args(const memhip_seg_args_t* a, const memhip_seg_plan_t& p) {
   return k;
 }
 
+// the training kernel of either entry and its finish kernel
+template <bool WEIGHTED>
+void launch_ce(const memhip_seg_args_t* a, const memhip_seg_plan_t& p, const SegW& sw, memhip_stream_t stream) {
+  const SegK k = kernel_args(a, p);
+  const dim3 grid(p.grid), block(p.block);
+  switch (padded_channels(a->C)) {
+    case 8: hipLaunchKernelGGL((seg_ce_kernel<8, WEIGHTED>), grid, block, p.lds_bytes, as_stream(stream), k, sw); break;
+    case 12: hipLaunchKernelGGL((seg_ce_kernel<12, WEIGHTED>), grid, block, p.lds_bytes, as_stream(stream), k, sw); break;
+    case 16: hipLaunchKernelGGL((seg_ce_kernel<16, WEIGHTED>), grid, block, p.lds_bytes, as_stream(stream), k, sw); break;
+    case 20: hipLaunchKernelGGL((seg_ce_kernel<20, WEIGHTED>), grid, block, p.lds_bytes, as_stream(stream), k, sw); break;
+    case 24: hipLaunchKernelGGL((seg_ce_kernel<24, WEIGHTED>), grid, block, p.lds_bytes, as_stream(stream), k, sw); break;
+    case 28: hipLaunchKernelGGL((seg_ce_kernel<28, WEIGHTED>), grid, block, p.lds_bytes, as_stream(stream), k, sw); break;
+    default: hipLaunchKernelGGL((seg_ce_kernel<32, WEIGHTED>), grid, block, p.lds_bytes, as_stream(stream), k, sw); break;
+  }
+  hipLaunchKernelGGL(seg_finish_kernel, dim3(1), dim3(kThreads), 0, as_stream(stream), k.ws, p.grid, (long long)a->B * a->H * a->W,
+                     a->avg_non_ignore, a->loss_weight, a->loss, reinterpret_cast<long long*>(a->stats), WEIGHTED ? 1 : 0);
+}
+
 }  // namespace
 
 extern "C" int memhip_seg_ce(const memhip_seg_args_t* a, memhip_stream_t stream) {
   memhip_seg_plan_t p;
   if (int rc = seg_plan(a, SEG_CE, &p)) return rc;
-  const SegK k = kernel_args(a, p);
-  const dim3 grid(p.grid), block(p.block);
-  switch (padded_channels(a->C)) {
-    case 8: hipLaunchKernelGGL(seg_ce_kernel<8>, grid, block, p.lds_bytes, as_stream(stream), k); break;
-    case 12: hipLaunchKernelGGL(seg_ce_kernel<12>, grid, block, p.lds_bytes, as_stream(stream), k); break;
-    case 16: hipLaunchKernelGGL(seg_ce_kernel<16>, grid, block, p.lds_bytes, as_stream(stream), k); break;
-    case 20: hipLaunchKernelGGL(seg_ce_kernel<20>, grid, block, p.lds_bytes, as_stream(stream), k); break;
-    case 24: hipLaunchKernelGGL(seg_ce_kernel<24>, grid, block, p.lds_bytes, as_stream(stream), k); break;
-    case 28: hipLaunchKernelGGL(seg_ce_kernel<28>, grid, block, p.lds_bytes, as_stream(stream), k); break;
-    default: hipLaunchKernelGGL(seg_ce_kernel<32>, grid, block, p.lds_bytes, as_stream(stream), k); break;
-  }
-  hipLaunchKernelGGL(seg_finish_kernel, dim3(1), dim3(kThreads), 0, as_stream(stream), k.ws, p.grid, (long long)a->B * a->H * a->W,
-                     a->avg_non_ignore, a->loss_weight, a->loss, reinterpret_cast<long long*>(a->stats));
+  launch_ce<false>(a, p, SegW{}, stream);
   return check_launch("seg_ce");
+}
+
+extern "C" int memhip_seg_ce_w(const memhip_segohem_args_t* a, memhip_stream_t stream) {
+  memhip_segohem_plan_t p;
+  if (int rc = seg_ohem_plan(a, OHEM_CE, &p)) return rc;
+  launch_ce<true>(&a->seg, p.seg, SegW{a->class_weight, a->keys, a->threshold, a->sampler}, stream);
+  return check_launch("seg_ce_w");
 }
 
 extern "C" int memhip_seg_confusion(const memhip_seg_args_t* a, memhip_stream_t stream) {
@@ -307,4 +402,12 @@ extern "C" int memhip_seg_confusion(const memhip_seg_args_t* a, memhip_stream_t 
   hipLaunchKernelGGL(seg_confusion_kernel, dim3(p.conf_grid), dim3(p.conf_block), 0, as_stream(stream), kernel_args(a, p),
                      (long long)a->B * a->H * a->W, reinterpret_cast<unsigned long long*>(a->confusion));
   return check_launch("seg_confusion");
+}
+
+extern "C" int memhip_seg_ohem_keys(const memhip_segohem_args_t* a, memhip_stream_t stream) {
+  memhip_segohem_plan_t p;
+  if (int rc = seg_ohem_plan(a, OHEM_KEYS, &p)) return rc;
+  hipLaunchKernelGGL(seg_ohem_keys_kernel, dim3(p.keys_grid), dim3(p.keys_block), 0, as_stream(stream), kernel_args(&a->seg, p.seg),
+                     (long long)a->seg.B * a->seg.H * a->seg.W, a->sampler, a->class_weight, a->keys);
+  return check_launch("seg_ohem_keys");
 }

@@ -1232,6 +1232,114 @@ def seg_confusion(logits, labels, confusion, ignore_index=255, align_corners=Fal
     check(lib.memhip_seg_confusion(C.byref(a), stream_ptr()), "seg_confusion")
 
 
+# ---------------------------------------------------------------- class weights and OHEM in the fused loss (csrc/seg_ohem.hip, seg_loss.hip)
+SEG_SAMPLER_NONE, SEG_SAMPLER_THRESH, SEG_SAMPLER_TOPK = 0, 1, 2
+
+
+class SegOhemArgs(C.Structure):
+    """== memhip_segohem_args_t."""
+    _fields_ = [("seg", SegArgs), ("class_weight", vp), ("sampler", i32), ("thresh", f32), ("min_kept", i64), ("keys", vp),
+                ("threshold", vp)]
+
+
+class SegOhemPlan(C.Structure):
+    """== memhip_segohem_plan_t."""
+    _fields_ = [("seg", SegPlan)] + \
+               [(n, i32) for n in ("keys_grid", "keys_block", "select_grid", "select_block", "select_passes", "select_bins",
+                                   "select_lds_bytes", "reserved")] + \
+               [(n, C.c_uint64) for n in ("select_ws_offset", "select_ws_bytes", "ws_bytes")]
+
+
+declare({
+    "memhip_seg_ohem_plan": (i32, [C.POINTER(SegOhemArgs), C.POINTER(SegOhemPlan)]),
+    "memhip_seg_ohem_keys": (i32, [C.POINTER(SegOhemArgs), vp]),
+    "memhip_seg_ohem_select": (i32, [C.POINTER(SegOhemArgs), vp]),
+    "memhip_seg_ce_w": (i32, [C.POINTER(SegOhemArgs), vp]),
+})
+
+
+def seg_ohem_args(seg, sampler=0, thresh=None, min_kept=0, **fields):
+    """The memhip_segohem_args_t around a SegArgs; sampler: 0 none, 1 thresh, 2 top-k; pointer fields are addresses or None."""
+    a = SegOhemArgs(seg=seg, sampler=int(sampler), thresh=0.0 if thresh is None else float(thresh), min_kept=int(min_kept))
+    for k, v in fields.items():
+        setattr(a, k, v)
+    return a
+
+
+def seg_ohem_plan(B, C_, h, w, H, W, align_corners=False, sampler=0, thresh=None, min_kept=0):
+    """The SegOhemPlan of calls with these shapes and this sampler: the training kernel's plan, the grids of the key and
+    selection passes, and the workspace bytes (the selection's part behind the partials).  Validates like the calls; no device."""
+    keys = 0x1000 if sampler else None                  # the query wants to know that they will be there, not where
+    a = seg_ohem_args(seg_args(B, C_, h, w, H, W, align_corners=align_corners), sampler, thresh, min_kept, keys=keys, threshold=keys)
+    plan = SegOhemPlan()
+    check(lib.memhip_seg_ohem_plan(C.byref(a), C.byref(plan)), "seg_ohem_plan")
+    return plan
+
+
+def _f32_ptr(t, n, name):
+    assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n, "%s: a contiguous CUDA f32 tensor of %d" % (name, n)
+    return t.data_ptr()
+
+
+def _seg_ohem_common(logits, labels, ignore_index, align_corners, sampler, thresh, min_kept, class_weight, keys, threshold, **kw):
+    a, keep = _seg_common(logits, labels, ignore_index, align_corners, **kw)
+    B, C_ = logits.shape[:2]
+    f = {}
+    if class_weight is not None:
+        f["class_weight"] = _f32_ptr(class_weight, C_, "class_weight")
+    if keys is not None:
+        f["keys"] = _f32_ptr(keys, labels.numel(), "keys")
+    if threshold is not None:
+        f["threshold"] = _f32_ptr(threshold, 1, "threshold")
+    return seg_ohem_args(a, sampler, thresh, min_kept, **f), keep
+
+
+def seg_ohem_keys(logits, labels, keys, threshold, sampler, class_weight=None, ignore_index=255, align_corners=False):
+    """keys f32 [B, H, W] <- the sampler's key of every output pixel of the resized logits: sampler 1 softmax[label], sampler 2
+    class_weight[label] * nll (class_weight f32 [C] or None: ones); -1.0 where the label is ignored or >= C.  threshold f32 [1]
+    is the sampler's (the three calls of a sampler take one struct); this call does not touch it."""
+    a, keep = _seg_ohem_common(logits, labels, ignore_index, align_corners, sampler, 1.0, 0, class_weight, keys, threshold)
+    check(lib.memhip_seg_ohem_keys(C.byref(a), stream_ptr()), "seg_ohem_keys")
+    return keys
+
+
+def seg_ohem_select(keys, threshold, stats, workspace, sampler, thresh=None, min_kept=100000, logits_shape=None):
+    """threshold f32 [1] <- the sampler's threshold over the keys >= 0 of keys f32 [B, H, W] (batch = B; K = min_kept * B):
+    sampler 1: max(the key of ascending rank min(K, n - 1), thresh), kept are the keys below it (-inf: none); sampler 2: the
+    K-th largest key, kept are the keys >= it, ties included (+inf: none).  stats i64 [4]: stats[3] <- n_kept.  workspace: >=
+    seg_ohem_plan(...).ws_bytes bytes for logits_shape = (C, h, w), cleared by the call where it needs it cleared; the
+    selection reads no logits, and without logits_shape the smallest map stands in (the selection's part of the workspace
+    lies behind the partials of that shape).  Exact, no host synchronisation."""
+    assert keys.is_cuda and keys.dtype == torch.float32 and keys.is_contiguous() and keys.dim() == 3
+    assert stats.dtype == torch.int64 and stats.numel() >= 4 and stats.is_contiguous() and stats.is_cuda
+    assert workspace.is_cuda
+    B, H, W = keys.shape
+    C_, h, w = (2, 1, 1) if logits_shape is None else logits_shape
+    seg = seg_args(B, C_, h, w, H, W, stats=stats.data_ptr(), workspace=workspace.data_ptr(),
+                   workspace_bytes=workspace.numel() * workspace.element_size())
+    a = seg_ohem_args(seg, sampler, thresh, min_kept, keys=keys.data_ptr(), threshold=_f32_ptr(threshold, 1, "threshold"))
+    check(lib.memhip_seg_ohem_select(C.byref(a), stream_ptr()), "seg_ohem_select")
+    return threshold
+
+
+def seg_ce_w(logits, labels, dz, loss, stats, workspace, ignore_index=255, align_corners=False, avg_non_ignore=False, loss_weight=1.0,
+             class_weight=None, sampler=0, keys=None, threshold=None):
+    """seg_ce with class weights and the sampler's pixel weight: q and the loss term of a valid pixel are multiplied by
+    class_weight[label] * s, s = 1 without a sampler, else [key < threshold] (sampler 1) or [key >= threshold] (sampler 2) on
+    the stored keys f32 [B, H, W] and threshold f32 [1] of seg_ohem_keys / seg_ohem_select.  stats i64 [4] <- n_valid, n_correct,
+    n_bad, n_kept.  With neither, or with weights of 1.0, loss, dz and stats[:3] are seg_ce's bits.  workspace: >=
+    seg_ohem_plan(...).ws_bytes bytes."""
+    assert dz.dtype == torch.float32 and tuple(dz.shape) == tuple(logits.shape) and dz.is_cuda
+    assert loss.dtype == torch.float32 and loss.numel() >= 3 and loss.is_contiguous()
+    assert stats.dtype == torch.int64 and stats.numel() >= 4 and stats.is_contiguous()
+    a, keep = _seg_ohem_common(logits, labels, ignore_index, align_corners, sampler, 1.0, 0, class_weight, keys, threshold,
+                               avg_non_ignore=int(avg_non_ignore), loss_weight=float(loss_weight), dz=dz.data_ptr(),
+                               loss=loss.data_ptr(), stats=stats.data_ptr(), workspace=workspace.data_ptr(),
+                               workspace_bytes=workspace.numel() * workspace.element_size())
+    a.seg.db, a.seg.dc, a.seg.dy, a.seg.dx = dz.stride()
+    check(lib.memhip_seg_ce_w(C.byref(a), stream_ptr()), "seg_ce_w")
+
+
 # ---------------------------------------------------------------- segmentation inference (csrc/seg_predict.hip, seg_predict_plan.cpp)
 class SegPredictArgs(C.Structure):
     """== memhip_segpredict_args_t."""

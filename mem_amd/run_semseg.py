@@ -16,6 +16,11 @@ registries are not carried; what they decide is restated here:
                  ``--checkpoint_interval`` iterations and at the end (``iter_<n>.pth``, mmseg's keys); an evaluation every
                  ``--eval_interval`` iterations and under ``--eval_only``: test pipeline -> ``encode_decode`` -> ``SegEvaluator`` ->
                  one JSON line.  The data chain is ``mem_amd.seg_data``.
+  * loss         ``--class_weight`` (a comma list, or a JSON file holding a list or an object with a ``"class_weight"`` key, such as
+                 ``tools/seg_class_weights.py`` prints) weights the classes in both heads' losses; ``--ohem_min_kept N`` with the
+                 optional ``--ohem_thresh T`` puts an ``OHEMPixelSampler`` on the decode head, as mmseg's OHEM configs do (no
+                 per-head OHEM flags).  Both are off by default, are recorded in the checkpoint's ``meta``, and with a sampler the
+                 training record gains ``decode.n_kept``.
 
 Single GPU.  Distributed training, launchers, deepspeed, ``--aug-test``, the ``slide`` test mode and ``cat_max_ratio < 1`` parse
 and are refused by name."""
@@ -82,6 +87,32 @@ def add_model_data_flags(p):
     p.add_argument("--samples_per_gpu", default=16, type=int)
 
 
+def parse_class_weight(text, num_classes=None):
+    """``--class_weight``: "1,2.5,0" or a path to a JSON list / a JSON object with a "class_weight" key -> [float] or None"""
+    if text is None or text == "":
+        return None
+    if os.path.exists(text):
+        with open(text) as f:
+            data = json.load(f)
+        if isinstance(data, dict):
+            if "class_weight" not in data:
+                raise ValueError(f"--class_weight {text}: a JSON object needs a \"class_weight\" key")
+            data = data["class_weight"]
+    else:
+        try:
+            data = [float(v) for v in text.split(",")]
+        except ValueError:
+            raise ValueError(f"--class_weight {text!r}: neither a comma list of numbers nor an existing JSON file") from None
+    if not isinstance(data, list) or not data or not all(isinstance(v, (int, float)) and not isinstance(v, bool) for v in data):
+        raise ValueError(f"--class_weight {text}: a non-empty list of numbers")
+    weights = [float(v) for v in data]
+    if any(not math.isfinite(v) or v < 0 for v in weights):
+        raise ValueError(f"--class_weight {text}: weights must be finite and >= 0")
+    if num_classes is not None and len(weights) != num_classes:
+        raise ValueError(f"--class_weight names {len(weights)} weights, --num_classes is {num_classes}")
+    return weights
+
+
 def resolve_model_args(args):
     """The values that follow from others: the width and heads of --vit, the last four blocks."""
     dim, heads = VIT_SIZES[args.vit]
@@ -110,6 +141,10 @@ def get_args(argv=None):
     p.add_argument("--log_interval", default=50, type=int)
     p.add_argument("--resume", default="", help="a checkpoint of this entrypoint: iteration, optimizer and mask streams continue")
     p.add_argument("--eval_only", action="store_true")
+    # the loss: class weights (both heads) and OHEM pixel sampling (decode head)
+    p.add_argument("--class_weight", default="", help="comma list, or a JSON file: a list or an object with a class_weight key")
+    p.add_argument("--ohem_min_kept", default=None, type=int, help="OHEMPixelSampler(min_kept=N) on the decode head; off when absent")
+    p.add_argument("--ohem_thresh", default=None, type=float, help="its thresh; absent: the top-k mode")
     # parsed and refused
     p.add_argument("--launcher", default="none")
     p.add_argument("--distributed", action="store_true")
@@ -128,6 +163,13 @@ def get_args(argv=None):
         raise NotImplementedError(f"--cat_max_ratio {args.cat_max_ratio}: class-balanced crops are not mirrored (dsec.py sets 1.0)")
     resolve_model_args(args)
     args.num_layers = args.num_layers or args.depth
+    args.class_weight = parse_class_weight(args.class_weight, args.num_classes)
+    if args.ohem_thresh is not None and args.ohem_min_kept is None:
+        raise ValueError("--ohem_thresh needs --ohem_min_kept")
+    if args.ohem_min_kept is not None and args.ohem_min_kept < 0:
+        raise ValueError(f"--ohem_min_kept {args.ohem_min_kept}: an integer >= 0")
+    if args.ohem_thresh is not None and not 0.0 < args.ohem_thresh <= 1.0:
+        raise ValueError(f"--ohem_thresh {args.ohem_thresh}: a probability in (0, 1]")
     return args
 
 
@@ -139,10 +181,18 @@ def build_model(args):
     backbone = EvBEiT(img_size=tuple(args.net_size), patch_size=16, embed_dim=D, depth=args.depth, num_heads=args.num_heads,
                       mlp_ratio=4, use_abs_pos_emb=False, use_rel_pos_bias=True, init_values=args.init_values,
                       drop_path_rate=args.drop, out_indices=tuple(args.out_indices), necks=args.necks)
+    # the loss arguments: absent (the inference tool's flags) or off, both heads are built exactly as without them
+    cw, min_kept = getattr(args, "class_weight", None), getattr(args, "ohem_min_kept", None)
+    sampler = None if min_kept is None else dict(type="OHEMPixelSampler", thresh=getattr(args, "ohem_thresh", None), min_kept=min_kept)
+    kw_decode, kw_aux = dict(loss_weight=1.0), dict(loss_weight=args.aux_loss_weight)
+    if cw is not None or sampler is not None:
+        kw_decode = dict(loss_decode=dict(type="CrossEntropyLoss", use_sigmoid=False, loss_weight=1.0, class_weight=cw, sampler=sampler))
+    if cw is not None:
+        kw_aux = dict(loss_decode=dict(type="CrossEntropyLoss", use_sigmoid=False, loss_weight=args.aux_loss_weight, class_weight=cw))
     decode = UPerHead(in_channels=(D,) * 4, in_index=(0, 1, 2, 3), pool_scales=tuple(args.pool_scales), channels=args.decode_channels,
-                      num_classes=args.num_classes, dropout_ratio=args.drop, align_corners=False, loss_weight=1.0)
+                      num_classes=args.num_classes, dropout_ratio=args.drop, align_corners=False, **kw_decode)
     aux = FCNHead(in_channels=D, in_index=2, channels=args.aux_channels, num_convs=1, concat_input=False, dropout_ratio=args.drop,
-                  num_classes=args.num_classes, align_corners=False, loss_weight=args.aux_loss_weight)
+                  num_classes=args.num_classes, align_corners=False, **kw_aux)
     return SegModel(backbone, decode, aux)
 
 
@@ -376,7 +426,8 @@ def save_checkpoint(path, model, optimizer, it, stream, args):
     """mmcv's layout: ``meta`` / ``state_dict`` / ``optimizer``; ``meta`` also carries the state of the mask stream (drop path
     and both heads' Dropout2d keys) and the run's seed."""
     meta = {"iter": it, "seed": args.seed, "drop_path_rng": stream.state(), "CLASSES": getattr(args, "CLASSES", None),
-            "time": time.asctime()}
+            "class_weight": getattr(args, "class_weight", None), "ohem_min_kept": getattr(args, "ohem_min_kept", None),
+            "ohem_thresh": getattr(args, "ohem_thresh", None), "time": time.asctime()}
     tmp = str(path) + ".tmp"
     torch.save({"meta": meta, "state_dict": {k: v.detach().cpu() for k, v in model.state_dict().items()},
                 "optimizer": optimizer.state_dict()}, tmp)
@@ -465,6 +516,8 @@ def main(args):
         if it % args.log_interval == 0 or it == args.max_iters:
             rec = {"iter": it, "lr": optimizer.param_groups[-1]["lr"], "loss": float(loss.detach()),
                    **{k: float(v.detach()) for k, v in losses.items()}, "time": round(time.time() - t0, 3)}
+            if model.decode_head.loss_decode.sampler is not None:          # read where the loss is read: no other synchronisation
+                rec["decode.n_kept"] = int(model.decode_head.loss_decode.last_stats["n_kept"])
             print(json.dumps(rec), flush=True)
             out["train"].append(rec)
         if work_dir is not None and (it % args.checkpoint_interval == 0 or it == args.max_iters):

@@ -36,8 +36,17 @@ each convolution output rounded to bf16 once; pooling sums, statistics, normalis
 -> classifier in fp32 on fp32 parameters; a value is rounded to bf16 once where it becomes a convolution operand or the
 gradient of a convolution's output; logits, parameter gradients and the returned map gradient fp32.
 
+The loss: every head takes ``loss_decode=``, a ``SegCrossEntropy`` or mmseg's ``dict(type='CrossEntropyLoss', use_sigmoid=False,
+loss_weight=..., class_weight=[...], avg_non_ignore=...)`` with this project's extra key ``sampler=dict(type='OHEMPixelSampler',
+thresh=..., min_kept=...)`` (mmseg puts the sampler beside the loss in the head's config; here it belongs to the loss that
+applies it).  The head builds ``self.loss_decode`` from it with its own ``ignore_index`` and ``align_corners``; a dict's loss runs
+on the head's arm (``impl="torch"``: ``seg_loss.torch_seg_ce``, plain torch ops on any device).  A ``SegCrossEntropy`` instance is
+used as it is, not copied: the head WRITES its own ``ignore_index`` and ``align_corners`` into the caller's object, and one instance given
+to two heads is shared by them (one ``last_stats``, one workspace); give each head its own.  Without ``loss_decode=`` the loss is
+the plain fused one at the head's ``loss_weight``, as before.  The head keywords ``class_weight=`` and ``sampler=`` still raise.
+
 Out of scope: the mmseg runner, schedules and data pipeline, sliding-window test mode, ``num_convs != 1``, ``concat_input``,
-dilation, class weights, OHEM samplers, more than 32 classes, ``channels > 512``, more than 4 levels on the hip arm.
+dilation, ``use_sigmoid`` and other loss types, more than 32 classes, ``channels > 512``, more than 4 levels on the hip arm.
 """
 import torch
 import torch.nn as nn
@@ -92,7 +101,10 @@ class _BnClsHead(BufferCache, nn.Module):
     """What the decode heads share: the walk from the padded bf16 operand of a head's last 3x3 ConvModule (``_cm()``) to the
     logits and back (``_tail_forward`` / ``_tail_backward``), the bf16 weight copies, Dropout2d's keys, and mmseg's interface."""
 
-    def _init_tail(self, channels, num_classes, in_index, dropout_ratio, align_corners, loss_weight, ignore_index, impl):
+    _default_loss_weight = 1.0           # the constructor's default: what ``loss_weight=`` may be beside ``loss_decode=``
+
+    def _init_tail(self, channels, num_classes, in_index, dropout_ratio, align_corners, loss_weight, ignore_index, impl,
+                   loss_decode=None):
         self.channels, self.num_classes, self.in_index = channels, num_classes, in_index
         self.dropout_ratio = float(dropout_ratio)
         self.align_corners = bool(align_corners)
@@ -101,7 +113,7 @@ class _BnClsHead(BufferCache, nn.Module):
         self.conv_seg = nn.Conv2d(channels, num_classes, 1)
         nn.init.normal_(self.conv_seg.weight, mean=0.0, std=0.01)          # mmseg: normal_init(self.conv_seg, mean=0, std=0.01)
         nn.init.constant_(self.conv_seg.bias, 0.0)
-        self.loss_decode = SegCrossEntropy(ignore_index=ignore_index, align_corners=align_corners, loss_weight=loss_weight)
+        self.loss_decode = self._make_loss(loss_decode, loss_weight, ignore_index, align_corners, impl)
         self.reduce = all_reduce_sum
         self.dropout_site = None             # ops.DROPOUT_SITE_HEAD (+ the head's number in a SegModel)
         self.drop_key = None
@@ -111,12 +123,43 @@ class _BnClsHead(BufferCache, nn.Module):
         self._w = {}
 
     @classmethod
+    def _make_loss(cls, loss_decode, loss_weight, ignore_index, align_corners, impl):
+        """the head's ``SegCrossEntropy``: the plain one at ``loss_weight``, or what ``loss_decode=`` describes"""
+        if loss_decode is None:
+            return SegCrossEntropy(ignore_index=ignore_index, align_corners=align_corners, loss_weight=loss_weight)
+        if loss_weight != cls._default_loss_weight:
+            raise ValueError(f"{cls.__name__}: loss_decode= carries the loss weight; loss_weight={loss_weight!r} beside it is ambiguous")
+        if isinstance(loss_decode, SegCrossEntropy):
+            loss_decode.ignore_index, loss_decode.align_corners = ignore_index, bool(align_corners)
+            return loss_decode
+        if not isinstance(loss_decode, dict):
+            raise TypeError(f"loss_decode: a SegCrossEntropy or mmseg's dict, got {type(loss_decode).__name__}")
+        cfg = dict(loss_decode)
+        kind = cfg.pop("type", "CrossEntropyLoss")
+        if kind != "CrossEntropyLoss":
+            raise NotImplementedError(f"loss_decode: type={kind!r}; CrossEntropyLoss is the loss of mem_amd.seg_loss")
+        if cfg.pop("use_sigmoid", False):
+            raise NotImplementedError("loss_decode: use_sigmoid=True (binary cross entropy) is not part of mem_amd.seg_loss")
+        if cfg.pop("use_mask", False):
+            raise NotImplementedError("loss_decode: use_mask=True is not part of mem_amd.seg_loss")
+        if cfg.pop("reduction", "mean") != "mean":
+            raise NotImplementedError("loss_decode: reduction='mean' only")
+        cfg.pop("loss_name", None)
+        extra = set(cfg) - {"loss_weight", "class_weight", "avg_non_ignore", "sampler", "check_labels", "impl"}
+        if extra:
+            raise TypeError(f"loss_decode: unsupported keys {sorted(extra)}")
+        cfg.setdefault("impl", impl)
+        return SegCrossEntropy(ignore_index=ignore_index, align_corners=align_corners, **cfg)
+
+    @classmethod
     def _check_common(cls, impl, dropout_ratio, in_channels, channels, num_classes, class_weight, sampler, kwargs):
         name = cls.__name__
         if class_weight is not None:
-            raise NotImplementedError("class_weight: class weights are not part of mem_amd.seg_loss")
+            raise NotImplementedError("class_weight: the head takes class weights through loss_decode=dict(type='CrossEntropyLoss', "
+                                      "class_weight=[...]), not as a keyword of its own")
         if sampler is not None:
-            raise NotImplementedError("sampler: pixel samplers (OHEM) are not part of mem_amd.seg_loss")
+            raise NotImplementedError("sampler: the head takes a pixel sampler (OHEM) through loss_decode=dict(type='CrossEntropyLoss', "
+                                      "sampler=dict(type='OHEMPixelSampler', ...)), not as a keyword of its own")
         if kwargs:
             raise TypeError(f"{name}: unsupported arguments {sorted(kwargs)}")
         if impl not in ("hip", "torch"):
@@ -298,9 +341,11 @@ class FCNHead(_BnClsHead):
     at site ``dropout_site``, row = sample, column = channel; the key of a training forward is ``drop_key`` when the caller
     sets one (a ``(key0, key1)`` per step, like the engine's), else ``(torch.initial_seed(), number of the call)``."""
 
+    _default_loss_weight = 0.4
+
     def __init__(self, in_channels=768, channels=256, num_classes=11, in_index=2, dropout_ratio=0.1, align_corners=False,
                  loss_weight=0.4, ignore_index=255, impl="hip", num_convs=1, concat_input=False, kernel_size=3, dilation=1,
-                 class_weight=None, sampler=None, **kwargs):
+                 class_weight=None, sampler=None, loss_decode=None, **kwargs):
         super().__init__()
         if num_convs != 1:
             raise NotImplementedError("num_convs: FCNHead mirrors num_convs=1 only (one conv + BN + ReLU block)")
@@ -313,7 +358,7 @@ class FCNHead(_BnClsHead):
         self._check_common(impl, dropout_ratio, in_channels, channels, num_classes, class_weight, sampler, kwargs)
         self.in_channels = in_channels
         self.convs = nn.Sequential(ConvModule(in_channels, channels))
-        self._init_tail(channels, num_classes, in_index, dropout_ratio, align_corners, loss_weight, ignore_index, impl)
+        self._init_tail(channels, num_classes, in_index, dropout_ratio, align_corners, loss_weight, ignore_index, impl, loss_decode)
 
     def _cm(self):
         return self.convs[0]
@@ -429,7 +474,8 @@ class PSPHead(_BnClsHead):
     forward and "bwd", "bwd" (bottleneck, pyramid) in its backward."""
 
     def __init__(self, in_channels=768, channels=512, num_classes=11, in_index=3, pool_scales=(1, 2, 3, 6), dropout_ratio=0.1,
-                 align_corners=False, loss_weight=1.0, ignore_index=255, impl="hip", class_weight=None, sampler=None, **kwargs):
+                 align_corners=False, loss_weight=1.0, ignore_index=255, impl="hip", class_weight=None, sampler=None, loss_decode=None,
+                 **kwargs):
         super().__init__()
         self._check_common(impl, dropout_ratio, in_channels, channels, num_classes, class_weight, sampler, kwargs)
         pool_scales = tuple(pool_scales)
@@ -444,7 +490,7 @@ class PSPHead(_BnClsHead):
         self.psp_modules = nn.ModuleList(nn.Sequential(nn.AdaptiveAvgPool2d(s), ConvModule(in_channels, channels, 1))
                                          for s in self.pool_scales)
         self.bottleneck = ConvModule(in_channels + len(self.pool_scales) * channels, channels)
-        self._init_tail(channels, num_classes, in_index, dropout_ratio, align_corners, loss_weight, ignore_index, impl)
+        self._init_tail(channels, num_classes, in_index, dropout_ratio, align_corners, loss_weight, ignore_index, impl, loss_decode)
         self.ppm = PyramidPooling(self, [seq[1] for seq in self.psp_modules], self.pool_scales, in_channels, channels, align_corners)
 
     def _cm(self):
@@ -515,7 +561,7 @@ class UPerHead(_BnClsHead):
 
     def __init__(self, in_channels=(768,) * 4, channels=512, num_classes=11, in_index=(0, 1, 2, 3), pool_scales=(1, 2, 3, 6),
                  dropout_ratio=0.1, align_corners=False, loss_weight=1.0, ignore_index=255, impl="hip", class_weight=None,
-                 sampler=None, **kwargs):
+                 sampler=None, loss_decode=None, **kwargs):
         super().__init__()
         in_channels, in_index = tuple(in_channels), tuple(in_index)
         if len(in_channels) != len(in_index):
@@ -541,7 +587,7 @@ class UPerHead(_BnClsHead):
         self.lateral_convs = nn.ModuleList(ConvModule(c, channels, 1) for c in in_channels[:-1])
         self.fpn_convs = nn.ModuleList(ConvModule(channels, channels) for _ in in_channels[:-1])
         self.fpn_bottleneck = ConvModule(len(in_channels) * channels, channels)
-        self._init_tail(channels, num_classes, in_index, dropout_ratio, align_corners, loss_weight, ignore_index, impl)
+        self._init_tail(channels, num_classes, in_index, dropout_ratio, align_corners, loss_weight, ignore_index, impl, loss_decode)
         self.ppm = PyramidPooling(self, [seq[1] for seq in self.psp_modules], self.pool_scales, in_channels[-1], channels, align_corners)
 
     def _cm(self):

@@ -1,6 +1,7 @@
 // Host-only exercise of seg_plan.cpp for the sanitizers: memhip_seg_axis_table over every (in, out, align_corners) up to a
 // few hundred outputs with its arrays allocated at their exact sizes, and memhip_seg_plan over a few hundred thousand
-// memhip_seg_args_t, accepted and rejected, with the invariants the launcher and the kernel rely on checked on the way.
+// memhip_seg_args_t, accepted and rejected, with the invariants the launcher and the kernel rely on checked on the way; then
+// memhip_seg_ohem_plan over a hundred thousand memhip_segohem_args_t in the same way.
 // The one variable of core.cpp it needs is defined here; no device:
 //
 //   clang++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include \
@@ -75,7 +76,37 @@ int main() {
     CHECK(rc == MEMHIP_OK || (rc == MEMHIP_EWORKSPACE && a.workspace && a.workspace_bytes < plan.ws_bytes));
     ++ok;
   }
-  std::printf("seg_plan_sanitize: %lld tables, %lld plans accepted, %lld rejected\n", tables, ok, rejected);
-  CHECK(ok > 100000 && rejected > 10000);
+  // memhip_seg_ohem_plan: the same struct as the first member, the sampler's fields behind it
+  long long ok_w = 0, rejected_w = 0;
+  memhip_segohem_plan_t wplan;
+  CHECK(memhip_seg_ohem_plan(nullptr, &wplan) == MEMHIP_EINVAL);
+  for (int it = 0; it < 100000; ++it) {
+    memhip_segohem_args_t a = {};
+    a.seg.B = rnd(1, 64); a.seg.C = rnd(0, 19) ? rnd(2, 32) : rnd(-1, 40);
+    a.seg.h = rnd(1, 130); a.seg.w = rnd(1, 130);
+    a.seg.H = a.seg.h * rnd(1, 5) + rnd(0, 3); a.seg.W = a.seg.w * rnd(1, 5) + rnd(0, 3);
+    a.seg.ignore_index = 255; a.seg.loss_weight = 1.f;
+    a.sampler = rnd(0, 19) ? rnd(0, 2) : rnd(-1, 3);
+    a.thresh = rnd(0, 9) ? 0.7f : (float)rnd(-1, 2);
+    a.min_kept = rnd(0, 19) ? rnd(0, 200000) : -1;
+    if (rnd(0, 9)) { a.keys = (float*)P; a.threshold = (float*)P; }
+    if (rnd(0, 1)) { a.seg.workspace = P; a.seg.workspace_bytes = (size_t)rnd(0, 1 << 20); }
+    const int rc = memhip_seg_ohem_plan(&a, &wplan);
+    if (rc == MEMHIP_EINVAL) { ++rejected_w; continue; }
+    CHECK(a.sampler >= 0 && a.sampler <= 2 && (a.sampler == 0 || (a.keys && a.threshold && a.min_kept >= 0)));
+    CHECK(a.sampler != 1 || (a.thresh > 0.f && a.thresh <= 1.f));
+    const memhip_seg_plan_t& q = wplan.seg;
+    CHECK(q.grid == a.seg.B * q.tiles_y * q.tiles_x && q.lds_bytes <= kLdsLimit && q.lds_bytes % 8 == 0);
+    CHECK(q.lds_bytes >= lds_fixed_bytes(padded_channels(a.seg.C)) + kMaxC * 4 + (q.tables_in_lds ? (q.max_fh + q.max_fw) * 8 : 0));
+    CHECK(wplan.keys_grid >= 1 && wplan.keys_grid <= kConfMaxGrid && wplan.select_grid >= 1 && wplan.select_grid <= kSelMaxGrid);
+    CHECK(wplan.select_bins == kSelBins && wplan.select_lds_bytes == kSelBins * 4 && wplan.select_passes == kSelPasses);
+    CHECK(wplan.select_ws_offset % 8 == 0 && wplan.select_ws_offset >= q.ws_bytes && wplan.select_ws_offset < q.ws_bytes + 8);
+    CHECK(wplan.select_ws_bytes == (a.sampler ? select_ws_bytes() : 0) && wplan.ws_bytes == wplan.select_ws_offset + wplan.select_ws_bytes);
+    CHECK(rc == MEMHIP_OK || (rc == MEMHIP_EWORKSPACE && a.seg.workspace && a.seg.workspace_bytes < wplan.ws_bytes));
+    ++ok_w;
+  }
+  std::printf("seg_plan_sanitize: %lld tables, %lld plans accepted, %lld rejected; ohem: %lld accepted, %lld rejected\n", tables, ok,
+              rejected, ok_w, rejected_w);
+  CHECK(ok > 100000 && rejected > 10000 && ok_w > 30000 && rejected_w > 3000);
   return 0;
 }
